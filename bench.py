@@ -12,7 +12,10 @@ touches the GPU; under `python -m torch.distributed.run --nproc-per-node N bench
 WORLD_SIZE must agree.
 
 This file holds the contract path only (W warm-up proofs, barrier, K timed proofs, barrier, MAX over ranks, ONE JSON line on rank 0); everything
-that rides beside it lives in tools/benchlib/ (one paragraph per module in its __init__.py). Checked and measured inside this run:
+that rides beside it lives in tools/benchlib/ (one paragraph per module in its __init__.py).
+A plain N = 1 run does only that: set up, W warm-up proofs, K timed proofs, --dump-outputs if given, the line (metric, value, unit, higher_is_better,
+dtype, ms_per_step, the proof's SHA-256). --dump-outputs DIR writes the last timed proof as DIR/proof_bytes.npy (its bytes, float32) and DIR/proof_numbers.npy
+(every number of the proof JSON in document order, float64). Everything below runs only with --full (N > 1 runs always do the full run):
   parity_checked  SHA-256 of the last timed proof == the committed digest of the CPU oracle's proof of the same workload
   roofline        dominant kernel, HIP events on the library's own stream over the timed region (k_merkle_layer: integer-VALU bound, Blake2s compressions
                   counted from the launch shapes; HBM figure beside it); sustained_clock_ghz / frac_at_sustained_clock from the library's in-run clock probe
@@ -51,6 +54,9 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--log-max-rows", type=int, default=24)
+    ap.add_argument("--full", action="store_true", help="N = 1: also run every check and measurement beside the headline (parity with the committed digest, roofline, "
+                    "clock probe, FFT report, sweep, Poseidon252 point, proofs in flight, cpu_baseline). Off by default; N > 1 runs always do them")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step computed (the proof) to DIR/*.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--pin", action="store_true", help="pin the proving host thread to one core of the GPU's NUMA node during the timed regions (default off: the gain "
                     "is box dependent, profiles/r03_bench_host_pinning_ab.txt)")
@@ -92,6 +98,24 @@ def parse_args():
     return ap.parse_args()
 
 
+def dump_outputs(out_dir, proof):
+    """--dump-outputs: the last timed proof as arrays — its bytes (float32, exact) and the numbers of its JSON in document order (float64)."""
+    import numpy as np
+    nums = []
+
+    def walk(v):
+        if isinstance(v, dict):
+            v = list(v.values())
+        if isinstance(v, list):
+            [walk(x) for x in v]
+        elif isinstance(v, (int, float)) and not isinstance(v, bool):
+            nums.append(float(v))
+    walk(json.loads(proof))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "proof_bytes.npy"), np.frombuffer(proof, dtype=np.uint8).astype(np.float32))
+    np.save(os.path.join(out_dir, "proof_numbers.npy"), np.asarray(nums, dtype=np.float64))
+
+
 def main():
     args = parse_args()
     if args.shard_probe:
@@ -106,6 +130,9 @@ def main():
         raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started WORLD_SIZE={world} ranks: the two must agree "
                          f"(python -m torch.distributed.run --nproc-per-node {args.gpus} bench.py --gpus {args.gpus}, or plain python3 bench.py --gpus {args.gpus})")
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    lean = world == 1 and not args.full
+    if lean:        # a plain run: the headline only, no check or measurement beside it (module docstring)
+        args.no_kernel_events = args.no_sweep = args.no_poseidon = args.no_cpu_baseline = True
     if world > 1:
         # a rank that is ended from outside (the self-launcher's time limit, a driver's timeout) says where it was: Python stacks of all its threads
         import faulthandler
@@ -196,9 +223,9 @@ def main():
     def build_line(S, g, extras_error=None):
         sharded, dt, proof, phases = S["sharded"], S["dt"], S["proof"], S["phases"]
         digest = hashlib.sha256(proof).hexdigest()
-        want = want_digest(conv, args.log_max_rows)
-        parity_checked = bool(want is not None and want["sha256"] == digest and want["proof_bytes"] == len(proof))
-        verified, _ = pkg.verify_brainfuck(proof, args.log_max_rows)
+        want = None if lean else want_digest(conv, args.log_max_rows)
+        parity_checked = None if lean else bool(want is not None and want["sha256"] == digest and want["proof_bytes"] == len(proof))
+        verified = None if lean else pkg.verify_brainfuck(proof, args.log_max_rows)[0]
         sweep = S["sweep"]
         p22 = next((p for p in sweep if p["log_domain_rows"] == 22), None) if isinstance(sweep, list) else None
         p22_name = "synthetic nested-counter trace, Memory component 2^22 domain rows, LOG_MAX_ROWS 22 (BASELINE metric 'at 2^22 rows')"
@@ -219,7 +246,7 @@ def main():
             "parity_checked": parity_checked,
             "parity": {"proof_sha256": digest, "proof_bytes": len(proof), "expected_sha256": want["sha256"] if want else None,
                        "expected_from": "tests/golden/fib19_lmr24_oracle_proof.json (CPU oracle's proof of this workload under the same conventions)" if want else None,
-                       "conventions": list(conv), "own_verifier_accepts": bool(verified)},
+                       "conventions": list(conv), "own_verifier_accepts": None if lean else bool(verified)},
             "config": {"workload": ("fib19.bf (BASELINE config 2; largest component 2^20 table rows = 2^24 domain rows, Blake2s Merkle), 1 proof per step"
                                     + (f" = ONE proof over the {world}-GPU shard group (BASELINE config 4's size: a 2^24-domain-row trace, column-sharded transforms, row-sharded "
                                        "Merkle / constraints / quotients / folds, RCCL); the synthetic 2^24-row trace of configs 3/4 and config 5 ride in strong_scaling" if sharded else "")
@@ -292,6 +319,8 @@ def main():
             dt, (proof, phases) = replicas.timed_region(one_step, args.steps, args.warmup, dist=dist, sync_fn=sync, backend_tensor=R.cuda_t, on_timed_start=start_events)
         total_cells = replicas.aggregate_units(trace.cells * args.inflight, dist=dist, backend_tensor=R.cuda_t)
     S.update(sharded=sharded, dt=dt, proof=proof, phases=phases, total_cells=total_cells)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, proof)
 
     # ---- roofline of the dominant kernel over the TIMED region; the sustained clock right behind it; the FFT kernels from one extra untimed proof -------------
     if not args.no_kernel_events:

@@ -103,3 +103,24 @@ def test_launcherless_run_without_gpus_fails_loudly():
                        env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0, r.stdout
     assert not any(l.startswith("{") for l in r.stdout.splitlines())
+
+
+def test_dump_outputs_writes_the_proof_exactly(tmp_path):
+    """bench.py --dump-outputs: the proof's bytes as float32 (exact) and every number of its JSON in document order as float64; strings, booleans and nulls are not numbers."""
+    import numpy as np
+    proof = b'{"claim":{"memory":{"log_size":10,"_marker":null}},"proof":[7,[2147483646,3],{"hash":[255,0]}],"s":"x","ok":true}'
+    bench_module().dump_outputs(str(tmp_path / "out"), proof)
+    raw, nums = np.load(tmp_path / "out" / "proof_bytes.npy"), np.load(tmp_path / "out" / "proof_numbers.npy")
+    assert raw.dtype == np.float32 and raw.astype(np.uint8).tobytes() == proof
+    assert nums.dtype == np.float64 and nums.tolist() == [10, 7, 2147483646, 3, 255, 0]
+
+
+def test_plain_run_options(monkeypatch):
+    """--full is off by default (a plain run is the headline only); --dump-outputs takes a directory."""
+    b = bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = b.parse_args()
+    assert a.full is False and a.dump_outputs is None and a.steps == 3 and a.warmup == 1
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = b.parse_args()
+    assert a.full is True and a.dump_outputs == "d"

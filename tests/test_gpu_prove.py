@@ -421,7 +421,7 @@ def test_bench_line_contract(tmp_path):
     the roofline is the VALU one with a measured compression count, and the sweep points verify."""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-baseline", "sample", "--sweep-logs", "20,22", "--sweep-steps", "1",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--cpu-baseline", "sample", "--sweep-logs", "20,22", "--sweep-steps", "1",
                         "--poseidon-log", "20"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -451,6 +451,30 @@ def test_bench_line_contract(tmp_path):
     assert "2^22 rows" in d["config"]["workload"] and "fib19" in d["config"]["workload"]
 
 
+def test_plain_bench_run_is_the_headline_only_and_dumps_the_last_proof(tmp_path):
+    """A plain `bench.py --steps K --warmup W` runs the headline only (no roofline, sweep, proofs in flight, CPU baseline or parity check beside it) and
+    --dump-outputs writes the last timed proof: its bytes are the CPU oracle's proof of the same workload (the committed digest)."""
+    import hashlib, json, subprocess, sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "trace cells committed+proved/sec" and d["unit"] == "trace cells/s" and d["higher_is_better"] is True and d["dtype"].startswith("u32")
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert abs(d["value"] - d["config"]["cells_per_proof"] / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    assert d["roofline"] is None and d["sweep"] is None and d["pipelined"] is None and d["fft"] is None and "cpu_baseline" not in d and d["parity_checked"] is None
+    raw = np.load(tmp_path / "out" / "proof_bytes.npy")
+    nums = np.load(tmp_path / "out" / "proof_numbers.npy")
+    proof = raw.astype(np.uint8).tobytes()
+    want = json.load(open(os.path.join(root, "tests", "golden", "fib19_lmr24_oracle_proof.json")))["stwo"]
+    assert hashlib.sha256(proof).hexdigest() == d["parity"]["proof_sha256"] == want["sha256"] and len(proof) == want["proof_bytes"]
+    assert nums.dtype == np.float64 and len(nums) > 1000 and raw.nbytes + nums.nbytes < 64 << 20
+
+
 def test_bench_line_is_self_explaining(tmp_path):
     """the line must say whether the box was slow (roofline.sustained_clock_ghz from the library's in-run clock probe, the VALU
     fraction at THAT clock beside the one at the nominal 2.4 GHz), carry the metric's own numbers inside `config` (the object the driver's record keeps
@@ -458,7 +482,7 @@ def test_bench_line_is_self_explaining(tmp_path):
     sweep's ms per proof — and report the FFT kernels against their VALU bound as well as against HBM."""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--sweep-logs", "20,22", "--sweep-steps", "2", "--no-poseidon"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--sweep-logs", "20,22", "--sweep-steps", "2", "--no-poseidon"],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

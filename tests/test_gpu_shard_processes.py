@@ -222,7 +222,7 @@ def test_bench_replicas_headline_and_python_threads_in_flight():
     line = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["parity_checked"] is True and "strong_scaling" not in line and "shard_group_error" not in line
     assert abs(line["value"] - 2 * line["config"]["cells_per_proof"] / (line["ms_per_step"] * 1e-3)) / line["value"] < 1e-6 and line["config"]["parallelism"] == "replicas"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--inflight", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-sweep"], env=env, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--inflight", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-sweep"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
     assert line["n_gpus"] == 1 and line["config"]["proofs_in_flight_per_gpu"] == 2 and line["roofline"] is None and line["parity_checked"] is True

@@ -8,7 +8,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 env = dict(os.environ, BFHIP_SINGLE_STREAM="1")
-r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "15", "--warmup", "3", "--no-sweep", "--no-poseidon", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "15", "--warmup", "3", "--no-sweep", "--no-poseidon", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
 d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
 rf = d["roofline"]
 cp = rf["clock_probe"]

@@ -17,11 +17,11 @@ RP="timeout 900 rocprofv3"
 
 if has bench; then
 # 1. headline bench line (roofline measured live with HIP events, CPU baseline on the host cores)
-python3 "$ROOT/bench.py" > "$OUT/bench.log" 2>&1; grep '^{"metric"' "$OUT/bench.log" | tail -1 > "$OUT/${R}_bench.json"
+python3 "$ROOT/bench.py" --full > "$OUT/bench.log" 2>&1; grep '^{"metric"' "$OUT/bench.log" | tail -1 > "$OUT/${R}_bench.json"
 # 2. same command under rocprofv3 --kernel-trace --stats (per-kernel average durations must agree with the roofline object)
-rm -rf /tmp/prof_stats; $RP --kernel-trace --stats --output-format csv -d /tmp/prof_stats -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-sweep --no-poseidon --no-clock-probe > "$OUT/bench_under_rocprof.log" 2>&1
+rm -rf "$TMPDIR/prof_stats"; $RP --kernel-trace --stats --output-format csv -d "$TMPDIR/prof_stats" -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-sweep --no-poseidon --no-clock-probe > "$OUT/bench_under_rocprof.log" 2>&1
 grep '^{"metric"' "$OUT/bench_under_rocprof.log" | tail -1 > "$OUT/${R}_bench_under_rocprof.json"
-cp $(ls /tmp/prof_stats/*/*kernel_stats.csv | head -1) "$OUT/${R}_bench_kernel_stats.csv"
+cp $(ls $TMPDIR/prof_stats/*/*kernel_stats.csv | head -1) "$OUT/${R}_bench_kernel_stats.csv"
 fi
 
 if has roofline; then
@@ -30,8 +30,8 @@ if has roofline; then
 #     depend on how the profiler lets two queues share the GPU) and, beside it, with the default two streams. tools/recompute_from_profiles.py reads them.
 for ss in 1 0; do
   tag=$([ $ss = 1 ] && echo single_stream || echo two_streams)
-  BFHIP_SINGLE_STREAM=$ss python3 "$ROOT/bench.py" --steps 20 --warmup 5 --no-sweep --no-poseidon --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | tail -1 > "$OUT/${R}_roofline_${tag}_events.json"
-  rm -rf /tmp/prof_rf; BFHIP_SINGLE_STREAM=$ss $RP --kernel-trace --stats --output-format csv -d /tmp/prof_rf -- python3 "$ROOT/bench.py" --steps 20 --warmup 5 --no-sweep --no-poseidon --no-cpu-baseline --no-clock-probe > "$OUT/roofline_${tag}_under_rocprof.log" 2>&1      # no probe: its k_merkle_layer launches would join the CSV's average
+  BFHIP_SINGLE_STREAM=$ss python3 "$ROOT/bench.py" --full --steps 20 --warmup 5 --no-sweep --no-poseidon --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | tail -1 > "$OUT/${R}_roofline_${tag}_events.json"
+  rm -rf "$TMPDIR/prof_rf"; BFHIP_SINGLE_STREAM=$ss $RP --kernel-trace --stats --output-format csv -d "$TMPDIR/prof_rf" -- python3 "$ROOT/bench.py" --full --steps 20 --warmup 5 --no-sweep --no-poseidon --no-cpu-baseline --no-clock-probe > "$OUT/roofline_${tag}_under_rocprof.log" 2>&1      # no probe: its k_merkle_layer launches would join the CSV's average
   grep '^{"metric"' "$OUT/roofline_${tag}_under_rocprof.log" | tail -1 > "$OUT/${R}_roofline_${tag}_under_rocprof.json"
   cp $(ls /tmp/prof_rf/*/*kernel_stats.csv | head -1) "$OUT/${R}_roofline_${tag}_kernel_stats.csv"
   python3 "$ROOT/tools/merkle_launches.py" $(kt /tmp/prof_rf) > "$OUT/${R}_roofline_${tag}_merkle_launches.txt" 2>&1
@@ -81,7 +81,7 @@ fi
 if has pmc; then
 # 3. HBM traffic counters, one pass each, kernel trace only
 for C in FETCH_SIZE WRITE_SIZE; do
-  rm -rf /tmp/prof_$C; $RP --kernel-trace --pmc $C --output-format csv -d /tmp/prof_$C -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events --no-sweep --no-poseidon > "$OUT/pmc_$C.log" 2>&1
+  rm -rf "$TMPDIR/prof_$C"; $RP --kernel-trace --pmc $C --output-format csv -d "$TMPDIR/prof_$C" -- python3 "$ROOT/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events --no-sweep --no-poseidon > "$OUT/pmc_$C.log" 2>&1
 done
 python3 "$ROOT/tools/pmc_traffic.py" /tmp/prof_FETCH_SIZE /tmp/prof_WRITE_SIZE > "$OUT/${R}_pmc_traffic.json"
 fi
@@ -148,8 +148,8 @@ fi
 if has misc; then
 python3 "$ROOT/tools/trace_time.py" > "$OUT/${R}_one_call.txt" 2>&1
 python3 "$ROOT/tools/big_trace.py" > "$OUT/${R}_big_trace.json" 2> "$OUT/big_trace.err"
-for n in 2 3; do python3 "$ROOT/bench.py" --no-cpu-baseline --no-kernel-events --no-sweep --no-poseidon --inflight $n 2>/dev/null | tail -1 > "$OUT/${R}_bench_inflight$n.json"; done
-python3 "$ROOT/bench.py" --no-cpu-baseline --no-kernel-events --no-sweep --no-poseidon 2>/dev/null | tail -1 > "$OUT/${R}_bench_no_events.json"
-python3 "$ROOT/bench.py" --no-cpu-baseline --no-kernel-events --no-sweep --no-poseidon --reuse-preprocessed 2>/dev/null | tail -1 > "$OUT/${R}_bench_reuse_preprocessed.json"
+for n in 2 3; do python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-kernel-events --no-sweep --no-poseidon --inflight $n 2>/dev/null | tail -1 > "$OUT/${R}_bench_inflight$n.json"; done
+python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-kernel-events --no-sweep --no-poseidon 2>/dev/null | tail -1 > "$OUT/${R}_bench_no_events.json"
+python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-kernel-events --no-sweep --no-poseidon --reuse-preprocessed 2>/dev/null | tail -1 > "$OUT/${R}_bench_reuse_preprocessed.json"
 fi
 ls -la "$OUT"

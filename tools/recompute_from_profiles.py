@@ -77,7 +77,7 @@ def main():
         print(f"   simd_bound (floor of hashing + transforms on the vector units): {cb['simd_bound']['seconds_lower_bound']['total']:.3f} s as run on the granted cores")
 
     if os.path.exists(P("roofline_single_stream_kernel_stats.csv")):
-        print(f"\n== {R}: headline roofline, reproducible (bench.py --steps 20 --warmup 5 --no-sweep --no-poseidon --no-cpu-baseline)")
+        print(f"\n== {R}: headline roofline, reproducible (bench.py --full --steps 20 --warmup 5 --no-sweep --no-poseidon --no-cpu-baseline)")
         for tag in ("single_stream", "two_streams"):
             ev = last_json_line(P(f"roofline_{tag}_events.json")); pr = last_json_line(P(f"roofline_{tag}_under_rocprof.json"))
             st = stats(P(f"roofline_{tag}_kernel_stats.csv"))
