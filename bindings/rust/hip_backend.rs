@@ -363,7 +363,7 @@ impl FriOps for HipBackend {
         check(unsafe { sys::bfhip_fold_circle_into_line(ctx().p(), d.as_ptr(), s.as_ptr(), src.domain.log_size(), a.as_ptr()) });
     }
     fn decompose(_eval: &SecureEvaluation<Self, BitReversedOrder>) -> (SecureEvaluation<Self, BitReversedOrder>, SecureField) {
-        unimplemented!("only reached for column sizes outside the FRI log-size range; the reference's PcsConfig::default() never does")
+        unimplemented!("only reached for column sizes outside the FRI log-size range; no config bfhip_ctx_set_pcs_config accepts reaches it")
     }
 }
 impl GrindOps<Blake2sChannel> for HipBackend {

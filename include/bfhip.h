@@ -109,6 +109,33 @@ int32_t bfhip_ctx_set_mailbox(bfhip_ctx* ctx, int32_t mode, uint32_t timeout_ms,
 int32_t bfhip_ctx_set_conventions(bfhip_ctx* ctx, const bfhip_conventions* conv);
 int32_t bfhip_ctx_get_conventions(bfhip_ctx* ctx, bfhip_conventions* out);
 
+/* PcsConfig of the commitment scheme (stwo's `PcsConfig { pow_bits, fri_config: FriConfig { log_last_layer_degree_bound, log_blowup_factor,
+ * n_queries } }`): what CommitmentSchemeProver::new(config, ..) and CommitmentSchemeVerifier::new(config) take. Conjectured security in bits:
+ * pow_bits + log_blowup_factor x n_queries (the default's 5 + 1 x 3 = 8 bits only shows that the pipeline works).
+ * The proof JSON does not carry the config (the reference's has no field for it either): a verifier must be given the config the proof was
+ * made with, and a proof checked under any other config is rejected.
+ * Accepted values (anything else is rejected with -1 and a message in bfhip_last_error()):
+ *   pow_bits                     <= 32
+ *   log_blowup_factor            1 <= b <= 16 (stwo's FriConfig range); every column domain must stay within the M31 circle: a proof needs
+ *                                log_max_rows + b + 1 <= 30 (the verifier rejects anything larger, the prover's twiddle tree stops at 2^29)
+ *   log_last_layer_degree_bound  0 only
+ *   n_queries                    1 <= q <= 256 (BFHIP_MAX_QUERIES)
+ *   reserved                     all zero
+ * A Poseidon252-channel proof (bfhip_conventions.merkle_channel = 1) with pow_bits > 12 is refused when the proof starts: that channel's nonce
+ * search runs on the host. A context in a shard group keeps the default config (set refuses, and joining refuses a context that has another). */
+enum { BFHIP_MAX_QUERIES = 256, BFHIP_MAX_LOG_BLOWUP = 16, BFHIP_MAX_POW_BITS = 32 };
+typedef struct bfhip_pcs_config {
+    uint32_t pow_bits;                    /* PcsConfig::pow_bits                      default 5 */
+    uint32_t log_blowup_factor;           /* FriConfig::log_blowup_factor             default 1 */
+    uint32_t log_last_layer_degree_bound; /* FriConfig::log_last_layer_degree_bound   default 0 (only 0 supported) */
+    uint32_t n_queries;                   /* FriConfig::n_queries                     default 3 */
+    uint32_t reserved[4];                 /* must be zero */
+} bfhip_pcs_config;
+/* The config of every later proof of this context (pcs == NULL: the defaults). A context proving under log_blowup_factor b needs
+ * max_log_domain >= log_max_rows + b + 1 (bfhip_ctx_create); the proof names the size it needs otherwise. */
+int32_t bfhip_ctx_set_pcs_config(bfhip_ctx* ctx, const bfhip_pcs_config* pcs);
+int32_t bfhip_ctx_get_pcs_config(bfhip_ctx* ctx, bfhip_pcs_config* out);
+
 /* Device buffers (ColumnOps storage: BaseColumn / SecureColumnByCoords live in HBM behind these). */
 int32_t bfhip_malloc(bfhip_ctx* ctx, size_t bytes, void** out_d);
 int32_t bfhip_free(bfhip_ctx* ctx, void* ptr_d);
@@ -219,7 +246,8 @@ void bfhip_free_host(void* p);
 /* What the last COMPLETED proof of this context actually did (0 before the first): bit 0 = it ran in the mailbox order (forcing mode 1 does not
  * guarantee it: one proof per GPU holds that order at a time, see bfhip_ctx_set_sync_policy), bit 1 = it took the context's kept preprocessed tree
  * (bfhip_ctx_reuse_preprocessed), bit 2 = it took a pool's shared preprocessed tree (bfhip_pool_set_preprocessed), bit 3 = shard group: the transforms were replicated
- * (bfhip_ctx_set_shard_policy). Tests and tools read it so that
+ * (bfhip_ctx_set_shard_policy), bit 4 = the decommitment's gather request table outgrew a quarter of the staging ring and was split over
+ * several launches (many queries at a large LOG_MAX_ROWS). Tests and tools read it so that
  * a setting that silently did not apply is visible. */
 int32_t bfhip_ctx_last_proof_flags(bfhip_ctx* ctx, uint32_t* flags);
 /* ---- one proof over several GPUs (shard group) ------------------------------------------------------------------------------------------
@@ -317,7 +345,8 @@ int32_t bfhip_prove_trace(bfhip_ctx* ctx, const bfhip_trace* trace, uint32_t log
  * The sub-contexts share the twiddle tree and point tables of the first one, and — by default — ONE preprocessed commitment per batch:
  *   bfhip_pool_set_preprocessed(pool, mode): 0 = every proof recommits IsFirst(LOG_MAX_ROWS..=4) as the reference does in every prove_brainfuck
  *   call (mod.rs:495-500); 1 (default) = once per batch, committed by a builder context beside the first proofs' main-trace phase; 2 = kept
- *   across batches while LOG_MAX_ROWS and the hasher stay the same. Byte-neutral: the tree depends on LOG_MAX_ROWS and the hasher only.
+ *   across batches while LOG_MAX_ROWS, the hasher and log_blowup_factor stay the same. Byte-neutral: the tree depends on LOG_MAX_ROWS, the hasher
+ *   and log_blowup_factor only.
  * Traces of a batch must be resident on the pool's device: create them with bfhip_trace_create*(bfhip_pool_ctx(pool, i), ...) — any i — between
  * batches (a sub-context must not be used by the caller while a batch runs). n_in_flight in [1, 16]; 2-3 is where the gain saturates. */
 typedef struct bfhip_pool bfhip_pool;
@@ -329,6 +358,8 @@ int32_t bfhip_pool_ctx(bfhip_pool* pool, uint32_t i, bfhip_ctx** out);
 /* bfhip_ctx_set_conventions on every sub-context and on the builder of the shared preprocessed tree (conv == NULL: the defaults). */
 int32_t bfhip_pool_set_conventions(bfhip_pool* pool, const bfhip_conventions* conv);
 int32_t bfhip_pool_set_preprocessed(bfhip_pool* pool, int32_t mode);
+/* bfhip_ctx_set_pcs_config on every sub-context and on the builder of the shared preprocessed tree (pcs == NULL: the defaults). */
+int32_t bfhip_pool_set_pcs_config(bfhip_pool* pool, const bfhip_pcs_config* pcs);
 /* n x bfhip_prove_trace. Outputs are arrays of n entries, each optional (NULL): proofs_json[i] (malloc'd, bfhip_free_host; NULL when proof i failed),
  * proof_lens[i], statuses[i] (0 = ok, < 0 = that proof's error). seconds (optional) has n + 1 entries: each proof's own wall time from its start on
  * its worker, then the wall time of the whole batch. Returns 0 when every proof succeeded, -1 otherwise (bfhip_last_error: the first failed
@@ -346,6 +377,10 @@ int32_t bfhip_prove_batch_brainfuck(bfhip_pool* pool, const char* const* codes, 
 int32_t bfhip_verify_brainfuck(const char* proof_json, size_t proof_len, uint32_t log_max_rows, char* err, size_t err_cap);
 /* The same under explicit conventions (NULL = defaults): a proof verifies only under the conventions it was produced with. */
 int32_t bfhip_verify_brainfuck_conv(const char* proof_json, size_t proof_len, uint32_t log_max_rows, const bfhip_conventions* conv, char* err, size_t err_cap);
+/* The same under an explicit PcsConfig as well (pcs == NULL: PcsConfig::default()): a proof verifies only under the config it was made with.
+ * An invalid config (see bfhip_pcs_config) returns -1. */
+int32_t bfhip_verify_brainfuck_pcs(const char* proof_json, size_t proof_len, uint32_t log_max_rows, const bfhip_conventions* conv,
+                                   const bfhip_pcs_config* pcs, char* err, size_t err_cap);
 
 /* Host-only pieces of the drop-in (usable without a GPU): the Brainfuck compiler (crates/brainfuck_vm/src/compiler.rs:17-37), the VM
  * (crates/brainfuck_vm/src/machine.rs:141-238; trace rows are 7 u32: clk, ip, ci, ni, mp, mv, mvi) and the 13 table builders

@@ -93,6 +93,41 @@ def set_default_conventions(merkle_node_hash=0, mix_u64=0, logup_mask_order=0, m
             c.set_conventions(*_default_conventions)
 
 
+class PcsConfig(ctypes.Structure):
+    """include/bfhip.h `bfhip_pcs_config`: stwo's PcsConfig (pow_bits, FriConfig { log_last_layer_degree_bound, log_blowup_factor, n_queries }).
+    PcsConfig() = PcsConfig::default() = pow_bits 5, log_blowup_factor 1, log_last_layer_degree_bound 0, n_queries 3. The proof JSON does not
+    carry it: verify a proof under the config it was made with."""
+    _fields_ = [("pow_bits", ctypes.c_uint32), ("log_blowup_factor", ctypes.c_uint32), ("log_last_layer_degree_bound", ctypes.c_uint32),
+                ("n_queries", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 4)]
+
+    def __init__(self, pow_bits=5, log_blowup_factor=1, n_queries=3, log_last_layer_degree_bound=0):
+        super().__init__(pow_bits, log_blowup_factor, log_last_layer_degree_bound, n_queries)
+
+    def security_bits(self):
+        return security_bits(self)
+
+    def as_dict(self):
+        return {"pow_bits": self.pow_bits, "log_blowup_factor": self.log_blowup_factor, "log_last_layer_degree_bound": self.log_last_layer_degree_bound,
+                "n_queries": self.n_queries}
+
+    def __eq__(self, other):
+        return isinstance(other, PcsConfig) and self.as_dict() == other.as_dict() and list(self.reserved) == list(other.reserved)
+
+    def __repr__(self):
+        return "PcsConfig(pow_bits=%d, log_blowup_factor=%d, n_queries=%d, log_last_layer_degree_bound=%d)" % (
+            self.pow_bits, self.log_blowup_factor, self.n_queries, self.log_last_layer_degree_bound)
+
+
+def security_bits(pcs_config=None):
+    """stwo's conjectured security of a PcsConfig: pow_bits + log_blowup_factor x n_queries (the default: 5 + 1 x 3 = 8)."""
+    c = PcsConfig() if pcs_config is None else pcs_config
+    return c.pow_bits + c.log_blowup_factor * c.n_queries
+
+
+def _pcs_ref(pcs_config):
+    return None if pcs_config is None else ctypes.byref(pcs_config)
+
+
 CHANNEL_BLAKE2S, CHANNEL_POSEIDON252 = 0, 1
 MERKLE_STWO_COMPRESS, MERKLE_RFC7693 = 0, 1
 MIX_U64_COMPRESS, MIX_U64_HASH = 0, 1
@@ -133,6 +168,16 @@ class Context:
         _check(lib().bfhip_ctx_get_conventions(self._h, ctypes.byref(cv)))
         return cv.merkle_node_hash, cv.mix_u64, cv.logup_mask_order, cv.merkle_channel
 
+    def set_pcs_config(self, pcs_config=None):
+        """bfhip_ctx_set_pcs_config: the PcsConfig of every later proof of this context (None = the default). Needs
+        max_log_domain >= log_max_rows + log_blowup_factor + 1."""
+        _check(lib().bfhip_ctx_set_pcs_config(self._h, _pcs_ref(pcs_config)))
+
+    def pcs_config(self):
+        out = PcsConfig()
+        _check(lib().bfhip_ctx_get_pcs_config(self._h, ctypes.byref(out)))
+        return out
+
     def set_overlap(self, mask=1):
         """bit 0: tree commitment (Merkle beside the transforms of the smaller columns), bit 1: quotients / FRI first-layer tree, bit 2 (shard
         groups): the send-receive of a tree's largest size class on the partner stream beside the transforms of the smaller columns."""
@@ -148,10 +193,12 @@ class Context:
         _check(lib().bfhip_ctx_set_mailbox(self._h, int(mode), int(timeout_ms), int(test_delay_ms)))
 
     def last_proof_flags(self):
-        """bfhip_ctx_last_proof_flags: {mailbox_order, kept_preprocessed, shared_preprocessed} of the last completed proof."""
+        """bfhip_ctx_last_proof_flags: {mailbox_order, kept_preprocessed, shared_preprocessed, replicated_transforms, split_gather} of the last
+        completed proof."""
         f = ctypes.c_uint32()
         _check(lib().bfhip_ctx_last_proof_flags(self._h, ctypes.byref(f)))
-        return {"mailbox_order": bool(f.value & 1), "kept_preprocessed": bool(f.value & 2), "shared_preprocessed": bool(f.value & 4), "replicated_transforms": bool(f.value & 8)}
+        return {"mailbox_order": bool(f.value & 1), "kept_preprocessed": bool(f.value & 2), "shared_preprocessed": bool(f.value & 4), "replicated_transforms": bool(f.value & 8),
+                "split_gather": bool(f.value & 16)}
 
     def clock_probe(self, seconds=0.6):
         """bfhip_clock_probe: {ghz (median over workgroups), ghz_min, ghz_max, G_compressions_per_s, launches, ms_per_launch} of a register-only
@@ -398,6 +445,10 @@ class Pool:
     def set_preprocessed(self, mode):
         _check(lib().bfhip_pool_set_preprocessed(self._h, int(mode)))
 
+    def set_pcs_config(self, pcs_config=None):
+        """bfhip_pool_set_pcs_config: the PcsConfig of every sub-context and of the shared preprocessed tree's builder (None = the default)."""
+        _check(lib().bfhip_pool_set_pcs_config(self._h, _pcs_ref(pcs_config)))
+
     def _outputs(self, n, want_json):
         js = (ctypes.c_void_p * n)() if want_json else None
         return js, (ctypes.c_size_t * n)(), (ctypes.c_int32 * n)(), (ctypes.c_double * (n + 1))()
@@ -441,12 +492,17 @@ class Pool:
 PHASES = ("preprocessed", "tables_host", "main_trace", "interaction", "composition", "oods", "quotients", "fri", "decommit", "total")
 
 
-def prove_brainfuck(code, input_bytes=b"", ctx=None, log_max_rows=24, with_transcript=False, with_timings=False):
-    """prove_brainfuck (mod.rs:471): returns the proof as serde_json bytes of BrainfuckProof. GPU only."""
+def prove_brainfuck(code, input_bytes=b"", ctx=None, log_max_rows=24, with_transcript=False, with_timings=False, pcs_config=None):
+    """prove_brainfuck (mod.rs:471): returns the proof as serde_json bytes of BrainfuckProof. GPU only.
+    pcs_config: a PcsConfig for this proof (None: the context's own, PcsConfig::default() for a new context). A context passed in keeps it
+    afterwards."""
     own = ctx is None
     if own:
-        ctx = Context(0, max_log_domain=log_max_rows + 2)
+        blowup = 1 if pcs_config is None else pcs_config.log_blowup_factor
+        ctx = Context(0, max_log_domain=log_max_rows + blowup + 1)
     try:
+        if pcs_config is not None:
+            ctx.set_pcs_config(pcs_config)
         js, n, tr = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_void_p()
         times = (ctypes.c_double * 10)()
         _check(lib().bfhip_prove_brainfuck(ctx._h, code.encode(), input_bytes, ctypes.c_size_t(len(input_bytes)), log_max_rows,
@@ -466,12 +522,14 @@ def prove_brainfuck(code, input_bytes=b"", ctx=None, log_max_rows=24, with_trans
             ctx.close()
 
 
-def verify_brainfuck(proof_json: bytes, log_max_rows=24, conventions=None):
+def verify_brainfuck(proof_json: bytes, log_max_rows=24, conventions=None, pcs_config=None):
     """verify_brainfuck (mod.rs:738): returns (ok, reason). Host only — no GPU needed, like the reference's verifier.
-    conventions: (merkle_node_hash, mix_u64, logup_mask_order) the proof was produced under; None = the defaults."""
+    conventions: (merkle_node_hash, mix_u64, logup_mask_order) the proof was produced under; None = the defaults.
+    pcs_config: the PcsConfig the proof was made with; None = PcsConfig::default(). An invalid config raises BfhipError."""
     err = ctypes.create_string_buffer(512)
     cv = ctypes.byref(Conventions(*(_default_conventions if conventions is None else conventions)))
-    rc = lib().bfhip_verify_brainfuck_conv(proof_json, ctypes.c_size_t(len(proof_json)), log_max_rows, cv, err, ctypes.c_size_t(512))
+    rc = lib().bfhip_verify_brainfuck_pcs(proof_json, ctypes.c_size_t(len(proof_json)), log_max_rows, cv, _pcs_ref(pcs_config), err,
+                                          ctypes.c_size_t(512))
     if rc < 0:
         raise BfhipError(lib().bfhip_last_error().decode())
     return rc == 0, err.value.decode()

@@ -116,6 +116,21 @@ void Ctx::destroy() {
 
 }  // namespace bf
 
+// include/bfhip.h `bfhip_pcs_config`: the accepted ranges (the same for a context and for the verifier).
+PcsConfig pcs_config_from(const bfhip_pcs_config* p) {
+    PcsConfig cfg;
+    if (!p) return cfg;
+    for (uint32_t r : p->reserved) if (r) throw HipError("bfhip_pcs_config: reserved fields must be zero");
+    if (p->log_blowup_factor < 1 || p->log_blowup_factor > BFHIP_MAX_LOG_BLOWUP)
+        throw HipError("bfhip_pcs_config: log_blowup_factor must be in [1, 16], got " + std::to_string(p->log_blowup_factor));
+    if (p->n_queries < 1 || p->n_queries > BFHIP_MAX_QUERIES) throw HipError("bfhip_pcs_config: n_queries must be in [1, 256], got " + std::to_string(p->n_queries));
+    if (p->pow_bits > BFHIP_MAX_POW_BITS) throw HipError("bfhip_pcs_config: pow_bits must be at most 32, got " + std::to_string(p->pow_bits));
+    if (p->log_last_layer_degree_bound != 0)
+        throw HipError("bfhip_pcs_config: only log_last_layer_degree_bound 0 is supported, got " + std::to_string(p->log_last_layer_degree_bound));
+    cfg.pow_bits = p->pow_bits; cfg.log_blowup = p->log_blowup_factor; cfg.log_last_layer_degree_bound = 0; cfg.n_queries = p->n_queries;
+    return cfg;
+}
+
 extern "C" {
 
 const char* bfhip_last_error(void) { return g_err.c_str(); }
@@ -263,13 +278,15 @@ static void join_group(bfhip_ctx* ctx, std::unique_ptr<Comm> comm) {
     ShardGroup g; g.rank = comm->rank; g.count = count; g.log_count = lc; g.comm = std::shared_ptr<Comm>(std::move(comm));
     ctx->c.shard = g;
 }
-static void check_group_size(uint32_t rank, uint32_t count) {
+// checked before the rendezvous: prev_row_copy and the row exchanges of a shard group assume blowup 1, and every rank must prove under one config
+static void check_group_size(const bfhip_ctx* ctx, uint32_t rank, uint32_t count) {
+    if (ctx && !ctx->c.pcs.is_default()) throw HipError("a context with a non-default PcsConfig cannot join a shard group (bfhip_ctx_set_pcs_config(ctx, NULL) first)");
     if (count < 2 || (count & (count - 1)) != 0 || count > 64) throw HipError("shard count must be a power of two in [2, 64]");
     if (rank >= count) throw HipError("shard rank out of range");
 }
 int32_t bfhip_local_group_create(uint32_t count, bfhip_local_group** out) {
     API_TRY
-    check_group_size(0, count);
+    check_group_size(nullptr, 0, count);
     *out = new bfhip_local_group{local_group_create(count), count};
     return 0;
     API_CATCH
@@ -278,7 +295,7 @@ int32_t bfhip_local_group_destroy(bfhip_local_group* g) { delete g; return 0; } 
 int32_t bfhip_ctx_join_local_group(bfhip_ctx* ctx, bfhip_local_group* group, uint32_t rank) {
     API_CTX(ctx)
     if (!group) throw HipError("null group");
-    check_group_size(rank, group->count);
+    check_group_size(ctx, rank, group->count);
     ctx->c.ensure_aux();                  // a group's exchange may run on the partner stream (Ctx::exchange_overlapped)
     join_group(ctx, local_comm_join(group->g, rank));
     return 0;
@@ -287,7 +304,7 @@ int32_t bfhip_ctx_join_local_group(bfhip_ctx* ctx, bfhip_local_group* group, uin
 int32_t bfhip_rccl_unique_id(uint8_t id[128]) { API_TRY rccl_unique_id(id); return 0; API_CATCH }
 int32_t bfhip_ctx_join_rccl_group(bfhip_ctx* ctx, const uint8_t id[128], uint32_t rank, uint32_t count) {
     API_CTX(ctx)
-    check_group_size(rank, count);
+    check_group_size(ctx, rank, count);
     ctx->c.ensure_aux();
     join_group(ctx, rccl_comm_join(id, rank, count));
     return 0;
@@ -331,7 +348,7 @@ int32_t bfhip_rccl_exchange_raw(const uint8_t id[128], uint32_t rank, uint32_t c
                                 uint32_t n_recvs, const uint32_t* recv_peer, void* const* recv_ptr, const size_t* recv_bytes, uint64_t stats_out[4]) {
     API_TRY
     if (!id || (n_sends && (!send_peer || !send_ptr || !send_bytes)) || (n_recvs && (!recv_peer || !recv_ptr || !recv_bytes))) throw HipError("null argument");
-    check_group_size(rank, count);
+    check_group_size(nullptr, rank, count);
     std::unique_ptr<Comm> comm = rccl_comm_join(id, rank, count);
     std::vector<Xfer> sends, recvs;
     for (u32 i = 0; i < n_sends; i++) sends.push_back({send_peer[i], send_ptr[i], send_bytes[i]});
@@ -396,6 +413,26 @@ int32_t bfhip_ctx_set_conventions(bfhip_ctx* ctx, const bfhip_conventions* conv)
     // a kept preprocessed tree is keyed on the hasher it was built with (prover.hip: PreprocessedCache::matches) and dropped here as well
     if (cv.merkle_node_hash != ctx->c.conv.merkle_node_hash || cv.merkle_channel != ctx->c.conv.merkle_channel) preprocessed_cache_invalidate(&ctx->c);
     ctx->c.conv = cv;
+    return 0;
+    API_CATCH
+}
+int32_t bfhip_ctx_set_pcs_config(bfhip_ctx* ctx, const bfhip_pcs_config* pcs) {
+    API_CTX(ctx)
+    PcsConfig cfg = pcs_config_from(pcs);
+    if (ctx->c.shard.count > 1 && !cfg.is_default()) throw HipError("bfhip_ctx_set_pcs_config: a context in a shard group keeps the default config");
+    ctx->c.sync();
+    // a kept preprocessed tree is keyed on the blowup it was built with (prover.hip: PreprocessedCache::matches)
+    ctx->c.pcs = cfg;
+    return 0;
+    API_CATCH
+}
+int32_t bfhip_ctx_get_pcs_config(bfhip_ctx* ctx, bfhip_pcs_config* out) {
+    API_CTX(ctx)
+    if (!out) throw HipError("null argument");
+    bfhip_pcs_config r{};
+    r.pow_bits = ctx->c.pcs.pow_bits; r.log_blowup_factor = ctx->c.pcs.log_blowup; r.log_last_layer_degree_bound = ctx->c.pcs.log_last_layer_degree_bound;
+    r.n_queries = ctx->c.pcs.n_queries;
+    *out = r;
     return 0;
     API_CATCH
 }

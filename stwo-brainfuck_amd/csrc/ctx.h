@@ -48,6 +48,7 @@ struct ShardGroup {
 struct Ctx {
     int device = 0;
     Conventions conv;               // byte-level stwo conventions (bfhip_ctx_set_conventions)
+    PcsConfig pcs;                  // commitment-scheme config of the next proofs (bfhip_ctx_set_pcs_config)
     bool tables_on_gpu = true;      // where the 13 component tables are built (bfhip_ctx_set_table_builder)
     ShardGroup shard;
     int shard_policy = -1;          // bfhip_ctx_set_shard_policy: -1 automatic, 0 exchange columns -> rows (column-sharded transforms), 1 replicate the transforms
@@ -310,3 +311,6 @@ struct StageBatch {
 
 struct bfhip_ctx { bf::Ctx c; };
 void bfhip_set_error(const std::string& s);
+// api.hip: a bfhip_pcs_config checked against the accepted ranges (throws with the reason); NULL = the defaults.
+struct bfhip_pcs_config;
+bf::PcsConfig pcs_config_from(const bfhip_pcs_config* p);

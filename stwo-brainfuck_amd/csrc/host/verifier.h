@@ -138,7 +138,7 @@ inline BrainfuckProof proof_from_json(const char* s, size_t len, bool felt = fal
 }
 
 // ---- verifier ----------------------------------------------------------------------------------------------------------------------------
-struct VerifierConfig { u32 pow_bits = 5, log_blowup = 1, log_last_layer_degree_bound = 0, n_queries = 3; };   // PcsConfig::default() (mod.rs:743)
+using VerifierConfig = PcsConfig;   // the proof's PcsConfig: the JSON does not carry it, the caller supplies it (default: mod.rs:743)
 
 // MerkleVerifier::verify — "" on success, else the error name
 inline std::string merkle_verify(const Hash32& root, const std::vector<u32>& column_log_sizes, const std::map<u32, std::vector<size_t>>& queries_per_log,
@@ -278,6 +278,8 @@ inline std::string verify_brainfuck(const BrainfuckProof& bp, u32 log_max_rows, 
             comp_log = std::max(comp_log, bp.log_sizes[k] + 1);
         }
         col_logs[3].assign(4, comp_log + cfg.log_blowup);
+        // CanonicCoset(n) is a coset of the order-2^(n+1) subgroup of the M31 circle (order 2^31): n <= 30 for every column domain
+        if (comp_log + cfg.log_blowup > 30 || log_max_rows + cfg.log_blowup > 30) return "InvalidStructure: evaluation domain beyond the M31 circle";
         ch.mix_root(pf.commitments[0]);
         for (int k = 0; k < N_COMPONENTS; k++) ch.mix_u64(bp.log_sizes[k]);
         ch.mix_root(pf.commitments[1]);

@@ -31,6 +31,12 @@ struct Conventions {
     u32 merkle_channel = 0;     // 0 BFHIP_CHANNEL_BLAKE2S: Blake2sMerkleChannel (the reference, mod.rs:56,486-487); 1 BFHIP_CHANNEL_POSEIDON252
 };
 
+// PcsConfig of the commitment scheme (include/bfhip.h `bfhip_pcs_config`; bfhip_ctx_set_pcs_config). Defaults = PcsConfig::default() (mod.rs:479,743).
+struct PcsConfig {
+    u32 pow_bits = 5, log_blowup = 1, log_last_layer_degree_bound = 0, n_queries = 3;
+    bool is_default() const { return pow_bits == 5 && log_blowup == 1 && log_last_layer_degree_bound == 0 && n_queries == 3; }
+};
+
 BF_HD u32 m_add(u32 a, u32 b) { u32 s = a + b; u32 t = s - P31; return t < s ? t : s; }           // min(s, s-P) with wraparound
 BF_HD u32 m_sub(u32 a, u32 b) { u32 s = a - b; u32 t = s + P31; return t < s ? t : s; }           // a-b or a-b+P
 // Lazy reduction for dot products: a product of canonical values is < 2^62, so three products fit on top of a folded accumulator

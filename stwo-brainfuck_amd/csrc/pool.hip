@@ -92,6 +92,7 @@ struct bfhip_pool {
         const SharedPreprocessed* use = nullptr;
         if (pre_mode != 0 && j.n > 0) {
             builder->c.conv = subs[0]->c.conv;          // a worker whose conventions were changed individually does not match and commits its own
+            builder->c.pcs = subs[0]->c.pcs;
             if (pre_mode == 1 || !shared_preprocessed_matches(shared, builder->c, j.log_max_rows)) shared_preprocessed_build(shared, builder->c, j.log_max_rows);
             use = shared;
         }
@@ -162,6 +163,16 @@ int32_t bfhip_pool_set_conventions(bfhip_pool* pool, const bfhip_conventions* co
     std::lock_guard<std::mutex> call(pool->call_mu);
     for (auto* s : pool->subs) if (bfhip_ctx_set_conventions(s, conv) != 0) return -1;
     if (bfhip_ctx_set_conventions(pool->builder, conv) != 0) return -1;
+    shared_preprocessed_invalidate(pool->shared);
+    return 0;
+    POOL_CATCH
+}
+
+int32_t bfhip_pool_set_pcs_config(bfhip_pool* pool, const bfhip_pcs_config* pcs) {
+    POOL_TRY
+    std::lock_guard<std::mutex> call(pool->call_mu);
+    for (auto* s : pool->subs) if (bfhip_ctx_set_pcs_config(s, pcs) != 0) return -1;
+    if (bfhip_ctx_set_pcs_config(pool->builder, pcs) != 0) return -1;
     shared_preprocessed_invalidate(pool->shared);
     return 0;
     POOL_CATCH

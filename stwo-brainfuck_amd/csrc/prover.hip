@@ -23,8 +23,6 @@ namespace bf {
 void build_tables_device(Ctx& c, const std::vector<u32> trace7_soa[7], u32 n, const std::vector<u32>& code, const std::function<u32*(size_t)>& alloc,
                          std::vector<std::vector<u32*>>& cols_out, u32 log_sizes_out[13]);
 
-struct PcsConfig { u32 pow_bits = 5, log_blowup = 1, log_last_layer_degree_bound = 0, n_queries = 3; };  // PcsConfig::default() (mod.rs:479)
-
 static constexpr u32 OWNER_ALL = 0xFFFFFFFFu;   // a polynomial every rank of a shard group holds and transforms itself
 
 struct DCol {
@@ -64,7 +62,6 @@ struct Gather {
         std::vector<u32> out(n_words);
         if (reqs.empty()) return out;
         c.stage_checkpoint();
-        if (reqs.size() * sizeof(GatherReq) > c.stage_bytes / 4) throw HipError("decommitment: too many gather requests");
         if (c.shard.count == 1 && n_words * sizeof(u32) <= c.h_small_bytes - 4096) {
             // One process per proof: the kernel reads the request list where the host wrote it (the pinned side of the staging ring) and
             // writes the words into the pinned bounce buffer — two copy commands and their barriers less on the last round trip of a proof.
@@ -79,9 +76,17 @@ struct Gather {
             memcpy(out.data(), c.h_small + 4096, n_words * sizeof(u32));
             return out;
         }
-        GatherReq* d = c.stage(reqs.data(), reqs.size());
         u32* dout = c.alloc_u32(n_words);
-        gather_u32(c.stream, d, (u32)reqs.size(), dout);
+        // one launch unless the request table outgrows a quarter of the staging ring (many queries at a large LOG_MAX_ROWS): then one launch
+        // per quarter, the ring recycled in between
+        const size_t per_launch = c.stage_bytes / 4 / sizeof(GatherReq);
+        if (reqs.size() > per_launch) c.last_proof_flags |= 16u;      // bfhip_ctx_last_proof_flags bit 4
+        for (size_t i = 0; i < reqs.size(); i += per_launch) {
+            const size_t n = std::min(per_launch, reqs.size() - i);
+            if (i) c.stage_checkpoint();
+            GatherReq* d = c.stage(reqs.data() + i, n);
+            gather_u32(c.stream, d, (u32)n, dout);
+        }
         // shard group: every word is either identical on all ranks (replicated columns, complete layers) or held by one rank and zero
         // elsewhere (rows of sharded columns, hashes of share-wise layers) — an element-wise maximum completes it everywhere
         if (c.shard.count > 1) c.shard.comm->all_reduce_max_u32(c.stream, dout, n_words);
@@ -103,13 +108,14 @@ struct TraceInput {
 // Optional, off by default: the preprocessed tree (IsFirst columns) depends only on LOG_MAX_ROWS, so a deployment that proves many
 // programs can commit it once per context and reuse polynomials, LDE columns and Merkle layers. The reference recomputes it in every
 // prove_brainfuck call (mod.rs:495-500); bench.py's headline number does the same (reuse only with --reuse-preprocessed).
-// The kept tree is only valid for the configuration it was built under: LOG_MAX_ROWS, the node-hash convention and the shard group
+// The kept tree is only valid for the configuration it was built under: LOG_MAX_ROWS, the node-hash convention, the blowup and the shard group
 // (share-wise layers hold one rank's share only) — any change rebuilds it.
 struct PreprocessedCache {
-    bool enabled = false, valid = false, replicate = false; u32 lmr = 0, node_conv = 0, channel = 0, shard_rank = 0, shard_count = 1; DTree tree; Arena keep;
+    bool enabled = false, valid = false, replicate = false; u32 lmr = 0, node_conv = 0, channel = 0, log_blowup = 0, shard_rank = 0, shard_count = 1; DTree tree; Arena keep;
     bool matches(const Ctx& c, u32 log_max_rows) const {
-        // the hasher is (merkle_channel, merkle_node_hash): a Blake2s tree must never serve a Poseidon252 proof or the reverse
-        return enabled && valid && lmr == log_max_rows && node_conv == c.conv.merkle_node_hash && channel == c.conv.merkle_channel &&
+        // the hasher is (merkle_channel, merkle_node_hash): a Blake2s tree must never serve a Poseidon252 proof or the reverse; the IsFirst LDE
+        // lives on a domain of log_size + log_blowup_factor
+        return enabled && valid && lmr == log_max_rows && node_conv == c.conv.merkle_node_hash && channel == c.conv.merkle_channel && log_blowup == c.pcs.log_blowup &&
                shard_rank == c.shard.rank && shard_count == c.shard.count && replicate == (c.shard.count > 1 && c.shard_replicate);
     }
 };
@@ -126,17 +132,18 @@ void preprocessed_cache_invalidate(Ctx* c) {
 }
 
 // A pool's shared preprocessed tree (include/bfhip.h: bfhip_pool_*; pool.hip): committed ONCE per batch (or once per pool) by the pool's
-// builder context and read by every proof of the batch instead of being recommitted by each — byte-neutral, the tree depends on LOG_MAX_ROWS
-// and the hasher only. The builder enqueues the commitment and records `ready` behind it BEFORE the workers are woken; a proof copies the
+// builder context and read by every proof of the batch instead of being recommitted by each — byte-neutral, the tree depends on LOG_MAX_ROWS,
+// the hasher and the blowup only. The builder enqueues the commitment and records `ready` behind it BEFORE the workers are woken; a proof copies the
 // layout at its start and waits (host side) for `ready` where it would have joined its own side stream, so the commitment runs beside the
 // batch's first main-trace phases like a proof's own would.
 struct SharedPreprocessed {
-    bool valid = false; u32 lmr = 0, node_conv = 0, channel = 0;
+    bool valid = false; u32 lmr = 0, node_conv = 0, channel = 0, log_blowup = 0;
     DTree tree;                         // storage: the builder context's arena (not reset while a batch can read it)
     hipEvent_t ready = nullptr;         // recorded on the builder's stream behind the tree (and the root's copy into pinned memory)
     const Hash32* pinned_root = nullptr;
     bool matches(const Ctx& c, u32 log_max_rows) const {
-        return valid && lmr == log_max_rows && node_conv == c.conv.merkle_node_hash && channel == c.conv.merkle_channel && c.shard.count == 1;
+        return valid && lmr == log_max_rows && node_conv == c.conv.merkle_node_hash && channel == c.conv.merkle_channel && log_blowup == c.pcs.log_blowup &&
+               c.shard.count == 1;
     }
 };
 
@@ -151,7 +158,7 @@ struct HipProver {
     std::string transcript;   // "name:hexdigest\n" per stage, for divergence hunting against the oracle
     bool want_transcript = false;
 
-    HipProver(Ctx& ctx, u32 lmr) : c(ctx), log_max_rows(lmr) {}
+    HipProver(Ctx& ctx, u32 lmr) : c(ctx), cfg(ctx.pcs), log_max_rows(lmr) {}
 
     void tap(const char* name) {
         if (!want_transcript) return;
@@ -750,7 +757,7 @@ struct HipProver {
     void build_shared_preprocessed(SharedPreprocessed& sp) {
         if (sharded()) throw HipError("pool: the builder context must not be a member of a shard group");
         if (log_max_rows < LOG_N_LANES) throw HipError("log_max_rows must be at least LOG_N_LANES (4)");
-        if (log_max_rows + cfg.log_blowup + 1 > c.tw_root_log + 1) throw HipError("context twiddle tree too small for log_max_rows");
+        check_config();
         sp.valid = false;
         c.sync();                       // nothing of an earlier batch's build is in flight (its readers are done: the pool's batches are serial)
         c.arena.reset(); c.stage_used = 0; c.use_mailbox = false;
@@ -759,7 +766,18 @@ struct HipProver {
         Hash32* root = reinterpret_cast<Hash32*>(c.h_small);
         build_preprocessed(sp.tree, root);
         BF_HIP(hipEventRecord(sp.ready, c.stream));
-        sp.pinned_root = root; sp.lmr = log_max_rows; sp.node_conv = c.conv.merkle_node_hash; sp.channel = c.conv.merkle_channel; sp.valid = true;
+        sp.pinned_root = root; sp.lmr = log_max_rows; sp.node_conv = c.conv.merkle_node_hash; sp.channel = c.conv.merkle_channel; sp.log_blowup = cfg.log_blowup; sp.valid = true;
+    }
+
+    // What every proof and the pool's preprocessed build check first, before anything is enqueued (the context stays usable).
+    void check_config() const {
+        if (log_max_rows + cfg.log_blowup + 1 > c.tw_root_log + 1)
+            throw HipError("context twiddle tree too small for log_max_rows " + std::to_string(log_max_rows) + " at log_blowup_factor " + std::to_string(cfg.log_blowup) +
+                           ": create the context with max_log_domain >= " + std::to_string(log_max_rows + cfg.log_blowup + 1));
+        if (cfg.log_last_layer_degree_bound != 0) throw HipError("the device prover supports log_last_layer_degree_bound 0 only");
+        if (sharded() && !cfg.is_default()) throw HipError("a shard group proves under the default PcsConfig only");
+        if (c.conv.merkle_channel == 1 && cfg.pow_bits > 12)
+            throw HipError("Poseidon252 channel: pow_bits > 12 is not supported (its nonce search runs on the host), got " + std::to_string(cfg.pow_bits));
     }
 
     BrainfuckProof prove(const TraceInput& in) { return prove([&]() -> const TraceInput& { return in; }); }
@@ -769,6 +787,7 @@ struct HipProver {
     BrainfuckProof prove(const std::function<const TraceInput&()>& get_input) {
         double t_start = now();
         mark_t0 = t_start;
+        check_config();
         struct SpinScope { Ctx& c; double saved; ~SpinScope() { c.spin_seconds = saved; } } spin_scope{c, c.spin_seconds};
         if (!c.sync_blocking) c.spin_seconds = 8e-3;      // bfhip_ctx_set_sync_policy(blocking): hosts with more contexts than cores keep the short poll
         c.arena.reset();
@@ -811,7 +830,6 @@ struct HipProver {
         Mailbox mb_logup(c, 1), mb_constraints(c, 2), mb_samples(c, 3), mb_quot0(c, 4), mb_quot1(c, 5);
         ch = Channel(c.conv);
         if (log_max_rows < LOG_N_LANES) throw HipError("log_max_rows must be at least LOG_N_LANES (4)");
-        if (log_max_rows + cfg.log_blowup + 1 > c.tw_root_log + 1) throw HipError("context twiddle tree too small for log_max_rows");
         std::vector<DTree> trees(4);
         BrainfuckProof bp;
 
@@ -979,7 +997,7 @@ struct HipProver {
         if (!reuse) {
             trees[0].mk.root = *pinned_root0;
             if (cache.enabled) {
-                cache.tree = trees[0]; cache.lmr = log_max_rows; cache.node_conv = c.conv.merkle_node_hash; cache.channel = c.conv.merkle_channel;
+                cache.tree = trees[0]; cache.lmr = log_max_rows; cache.node_conv = c.conv.merkle_node_hash; cache.channel = c.conv.merkle_channel; cache.log_blowup = cfg.log_blowup;
                 cache.shard_rank = c.shard.rank; cache.shard_count = c.shard.count; cache.replicate = replicate(); cache.valid = true;
             }
         }
@@ -1221,7 +1239,7 @@ struct HipProver {
             tm.fri = (now() - t0) - tm.quotients;
         }
 
-        c.last_proof_flags = (mb ? 1u : 0u) | (reuse && !shared ? 2u : 0u) | (shared ? 4u : 0u) | (replicate() ? 8u : 0u);
+        c.last_proof_flags = (c.last_proof_flags & 16u) | (mb ? 1u : 0u) | (reuse && !shared ? 2u : 0u) | (shared ? 4u : 0u) | (replicate() ? 8u : 0u);
         tm.total = now() - t_start;
         mark("done");
         print_marks();
@@ -1238,6 +1256,18 @@ struct HipProver {
     CompositionPlan composition_prepare(std::vector<DTree>& trees, const BrainfuckProof& bp, const size_t* main_off, const size_t* inter_off, const Lookups& el) {
         CompositionPlan cp;
         for (int k = 0; k < N_COMPONENTS; k++) { cp.total += n_constraints(k); cp.max_log = std::max(cp.max_log, bp.log_sizes[k] + 1); }
+        // The constraints are evaluated on CanonicCoset(log + 1) (stwo's component prover). At log_blowup_factor 1 that domain IS the trace LDE
+        // domain and the kernels read the committed evaluations. Above 1 the LDE lives on CanonicCoset(log + b), which does not contain
+        // CanonicCoset(log + 1) (odd powers of another generator): the main, interaction and IsFirst polynomials are evaluated on exactly that
+        // coset by one extra batch of forward transforms, into arena memory that only the constraint kernels read.
+        const bool own_domain = cfg.log_blowup != 1;
+        std::vector<DCol> cd_src, cd_dst;
+        auto on_constraint_domain = [&](const DCol& poly) {
+            if (poly.sliced()) throw HipError("composition: a row-sharded polynomial on the constraint domain");
+            DCol e; e.log_size = poly.log_size + 1; e.shift = poly.shift; e.ptr = c.alloc_u32(e.stored());
+            cd_src.push_back(poly); cd_dst.push_back(e);
+            return e;
+        };
         cp.acc.resize(cp.max_log + 1); cp.have.assign(cp.max_log + 1, false); cp.launches.resize(N_COMPONENTS);
         for (int k = 0; k < N_COMPONENTS; k++) {
             u32 log = bp.log_sizes[k], eval_log = log + 1;
@@ -1251,10 +1281,18 @@ struct HipProver {
             ConstraintLaunch L{};
             L.overwrite = cp.have[eval_log] ? 0u : 1u;      // the first component of a size writes the accumulator (no zero fill)
             cp.have[eval_log] = true;
-            L.is_first = trees[0].evals[log_max_rows - log].ptr;
-            for (u32 j = 0; j < n_main_cols(k); j++) L.trace[j] = trees[1].evals[main_off[k] + j].desc();
             const u32 ni = 4 * n_logup_cols(k);
-            for (u32 j = 0; j < ni; j++) L.inter[j] = trees[2].evals[inter_off[k] + j].desc();
+            if (!own_domain) {
+                L.is_first = trees[0].evals[log_max_rows - log].ptr;
+                for (u32 j = 0; j < n_main_cols(k); j++) L.trace[j] = trees[1].evals[main_off[k] + j].desc();
+                for (u32 j = 0; j < ni; j++) L.inter[j] = trees[2].evals[inter_off[k] + j].desc();
+            } else {
+                const DCol& isf = trees[0].polys[log_max_rows - log];
+                if (isf.shift != 0 || isf.log_size != log) throw HipError("composition: unexpected IsFirst polynomial layout");
+                L.is_first = on_constraint_domain(isf).ptr;
+                for (u32 j = 0; j < n_main_cols(k); j++) L.trace[j] = on_constraint_domain(trees[1].polys[main_off[k] + j]).desc();
+                for (u32 j = 0; j < ni; j++) L.inter[j] = on_constraint_domain(trees[2].polys[inter_off[k] + j]).desc();
+            }
             for (int w = 0; w < 4; w++) { const DCol& pv = trees[2].prev[inter_off[k] + ni - 4 + w]; L.inter_prev[w] = pv.ptr; }   // nullptr unless row-sharded
             if (sl) { L.row0 = (u32)slice_first(eval_log); L.n_rows = (u32)slice_cells(eval_log); }
             for (int w = 0; w < 4; w++) L.acc[w] = cp.acc[eval_log].c[w];
@@ -1263,6 +1301,7 @@ struct HipProver {
             for (u32 i = 0; i < 2; i++) L.denom_inv[i] = m_inv(coset_vanishing_m(log, canonic_domain_at(eval_log, i)));
             cp.launches[k] = L;
         }
+        if (own_domain) fft_cols(false, cd_src, cd_dst);      // on the stream behind the interaction tree (its polynomials), before the constraints
         return cp;
     }
     // the challenge-side fields of the 13 launches: coefficient powers and claimed sums
@@ -1849,8 +1888,9 @@ struct HipProver {
         }
         // last layer: 2^last_log evaluations -> line polynomial (host; LineEvaluation::interpolate on <= 2 values for the default config)
         {
-            if (last_log != 1 || cfg.log_last_layer_degree_bound != 0) throw HipError("only the default FRI last-layer configuration is supported");
-            std::vector<size_t> pos = {0, 1};
+            if (cfg.log_last_layer_degree_bound != 0) throw HipError("only log_last_layer_degree_bound 0 is supported");
+            std::vector<size_t> pos;
+            for (size_t p = 0; p < (size_t(1) << last_log); p++) pos.push_back(p);
             mark("FRI commit phase enqueued");
             Gather gl;
             for (size_t p : pos) for (int w = 0; w < 4; w++) gl.add(layer.c[w], p, layer.mine(p, c.shard.rank));
@@ -1869,10 +1909,10 @@ struct HipProver {
                 for (size_t li = 0; li < inner.size(); li++) { inner[li].tree.root = pinned_roots[1 + li]; ch.mix_root(inner[li].tree.root); (void)ch.draw_felt(); }
                 if (memcmp(pinned_chan, ch.digest.b, 32) != 0 || pinned_chan[8] != ch.n_sent) throw HipError("FRI: device channel diverged from the host channel");
             }
-            // line_ifft on 2 values over LineDomain(half_odds(1)): c0 = (v0 + v1) / 2, c1 = (v0 - v1) / (2 x0) must vanish
-            u32 inv2 = m_inv(2);
-            Q31 c0 = q_mulm(q_add(v[0], v[1]), inv2);
-            if (!q_eq(v[0], v[1])) throw HipError("invalid degree");
+            // bound 0: the 2^b evaluations are those of a constant line polynomial — all equal, and line_ifft's only nonzero coefficient is
+            // that value (at b = 1: c0 = (v0 + v1) / 2 = v0, c1 = (v0 - v1) / (2 x0) = 0)
+            for (const Q31& x : v) if (!q_eq(x, v[0])) throw HipError("invalid degree");
+            Q31 c0 = v[0];
             pf.fri_proof.last_layer_coeffs = {c0};
             pf.fri_proof.last_layer_log_size = 0;
             ch.mix_felts(&c0, 1);
@@ -1900,8 +1940,11 @@ struct HipProver {
             unsigned long long init = ~0ull;
             unsigned long long* d_best = (unsigned long long*)c.stage(&init, 1);
             unsigned long long best = ~0ull;
-            const u32 span = 1u << 16;
+            // one span per launch and read-back: 2^pow_bits nonces (one expected hit), at least 2^16 and at most 2^22 (~0.12 ms of the grid) —
+            // pow 26 takes ~16 round trips instead of the ~1024 of fixed 2^16-nonce spans
+            const u32 span = 1u << std::min(std::max(cfg.pow_bits, 16u), 22u);
             for (u64 base = 0; best == ~0ull; base += span) {
+                if (base >= (u64(1) << 40)) throw HipError("grind: no nonce found below 2^40");
                 grind_span(c.stream, d_digest, base, span, cfg.pow_bits, d_best, c.conv.mix_u64);
                 c.read_back(&best, d_best, 8);
             }
@@ -2140,19 +2183,25 @@ extern "C" int32_t bfhip_ctx_reuse_preprocessed(bfhip_ctx* ctx, int32_t on) {
 }
 
 // verify_brainfuck (mod.rs:738-797). Host only. 0 = accepted, 1 = rejected (reason in err), -1 = internal error.
-extern "C" int32_t bfhip_verify_brainfuck_conv(const char* proof_json, size_t proof_len, uint32_t log_max_rows, const bfhip_conventions* conv, char* err, size_t err_cap) {
+extern "C" int32_t bfhip_verify_brainfuck_pcs(const char* proof_json, size_t proof_len, uint32_t log_max_rows, const bfhip_conventions* conv,
+                                              const bfhip_pcs_config* pcs, char* err, size_t err_cap) {
     try {
+        PcsConfig cfg;
+        try { cfg = pcs_config_from(pcs); } catch (const std::exception& e) { bfhip_set_error(e.what()); return -1; }
         Conventions cv;
         if (conv) {
             if (conv->merkle_node_hash > 1 || conv->mix_u64 > 1 || conv->logup_mask_order > 1 || conv->merkle_channel > 1) { bfhip_set_error("unknown convention value"); return -1; }
             cv.merkle_node_hash = conv->merkle_node_hash; cv.mix_u64 = conv->mix_u64; cv.logup_mask_order = conv->logup_mask_order; cv.merkle_channel = conv->merkle_channel;
         }
         std::string reason;
-        try { BrainfuckProof bp = proof_from_json(proof_json, proof_len, cv.merkle_channel == 1); reason = verify_brainfuck(bp, log_max_rows, cv); }
+        try { BrainfuckProof bp = proof_from_json(proof_json, proof_len, cv.merkle_channel == 1); reason = verify_brainfuck(bp, log_max_rows, cv, cfg); }
         catch (const std::exception& e) { reason = std::string("InvalidStructure: ") + e.what(); }
         if (err && err_cap) snprintf(err, err_cap, "%s", reason.c_str());
         return reason.empty() ? 0 : 1;
     } catch (...) { bfhip_set_error("unknown error"); return -1; }
+}
+extern "C" int32_t bfhip_verify_brainfuck_conv(const char* proof_json, size_t proof_len, uint32_t log_max_rows, const bfhip_conventions* conv, char* err, size_t err_cap) {
+    return bfhip_verify_brainfuck_pcs(proof_json, proof_len, log_max_rows, conv, nullptr, err, err_cap);
 }
 
 extern "C" int32_t bfhip_verify_brainfuck(const char* proof_json, size_t proof_len, uint32_t log_max_rows, char* err, size_t err_cap) {

@@ -2,8 +2,11 @@
 """prove | verify over the C ABI — the two sub-commands of the reference's bin/brainfuck_prover.rs (prove: :79-139, verify: :141-151):
 
   bfprove.py prove  (--file prog.bf | --code '++>,<[>+.<-]') [--input-file in.bin] [--ram-size N] [--output proof.json]
-                    [--log-max-rows 24] [--conventions a,b,c,d | --poseidon252] [--all-sets DIR]
-  bfprove.py verify proof.json [--log-max-rows 24] [--conventions a,b,c,d | --poseidon252 | --try-all]
+                    [--log-max-rows 24] [--conventions a,b,c,d | --poseidon252] [--all-sets DIR] [PCS options]
+  bfprove.py verify proof.json [--log-max-rows 24] [--conventions a,b,c,d | --poseidon252 | --try-all] [PCS options]
+
+PCS options (stwo's PcsConfig; the defaults are PcsConfig::default()): --pow-bits 5 --log-blowup-factor 1 --n-queries 3. The proof file does
+not record them: verify with the values the proof was made with. prove prints the config and its security bits (pow + blowup x queries).
 
 The proof file is the serde_json form of BrainfuckProof (mod.rs:71-76), as the reference writes it (:129-131) and reads it (:146-151).
 stdin supplies the program input when --input-file is absent (the reference's VM reads stdin).
@@ -52,12 +55,21 @@ def all_sets(channels=(0, 1)):
     return sets
 
 
-def try_all(pkg, proof, log_max_rows):
+def add_pcs_options(p):
+    p.add_argument("--pow-bits", type=int, default=5); p.add_argument("--log-blowup-factor", type=int, default=1)
+    p.add_argument("--n-queries", type=int, default=3)
+
+
+def parse_pcs(pkg, a):
+    return pkg.PcsConfig(pow_bits=a.pow_bits, log_blowup_factor=a.log_blowup_factor, n_queries=a.n_queries)
+
+
+def try_all(pkg, proof, log_max_rows, pcs_config=None):
     """Verifies `proof` under every convention set. Returns (accepting sets, {set: first failing check})."""
     accepted, reasons = [], {}
     for conv in all_sets():
         try:
-            ok, why = pkg.verify_brainfuck(proof, log_max_rows, conventions=conv)
+            ok, why = pkg.verify_brainfuck(proof, log_max_rows, conventions=conv, pcs_config=pcs_config)
         except Exception as e:                      # a proof of the other channel's shape does not even parse
             ok, why = False, f"error: {e}"
         if ok:
@@ -77,8 +89,17 @@ def main():
     v = sub.add_parser("verify")
     v.add_argument("proof"); v.add_argument("--log-max-rows", type=int, default=24); v.add_argument("--poseidon252", action="store_true")
     v.add_argument("--conventions"); v.add_argument("--try-all", action="store_true")
+    add_pcs_options(p); add_pcs_options(v)
     a = ap.parse_args()
     pkg = load_package()
+    try:
+        return run(pkg, a, ap)
+    except pkg.BfhipError as e:
+        print(f"error: {e}", file=sys.stderr)
+        return 2
+
+
+def run(pkg, a, ap):
     if a.cmd == "prove":
         code = open(a.file).read() if a.file else a.code
         if code is None:
@@ -87,7 +108,11 @@ def main():
         sets = all_sets(channels=(0,)) if a.all_sets else [parse_conventions(a)]
         if a.all_sets:
             os.makedirs(a.all_sets, exist_ok=True)
-        ctx = pkg.Context(0, max_log_domain=a.log_max_rows + 2)
+        pcs = parse_pcs(pkg, a)
+        ctx = pkg.Context(0, max_log_domain=a.log_max_rows + pcs.log_blowup_factor + 1)
+        ctx.set_pcs_config(pcs)
+        print(f"PcsConfig: pow_bits={pcs.pow_bits} log_blowup_factor={pcs.log_blowup_factor} n_queries={pcs.n_queries} "
+              f"log_last_layer_degree_bound={pcs.log_last_layer_degree_bound}; security {pkg.security_bits(pcs)} bits", file=sys.stderr)
         t0 = time.time()
         tr = pkg.Trace(ctx, code, inp, ram_size=a.ram_size)
         t_prep = time.time() - t0           # VM run + table build + upload, once, whatever the number of convention sets
@@ -109,7 +134,7 @@ def main():
         return 0
     proof = open(a.proof, "rb").read()
     if a.try_all:
-        accepted, reasons = try_all(pkg, proof, a.log_max_rows)
+        accepted, reasons = try_all(pkg, proof, a.log_max_rows, parse_pcs(pkg, a))
         for conv in accepted:
             print("Proof verified under --conventions %d,%d,%d,%d  (%s)" % (conv + (describe(conv),)))
         if not accepted:
@@ -118,7 +143,7 @@ def main():
                 print("  %d,%d,%d,%d  %s" % (conv + (why,)))
         return 0 if accepted else 1
     conv = parse_conventions(a)
-    ok, why = pkg.verify_brainfuck(proof, a.log_max_rows, conventions=conv)
+    ok, why = pkg.verify_brainfuck(proof, a.log_max_rows, conventions=conv, pcs_config=parse_pcs(pkg, a))
     print("Proof verified" if ok else f"Verification failed: {why}")
     return 0 if ok else 1
 
