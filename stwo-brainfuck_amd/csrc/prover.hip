@@ -147,6 +147,9 @@ struct SharedPreprocessed {
     }
 };
 
+// waits for the context's main, side and partner streams
+static void sync_both(Ctx& c) { c.sync(); if (c.stream2) BF_HIP(hipStreamSynchronize(c.stream2)); for (auto a : c.aux) if (a) BF_HIP(hipStreamSynchronize(a)); }
+
 struct PhaseTimes { double preprocessed = 0, main_trace = 0, interaction = 0, composition = 0, oods = 0, quotients = 0, fri = 0, decommit = 0, tables = 0, total = 0; };
 
 struct HipProver {
@@ -230,6 +233,13 @@ struct HipProver {
     void fft_cols(bool inverse, const std::vector<DCol>& src, const std::vector<DCol>& dst) {
         c.stage_checkpoint();
         fft_launch(fft_prepare(inverse, src, dst));
+    }
+
+    // A phase's parameter blocks, staged by f(), reach the device in ONE copy: made by the kernel of mailbox mbx once the host posts (mailbox
+    // order: the launches that follow wait behind it), or without a mailbox by the staging batch's copy at once.
+    template <class F> void stage_blocks(Mailbox* mbx, F&& f) {
+        if (mbx) { mbx->begin(); f(); mbx->arm(); }
+        else { StageBatch sb(c); f(); sb.end(); }
     }
 
     // ---- Merkle (a4) -----------------------------------------------------------------------------------------------------------
@@ -823,7 +833,7 @@ struct HipProver {
         if (++c.proof_seq == 0) c.proof_seq = 1;
         c.reap_some();
         if (mb && c.stage_used > c.stage_bytes / 4) {
-            c.sync(); if (c.stream2) BF_HIP(hipStreamSynchronize(c.stream2)); for (auto a : c.aux) if (a) BF_HIP(hipStreamSynchronize(a));
+            sync_both(c);
             c.stage_used = 0;
         }
         for (int k = 0; k <= 5; k++) c.mailbox_err_host()[2 * k] = 0;
@@ -919,25 +929,28 @@ struct HipProver {
                 L.wloc = c.arena.alloc(sizeof(uint4) * M);
                 L.totals = c.arena.alloc(sizeof(uint4) * (M / 1024 + 2));
                 L.claimed = d_claimed + k;
-                L.log_rows = log_rows; L.comp = k;       // L.el: drawn after the main-trace root
+                L.log_rows = log_rows; L.comp = k;       // L.el stays empty: the lookup elements, drawn after the main-trace root, go into the batch
                 logups[k] = L;
             }
         };
         uint4* pinned_claimed = reinterpret_cast<uint4*>(c.h_small + 2048);
         Hash32* pinned_root2 = reinterpret_cast<Hash32*>(c.h_small + 2304);
         LogupBatch* h_lb = nullptr;           // the logUp batch in the staging ring (mailbox mode): its `el` is filled in after the draw
-        auto enqueue_interaction = [&]() {
+        // The 13 interaction_trace_evaluation calls (mod.rs:596-687) as one batch: four launches; one process per proof: then the interaction
+        // tree. mbx: the launches wait behind that mailbox, and the staged batch is returned for the host to fill in the lookup elements.
+        auto enqueue_interaction = [&](const Lookups& el, Mailbox* mbx) {
             LogupBatch lb;
-            logup_batch_init(lb, Lookups{}, logups.data(), N_COMPONENTS);
+            logup_batch_init(lb, el, logups.data(), N_COMPONENTS);
             c.stage_checkpoint();
-            mb_logup.begin();
+            if (mbx) mbx->begin();
             const LogupBatch* d_lb = c.stage(&lb, 1);
-            mb_logup.arm();
-            h_lb = mb_logup.host(d_lb);
-            logup_batch_run(c.stream, d_lb, lb);          // the 13 interaction_trace_evaluation calls (mod.rs:596-687) as one batch: four launches
+            if (mbx) mbx->arm();
+            logup_batch_run(c.stream, d_lb, lb);
+            mark("logUp launched");
             BF_HIP(hipGetLastError());
             trees[2].polys = inter_vals;                  // interpolate in place
-            commit_tree_overlapped(trees[2], pinned_root2, &inter_vals, 2);
+            if (!sharded()) commit_tree_overlapped(trees[2], pinned_root2, &inter_vals, mbx ? 2 : -1);
+            return mbx ? mbx->host(d_lb) : nullptr;
         };
         try {
             for (int k = 0; k < N_COMPONENTS; k++) {
@@ -971,7 +984,7 @@ struct HipProver {
             prepare_logup();                 // host work under the main tree's kernels: only the lookup elements are missing afterwards
             if (mb) {
                 // the whole interaction phase goes onto the stream now, behind a mailbox that will deliver the lookup elements
-                enqueue_interaction();
+                h_lb = enqueue_interaction(Lookups{}, &mb_logup);
                 mark("interaction phase enqueued behind its mailbox");
                 c.wait_stamp(1);
             } else c.sync();
@@ -1018,7 +1031,6 @@ struct HipProver {
         { Q31 z, a; ch.draw_two_felts(z, a); el.instruction = make_lookup(z, a); }    // InstructionElements::draw
         { Q31 z, a; ch.draw_two_felts(z, a); el.processor = make_lookup(z, a); }      // ProcessorElements::draw
         mark("lookup elements drawn");
-        for (auto& L : logups) L.el = el;
         auto take_claimed = [&](const uint4* h_claimed) {
             for (int k = 0; k < N_COMPONENTS; k++) bp.claimed_sums[k] = q_make(h_claimed[k].x, h_claimed[k].y, h_claimed[k].z, h_claimed[k].w);
             for (int k = 0; k < N_COMPONENTS; k++) ch.mix_felts(&bp.claimed_sums[k], 1);   // interaction_claim.mix_into (mod.rs:189-203)
@@ -1068,15 +1080,7 @@ struct HipProver {
             mb_constraints.post();
             mark("random coefficient posted");
         } else {
-            {   // the 13 interaction_trace_evaluation calls (mod.rs:596-687) as one batch: four launches
-                LogupBatch lb;
-                logup_batch_init(lb, el, logups.data(), N_COMPONENTS);
-                c.stage_checkpoint();
-                logup_batch_run(c.stream, c.stage(&lb, 1), lb);
-            }
-            mark("logUp launched");
-            BF_HIP(hipGetLastError());
-            trees[2].polys = inter_vals;          // interpolate in place
+            enqueue_interaction(el, nullptr);
             if (sharded()) {
                 uint4 h_claimed[N_COMPONENTS];
                 c.read_back(h_claimed, d_claimed, sizeof(h_claimed));
@@ -1089,7 +1093,6 @@ struct HipProver {
                 // Nothing on the GPU waits for the claimed sums: they travel to their pinned slot behind the logUp kernels, the interaction tree is
                 // enqueued right away, and the host mixes claim and root in protocol order after ONE synchronisation (no idle gap between the logUp
                 // kernels and the transforms).
-                commit_tree_overlapped(trees[2], pinned_root2, &inter_vals);
                 composition_plan = composition_prepare(trees, bp, main_off, inter_off, el);      // host work under the tree's kernels
                 mark("interaction tree enqueued + composition prepared");
                 c.sync();
@@ -1139,7 +1142,7 @@ struct HipProver {
         std::vector<DSecure> quotients;
         if (mb) {
             // the sampling kernels behind their mailbox (the point's factor tables still empty) while the GPU evaluates the constraints
-            SampleRun sr = sample_enqueue(sample_plan, points.size(), &mb_samples);
+            const SampleRun sr = sample_launch(sample_plan, points, &mb_samples);
             c.post_stamp(4);
             mark("sampling enqueued behind its mailbox");
             c.wait_stamp(3);
@@ -1150,16 +1153,16 @@ struct HipProver {
             tm.composition = now() - t0;
             t0 = now();
             draw_oods();
-            sample_fill(sr, points);
+            sample_factors(points, sr.h_factors);
             mb_samples.post();
             mark("out-of-domain point posted");
             // the quotient kernels behind two mailboxes (largest size group; the rest): batch structure from the points, sampled values still empty
-            QuotientRun qr = quotients_enqueue(trees, mask, points, &mb_quot0, &mb_quot1);
+            QuotientRun qr = compute_quotients(trees, mask, points, nullptr, q_one(), nullptr, &mb_quot0, &mb_quot1);
             BF_HIP(hipEventRecord(c.ev[5], c.stream));
             quotients = qr.out;
             mark("quotients enqueued behind their mailboxes");
             c.wait_stamp(4);
-            sample_finish(trees, mask, bp.proof, sr);
+            sample_unpack(trees, mask, sample_results(), sample_plan.n_all, bp.proof);
             mark("sampled values arrived");
             mix_samples();
             tap("sampled");
@@ -1167,7 +1170,7 @@ struct HipProver {
             t0 = now();
             Q31 q_coeff = ch.draw_felt();
             mark("sampled values mixed, quotient coefficient drawn");
-            quotients_fill(qr, mask, points, bp.proof, q_coeff, &mb_quot0, &mb_quot1);
+            quotients_fill(qr, points, bp.proof, q_coeff, &mb_quot0, &mb_quot1);
             mark("quotient constants posted");
         } else {
             if (!sharded()) {
@@ -1192,7 +1195,7 @@ struct HipProver {
             Q31 q_coeff = ch.draw_felt();
             mark("sampled values mixed, quotient coefficient drawn");
             BF_HIP(hipEventRecord(c.ev[4], c.stream));
-            quotients = compute_quotients(trees, mask, points, bp.proof, q_coeff, &q_waits);
+            quotients = compute_quotients(trees, mask, points, &bp.proof, q_coeff, &q_waits).out;
             BF_HIP(hipEventRecord(c.ev[5], c.stream));
             mark("quotients launched");
         }
@@ -1216,12 +1219,10 @@ struct HipProver {
         };
         fri_and_decommit(trees, quotients, bp.proof, q_waits, sanity_check);
         for (int k = 1; k <= 5; k++) if (c.mailbox_err_host()[2 * k]) *c.mailbox_err_host() = c.mailbox_err_host()[2 * k];
-        if (mb) {
-            mark("mailbox 1 waited for the host (GPU clock, 10 ns ticks):"); if (trace_host) host_marks.back().second = host_marks[host_marks.size() - 2].second + c.mailbox_err_host()[3] * 0.01;
-            mark("mailbox 2 waited"); if (trace_host) host_marks.back().second = host_marks[host_marks.size() - 2].second + c.mailbox_err_host()[5] * 0.01;
-            mark("mailbox 3 waited"); if (trace_host) host_marks.back().second = host_marks[host_marks.size() - 2].second + c.mailbox_err_host()[7] * 0.01;
-            mark("mailbox 4 waited"); if (trace_host) host_marks.back().second = host_marks[host_marks.size() - 2].second + c.mailbox_err_host()[9] * 0.01;
-            mark("mailbox 5 waited"); if (trace_host) host_marks.back().second = host_marks[host_marks.size() - 2].second + c.mailbox_err_host()[11] * 0.01;
+        if (mb && trace_host) {
+            // how long each mailbox kernel waited for the host (second word of its error slot, GPU clock in 10 ns ticks), as that far after the previous mark
+            static const char* const waited[5] = {"mailbox 1 waited for the host (GPU clock, 10 ns ticks):", "mailbox 2 waited", "mailbox 3 waited", "mailbox 4 waited", "mailbox 5 waited"};
+            for (int k = 1; k <= 5; k++) host_marks.push_back({waited[k - 1], host_marks.back().second + c.mailbox_err_host()[2 * k + 1] * 0.01});
         }
         if (*c.mailbox_err_host()) throw HipError(mailbox_msg);
         {
@@ -1333,19 +1334,12 @@ struct HipProver {
         {   // the 13 evaluate_constraint_quotients_on_domain calls as ONE launch (air.hip: k_constraints_batch), one staging copy
             ConstraintBatch cb;
             constraint_batch_init(cb, launches.data(), N_COMPONENTS);
-            const ConstraintLaunch* d_launches; const ConstraintBatch* d_cb;
-            if (mbx) {
-                mbx->begin();
+            const ConstraintLaunch* d_launches = nullptr; const ConstraintBatch* d_cb = nullptr;
+            stage_blocks(mbx, [&] {
                 d_launches = c.stage(launches.data(), launches.size());
                 d_cb = c.stage(&cb, 1);
-                mbx->arm();
-                cp.h_staged = mbx->host(d_launches);
-            } else {
-                StageBatch sb(c);
-                d_launches = c.stage(launches.data(), launches.size());
-                d_cb = c.stage(&cb, 1);
-                sb.end();
-            }
+            });
+            if (mbx) cp.h_staged = mbx->host(d_launches);
             eval_constraints_batch(c.stream, d_cb, cb, d_launches);
         }
         BF_HIP(hipGetLastError());
@@ -1447,27 +1441,37 @@ struct HipProver {
             for (u32 b = 1; b < 32; b++) { factors[p * 32 + b] = pk(x); x = q_double_x(x); }
         }
     }
-    // Mailbox mode (one process per proof): the sampling kernels go onto the stream before the point is drawn — jobs staged, factor tables
-    // empty —, sample_fill writes the tables into the ring (the caller posts), sample_finish reads the values from their pinned slot.
-    struct SampleRun { uint4* h_factors = nullptr; u32 n_all = 0; };
-    SampleRun sample_enqueue(const SamplePlan& sp, size_t n_points, Mailbox* mbx) {
-        SampleRun sr; sr.n_all = sp.n_all;
-        if (sp.n_all * sizeof(uint4) > c.h_small_bytes - 4096) throw HipError("sampling: too many samples for the pinned result buffer");
-        std::vector<uint4> factors(n_points * 32, make_uint4(0, 0, 0, 0));
+    // The sampling launches. The values go to the pinned bounce buffer (sample_results), or, in a shard group (completed by a max-reduce) or when
+    // they do not fit it, to d_out in HBM. mbx (mailbox order, one process per proof): the launches go onto the stream before the point is drawn,
+    // behind that mailbox, with the factor tables staged empty — h_factors is where sample_factors writes them before the host posts.
+    struct SampleRun { uint4* h_factors = nullptr; uint4* d_out = nullptr; };
+    SampleRun sample_launch(const SamplePlan& sp, const std::vector<PtQ>& points, Mailbox* mbx) {
+        SampleRun sr;
+        const bool pinned = !sharded() && sp.n_all * sizeof(uint4) <= c.h_small_bytes - 4096;
+        if (mbx && !pinned) throw HipError("sampling: too many samples for the pinned result buffer");
+        std::vector<uint4> factors(points.size() * 32, make_uint4(0, 0, 0, 0));
+        if (!mbx) sample_factors(points, factors.data());
         c.stage_checkpoint();
-        mbx->begin();
-        const uint4* d_factors = c.stage(factors.data(), factors.size());
-        const EvalJob* d_jobs = sp.jobs.empty() ? nullptr : c.stage(sp.jobs.data(), sp.jobs.size());
-        mbx->arm();
-        sr.h_factors = mbx->host(d_factors);
+        const uint4* d_factors = nullptr; const EvalJob* d_jobs = nullptr;
+        stage_blocks(mbx, [&] {
+            d_factors = c.stage(factors.data(), factors.size());     // through the pinned staging ring (no pageable copies)
+            d_jobs = sp.jobs.empty() ? nullptr : c.stage(sp.jobs.data(), sp.jobs.size());
+        });
+        if (mbx) sr.h_factors = mbx->host(d_factors);
         void* d_partials = c.arena.alloc(size_t(sp.partial_off ? sp.partial_off : 1) * sizeof(uint4));
-        eval_at_points(c.stream, d_jobs, (u32)sp.jobs.size(), sp.partial_off, d_factors, d_partials, c.d_small_alias + 4096);
+        if (!pinned) {
+            sr.d_out = (uint4*)c.arena.alloc(sp.n_all * sizeof(uint4));
+            if (sharded()) BF_HIP(hipMemsetAsync(sr.d_out, 0, sp.n_all * sizeof(uint4), c.stream));
+        }
+        // pinned: the second stage writes the samples into the bounce buffer itself
+        eval_at_points(c.stream, d_jobs, (u32)sp.jobs.size(), sp.partial_off, d_factors, d_partials, pinned ? (void*)(c.d_small_alias + 4096) : sr.d_out);
         BF_HIP(hipGetLastError());
+        if (sharded()) c.shard.comm->all_reduce_max_u32(c.stream, reinterpret_cast<u32*>(sr.d_out), size_t(sp.n_all) * 4);
         return sr;
     }
-    void sample_fill(const SampleRun& sr, const std::vector<PtQ>& points) { sample_factors(points, sr.h_factors); }
-    void sample_finish(const std::vector<DTree>& trees, const std::vector<std::vector<std::vector<u32>>>& mask, StarkProof& pf, const SampleRun& sr) {
-        const uint4* out = reinterpret_cast<const uint4*>(c.h_small + 4096);
+    const uint4* sample_results() const { return reinterpret_cast<const uint4*>(c.h_small + 4096); }
+    // the values in job order -> pf.sampled_values (per tree, column and mask point)
+    void sample_unpack(const std::vector<DTree>& trees, const std::vector<std::vector<std::vector<u32>>>& mask, const uint4* out, u32 n_all, StarkProof& pf) {
         pf.sampled_values.resize(trees.size());
         size_t ji = 0;
         for (size_t t = 0; t < trees.size(); t++) {
@@ -1475,213 +1479,140 @@ struct HipProver {
             for (size_t col = 0; col < trees[t].polys.size(); col++)
                 for (size_t k = 0; k < mask[t][col].size(); k++, ji++) pf.sampled_values[t][col].push_back(q_make(out[ji].x, out[ji].y, out[ji].z, out[ji].w));
         }
-        if (ji != sr.n_all) throw HipError("sampling: job count mismatch");
+        if (ji != n_all) throw HipError("sampling: job count mismatch");
     }
-    void sample(std::vector<DTree>& trees, const std::vector<std::vector<std::vector<u32>>>& mask, const std::vector<PtQ>& points, StarkProof& pf, const SamplePlan& sp) {
-        std::vector<uint4> factors(points.size() * 32, make_uint4(0, 0, 0, 0));
-        sample_factors(points, factors.data());
-        const std::vector<EvalJob>& jobs = sp.jobs;
-        const u32 partial_off = sp.partial_off, n_all = sp.n_all;
-        c.stage_checkpoint();
-        StageBatch sb(c);
-        const uint4* d_factors = c.stage(factors.data(), factors.size());     // through the pinned staging ring (no pageable copies)
-        const EvalJob* d_jobs = jobs.empty() ? nullptr : c.stage(jobs.data(), jobs.size());
-        sb.end();
-        void* d_partials = c.arena.alloc(size_t(partial_off ? partial_off : 1) * sizeof(uint4));
-        std::vector<uint4> out(n_all);
-        if (!sharded() && n_all * sizeof(uint4) <= c.h_small_bytes - 4096) {
-            // the second stage writes the samples into the pinned bounce buffer itself
-            eval_at_points(c.stream, d_jobs, (u32)jobs.size(), partial_off, d_factors, d_partials, c.d_small_alias + 4096);
-            BF_HIP(hipGetLastError());
-            c.sync();
-            memcpy(out.data(), c.h_small + 4096, out.size() * sizeof(uint4));
-        } else {
-            uint4* d_out = (uint4*)c.arena.alloc(n_all * sizeof(uint4));
-            if (sharded()) BF_HIP(hipMemsetAsync(d_out, 0, n_all * sizeof(uint4), c.stream));
-            eval_at_points(c.stream, d_jobs, (u32)jobs.size(), partial_off, d_factors, d_partials, d_out);
-            BF_HIP(hipGetLastError());
-            if (sharded()) c.shard.comm->all_reduce_max_u32(c.stream, reinterpret_cast<u32*>(d_out), size_t(n_all) * 4);
-            c.read_back(out.data(), d_out, out.size() * sizeof(uint4));
-        }
-        pf.sampled_values.resize(trees.size());
-        size_t ji = 0;
-        for (size_t t = 0; t < trees.size(); t++) {
-            pf.sampled_values[t].resize(trees[t].polys.size());
-            for (size_t col = 0; col < trees[t].polys.size(); col++)
-                for (size_t k = 0; k < mask[t][col].size(); k++, ji++) pf.sampled_values[t][col].push_back(q_make(out[ji].x, out[ji].y, out[ji].z, out[ji].w));
-        }
+    void sample(const std::vector<DTree>& trees, const std::vector<std::vector<std::vector<u32>>>& mask, const std::vector<PtQ>& points, StarkProof& pf, const SamplePlan& sp) {
+        const SampleRun sr = sample_launch(sp, points, nullptr);
+        std::vector<uint4> out;
+        if (sr.d_out) { out.resize(sp.n_all); c.read_back(out.data(), sr.d_out, out.size() * sizeof(uint4)); }
+        else c.sync();
+        sample_unpack(trees, mask, sr.d_out ? out.data() : sample_results(), sp.n_all, pf);
     }
 
-    // Mailbox mode of compute_quotients (one process per proof). quotients_enqueue: the size groups, their storage, the batch STRUCTURE (which
-    // depends on the sample points, known by now, not on the sampled values) and the launches — the largest group behind mailbox mb0, the other
-    // groups behind mb1. quotients_fill: the same constants as compute_quotients, written over the staged blocks; mb0 is posted as soon as the
-    // largest group's constants are in place, mb1 after the rest (computed while the first launch runs).
+    // compute_fri_quotients: one secure column per distinct LDE size, descending. A size group: the LDE columns of that size, their mask points
+    // (ColumnSampleBatch::new_vec) and where each column's sampled values are in the proof.
     struct QuotientGroup {
         u32 log = 0; std::vector<ColDesc> descs; std::vector<ColSamples> cols; std::vector<std::pair<size_t, size_t>> src;   // (tree, column) per column
-        QuotientBatch* h_batches = nullptr; QuotientEntry* h_entries = nullptr; size_t n_batches = 0, n_entries = 0;
+        QuotientBatch* h_batches = nullptr; QuotientEntry* h_entries = nullptr; size_t n_batches = 0, n_entries = 0;      // mailbox order: the staged tables
     };
     struct QuotientRun { std::vector<QuotientGroup> groups; std::vector<DSecure> out; };
-    QuotientRun quotients_enqueue(std::vector<DTree>& trees, const std::vector<std::vector<std::vector<u32>>>& mask, const std::vector<PtQ>& points, Mailbox* mb0, Mailbox* mb1) {
+    std::vector<QuotientGroup> quotient_groups(const std::vector<DTree>& trees, const std::vector<std::vector<std::vector<u32>>>& mask) {
         struct FlatCol { DCol col; size_t tree, idx; };
         std::vector<FlatCol> flat;
         for (size_t t = 0; t < trees.size(); t++) for (size_t i = 0; i < trees[t].evals.size(); i++) flat.push_back({trees[t].evals[i], t, i});
         std::stable_sort(flat.begin(), flat.end(), [](const FlatCol& a, const FlatCol& b) { return a.col.log_size > b.col.log_size; });
-        QuotientRun qr;
+        std::vector<QuotientGroup> groups;
         for (size_t i = 0; i < flat.size();) {
             size_t j = i; const u32 log = flat[i].col.log_size;
             while (j < flat.size() && flat[j].col.log_size == log) j++;
             QuotientGroup g; g.log = log;
             for (size_t k = i; k < j; k++) {
-                g.descs.push_back(flat[k].col.desc());
                 const auto& pts = mask[flat[k].tree][flat[k].idx];
                 if (pts.size() > 2) throw HipError("quotients: more than two mask points on a column");
+                // shard group: a full-size column of the group is row-sharded exactly when the group is; a replicated one may also be complete
+                // on every rank
+                if (flat[k].col.sliced() != slice_log(log) && (flat[k].col.shift == 0 || flat[k].col.sliced())) throw HipError("quotients: inconsistent row-sharding in a size group");
+                g.descs.push_back(flat[k].col.desc());
                 ColSamples cs{};
                 for (size_t s = 0; s < pts.size(); s++) { cs.point[cs.n] = pts[s]; cs.value[cs.n] = q_zero(); cs.n++; }
                 g.cols.push_back(cs); g.src.push_back({flat[k].tree, flat[k].idx});
             }
-            qr.groups.push_back(std::move(g));
+            groups.push_back(std::move(g));
             i = j;
         }
+        return groups;
+    }
+    // quotient_constants (host/quotients.h) of one size group. pf == nullptr: the sampled values stay zero — the tables' structure depends on
+    // the sample points only.
+    static void quotient_constants(QuotientGroup& g, const std::vector<PtQ>& points, const StarkProof* pf, Q31 random_coeff,
+                                   std::vector<QuotientBatch>& batches, std::vector<QuotientEntry>& entries) {
+        if (pf)
+            for (size_t k = 0; k < g.cols.size(); k++)
+                for (u32 s = 0; s < g.cols[k].n; s++) g.cols[k].value[s] = pf->sampled_values[g.src[k].first][g.src[k].second][s];
+        batches.clear(); entries.clear();
+        build_quotient_batches_indexed(g.cols.data(), g.cols.size(), points, random_coeff, batches, entries);
+        quotient_entries_finish(batches.data(), batches.size(), entries.data(), g.descs.data());
+    }
+    // Launches: one per size group of >= 2^19 rows, largest first, each followed by an event (q_waits) — the FRI first-layer tree hashes level L
+    // as soon as the quotient of size L exists, on the partner stream, while the smaller groups are still being computed — and one launch for all
+    // the smaller groups together. (Shard group / host channel: one launch, no events.)
+    // Otherwise the LARGEST group is launched as soon as its own constants exist (four composition columns: a handful of products) and the host
+    // prepares the constants of the other groups — ~40 us of QM31 arithmetic, with the GPU idle behind the sampled values' round trip — while
+    // that launch runs; the rest follows as the second launch.
+    // mb0 / mb1 (mailbox order, one process per proof; pf == nullptr, random_coeff one): the largest group's launch goes behind mailbox mb0, the
+    // others' behind mb1, with the tables' structure staged (it depends on the sample points, known by now); quotients_fill writes the constants.
+    QuotientRun compute_quotients(const std::vector<DTree>& trees, const std::vector<std::vector<std::vector<u32>>>& mask, const std::vector<PtQ>& points,
+                                  const StarkProof* pf, Q31 random_coeff, std::vector<LevelWait>* q_waits, Mailbox* mb0 = nullptr, Mailbox* mb1 = nullptr) {
+        QuotientRun qr;
+        qr.groups = quotient_groups(trees, mask);
+        mark("quotient columns sorted");
+        const bool pipelined = (c.overlap & 2u) && q_waits && !sharded() && c.conv.merkle_channel == 0;
+        const bool early_first = !pipelined && !sharded();
         std::vector<QuotientArgs> launches;
         std::vector<QuotientBatch> batches; std::vector<QuotientEntry> entries;
-        c.stage_checkpoint();
         auto stage_group = [&](QuotientGroup& g, Mailbox* m) {
-            batches.clear(); entries.clear();
-            build_quotient_batches_indexed(g.cols.data(), g.cols.size(), points, q_one(), batches, entries);
-            quotient_entries_finish(batches.data(), batches.size(), entries.data(), g.descs.data());
-            DSecure q; q.log_size = g.log; q.lc = 0;
-            for (int w = 0; w < 4; w++) q.c[w] = c.alloc_u32(size_t(1) << g.log);
+            quotient_constants(g, points, pf, random_coeff, batches, entries);
+            // shard group: the quotient of a row-sharded size is computed for this rank's row range only
+            const bool sl = slice_log(g.log);
+            DSecure q; q.log_size = g.log; q.lc = sl ? lc() : 0;
+            for (int w = 0; w < 4; w++) q.c[w] = sl ? alloc_slice(g.log) : c.alloc_u32(size_t(1) << g.log);
             QuotientArgs a{};
+            if (sl) { a.row0 = (u32)slice_first(g.log); a.n_rows = (u32)slice_cells(g.log); }
             a.batches = batches.empty() ? nullptr : c.stage(batches.data(), batches.size());
             a.entries = entries.empty() ? nullptr : c.stage(entries.data(), entries.size());
-            g.n_batches = batches.size(); g.n_entries = entries.size();
-            g.h_batches = a.batches ? m->host(a.batches) : nullptr; g.h_entries = a.entries ? m->host(a.entries) : nullptr;
+            if (m) { g.n_batches = batches.size(); g.n_entries = entries.size(); g.h_batches = a.batches ? m->host(a.batches) : nullptr; g.h_entries = a.entries ? m->host(a.entries) : nullptr; }
             a.n_batches = (u32)batches.size(); a.log = g.log; a.tw = c.d_tw; a.tw_total = 1u << c.tw_root_log;
             for (int w = 0; w < 4; w++) a.out[w] = q.c[w];
             launches.push_back(a);
             qr.out.push_back(q);
         };
-        // the largest group behind its own mailbox
-        mb0->begin();
-        stage_group(qr.groups[0], mb0);
-        QuotientArgs first = launches[0];
-        const u32 nblocks0 = quotient_groups_layout(&first, 1);
-        const QuotientArgs* d_first = c.stage(&first, 1);
-        mb0->arm();
-        BF_HIP(hipEventRecord(c.ev[4], c.stream));       // the quotient phase's GPU time starts behind the mailbox, not in front of it
-        accumulate_quotients(c.stream, d_first, 1, nblocks0);
-        if (qr.groups.size() > 1) {
-            mb1->begin();
-            for (size_t g = 1; g < qr.groups.size(); g++) stage_group(qr.groups[g], mb1);
-            const u32 nblocks = quotient_groups_layout(launches.data() + 1, (u32)launches.size() - 1);
-            const QuotientArgs* d_groups = c.stage(launches.data() + 1, launches.size() - 1);
-            mb1->arm();
-            accumulate_quotients(c.stream, d_groups, (u32)launches.size() - 1, nblocks);
+        c.stage_checkpoint();
+        size_t launched = 0;
+        if (early_first && !qr.groups.empty()) {
+            u32 nblocks = 0; const QuotientArgs* d_first = nullptr;
+            stage_blocks(mb0, [&] {
+                stage_group(qr.groups[0], mb0);
+                nblocks = quotient_groups_layout(&launches[0], 1);
+                d_first = c.stage(&launches[0], 1);
+            });
+            if (mb0) BF_HIP(hipEventRecord(c.ev[4], c.stream));       // the quotient phase's GPU time starts behind the mailbox, not in front of it
+            accumulate_quotients(c.stream, d_first, 1, nblocks);
+            mark("largest quotient group launched");
+            launched = 1;
+        }
+        if (launched < qr.groups.size()) {
+            std::vector<std::pair<u32, u32>> ranges;      // [first group, count)
+            std::vector<u32> blocks;
+            const QuotientArgs* d_groups = nullptr;
+            stage_blocks(mb1, [&] {
+                for (size_t g = launched; g < qr.groups.size(); g++) stage_group(qr.groups[g], mb1);
+                u32 g = (u32)launched;
+                if (pipelined) while (g < launches.size() && launches[g].log >= 19) { ranges.push_back({g, 1u}); g++; }
+                if (g < launches.size()) ranges.push_back({g, (u32)launches.size() - g});
+                for (auto& r : ranges) blocks.push_back(quotient_groups_layout(launches.data() + r.first, r.second));
+                d_groups = c.stage(launches.data(), launches.size());      // one copy for the parameter blocks of every (remaining) size group
+            });
+            for (size_t k = 0; k < ranges.size(); k++) {
+                accumulate_quotients(c.stream, d_groups + ranges[k].first, ranges[k].second, blocks[k]);
+                if (pipelined) { hipEvent_t e = c.next_event(); BF_HIP(hipEventRecord(e, c.stream)); q_waits->push_back({(int)launches[ranges[k].first].log, e}); }
+            }
         }
         BF_HIP(hipGetLastError());
         return qr;
     }
-    void quotients_fill(QuotientRun& qr, const std::vector<std::vector<std::vector<u32>>>& mask, const std::vector<PtQ>& points, const StarkProof& pf, Q31 random_coeff,
-                        Mailbox* mb0, Mailbox* mb1) {
+    // mailbox order: the constants over the staged tables; mb0 is posted as soon as the largest group's are in place, mb1 after the rest
+    // (computed while the first launch runs)
+    void quotients_fill(QuotientRun& qr, const std::vector<PtQ>& points, const StarkProof& pf, Q31 random_coeff, Mailbox* mb0, Mailbox* mb1) {
         std::vector<QuotientBatch> batches; std::vector<QuotientEntry> entries;
         for (size_t gi = 0; gi < qr.groups.size(); gi++) {
             QuotientGroup& g = qr.groups[gi];
-            for (size_t k = 0; k < g.cols.size(); k++)
-                for (u32 s = 0; s < g.cols[k].n; s++) g.cols[k].value[s] = pf.sampled_values[g.src[k].first][g.src[k].second][s];
-            batches.clear(); entries.clear();
-            build_quotient_batches_indexed(g.cols.data(), g.cols.size(), points, random_coeff, batches, entries);
-            quotient_entries_finish(batches.data(), batches.size(), entries.data(), g.descs.data());
+            quotient_constants(g, points, &pf, random_coeff, batches, entries);
             if (batches.size() != g.n_batches || entries.size() != g.n_entries) throw HipError("quotients: the batch structure changed between enqueue and fill");
             if (g.n_batches) memcpy(g.h_batches, batches.data(), batches.size() * sizeof(QuotientBatch));
             if (g.n_entries) memcpy(g.h_entries, entries.data(), entries.size() * sizeof(QuotientEntry));
             if (gi == 0) mb0->post();
         }
         mb1->post();
-    }
-
-    // compute_fri_quotients: one secure column per distinct LDE size, descending.
-    std::vector<DSecure> compute_quotients(std::vector<DTree>& trees, const std::vector<std::vector<std::vector<u32>>>& mask, const std::vector<PtQ>& points,
-                                           const StarkProof& pf, Q31 random_coeff, std::vector<LevelWait>* q_waits = nullptr) {
-        struct FlatCol { DCol col; size_t tree, idx; };
-        std::vector<FlatCol> flat;
-        for (size_t t = 0; t < trees.size(); t++) for (size_t i = 0; i < trees[t].evals.size(); i++) flat.push_back({trees[t].evals[i], t, i});
-        std::stable_sort(flat.begin(), flat.end(), [](const FlatCol& a, const FlatCol& b) { return a.col.log_size > b.col.log_size; });
-        mark("quotient columns sorted");
-        std::vector<DSecure> out;
-        std::vector<QuotientArgs> launches;
-        // Launches: one per size group of >= 2^19 rows, largest first, each followed by an event (q_waits) — the FRI first-layer tree hashes
-        // level L as soon as the quotient of size L exists, on the partner stream, while the smaller groups are still being computed — and one
-        // launch for all the smaller groups together. (Shard group / host channel: one launch, no events.)
-        const bool pipelined = (c.overlap & 2u) && q_waits && !sharded() && c.conv.merkle_channel == 0;
-        // Otherwise the LARGEST group is launched as soon as its own constants exist (four composition columns: a handful of products) and the
-        // host prepares the constants of the other groups — ~40 us of QM31 arithmetic, with the GPU idle behind the sampled values' round trip —
-        // while that launch runs; the rest follows as the second launch.
-        const bool early_first = !pipelined && !sharded();
-        u32 launched = 0;
-        c.stage_checkpoint();
-        auto sb = std::make_unique<StageBatch>(c);
-        std::vector<ColDesc> descs; std::vector<ColSamples> col_samples;        // reused by every size group
-        std::vector<QuotientBatch> batches; std::vector<QuotientEntry> entries;
-        descs.reserve(flat.size()); col_samples.reserve(flat.size()); entries.reserve(2 * flat.size()); batches.reserve(32);
-        for (size_t i = 0; i < flat.size();) {
-            size_t j = i; u32 log = flat[i].col.log_size;
-            while (j < flat.size() && flat[j].col.log_size == log) j++;
-            // ColumnSampleBatch::new_vec + quotient_constants (host/quotients.h)
-            descs.clear(); col_samples.clear();
-            for (size_t k = i; k < j; k++) {
-                descs.push_back(flat[k].col.desc());
-                const auto& pts = mask[flat[k].tree][flat[k].idx];
-                ColSamples cs{};
-                if (pts.size() > 2) throw HipError("quotients: more than two mask points on a column");
-                for (size_t s = 0; s < pts.size(); s++) { cs.point[cs.n] = pts[s]; cs.value[cs.n] = pf.sampled_values[flat[k].tree][flat[k].idx][s]; cs.n++; }
-                col_samples.push_back(cs);
-            }
-            batches.clear(); entries.clear();
-            build_quotient_batches_indexed(col_samples.data(), col_samples.size(), points, random_coeff, batches, entries);
-            quotient_entries_finish(batches.data(), batches.size(), entries.data(), descs.data());
-            // shard group: the quotient of a row-sharded size is computed for this rank's row range only (every column of the group is
-            // either complete or row-sharded over the same range)
-            const bool sl = slice_log(log);
-            DSecure q; q.log_size = log; q.lc = sl ? lc() : 0;
-            for (int w = 0; w < 4; w++) q.c[w] = sl ? alloc_slice(log) : c.alloc_u32(size_t(1) << log);
-            QuotientArgs a{};
-            if (sl) { a.row0 = (u32)slice_first(log); a.n_rows = (u32)slice_cells(log); }
-            // a full-size column of the group is row-sharded exactly when the group is; a replicated one may also be complete on every rank
-            for (size_t k = i; k < j; k++) if (flat[k].col.sliced() != sl && (flat[k].col.shift == 0 || flat[k].col.sliced())) throw HipError("quotients: inconsistent row-sharding in a size group");
-            a.batches = batches.empty() ? nullptr : c.stage(batches.data(), batches.size());
-            a.entries = entries.empty() ? nullptr : c.stage(entries.data(), entries.size());
-            a.n_batches = (u32)batches.size(); a.log = log; a.tw = c.d_tw; a.tw_total = 1u << c.tw_root_log;
-            for (int w = 0; w < 4; w++) a.out[w] = q.c[w];
-            launches.push_back(a);
-            out.push_back(q);
-            i = j;
-            if (early_first && launches.size() == 1 && i < flat.size()) {
-                QuotientArgs first = launches[0];
-                const u32 nblocks = quotient_groups_layout(&first, 1);
-                const QuotientArgs* d_first = c.stage(&first, 1);
-                sb->end();
-                accumulate_quotients(c.stream, d_first, 1, nblocks);
-                mark("largest quotient group launched");
-                sb = std::make_unique<StageBatch>(c);
-                launched = 1;
-            }
-        }
-        std::vector<std::pair<u32, u32>> ranges;      // [first group, count)
-        {
-            u32 g = launched;
-            if (pipelined) while (g < launches.size() && launches[g].log >= 19) { ranges.push_back({g, 1u}); g++; }
-            if (g < launches.size()) ranges.push_back({g, (u32)launches.size() - g});
-        }
-        std::vector<u32> blocks;
-        for (auto& r : ranges) blocks.push_back(quotient_groups_layout(launches.data() + r.first, r.second));
-        const QuotientArgs* d_groups = launches.empty() ? nullptr : c.stage(launches.data(), launches.size());
-        sb->end();                                  // one copy for the parameter blocks of every (remaining) size group
-        for (size_t k = 0; k < ranges.size(); k++) {
-            accumulate_quotients(c.stream, d_groups + ranges[k].first, ranges[k].second, blocks[k]);
-            if (pipelined) { hipEvent_t e = c.next_event(); BF_HIP(hipEventRecord(e, c.stream)); q_waits->push_back({(int)launches[ranges[k].first].log, e}); }
-        }
-        BF_HIP(hipGetLastError());
-        return out;
     }
 
     static std::vector<size_t> fold_queries(const std::vector<size_t>& q, u32 n) {
@@ -2264,7 +2195,6 @@ extern "C" int32_t bfhip_host_table(const uint32_t* trace7, size_t n_trace, cons
     } catch (const std::exception& e) { bfhip_set_error(e.what()); return -1; }
 }
 // Profiler state is per stream, i.e. per context: contexts on other threads are not affected (prof.hip).
-static void sync_both(Ctx& c) { c.sync(); if (c.stream2) BF_HIP(hipStreamSynchronize(c.stream2)); for (auto a : c.aux) if (a) BF_HIP(hipStreamSynchronize(a)); }
 extern "C" int32_t bfhip_profile_enable(bfhip_ctx* ctx, int32_t mode) {
     try { if (!ctx) throw HipError("null context"); if (mode < 0 || mode > 2) throw HipError("bad profile mode"); ctx->c.bind(); ctx->c.ensure_side(); sync_both(ctx->c); prof_enable(ctx->c.stream, mode); prof_enable(ctx->c.stream2, mode); for (auto a : ctx->c.aux) if (a) prof_enable(a, mode); return 0; }
     catch (const std::exception& e) { bfhip_set_error(e.what()); return -1; }
