@@ -172,7 +172,8 @@ __device__ __forceinline__ void fft_pass_body(const PassArgs& a, const BlockOfGr
         // ---- load tile (16 B per lane) -----------------------------------------------------------------------------
         for (u32 e4 = t * 4; e4 < tile_n; e4 += 4 * FFT_THREADS) {
             u32 gidx = lo ? (base | ((e4 >> c) << lo) | (e4 & ((1u << c) - 1))) : (base + e4);
-            uint4 v = ld16(src + (gidx & a.src_mask));
+            // src_mask < 3 (uniform): 1 or 2 coefficients, zero-padded to the 4 cells of every load (fft_plan)
+            uint4 v = a.src_mask < 3u ? make_uint4(src[0], a.src_mask ? src[1] : 0u, 0u, 0u) : ld16(src + (gidx & a.src_mask));
             *reinterpret_cast<uint4*>(&s_val[e4]) = v;
         }
         __syncthreads();
@@ -628,8 +629,9 @@ void fft_plan(FftPlan& plan, bool inverse, const FftJob* jobs, size_t njobs, con
         if (ncols == 0) continue;
         PassArgs a{};
         a.ncols = ncols; a.log = log; a.circle = job.circle ? 1 : 0; a.tw = inverse ? itw : tw; a.tw_total = 1u << tw_root_log; a.scale = 1;
-        if (log > 5 && src_log < 2) throw std::runtime_error("fft: extending a polynomial with fewer than 4 coefficients to more than 32 cells is not supported");
-        const u32 nl = inverse ? log : src_log;   // forward: the layers >= src_log only duplicate (zero extension) = wrap-around load
+        // forward: the layers >= src_log only duplicate (zero extension) = wrap-around load. Past 32 cells a lane loads 4 cells at once: a polynomial of 1 or 2
+        // coefficients (the row-granular columns of a 2^4- or 2^5-row component under a large blowup) is zero-padded to 4 by the load (fft_pass_body) and runs 2 layers
+        const u32 nl = inverse ? log : (log > 5 && src_log < 2) ? 2u : src_log;
         if (log <= 5) {
             a.dst = job.d_dst; a.src = job.d_src; a.src_mask = (1u << src_log) - 1; a.lo = 0; a.k = nl;
             a.scale = inverse ? m_inv(1u << log) : 1;

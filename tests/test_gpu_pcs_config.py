@@ -138,6 +138,34 @@ def test_blowup_above_1_verifies_and_matches_the_oracle_through_root2(pkg, shim,
 
 
 @pytest.mark.single_conv
+@pytest.mark.parametrize("b,lmr,code,inp", [(5, 12, CODE, INP), (6, 12, CODE, INP), (6, 12, "++[-]+.", b""), (8, 12, CODE, INP), (16, 8, "+>+<-.", b"")],
+                         ids=["b5", "b6", "b6_with_a_32_row_component", "b8", "b16"])
+def test_large_blowups_the_config_promises(pkg, shim, conv, b, lmr, code, inp):
+    """bfhip_pcs_config advertises 1 <= log_blowup_factor <= 16. From 6 up (5 with a 2^5-row component) the row-granular columns of the 2^4- and
+    2^5-row components are polynomials of ONE or TWO coefficients extended past 32 cells, which the transform planner used to refuse: every
+    such proof failed. Same assertions as above; the oracle's taps are compared for 5 and 6 (at 8 and 16 the CPU proof is left out: the two
+    verifiers and the rejection under b - 1 carry the check)."""
+    pw, q = 8, 6
+    cfg = pkg.PcsConfig(pow_bits=pw, log_blowup_factor=b, n_queries=q)
+    c = pkg.Context(0, max_log_domain=lmr + b + 1)
+    try:
+        got, taps = pkg.prove_brainfuck(code, inp, ctx=c, log_max_rows=lmr, with_transcript=True, pcs_config=cfg)
+    finally:
+        c.close()
+    if b <= 6:
+        want_taps = shim.taps(code, inp, lmr, pow_bits=pw, log_blowup_factor=b, n_queries=q)
+        for k in ("root0", "root1", "root2"):
+            assert taps[k] == want_taps[k], k
+    assert pkg.verify_brainfuck(got, lmr, conventions=conv, pcs_config=cfg) == (True, "")
+    assert shim.verify(got, lmr, pow_bits=pw, log_blowup_factor=b, n_queries=q) == (True, "")
+    assert not pkg.verify_brainfuck(got, lmr, conventions=conv)[0]
+    assert not pkg.verify_brainfuck(got, lmr, conventions=conv, pcs_config=pkg.PcsConfig(pow_bits=pw, log_blowup_factor=b - 1, n_queries=q))[0]
+    bad = _flip_first_value(got, "proof", "queried_values", 1)
+    assert not pkg.verify_brainfuck(bad, lmr, conventions=conv, pcs_config=cfg)[0]
+    assert not shim.verify(bad, lmr, pow_bits=pw, log_blowup_factor=b, n_queries=q)[0]
+
+
+@pytest.mark.single_conv
 def test_unsupported_settings_fail_clearly(pkg, oracle, pctx):
     want = oracle.prove(CODE, INP, log_max_rows=17)[0]
     for bad in (pkg.PcsConfig(n_queries=0), pkg.PcsConfig(n_queries=257), pkg.PcsConfig(log_blowup_factor=0), pkg.PcsConfig(log_blowup_factor=17),
