@@ -4,11 +4,13 @@
 // node(i) absorbs left(32B) || right(32B) || LE-u32 value of every column of this layer's size at row i, 64 bytes per compression.
 // Conventions::merkle_node_hash (m31.h) selects how: 0 (default) = stwo's Blake2sMerkleHasher::hash_node of the period — zero initial state,
 // raw compress(state, block, 0,0,0,0) per block, column words zero padded to 16; 1 = RFC 7693 Blake2s-256 of the byte string (parameter
-// block, byte counter, final flag). Both cost the same number of compressions; the kernels take the choice as an all-ones/zero mask `rfc`.
+// block, byte counter, final flag). Both cost the same number of compressions. k_merkle_layer takes the choice as a template parameter (its
+// initial state is then a literal), the latency-chain kernels of the small end as an all-ones/zero mask `rfc`.
 //
 // One lane hashes one node. The message is streamed 64 bytes at a time through a fully unrolled compression (the sigma
 // schedule is compile-time, so the 16 message words and the 16 state words stay in VGPRs; rotations by 16/8 lower to
-// v_perm/v_alignbit). This kernel is integer-VALU bound (~1.0 k ops per 64-byte block), not HBM bound: see DESIGN.md.
+// v_perm/v_alignbit). This kernel is integer-VALU bound, not HBM bound: 977 ops per 64-byte block in general, 960 for the first
+// block of a node under the stwo convention, 939 / 926 for a leaf over 4 / 1 columns (tools/merkle_isa_count.py counts every instantiation).
 // Column reads are coalesced (lane i reads cell i of each column; replicated columns read cell i >> 4), child hashes are read as
 // 4 x 16 B per lane, hashes are stored as 2 x 16 B per lane in AoS [node][8 x u32] order (the order decommitment needs).
 #include "kernels.h"
@@ -89,22 +91,57 @@ __device__ __forceinline__ void load_col_block(u32 (&m)[16], const ColDesc* __re
     else if (left > 4) load_col_words<8>(m, cols, c0, ncols, i);
     else load_col_words<4>(m, cols, c0, ncols, i);
 }
-// Hash of node i: the two child hashes (a, b = left, c, d = right) when has_children, then the LE-u32 values of the ncols columns at row i.
-__device__ __forceinline__ void merkle_node_hash(u32 (&h)[8], bool has_children, uint4 a, uint4 b, uint4 c, uint4 d, const ColDesc* __restrict__ cols, u32 ncols, u32 i, u32 rfc) {
-    node_init(h, rfc);
-    const u32 total_bytes = (has_children ? 64u : 0u) + 4u * ncols;
+// ---- k_merkle_layer: one instantiation per hashing convention and node shape ------------------------------------------------------------
+// The kernel is VALU-issue bound, so its time is its instruction count. The general compression above costs 977 VALU; most of a proof's
+// compressions are special cases in which part of that work has compile-time inputs, and the compiler removes it once it can see them:
+//   * a node's FIRST block starts from a literal chaining value. Under the stwo convention that is all zeros with t0 = f0 = 0: the column step of
+//     round 1 loses an add and an xor per G and the feed-forward half of its xors; under RFC 7693 the IV ^ parameter-block words fold into literals;
+//   * a leaf over NC <= 4 columns has m[NC..15] = 0: with a literal state the G functions of round 1 that see no message word are constants.
+// The convention (RFC) and the shape are therefore template parameters; the host picks the instantiation per launch (merkle_layer below), so
+// every launch runs exactly one shape and an instantiation holds only the compression sites it needs (tools/merkle_isa_count.py prints them).
+enum MerkleShape : int {
+    MS_LEAF1 = 1, MS_LEAF2 = 2, MS_LEAF3 = 3, MS_LEAF4 = 4,   // leaf over NC = 1..4 columns (value = NC): one block, prefetching loop
+    MS_INNER0,                                                 // inner node without columns: one block
+    MS_LEAF_WIDE,                                              // leaf over 0 or > 4 columns: first 16 columns against the literal state, then the general loop
+    MS_INNER_COLS,                                             // inner node with columns: children against the literal state, then the general loop
+};
+// initial chaining value as literals: zeros (stwo convention) or IV ^ parameter block (RFC 7693)
+template <bool RFC>
+__device__ __forceinline__ void node_init_lit(u32 (&h)[8]) {
+    h[0] = RFC ? 0x6A09E667u ^ 0x01010020u : 0u; h[1] = RFC ? 0xBB67AE85u : 0u; h[2] = RFC ? 0x3C6EF372u : 0u; h[3] = RFC ? 0xA54FF53Au : 0u;
+    h[4] = RFC ? 0x510E527Fu : 0u; h[5] = RFC ? 0x9B05688Cu : 0u; h[6] = RFC ? 0x1F83D9ABu : 0u; h[7] = RFC ? 0x5BE0CD19u : 0u;
+}
+// First block of a node: h is an output only. `done` = message bytes up to and including this block, `last` = no block follows; the stwo
+// convention ignores both (raw compress(state, block, 0, 0, 0, 0)).
+template <bool RFC>
+__device__ __forceinline__ void blake2s_compress_first(u32 (&h)[8], const u32 (&m)[16], u32 done, bool last) {
+    node_init_lit<RFC>(h);
+    blake2s_compress(h, m, RFC ? done : 0u, RFC && last ? 0xFFFFFFFFu : 0u);
+}
+// Any later block: the general compression (runtime chaining value, 16 message words).
+template <bool RFC>
+__device__ __forceinline__ void blake2s_compress_next(u32 (&h)[8], const u32 (&m)[16], u32 done, bool last) {
+    blake2s_compress(h, m, RFC ? done : 0u, RFC && last ? 0xFFFFFFFFu : 0u);
+}
+// Hash of node i: the two child hashes (a, b = left, c, d = right) when HAS_CHILDREN, then the LE-u32 values of the ncols columns at row i.
+template <bool RFC, bool HAS_CHILDREN>
+__device__ __forceinline__ void merkle_node_hash(u32 (&h)[8], uint4 a, uint4 b, uint4 c, uint4 d, const ColDesc* __restrict__ cols, u32 ncols, u32 i) {
+    const u32 total_bytes = (HAS_CHILDREN ? 64u : 0u) + 4u * ncols;
     u32 m[16];
     u32 done = 0;   // bytes compressed so far
     u32 c0 = 0;     // next column to absorb
-    if (has_children) {
+    bool first = true;
+    if (HAS_CHILDREN) {
         m[0] = a.x; m[1] = a.y; m[2] = a.z; m[3] = a.w; m[4] = b.x; m[5] = b.y; m[6] = b.z; m[7] = b.w;
         m[8] = c.x; m[9] = c.y; m[10] = c.z; m[11] = c.w; m[12] = d.x; m[13] = d.y; m[14] = d.z; m[15] = d.w;
         done = 64;
-        bool last = total_bytes == 64;
-        blake2s_compress(h, m, done & rfc, last ? rfc : 0u);
+        const bool last = total_bytes == 64;
+        blake2s_compress_first<RFC>(h, m, done, last);
         if (last) return;
+        first = false;
     }
-    // remaining message: column values, 16 words per block (zero padded)
+    // remaining message: column values, 16 words per block (zero padded). One copy of the column loads feeds both compression sites of a
+    // leaf (its first block against the literal state, the later ones general): a second copy costs 23 VGPRs and measured slower.
     // (requesting the next block's words before the current block is compressed — two message buffers, 66 VGPRs — measured slower:
     // 64-column leaves 84.5 -> 82.4 % of the compression peak, r04)
     for (;;) {
@@ -113,23 +150,25 @@ __device__ __forceinline__ void merkle_node_hash(u32 (&h)[8], bool has_children,
 #pragma unroll
             for (u32 w = 0; w < 16; w++) m[w] = 0;          // a node with neither children nor columns: one empty block
         }
-        u32 take = min(64u, total_bytes - done);
-        done += take; c0 += 16;
-        bool last = done == total_bytes;
-        blake2s_compress(h, m, done & rfc, last ? rfc : 0u);
+        done += min(64u, total_bytes - done); c0 += 16;
+        const bool last = done == total_bytes;
+        if (!HAS_CHILDREN && first) blake2s_compress_first<RFC>(h, m, done, last);
+        else blake2s_compress_next<RFC>(h, m, done, last);
+        first = false;
         if (last) break;
     }
 }
+template <bool RFC, bool HAS_CHILDREN>
 __device__ __forceinline__ void merkle_node(u32 st, uint4* __restrict__ out, const uint4* __restrict__ prev, const ColDesc* __restrict__ cols, u32 ncols,
-                                            u32 out_shift, u32 prev_shift, u32 rfc) {
+                                            u32 out_shift, u32 prev_shift) {
     const u32 i = st << out_shift;          // representative node of this stored slot
     u32 h[8];
     uint4 a = make_uint4(0, 0, 0, 0), b = a, c = a, d = a;
-    if (prev) {
+    if (HAS_CHILDREN) {
         const size_t cl = ((size_t)2 * i) >> prev_shift, cr = ((size_t)2 * i + 1) >> prev_shift;   // stored slots of the two children
         a = prev[2 * cl]; b = prev[2 * cl + 1]; c = prev[2 * cr]; d = prev[2 * cr + 1];
     }
-    merkle_node_hash(h, prev != nullptr, a, b, c, d, cols, ncols, i, rfc);
+    merkle_node_hash<RFC, HAS_CHILDREN>(h, a, b, c, d, cols, ncols, i);
     store_hash(out, st, h);
 }
 // Grid-stride over the stored nodes: large layers give every lane several nodes, which amortises wave launch and the kernel prologue.
@@ -137,33 +176,42 @@ __device__ __forceinline__ void merkle_node(u32 st, uint4* __restrict__ out, con
 // Leaves over at most 4 columns (composition and FRI trees: ~200 M of a proof's 674 M compressions) get their own loop in which the
 // inputs of a lane's next node are fetched while the current node is compressed: with one compression per node the load latency is
 // otherwise exposed once per node and wave (85 -> 89 % of the compression peak). The same for column-less inner nodes measured worse.
+// The host guarantees the shape: MS_LEAF<NC>: !prev && ncols == NC; MS_INNER0: prev && !ncols; MS_LEAF_WIDE: !prev; MS_INNER_COLS: prev.
+template <bool RFC, int SHAPE>
 __global__ void __launch_bounds__(256) k_merkle_layer(uint4* __restrict__ out, const uint4* __restrict__ prev, const ColDesc* __restrict__ cols, u32 ncols, u32 n_stored,
-                                                      u32 out_shift, u32 prev_shift, u32 first, u32 rfc) {
+                                                      u32 out_shift, u32 prev_shift, u32 first) {
     const u32 stride = gridDim.x * blockDim.x;
     u32 st = blockIdx.x * blockDim.x + threadIdx.x;
     if (st >= n_stored) return;
-    if (!prev && ncols >= 1 && ncols <= 4) {
-        const u32 lastc = ncols - 1;
-        const ColDesc d0 = cols[0], d1 = cols[min(1u, lastc)], d2 = cols[min(2u, lastc)], d3 = cols[min(3u, lastc)];
+    if constexpr (SHAPE >= MS_LEAF1 && SHAPE <= MS_LEAF4) {
+        constexpr int NC = SHAPE;
+        ColDesc d[NC];
+#pragma unroll
+        for (int k = 0; k < NC; k++) d[k] = cols[k];
         u32 i = (first + st) << out_shift;
-        u32 n0 = ld_col(d0, i), n1 = ld_col(d1, i), n2 = ld_col(d2, i), n3 = ld_col(d3, i);
+        u32 nx[NC];
+#pragma unroll
+        for (int k = 0; k < NC; k++) nx[k] = ld_col(d[k], i);
         for (;;) {
             const u32 cur = first + st;
             u32 m[16];
 #pragma unroll
-            for (int k = 4; k < 16; k++) m[k] = 0;
-            m[0] = n0; m[1] = ncols > 1 ? n1 : 0u; m[2] = ncols > 2 ? n2 : 0u; m[3] = ncols > 3 ? n3 : 0u;
+            for (int k = 0; k < 16; k++) m[k] = k < NC ? nx[k < NC ? k : 0] : 0u;
             st += stride;
             const bool more = st < n_stored;
-            if (more) { i = (first + st) << out_shift; n0 = ld_col(d0, i); n1 = ld_col(d1, i); n2 = ld_col(d2, i); n3 = ld_col(d3, i); }
+            i = (first + min(st, n_stored - 1)) << out_shift;      // a lane without a next node re-reads the range's last one: no branch around the loads
+#pragma unroll
+            for (int k = 0; k < NC; k++) nx[k] = ld_col(d[k], i);
             u32 h[8];
-            node_init(h, rfc);
-            blake2s_compress(h, m, (4u * ncols) & rfc, rfc);
+            blake2s_compress_first<RFC>(h, m, 4u * NC, true);
             store_hash(out, cur, h);
             if (!more) return;
         }
+    } else {
+        constexpr bool HAS_CHILDREN = SHAPE == MS_INNER0 || SHAPE == MS_INNER_COLS;
+        if constexpr (SHAPE == MS_INNER0) ncols = 0;      // one block per node: the column loop and its compression site are not compiled
+        for (; st < n_stored; st += stride) merkle_node<RFC, HAS_CHILDREN>(first + st, out, prev, cols, ncols, out_shift, prev_shift);
     }
-    for (; st < n_stored; st += stride) merkle_node(first + st, out, prev, cols, ncols, out_shift, prev_shift, rfc);
 }
 
 // Blake2sChannel stepped on the device for the FRI commit phase (FriProver::commit: mix_root(layer root) then draw_felt per layer):
@@ -689,6 +737,19 @@ void fri_tail(hipStream_t stream, const FriTailArgs* d_args, double bytes, doubl
     hipLaunchKernelGGL(k_fri_tail, dim3(1), dim3(256), 0, stream, d_args);
 }
 
+template <bool RFC, int SHAPE>
+static void launch_merkle_shape(hipStream_t stream, u32 blocks, u32 threads, uint4* out, const uint4* prev, const ColDesc* d_cols, u32 ncols, u32 n, u32 out_shift, u32 prev_shift, u32 first) {
+    hipLaunchKernelGGL((k_merkle_layer<RFC, SHAPE>), dim3(blocks), dim3(threads), 0, stream, out, prev, d_cols, ncols, n, out_shift, prev_shift, first);
+}
+// the node shape of a launch from (prev, ncols): see MerkleShape
+template <bool RFC>
+static void launch_merkle_layer(hipStream_t stream, u32 blocks, u32 threads, uint4* out, const uint4* prev, const ColDesc* d_cols, u32 ncols, u32 n, u32 out_shift, u32 prev_shift, u32 first) {
+    auto* launch = prev ? (ncols ? launch_merkle_shape<RFC, MS_INNER_COLS> : launch_merkle_shape<RFC, MS_INNER0>)
+                 : ncols == 1 ? launch_merkle_shape<RFC, MS_LEAF1> : ncols == 2 ? launch_merkle_shape<RFC, MS_LEAF2>
+                 : ncols == 3 ? launch_merkle_shape<RFC, MS_LEAF3> : ncols == 4 ? launch_merkle_shape<RFC, MS_LEAF4> : launch_merkle_shape<RFC, MS_LEAF_WIDE>;
+    launch(stream, blocks, threads, out, prev, d_cols, ncols, n, out_shift, prev_shift, first);
+}
+
 #ifndef MERKLE_NODES_PER_LANE
 #define MERKLE_NODES_PER_LANE 4
 #endif
@@ -704,7 +765,7 @@ void merkle_layer(hipStream_t stream, void* out, const void* prev, const ColDesc
     ProfScope ps(stream, "k_merkle_layer", ((prev ? 64.0 * total : 0.0) + 32.0 * total + col_bytes) * frac, comp_per_node * n, /*dominant=*/true);
     u32 blocks = (n + threads - 1) / threads;
     if (blocks >= (1u << 14)) blocks /= MERKLE_NODES_PER_LANE;   // >= 2^22 nodes: several nodes per lane (measured: 2..16 equivalent, 4 kept)
-    hipLaunchKernelGGL(k_merkle_layer, dim3(blocks), dim3(threads), 0, stream, (uint4*)out, (const uint4*)prev, d_cols, ncols, n, out_shift, prev_shift, count ? first : 0u, node_conv ? 0xFFFFFFFFu : 0u);
+    (node_conv ? launch_merkle_layer<true> : launch_merkle_layer<false>)(stream, blocks, threads, (uint4*)out, (const uint4*)prev, d_cols, ncols, n, out_shift, prev_shift, count ? first : 0u);
 }
 void merkle_subtree(hipStream_t stream, const MerkleTreeDesc& tree, u32 hi, u32 node_conv, double bytes, double compressions) {
     ProfScope ps(stream, "k_merkle_subtree", bytes, compressions);
