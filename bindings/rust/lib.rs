@@ -76,6 +76,38 @@ impl Context {
         Ok(out)
     }
 
+    /// `assert_constraints` for an executed machine (`bfhip_trace_check`): the 13 AIRs asserted on the trace domain, logUp columns generated
+    /// with the default lookup elements of `include/bfhip.h`. `Ok(reports)` = every constraint holds on every row and the 13 claimed sums
+    /// cancel (`lookup_sum_valid`, `mod.rs:207-226`); `Err` names the first failing component, constraint and table row — where a proof of
+    /// the same trace would only say "ConstraintsNotSatisfied".
+    pub fn check_machine(&self, trace7: &[u32], program: &[u32]) -> Result<[sys::BfhipCheckReport; 13], String> {
+        assert!(trace7.len() % 7 == 0);
+        let mut tr: *mut sys::BfhipTrace = std::ptr::null_mut();
+        let rc = unsafe {
+            sys::bfhip_trace_create_from_registers(self.0, trace7.as_ptr(), trace7.len() / 7, program.as_ptr(), program.len(), &mut tr, std::ptr::null_mut(),
+                                                   std::ptr::null_mut(), std::ptr::null_mut())
+        };
+        if rc != 0 {
+            return Err(last_error());
+        }
+        let mut reports = [sys::BfhipCheckReport::default(); 13];
+        let (mut total, mut n_bad) = ([0u32; 4], 0i32);
+        let rc = unsafe { sys::bfhip_trace_check(self.0, tr, std::ptr::null(), reports.as_mut_ptr(), total.as_mut_ptr(), &mut n_bad) };
+        unsafe { sys::bfhip_trace_destroy(self.0, tr) };
+        if rc != 0 {
+            return Err(last_error());
+        }
+        if let Some(r) = reports.iter().find(|r| r.n_bad_cells != 0) {
+            let j = r.first_bad_constraint as usize;
+            return Err(format!("component {}: constraint {} fails at table row {} (cell {}), value {:?}; {} cells violate it",
+                               r.component, j, r.first_bad_cell >> 4, r.first_bad_cell, r.first_bad_value, r.bad_per_constraint[j]));
+        }
+        if total != [0u32; 4] {
+            return Err(format!("the 13 claimed logUp sums add up to {:?}, not zero", total));
+        }
+        Ok(reports)
+    }
+
     /// Byte-level stwo conventions / Merkle channel of this context (`bfhip_conventions`; all zero = defaults).
     pub fn set_conventions(&self, conv: &sys::BfhipConventions) -> Result<(), String> {
         if unsafe { sys::bfhip_ctx_set_conventions(self.0, conv) } != 0 { Err(last_error()) } else { Ok(()) }

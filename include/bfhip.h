@@ -225,6 +225,31 @@ int32_t bfhip_logup_generate(bfhip_ctx* ctx, int32_t component, uint32_t log_siz
 int32_t bfhip_eval_constraints(bfhip_ctx* ctx, int32_t component, uint32_t log_size, const uint32_t* is_first_d, const uint32_t* const* main_lde_h,
                                const uint32_t* main_shifts_h, const uint32_t* const* inter_lde_h, const uint32_t* inter_shifts_h, const uint32_t lookup_h[24],
                                const uint32_t claimed_sum_h[4], const uint32_t* coeffs_h, uint32_t* const acc_d[4]);
+/* ---- the AIRs asserted on the trace domain: which component, which constraint, which row ----
+ * stwo's `assert_constraints`, which every component test of the reference is built on (positive: memory/component.rs:201-208 and all 13
+ * components at mod.rs:252-396; negative: memory/component.rs:211-609, whose panic texts quote the failing row and value). A proof of a
+ * trace that is not a valid execution only fails with "ConstraintsNotSatisfied" at its out-of-domain check; these entry points say where.
+ * A cell is a storage index i in [0, 2^log_size) of CanonicCoset(log_size) in bit-reversed circle-domain order; table row = i >> 4.
+ * IsFirst is 1 at cell 0. Constraints are numbered in evaluation order (bfhip_component_shape gives their count, at most 12), the logUp
+ * constraints last. A base-field constraint's value is reported as (v, 0, 0, 0). */
+typedef struct bfhip_check_report {
+    uint32_t component, log_size;
+    uint64_t n_bad_cells;              /* cells where at least one constraint is non-zero */
+    uint64_t first_bad_cell;           /* storage index; table row = >> 4; UINT64_MAX if none */
+    int32_t  first_bad_constraint;     /* lowest constraint that is non-zero at first_bad_cell; -1 if none */
+    uint32_t first_bad_value[4];       /* its value there */
+    uint64_t bad_per_constraint[16];   /* cells where constraint j is non-zero */
+    uint32_t claimed_sum[4];           /* the component's logUp total the check ran with */
+    uint32_t reserved[3];
+} bfhip_check_report;
+/* One component on caller-supplied columns: the pointers and layouts bfhip_logup_generate takes and produces. main_rows_h: n_main device
+ * pointers to row-granular columns (2^(log_size-4) rows); logup_cols_h: 4 * n_logup device pointers to coordinate columns, the last 4 of
+ * 2^log_size cells, earlier ones row-granular; claimed_sum_h = the total the last logUp column closes on. The previous row of the last
+ * logUp column is its neighbour at coset offset -1 on the trace domain itself. Returns 0 whether or not the trace is valid — the verdict
+ * is in *out, and bfhip_last_error() is not touched by violations; -1 only for bad arguments (unknown component, log_size outside
+ * [4, 29], null pointers, a context in a shard group) and HIP errors. */
+int32_t bfhip_check_constraints(bfhip_ctx* ctx, int32_t component, uint32_t log_size, const uint32_t* const* main_rows_h, const uint32_t* const* logup_cols_h,
+                                const uint32_t lookup_h[24], const uint32_t claimed_sum_h[4], bfhip_check_report* out);
 /* `QuotientOps::accumulate_quotients` (compute_fri_quotients, reached from mod.rs:732) for the columns of one LDE size: n_cols
  * columns of 2^log_size cells on CanonicCoset(log_size).circle_domain() (bit-reversed; col_shifts_h as above: 0 or >= 2, may be NULL).
  * Column k has n_samples_h[k] samples; sample_points_h (u32[8] each: x[4] || y[4]) and sample_values_h (u32[4] each) list them column
@@ -336,6 +361,18 @@ int32_t bfhip_ctx_set_table_builder(bfhip_ctx* ctx, int32_t on_gpu);
 int32_t bfhip_trace_column(bfhip_ctx* ctx, const bfhip_trace* trace, uint32_t component, uint32_t column, uint32_t* out_h, size_t cap, size_t* n_rows);
 int32_t bfhip_prove_trace(bfhip_ctx* ctx, const bfhip_trace* trace, uint32_t log_max_rows, char** proof_json, size_t* proof_len,
                           char** transcript, double* phase_seconds);
+
+/* The 13 components of a resident trace (bfhip_trace_create*): for each the logUp columns are generated with the prover's own logUp kernels
+ * into the context's arena (which is reset like a proof resets it) and bfhip_check_constraints' pass runs over them; out[k] = component k.
+ * logup_total_h = the sum of the 13 claimed sums: zero iff `lookup_sum_valid` (mod.rs:207-226) holds. *n_bad_components = components with
+ * n_bad_cells != 0 (may be NULL). The trace is an execution trace the prover will accept iff that count is 0 and the total is zero.
+ * lookup_h: (z, alpha) of Memory, Instruction, Processor (u32[24], as above). NULL = what `MemoryElements::draw`, `InstructionElements::draw`
+ * and `ProcessorElements::draw` (mod.rs:589-597, in this order) give on `Blake2sChannel::default()`: the k-th `draw_felts(2)` is the
+ * eight base-field words of Blake2s-256(0^32 || LE32(k) || 0^28), each reduced mod 2^31 - 1 (no word of these three draws reaches
+ * 2 (2^31 - 1), so none is redrawn): z = words 0..3, alpha = words 4..7. Not the elements of any proof — those depend on the commitments —
+ * but fixed, so a report can be reproduced. A context in a shard group is refused. Returns 0 whether or not the trace is valid. */
+int32_t bfhip_trace_check(bfhip_ctx* ctx, const bfhip_trace* trace, const uint32_t* lookup_h /* u32[24] or NULL */,
+                          bfhip_check_report out[13], uint32_t logup_total_h[4], int32_t* n_bad_components);
 
 /* ---- proofs in flight: a pool of sub-contexts on one GPU behind ONE caller thread -------------------------------------------------------------
  * The reference's caller is a single thread of control (prove_brainfuck, mod.rs:471-735); a single proof leaves the GPU partly idle in its

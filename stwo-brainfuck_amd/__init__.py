@@ -134,6 +134,67 @@ MIX_U64_COMPRESS, MIX_U64_HASH = 0, 1
 LOGUP_MASK_CUR_PREV, LOGUP_MASK_PREV_CUR = 0, 1
 
 
+COMPONENT_NAMES = ("memory", "instruction", "program", "processor", "jnz", "jz", "input", "left", "minus", "output", "plus", "right", "end_of_execution")
+NO_CELL = (1 << 64) - 1
+
+
+class CheckReport(ctypes.Structure):
+    """include/bfhip.h `bfhip_check_report`: one component's AIR asserted on its trace domain (stwo's assert_constraints)."""
+    _fields_ = [("component", ctypes.c_uint32), ("log_size", ctypes.c_uint32), ("n_bad_cells", ctypes.c_uint64), ("first_bad_cell", ctypes.c_uint64),
+                ("first_bad_constraint", ctypes.c_int32), ("first_bad_value", ctypes.c_uint32 * 4), ("bad_per_constraint", ctypes.c_uint64 * 16),
+                ("claimed_sum", ctypes.c_uint32 * 4), ("reserved", ctypes.c_uint32 * 3)]
+
+    def as_dict(self):
+        """Named fields; first_bad_cell / first_bad_row are None for a component without violations (first_bad_constraint is -1 then)."""
+        none = self.first_bad_cell == NO_CELL
+        return {"component": int(self.component), "name": COMPONENT_NAMES[self.component], "log_size": int(self.log_size), "ok": self.n_bad_cells == 0,
+                "n_bad_cells": int(self.n_bad_cells), "first_bad_cell": None if none else int(self.first_bad_cell),
+                "first_bad_row": None if none else int(self.first_bad_cell) >> 4, "first_bad_constraint": int(self.first_bad_constraint),
+                "first_bad_value": [int(v) for v in self.first_bad_value], "bad_per_constraint": [int(v) for v in self.bad_per_constraint],
+                "claimed_sum": [int(v) for v in self.claimed_sum]}
+
+
+def format_check_failure(report):
+    """One line for a component's report (a dict of CheckReport.as_dict()), e.g.
+    "memory: constraint 6 fails at table row 0 (cell 0), value (2, 0, 0, 0); 16 cells violate it"; "<name>: ok" without violations."""
+    if report["n_bad_cells"] == 0:
+        return "%s: ok" % report["name"]
+    j = report["first_bad_constraint"]
+    return "%s: constraint %d fails at table row %d (cell %d), value (%s); %d cells violate it" % (
+        report["name"], j, report["first_bad_row"], report["first_bad_cell"], ", ".join(str(v) for v in report["first_bad_value"]), report["bad_per_constraint"][j])
+
+
+def default_check_lookup():
+    """The lookup elements bfhip_trace_check uses when none are given (include/bfhip.h): (z, alpha) of Memory, Instruction, Processor as
+    the three `draw_felts(2)` of mod.rs:589-597 on Blake2sChannel::default() — 24 u32. Fixed, so a report can be reproduced."""
+    import hashlib
+    import struct
+    out = []
+    for k in range(3):
+        words = struct.unpack("<8I", hashlib.blake2s(bytes(32) + struct.pack("<I", k) + bytes(28)).digest())
+        assert all(w < 2 * P for w in words)      # none of the three draws is redrawn
+        out += [w % P for w in words]
+    return out
+
+
+class CheckResult(list):
+    """Trace.check(): the 13 component reports (dicts, claim order) + logup_total (the sum of the 13 claimed sums, 4 u32),
+    n_bad_components and ok = no violation and a zero logUp total."""
+    logup_total = (0, 0, 0, 0)
+    n_bad_components = 0
+
+    @property
+    def ok(self):
+        return self.n_bad_components == 0 and not any(self.logup_total)
+
+    def failures(self):
+        """One format_check_failure line per failing component, then the logUp total if it is not zero."""
+        lines = [format_check_failure(r) for r in self if r["n_bad_cells"]]
+        if any(self.logup_total):
+            lines.append("logUp: the 13 claimed sums add up to (%s), not zero" % ", ".join(str(v) for v in self.logup_total))
+        return lines
+
+
 class Context:
     """One GPU + one HIP stream + the twiddle tree (mod.rs:480-487: twiddles, channel and commitment scheme setup)."""
 
@@ -386,6 +447,15 @@ class Context:
                                             None if inter_shifts is None else self._u32s(inter_shifts), self._u32s(lookup24), self._u32s(claimed4),
                                             self._u32s(coeffs), self._ptr_array(acc_ptrs)))
 
+    def check_constraints(self, component, log_size, main_row_ptrs, logup_col_ptrs, lookup24, claimed4):
+        """bfhip_check_constraints: one component's AIR asserted on its trace domain (stwo's assert_constraints). main_row_ptrs: row-granular
+        main columns; logup_col_ptrs: what logup_generate wrote (the last four full size). Returns CheckReport.as_dict(); violations are
+        a result, not an error."""
+        rep = CheckReport()
+        _check(lib().bfhip_check_constraints(self._h, component, log_size, self._ptr_array(main_row_ptrs), self._ptr_array(logup_col_ptrs),
+                                             self._u32s(lookup24), self._u32s(claimed4), ctypes.byref(rep)))
+        return rep.as_dict()
+
     def accumulate_quotients(self, log_size, col_ptrs, n_samples, sample_points, sample_values, random_coeff4, out_ptrs, col_shifts=None):
         """QuotientOps::accumulate_quotients for the columns of one LDE size."""
         _check(lib().bfhip_accumulate_quotients(self._h, log_size, self._ptr_array(col_ptrs), None if col_shifts is None else self._u32s(col_shifts), len(col_ptrs),
@@ -535,6 +605,26 @@ def verify_brainfuck(proof_json: bytes, log_max_rows=24, conventions=None, pcs_c
     return rc == 0, err.value.decode()
 
 
+def host_compile(code):
+    """bfhip_host_compile (compiler.rs:17-37): the program words, jump targets included. Host only."""
+    out = np.zeros(2 * len(code) + 4, dtype=np.uint32)
+    n = ctypes.c_size_t()
+    _check(lib().bfhip_host_compile(code.encode(), out.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(out.size), ctypes.byref(n)))
+    return out[: n.value].copy()
+
+
+def host_run(code, input_bytes=b"", ram_size=0):
+    """bfhip_host_run_ram (machine.rs:141-238): (output bytes, register trace as an (n, 7) u32 array: clk, ip, ci, ni, mp, mv, mvi). Host only."""
+    n_out, n_rows = ctypes.c_size_t(), ctypes.c_size_t()
+    args = (code.encode(), input_bytes, ctypes.c_size_t(len(input_bytes)), ctypes.c_size_t(ram_size))
+    _check(lib().bfhip_host_run_ram(*args, None, ctypes.c_size_t(0), ctypes.byref(n_out), None, ctypes.c_size_t(0), ctypes.byref(n_rows)))
+    out = (ctypes.c_ubyte * max(1, n_out.value))()
+    rows = np.zeros((n_rows.value, 7), dtype=np.uint32)
+    _check(lib().bfhip_host_run_ram(*args, out, ctypes.c_size_t(n_out.value), ctypes.byref(n_out), rows.ctypes.data_as(ctypes.c_void_p),
+                                    ctypes.c_size_t(rows.shape[0]), ctypes.byref(n_rows)))
+    return bytes(out[: n_out.value]), rows
+
+
 class Trace:
     """Prover input resident in HBM (bfhip_trace_create): VM trace -> 13 component tables -> row-granular device columns."""
 
@@ -579,6 +669,18 @@ class Trace:
             proof = ctypes.string_at(js, n.value)
             lib().bfhip_free_host(js)
         return proof, dict(zip(PHASES, list(times)))
+
+    def check(self, lookup24=None):
+        """bfhip_trace_check: the 13 AIRs asserted on this trace (logUp columns generated on the GPU), as a CheckResult. lookup24: (z, alpha)
+        of Memory, Instruction, Processor; None = default_check_lookup(). A trace that is not a valid execution gives ok = False and the
+        failing component, constraint and row — where a proof would only say ConstraintsNotSatisfied."""
+        reps = (CheckReport * 13)()
+        total = (ctypes.c_uint32 * 4)()
+        n_bad = ctypes.c_int32()
+        _check(lib().bfhip_trace_check(self.ctx._h, self._h, None if lookup24 is None else Context._u32s(lookup24), reps, total, ctypes.byref(n_bad)))
+        res = CheckResult(r.as_dict() for r in reps)
+        res.logup_total, res.n_bad_components = tuple(int(v) for v in total), n_bad.value
+        return res
 
     def column(self, component, column):
         n = ctypes.c_size_t()

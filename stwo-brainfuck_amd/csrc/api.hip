@@ -4,6 +4,7 @@
 #include <cstdlib>
 #include "host/circle.h"
 #include "host/quotients.h"
+#include "host/hash.h"
 #include <cstdio>
 #include <vector>
 #include <algorithm>
@@ -757,6 +758,139 @@ int32_t bfhip_eval_constraints(bfhip_ctx* ctx, int32_t component, uint32_t log_s
     c.stage_checkpoint();
     eval_constraints(c.stream, component, c.stage(&L, 1), log_size, 0, constraint_group_rows(L, component));
     BF_HIP(hipGetLastError());
+    return 0;
+    API_CATCH
+}
+// ---- the AIRs asserted on the trace domain (check.hip) -------------------------------------------------------------------------------
+static CheckReportDev check_report_init() { CheckReportDev r{}; r.first_bad_cell = ~u64(0); r.first_bad_constraint = 0xffffffffu; return r; }
+static void check_report_fill(bfhip_check_report& out, const CheckReportDev& r, int component, u32 log_size, Q31 claimed) {
+    out = bfhip_check_report{};
+    out.component = (u32)component; out.log_size = log_size;
+    out.n_bad_cells = r.n_bad_cells; out.first_bad_cell = r.first_bad_cell; out.first_bad_constraint = (int32_t)r.first_bad_constraint;
+    for (int w = 0; w < 4; w++) out.first_bad_value[w] = r.first_bad_value[w];
+    for (int j = 0; j < 16; j++) out.bad_per_constraint[j] = r.bad_per_constraint[j];
+    out.claimed_sum[0] = claimed.a.a; out.claimed_sum[1] = claimed.a.b; out.claimed_sum[2] = claimed.b.a; out.claimed_sum[3] = claimed.b.b;
+}
+// main: row-granular; logup: 4 coordinate columns per logUp column, the last logUp column full size, earlier ones row-granular
+static CheckLaunch check_launch_of(int component, u32 log_size, const u32* const* main_rows, const u32* const* logup_cols, const Lookups& el, Q31 total_sum,
+                                   CheckReportDev* d_report) {
+    CheckLaunch L{};
+    const u32 n_inter = 4 * n_logup_cols(component);
+    for (u32 j = 0; j < n_main_cols(component); j++) L.trace[j] = ColDesc{main_rows[j], LOG_N_LANES, 0};
+    for (u32 j = 0; j < n_inter; j++) L.inter[j] = ColDesc{logup_cols[j], j + 4 < n_inter ? LOG_N_LANES : 0u, 0};
+    L.el = el; L.total_sum = total_sum; L.log_size = log_size; L.report = d_report;
+    return L;
+}
+static void check_not_sharded(const Ctx& c) {
+    if (c.shard.count > 1) throw HipError("constraint check: a context in a shard group is not supported (bfhip_ctx_leave_group first)");
+}
+int32_t bfhip_check_constraints(bfhip_ctx* ctx, int32_t component, uint32_t log_size, const uint32_t* const* main_rows_h, const uint32_t* const* logup_cols_h,
+                                const uint32_t lookup_h[24], const uint32_t claimed_sum_h[4], bfhip_check_report* out) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    if (component < 0 || component >= N_COMPONENTS) throw HipError("unknown component");
+    if (log_size < LOG_N_LANES) throw HipError("component log_size below LOG_N_LANES (4)");
+    if (log_size > 29) throw HipError("component log_size above 29: columns hold at most 2^29 cells");
+    if (!main_rows_h || !logup_cols_h || !lookup_h || !claimed_sum_h || !out) throw HipError("null argument");
+    for (u32 j = 0; j < n_main_cols(component); j++) if (!main_rows_h[j]) throw HipError("null main column pointer");
+    for (u32 j = 0; j < 4 * n_logup_cols(component); j++) if (!logup_cols_h[j]) throw HipError("null logUp column pointer");
+    check_not_sharded(c);
+    const Q31 claimed = q_from_h(claimed_sum_h);
+    const CheckReportDev init = check_report_init();
+    c.stage_checkpoint();
+    CheckReportDev* d_report = c.stage(&init, 1);
+    const CheckLaunch L = check_launch_of(component, log_size, main_rows_h, logup_cols_h, lookups_from_h(lookup_h), claimed, d_report);
+    {
+        ProfScope ps(c.stream, "k_check_cells", 0);
+        check_constraints_launch(c.stream, component, c.stage(&L, 1), log_size);
+    }
+    BF_HIP(hipGetLastError());
+    CheckReportDev r;
+    c.read_back(&r, d_report, sizeof r);
+    check_report_fill(*out, r, component, log_size, claimed);
+    return 0;
+    API_CATCH
+}
+int32_t bfhip_trace_check(bfhip_ctx* ctx, const bfhip_trace* trace, const uint32_t* lookup_h, bfhip_check_report out[13], uint32_t logup_total_h[4],
+                          int32_t* n_bad_components) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    if (!trace || !out || !logup_total_h) throw HipError("null argument");
+    check_not_sharded(c);
+    Lookups el;
+    if (lookup_h) el = lookups_from_h(lookup_h);
+    else {
+        // MemoryElements::draw, InstructionElements::draw, ProcessorElements::draw (mod.rs:589-597) on Blake2sChannel::default()
+        Channel ch;
+        { Q31 z, a; ch.draw_two_felts(z, a); el.memory = make_lookup(z, a); }
+        { Q31 z, a; ch.draw_two_felts(z, a); el.instruction = make_lookup(z, a); }
+        { Q31 z, a; ch.draw_two_felts(z, a); el.processor = make_lookup(z, a); }
+    }
+    const u32* rows[N_COMPONENTS][13] = {};
+    u32 log_sizes[N_COMPONENTS];
+    trace_columns(trace, rows, log_sizes);
+    // like a proof: nothing of this context is in flight, and its per-proof memory starts empty
+    c.sync();
+    c.arena.reset();
+    c.stage_checkpoint();
+    uint4* d_claimed = (uint4*)c.arena.alloc(sizeof(uint4) * N_COMPONENTS);
+    const u32* inter[N_COMPONENTS][12] = {};
+    std::vector<LogupLaunch> logups(N_COMPONENTS);
+    for (int k = 0; k < N_COMPONENTS; k++) {
+        const u32 log = log_sizes[k], log_rows = log - LOG_N_LANES, nl = n_logup_cols(k);
+        if (log < LOG_N_LANES || log > 29) throw HipError("trace: component log_size out of range");
+        const size_t M = size_t(1) << log_rows;
+        LogupLaunch L{};
+        for (u32 j = 0; j < n_main_cols(k); j++) L.cols[j] = rows[k][j];
+        for (u32 j = 0; j < 4 * nl; j++) {
+            u32* p = c.alloc_u32(j + 4 < 4 * nl ? M : 16 * M);
+            inter[k][j] = p;
+            if (j + 4 < 4 * nl) L.out_rep[j] = p; else L.out_last[j - 4 * (nl - 1)] = p;
+        }
+        L.vrow = c.arena.alloc(sizeof(uint4) * M);
+        L.wloc = c.arena.alloc(sizeof(uint4) * M);
+        L.totals = c.arena.alloc(sizeof(uint4) * (M / 1024 + 2));
+        L.claimed = d_claimed + k;
+        L.log_rows = log_rows; L.comp = k;
+        logups[k] = L;
+    }
+    {
+        LogupBatch lb;
+        logup_batch_init(lb, el, logups.data(), N_COMPONENTS);
+        const LogupBatch* d_lb = c.stage(&lb, 1);
+        ProfScope ps(c.stream, "trace_check_logup", 0);      // bfhip_profile_enable mode 1: the two halves of a check, by HIP events (tools/trace_check_rate.py)
+        logup_batch_run(c.stream, d_lb, lb);
+    }
+    BF_HIP(hipGetLastError());
+    uint4 claimed_h[N_COMPONENTS];
+    c.read_back(claimed_h, d_claimed, sizeof claimed_h);
+    Q31 claimed[N_COMPONENTS], total = q_zero();
+    CheckReportDev reports[N_COMPONENTS];
+    for (int k = 0; k < N_COMPONENTS; k++) {
+        claimed[k] = q_make(claimed_h[k].x, claimed_h[k].y, claimed_h[k].z, claimed_h[k].w);
+        total = q_add(total, claimed[k]);
+        reports[k] = check_report_init();
+    }
+    CheckLaunch launches[N_COMPONENTS];
+    const CheckLaunch* d_launches = nullptr;
+    CheckReportDev* d_reports = nullptr;
+    {
+        StageBatch sb(c);
+        d_reports = c.stage(reports, N_COMPONENTS);
+        for (int k = 0; k < N_COMPONENTS; k++) launches[k] = check_launch_of(k, log_sizes[k], rows[k], inter[k], el, claimed[k], d_reports + k);
+        d_launches = c.stage(launches, N_COMPONENTS);
+        sb.end();
+    }
+    {
+        ProfScope ps(c.stream, "k_check_cells", 0);
+        for (int k = 0; k < N_COMPONENTS; k++) check_constraints_launch(c.stream, k, d_launches + k, log_sizes[k]);
+    }
+    BF_HIP(hipGetLastError());
+    c.read_back(reports, d_reports, sizeof reports);
+    int32_t n_bad = 0;
+    for (int k = 0; k < N_COMPONENTS; k++) { check_report_fill(out[k], reports[k], k, log_sizes[k], claimed[k]); n_bad += reports[k].n_bad_cells != 0; }
+    logup_total_h[0] = total.a.a; logup_total_h[1] = total.a.b; logup_total_h[2] = total.b.a; logup_total_h[3] = total.b.b;
+    if (n_bad_components) *n_bad_components = n_bad;
     return 0;
     API_CATCH
 }

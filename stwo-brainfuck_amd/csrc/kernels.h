@@ -6,6 +6,8 @@
 #include <string>
 #include <vector>
 
+struct bfhip_trace;   // include/bfhip.h; defined in prover.hip
+
 namespace bf {
 
 // A column in HBM. shift = 0: one u32 per domain cell. shift = 4: one u32 per table row, standing for a column whose values
@@ -201,6 +203,19 @@ struct LogupBatch { Lookups el; u32 n; u32 rows_blk0[14], scan_blk0[14], last_bl
 void logup_batch_init(LogupBatch& b, const Lookups& el, const LogupLaunch* L, u32 n);
 void logup_batch_run(hipStream_t stream, const LogupBatch* d_batch, const LogupBatch& h_batch);
 void broadcast16(hipStream_t stream, const u32* d_rows, u32* d_out, u32 n_cells);
+
+// check.hip — assertion of one AIR on its TRACE domain (stwo's `assert_constraints`; include/bfhip.h: bfhip_check_constraints)
+// The report as the kernels keep it: 64-bit counters updated with integer atomics only (the result does not depend on scheduling), then the
+// first failing constraint of the first bad cell and its value. The host zero-fills it and sets first_bad_cell = UINT64_MAX before the launch.
+struct CheckReportDev { u64 n_bad_cells, first_bad_cell; u64 bad_per_constraint[16]; u32 first_bad_constraint; u32 first_bad_value[4]; u32 pad_[3]; };
+// Cell i of a column = a storage index of CanonicCoset(log_size) in bit-reversed circle-domain order. trace: the main columns; inter: 4 coordinate
+// columns per logUp column (row-granular ones carry shift 4, the last logUp column shift 0). Staged in device memory like ConstraintLaunch.
+struct CheckLaunch { ColDesc trace[13]; ColDesc inter[12]; Lookups el; Q31 total_sum; u32 log_size; u32 pad_; CheckReportDev* report; };
+// k_check_cells (counters, first bad cell) followed by k_check_first (constraint index and value at that cell) on `stream`
+void check_constraints_launch(hipStream_t stream, int comp, const CheckLaunch* d_args, u32 log_size);
+
+// prover.hip — the row-granular main-trace columns and the log sizes of a resident trace (for bfhip_trace_check in api.hip)
+void trace_columns(const bfhip_trace* t, const u32* cols[N_COMPONENTS][13], u32 log_sizes[N_COMPONENTS]);
 
 // quotient.hip
 struct EvalJob { const u32* coeffs; u32 log_n; u32 point; u32 factor_shift; u32 partial_off; u32 out_idx; u32 pad_; };   // result -> out[out_idx]

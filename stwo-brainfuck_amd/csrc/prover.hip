@@ -1966,6 +1966,13 @@ void shared_preprocessed_invalidate(SharedPreprocessed* sp) { if (sp) sp->valid 
 using namespace bf;
 
 struct bfhip_trace { TraceInput in; };
+// api.hip (bfhip_trace_check): the row-granular main-trace columns and the log sizes of a resident trace
+void bf::trace_columns(const bfhip_trace* t, const u32* cols[N_COMPONENTS][13], u32 log_sizes[N_COMPONENTS]) {
+    for (int k = 0; k < N_COMPONENTS; k++) {
+        log_sizes[k] = t->in.log_sizes[k];
+        for (u32 j = 0; j < n_main_cols(k); j++) cols[k][j] = t->in.rows[k][j].ptr;
+    }
+}
 // Selects where bfhip_trace_create / bfhip_prove_brainfuck of THIS context build the 13 component tables: 1 = gfx950 kernels (default), 0 = host builders.
 extern "C" int32_t bfhip_ctx_set_table_builder(bfhip_ctx* ctx, int32_t on_gpu) { if (!ctx) { bfhip_set_error("null context"); return -1; } ctx->c.tables_on_gpu = on_gpu != 0; return 0; }
 // Downloads one row-granular column of a resident trace (tests: GPU tables == host tables).

@@ -1,9 +1,17 @@
 #!/usr/bin/env python3
-"""prove | verify over the C ABI — the two sub-commands of the reference's bin/brainfuck_prover.rs (prove: :79-139, verify: :141-151):
+"""prove | verify over the C ABI — the two sub-commands of the reference's bin/brainfuck_prover.rs (prove: :79-139, verify: :141-151) — and
+check, the reference's `assert_constraints` (memory/component.rs:201-208, mod.rs:252-396) for a whole execution:
 
   bfprove.py prove  (--file prog.bf | --code '++>,<[>+.<-]') [--input-file in.bin] [--ram-size N] [--output proof.json]
                     [--log-max-rows 24] [--conventions a,b,c,d | --poseidon252] [--all-sets DIR] [PCS options]
   bfprove.py verify proof.json [--log-max-rows 24] [--conventions a,b,c,d | --poseidon252 | --try-all] [PCS options]
+  bfprove.py check  (--file prog.bf | --code '++>,<[>+.<-]') [--input-file in.bin] [--ram-size N] [--set-register ROW:NAME=VALUE ...]
+
+check runs the program on the host VM, hands the register trace to the GPU (bfhip_trace_create_from_registers) and asserts the 13 AIRs on
+the trace domain (bfhip_trace_check). It prints `ok`, or one line per failing component — e.g.
+"memory: constraint 6 fails at table row 0 (cell 0), value (2, 0, 0, 0); 16 cells violate it" — and exits with 1: what lies behind a proof
+that fails with ConstraintsNotSatisfied. --set-register alters one register (clk, ip, ci, ni, mp, mv, mvi) of one row of the executed
+trace first: what a faulty VM would hand over.
 
 PCS options (stwo's PcsConfig; the defaults are PcsConfig::default()): --pow-bits 5 --log-blowup-factor 1 --n-queries 3. The proof file does
 not record them: verify with the values the proof was made with. prove prints the config and its security bits (pow + blowup x queries).
@@ -89,6 +97,9 @@ def main():
     v = sub.add_parser("verify")
     v.add_argument("proof"); v.add_argument("--log-max-rows", type=int, default=24); v.add_argument("--poseidon252", action="store_true")
     v.add_argument("--conventions"); v.add_argument("--try-all", action="store_true")
+    k = sub.add_parser("check")
+    k.add_argument("--file"); k.add_argument("--code"); k.add_argument("--input-file"); k.add_argument("--ram-size", type=int, default=0)
+    k.add_argument("--set-register", action="append", default=[], metavar="ROW:NAME=VALUE")
     add_pcs_options(p); add_pcs_options(v)
     a = ap.parse_args()
     pkg = load_package()
@@ -99,7 +110,36 @@ def main():
         return 2
 
 
+REGISTERS = ("clk", "ip", "ci", "ni", "mp", "mv", "mvi")
+
+
+def check(pkg, a, ap):
+    code = open(a.file).read() if a.file else a.code
+    if code is None:
+        ap.error("check needs --file or --code")
+    inp = open(a.input_file, "rb").read() if a.input_file else (b"" if sys.stdin.isatty() else sys.stdin.buffer.read())
+    _, rows = pkg.host_run(code, inp, ram_size=a.ram_size)
+    for spec in a.set_register:
+        try:
+            row, rest = spec.split(":")
+            name, value = rest.split("=")
+            rows[int(row), REGISTERS.index(name)] = int(value)
+        except (ValueError, IndexError):
+            ap.error(f"--set-register takes ROW:NAME=VALUE with NAME one of {', '.join(REGISTERS)} and ROW < {rows.shape[0]}, got {spec!r}")
+    ctx = pkg.Context(0, max_log_domain=8)       # the check needs no twiddle tree
+    tr = pkg.Trace.from_registers(ctx, rows, pkg.host_compile(code))
+    res = tr.check()
+    tr.close(); ctx.close()
+    for line in res.failures():
+        print(line)
+    if res.ok:
+        print("ok")
+    return 0 if res.ok else 1
+
+
 def run(pkg, a, ap):
+    if a.cmd == "check":
+        return check(pkg, a, ap)
     if a.cmd == "prove":
         code = open(a.file).read() if a.file else a.code
         if code is None:
