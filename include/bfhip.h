@@ -196,6 +196,14 @@ int32_t bfhip_hades_permutation(bfhip_ctx* ctx, const uint32_t in_h[24], uint32_
 int32_t bfhip_fold_line(bfhip_ctx* ctx, const uint32_t* const src_d[4], uint32_t* const dst_d[4], uint32_t log_size, const uint32_t alpha_h[4]);
 /* FriOps::fold_circle_into_line: dst = dst * alpha^2 + fold(src); src has 2^log_size cells on CanonicCoset(log_size).circle_domain(). */
 int32_t bfhip_fold_circle_into_line(bfhip_ctx* ctx, uint32_t* const dst_d[4], const uint32_t* const src_d[4], uint32_t log_size, const uint32_t alpha_h[4]);
+/* One FRI commit step on a layer of 2^log_size rows as ONE launch: the fold that produces the layer and the deepest level of its Merkle tree.
+ * Replaces FriOps::fold_line (src_d, 2^(log_size+1) rows) followed, when quot_d != NULL, by FriOps::fold_circle_into_line (quot_d, a circle
+ * evaluation of 2^(log_size+1) cells) on the result, followed by MerkleOps<Blake2sMerkleHasher>::commit_on_layer(log_size, prev = NULL, the 4
+ * coordinate columns) — what FriProver::commit does per layer (prover::prove, mod.rs:732). src_d == NULL: the first line layer, a
+ * fold_circle_into_line of quot_d into a zero destination. dst_d receives the folded coordinate columns, out_hashes_d the 2^log_size 32-byte
+ * leaf hashes under the context's merkle_node_hash convention. Whole layers only (no row range). */
+int32_t bfhip_fri_fold_leaf(bfhip_ctx* ctx, const uint32_t* const src_d[4], const uint32_t* const quot_d[4], uint32_t* const dst_d[4], uint32_t log_size,
+                            const uint32_t alpha_h[4], void* out_hashes_d);
 /* GrindOps::grind for Blake2sChannel: smallest nonce such that mix_u64(nonce) on `digest_h` (32 bytes) leaves >= pow_bits trailing zeros. */
 int32_t bfhip_grind(bfhip_ctx* ctx, const uint8_t digest_h[32], uint32_t pow_bits, uint64_t* nonce);
 /* Decommitment reads: out_h[j] = col_d[idx_h[j]] for n positions of one column. */
@@ -272,7 +280,8 @@ void bfhip_free_host(void* p);
  * guarantee it: one proof per GPU holds that order at a time, see bfhip_ctx_set_sync_policy), bit 1 = it took the context's kept preprocessed tree
  * (bfhip_ctx_reuse_preprocessed), bit 2 = it took a pool's shared preprocessed tree (bfhip_pool_set_preprocessed), bit 3 = shard group: the transforms were replicated
  * (bfhip_ctx_set_shard_policy), bit 4 = the decommitment's gather request table outgrew a quarter of the staging ring and was split over
- * several launches (many queries at a large LOG_MAX_ROWS). Tests and tools read it so that
+ * several launches (many queries at a large LOG_MAX_ROWS), bit 5 = FRI layers were folded inside the leaf launch of their Merkle tree
+ * (bfhip_fri_fold_leaf's kernel: layers of 2^17 rows and above, device channel, one process). Tests and tools read it so that
  * a setting that silently did not apply is visible. */
 int32_t bfhip_ctx_last_proof_flags(bfhip_ctx* ctx, uint32_t* flags);
 /* ---- one proof over several GPUs (shard group) ------------------------------------------------------------------------------------------

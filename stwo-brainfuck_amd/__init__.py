@@ -254,12 +254,12 @@ class Context:
         _check(lib().bfhip_ctx_set_mailbox(self._h, int(mode), int(timeout_ms), int(test_delay_ms)))
 
     def last_proof_flags(self):
-        """bfhip_ctx_last_proof_flags: {mailbox_order, kept_preprocessed, shared_preprocessed, replicated_transforms, split_gather} of the last
+        """bfhip_ctx_last_proof_flags: {mailbox_order, kept_preprocessed, shared_preprocessed, replicated_transforms, split_gather, fri_fold_leaf} of the last
         completed proof."""
         f = ctypes.c_uint32()
         _check(lib().bfhip_ctx_last_proof_flags(self._h, ctypes.byref(f)))
         return {"mailbox_order": bool(f.value & 1), "kept_preprocessed": bool(f.value & 2), "shared_preprocessed": bool(f.value & 4), "replicated_transforms": bool(f.value & 8),
-                "split_gather": bool(f.value & 16)}
+                "split_gather": bool(f.value & 16), "fri_fold_leaf": bool(f.value & 32)}
 
     def clock_probe(self, seconds=0.6):
         """bfhip_clock_probe: {ghz (median over workgroups), ghz_min, ghz_max, G_compressions_per_s, launches, ms_per_launch} of a register-only
@@ -413,6 +413,12 @@ class Context:
 
     def fold_line(self, src_ptrs, dst_ptrs, log_size, alpha4):
         _check(lib().bfhip_fold_line(self._h, self._ptr_array(src_ptrs), self._ptr_array(dst_ptrs), log_size, (ctypes.c_uint32 * 4)(*[int(v) for v in alpha4])))
+
+    def fri_fold_leaf(self, src_ptrs, quot_ptrs, dst_ptrs, log_size, alpha4, out_ptr):
+        """bfhip_fri_fold_leaf: fold into a layer of 2^log_size rows and hash its rows in one launch. src_ptrs None: the first line layer
+        (circle fold of quot_ptrs alone); quot_ptrs None: a plain line fold. Whole layers only."""
+        _check(lib().bfhip_fri_fold_leaf(self._h, self._ptr_array(src_ptrs) if src_ptrs is not None else None, self._ptr_array(quot_ptrs) if quot_ptrs is not None else None,
+                                         self._ptr_array(dst_ptrs), log_size, (ctypes.c_uint32 * 4)(*[int(v) for v in alpha4]), ctypes.c_void_p(out_ptr)))
 
     def fold_circle_into_line(self, dst_ptrs, src_ptrs, log_size, alpha4):
         _check(lib().bfhip_fold_circle_into_line(self._h, self._ptr_array(dst_ptrs), self._ptr_array(src_ptrs), log_size, (ctypes.c_uint32 * 4)(*[int(v) for v in alpha4])))

@@ -650,6 +650,21 @@ int32_t bfhip_fold_circle_into_line(bfhip_ctx* ctx, uint32_t* const dst_d[4], co
     fold_circle_into_line(ctx->c.stream, dst_d, src_d, stage_alpha(ctx->c, alpha_h), ctx->c.d_itw, ctx->c.tw_root_log, log_size); BF_HIP(hipGetLastError()); return 0;
     API_CATCH
 }
+int32_t bfhip_fri_fold_leaf(bfhip_ctx* ctx, const uint32_t* const src_d[4], const uint32_t* const quot_d[4], uint32_t* const dst_d[4], uint32_t log_size,
+                            const uint32_t alpha_h[4], void* out_hashes_d) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    if (!src_d && !quot_d) throw HipError("fri_fold_leaf: neither a line source nor a circle evaluation");
+    if (!dst_d || !alpha_h || !out_hashes_d) throw HipError("fri_fold_leaf: null argument");
+    if (log_size < 2 || log_size + 1 > c.tw_root_log + (src_d ? 0u : 1u)) throw HipError("fri_fold_leaf: log_size outside the twiddle tree");
+    FriFoldLeafArgs fa{};
+    for (int w = 0; w < 4; w++) { fa.src[w] = src_d ? src_d[w] : nullptr; fa.quot[w] = quot_d ? quot_d[w] : nullptr; fa.dst[w] = dst_d[w]; }
+    fa.alpha8 = stage_alpha(c, alpha_h); fa.itw = c.d_itw; fa.tw_total = 1u << c.tw_root_log; fa.log = log_size;
+    fri_fold_leaf(c.stream, out_hashes_d, fa, !src_d ? FF_CIRCLE : quot_d ? FF_LINE_CIRCLE : FF_LINE, c.conv.merkle_node_hash);
+    BF_HIP(hipGetLastError());
+    return 0;
+    API_CATCH
+}
 int32_t bfhip_grind(bfhip_ctx* ctx, const uint8_t digest_h[32], uint32_t pow_bits, uint64_t* nonce) {
     API_CTX(ctx)
     Ctx& c = ctx->c;

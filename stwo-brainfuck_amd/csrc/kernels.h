@@ -151,6 +151,15 @@ struct FriLayerArgs {
     u32* counter; u32* chan; u32* alpha_out; u32* root_out;
 };
 void fri_layer(hipStream_t stream, const FriLayerArgs& a);
+// The deepest level of a FRI layer's tree with the fold that produces the layer inside the same launch (merkle.hip: k_fri_fold_leaf): row i of
+// dst (2^log rows) from the sibling pair (2i, 2i + 1) of src and / or quot (2^(log + 1) rows each), then the row's leaf hash -> out[i].
+//   FF_LINE:        dst = fold_line(src, alpha)
+//   FF_LINE_CIRCLE: dst = fold_line(src, alpha) * alpha^2 + fold_circle(quot, alpha)
+//   FF_CIRCLE:      dst = fold_circle(quot, alpha)                 (the first line layer: nothing folded into it yet)
+// alpha8 = device pointer to alpha[4] || alpha^2[4], written before this launch starts. Whole layers only.
+enum FriFoldMode : int { FF_LINE = 0, FF_LINE_CIRCLE = 1, FF_CIRCLE = 2 };
+struct FriFoldLeafArgs { const u32* src[4]; const u32* quot[4]; u32* dst[4]; const u32* alpha8; const u32* itw; u32 tw_total, log; };
+void fri_fold_leaf(hipStream_t stream, void* out, const FriFoldLeafArgs& a, int mode, u32 node_conv);
 void grind_span(hipStream_t stream, const u32* d_digest, u64 base, u32 span, u32 pow_bits, unsigned long long* d_best, u32 mix_u64_conv);
 // diagnostic (bfhip_clock_probe): register-only Blake2s loop, per-workgroup {d s_memtime, d s_memrealtime} stamps
 void clock_probe_launch(hipStream_t stream, uint4* d_stamps, u32* d_sink, u32 blocks, u32 iters);

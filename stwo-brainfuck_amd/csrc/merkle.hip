@@ -214,6 +214,74 @@ __global__ void __launch_bounds__(256) k_merkle_layer(uint4* __restrict__ out, c
     }
 }
 
+// ---- FRI commit phase, layers of 2^17 rows and above: the fold inside the leaf launch -------------------------------------------------------
+// A FRI layer is produced by a fold (quotient.hip: k_fold_line_circle / k_fold_circle_into_line) and then hashed four words per row by the
+// MS_LEAF4 shape above: two dependent launches, the first of which writes what the second reads back, with the VALU idle during the first and
+// HBM three quarters idle during the second. Here one lane folds row i from the sibling pair (2i, 2i + 1) of the source, stores its four
+// words (the next fold and the decommitment read them) and hashes them as MS_LEAF4 does. The loop is the MS_LEAF loop: the raw inputs of a
+// lane's next row (source pair, quotient pair, inverse twiddles: 19 VGPRs) are requested before the current row is compressed.
+// The fold expressions are those of k_fold_line_circle and k_fold_circle_into_line, word for word.
+struct FriFoldIn { uint2 s[4]; u32 xinv; uint2 q[4]; u32 cx, cy; };      // a mode's unused members are never written
+template <int MODE>
+__device__ __forceinline__ void fri_fold_load(FriFoldIn& in, const FriFoldLeafArgs& a, u32 i) {
+    if constexpr (MODE != FF_CIRCLE) {
+        in.xinv = a.itw[a.tw_total - (2u << a.log) + i];
+#pragma unroll
+        for (int w = 0; w < 4; w++) in.s[w] = reinterpret_cast<const uint2*>(a.src[w])[i];
+    }
+    if constexpr (MODE != FF_LINE) {
+        const u32* t1 = a.itw + (a.tw_total - (1u << a.log));
+        in.cx = t1[(i >> 2) * 2]; in.cy = t1[(i >> 2) * 2 + 1];
+#pragma unroll
+        for (int w = 0; w < 4; w++) in.q[w] = reinterpret_cast<const uint2*>(a.quot[w])[i];
+    }
+}
+template <int MODE>
+__device__ __forceinline__ Q31 fri_fold_row(const FriFoldIn& in, u32 i, const QConst& k_alpha, const QConst& k_alpha_sq) {
+    Q31 r = q_make(0, 0, 0, 0);
+    if constexpr (MODE != FF_CIRCLE) {
+        const Q31 fx = q_make(in.s[0].x, in.s[1].x, in.s[2].x, in.s[3].x), fn = q_make(in.s[0].y, in.s[1].y, in.s[2].y, in.s[3].y);
+        r = q_add(q_add(fx, fn), q_mul_const(q_mulm(q_sub(fx, fn), in.xinv), k_alpha));
+    }
+    if constexpr (MODE != FF_LINE) {
+        const u32 cx = in.cx, cy = in.cy, sel = i & 3;
+        const u32 yinv = sel == 0 ? cy : sel == 1 ? m_neg(cy) : sel == 2 ? m_neg(cx) : cx;
+        const Q31 fp = q_make(in.q[0].x, in.q[1].x, in.q[2].x, in.q[3].x), fn = q_make(in.q[0].y, in.q[1].y, in.q[2].y, in.q[3].y);
+        const Q31 fprime = q_add(q_mul_const(q_mulm(q_sub(fp, fn), yinv), k_alpha), q_add(fp, fn));
+        r = MODE == FF_CIRCLE ? fprime : q_add(q_mul_const(r, k_alpha_sq), fprime);      // fresh destination: 0 * alpha^2 + f'
+    }
+    return r;
+}
+template <bool RFC, int MODE>
+__global__ void __launch_bounds__(256) k_fri_fold_leaf(uint4* __restrict__ out, const FriFoldLeafArgs a) {
+    const u32 stride = gridDim.x * blockDim.x, n = 1u << a.log;
+    u32 st = blockIdx.x * blockDim.x + threadIdx.x;
+    if (st >= n) return;
+    // alpha || alpha^2 were written by the launch in front of this one (the channel step): wave-uniform, scalar loads
+    u32 al[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) al[k] = ld_constant(a.alpha8 + k);
+    const QConst k_alpha = q_const(q_make(al[0], al[1], al[2], al[3])), k_alpha_sq = q_const(q_make(al[4], al[5], al[6], al[7]));
+    FriFoldIn nx;
+    fri_fold_load<MODE>(nx, a, st);
+    for (;;) {
+        const u32 cur = st;
+        const Q31 r = fri_fold_row<MODE>(nx, cur, k_alpha, k_alpha_sq);
+        st += stride;
+        const bool more = st < n;
+        fri_fold_load<MODE>(nx, a, min(st, n - 1));      // a lane without a next row re-reads the last one: no branch around the loads
+        u32 m[16];
+#pragma unroll
+        for (int k = 4; k < 16; k++) m[k] = 0u;
+        m[0] = r.a.a; m[1] = r.a.b; m[2] = r.b.a; m[3] = r.b.b;
+        a.dst[0][cur] = m[0]; a.dst[1][cur] = m[1]; a.dst[2][cur] = m[2]; a.dst[3][cur] = m[3];
+        u32 h[8];
+        blake2s_compress_first<RFC>(h, m, 16u, true);
+        store_hash(out, cur, h);
+        if (!more) return;
+    }
+}
+
 // Blake2sChannel stepped on the device for the FRI commit phase (FriProver::commit: mix_root(layer root) then draw_felt per layer):
 // removes the device -> host -> device round trip between consecutive layers. One lane; two compressions plus rare redraws.
 // chan = digest[8] || n_sent. alpha_out = alpha[4] || alpha^2[4]. root_out receives a copy of the root (the roots of all layers are
@@ -766,6 +834,24 @@ void merkle_layer(hipStream_t stream, void* out, const void* prev, const ColDesc
     u32 blocks = (n + threads - 1) / threads;
     if (blocks >= (1u << 14)) blocks /= MERKLE_NODES_PER_LANE;   // >= 2^22 nodes: several nodes per lane (measured: 2..16 equivalent, 4 kept)
     (node_conv ? launch_merkle_layer<true> : launch_merkle_layer<false>)(stream, blocks, threads, (uint4*)out, (const uint4*)prev, d_cols, ncols, n, out_shift, prev_shift, count ? first : 0u);
+}
+template <bool RFC>
+static void launch_fri_fold_leaf(hipStream_t stream, u32 blocks, u32 threads, uint4* out, const FriFoldLeafArgs& a, int mode) {
+    auto* k = mode == FF_LINE ? k_fri_fold_leaf<RFC, FF_LINE> : mode == FF_LINE_CIRCLE ? k_fri_fold_leaf<RFC, FF_LINE_CIRCLE> : k_fri_fold_leaf<RFC, FF_CIRCLE>;
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(threads), 0, stream, out, a);
+}
+// Same launch geometry and the same profiler line as the leaf launch it replaces (one compression per row); bytes = everything the launch
+// moves: the sibling pairs and inverse twiddles it reads, the folded row and the hash it writes.
+void fri_fold_leaf(hipStream_t stream, void* out, const FriFoldLeafArgs& a, int mode, u32 node_conv) {
+    if (mode != FF_LINE && mode != FF_LINE_CIRCLE && mode != FF_CIRCLE) throw std::runtime_error("fri_fold_leaf: unknown mode");
+    if (a.log > 29) throw std::runtime_error("fri_fold_leaf: layer too large");
+    const u32 n = 1u << a.log;
+    const u32 threads = n < 256 ? (n < 64 ? 64 : n) : 256;
+    const double per_row = 32.0 + 16.0 + (mode != FF_CIRCLE ? 32.0 + 4.0 : 0.0) + (mode != FF_LINE ? 32.0 + 2.0 : 0.0);
+    ProfScope ps(stream, "k_merkle_layer", per_row * n, (double)n, /*dominant=*/true);
+    u32 blocks = (n + threads - 1) / threads;
+    if (blocks >= (1u << 14)) blocks /= MERKLE_NODES_PER_LANE;
+    (node_conv ? launch_fri_fold_leaf<true> : launch_fri_fold_leaf<false>)(stream, blocks, threads, (uint4*)out, a, mode);
 }
 void merkle_subtree(hipStream_t stream, const MerkleTreeDesc& tree, u32 hi, u32 node_conv, double bytes, double compressions) {
     ProfScope ps(stream, "k_merkle_subtree", bytes, compressions);

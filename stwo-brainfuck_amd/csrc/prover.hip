@@ -260,8 +260,12 @@ struct HipProver {
         // shard group: the band's last levels [band_lo .. band_fuse_hi] as ONE launch over this rank's share (k_merkle_subtree in its general
         // form, a workgroup per 2^band_fuse_r nodes of level band_lo); band_fuse_hi < 0: single-level launches all the way down
         int band_fuse_hi = -1; u32 band_fuse_r = 0; double band_bytes = 0, band_comp = 0;
+        // FRI commit phase: the deepest level's four columns are PRODUCED by its launch (merkle.hip: k_fri_fold_leaf folds the previous layer
+        // into them and hashes each row) — planned with folded_leaves = true, `fold` filled in before merkle_run
+        bool folded_leaves = false; FriFoldLeafArgs fold{}; int fold_mode = -1;
     };
-    MerklePlan merkle_plan(const std::vector<DCol>& cols_in) {
+    // folded_leaves: the deepest level is a launch of its own (never part of the subtree kernel), to be issued as the fused fold + leaf kernel
+    MerklePlan merkle_plan(const std::vector<DCol>& cols_in, bool folded_leaves = false) {
         if (cols_in.empty()) throw HipError("merkle_commit: no columns");
         MerklePlan p;
         p.cols = cols_in;
@@ -327,6 +331,7 @@ struct HipProver {
         // shard group's tree); complete levels above sub_hi are single-level launches
         if (fused_top == 10 && mk.max_log >= 11) {
             u32 hi = std::min<u32>(banded ? (u32)mk.band_lo - 1 : mk.max_log, 17);
+            if (folded_leaves && hi == mk.max_log) hi--;
             while (hi > 10 && mk.shifts[hi] != 0) hi--;
             if (hi > 10) { p.sub_hi = hi; p.fused_top = fused_top = MERKLE_SUBTREE_ROOT_LEVEL; }     // the top starts below the subtree roots
         }
@@ -353,6 +358,11 @@ struct HipProver {
         for (int log = (int)fused_top - 1; log >= 0; log--) level_cost(log, p.top_bytes, p.top_comp);
         if (p.sub_hi) for (int log = (int)p.sub_hi; log >= (int)MERKLE_SUBTREE_ROOT_LEVEL; log--) level_cost(log, p.sub_bytes, p.sub_comp);
         p.d_all = all.empty() ? nullptr : c.stage(all.data(), all.size());
+        if (folded_leaves) {
+            if (banded || p.poseidon || mk.shifts[mk.max_log] != 0 || level_cols((int)mk.max_log) != 4 || (int)mk.max_log < (p.sub_hi ? (int)p.sub_hi + 1 : (int)fused_top))
+                throw HipError("merkle_plan: this tree's deepest level cannot be a fused fold + leaf launch");
+            p.folded_leaves = true;
+        }
         if (fused_top > 0) {
             MerkleTreeDesc td{};
             if (mk.max_log >= 32) throw HipError("merkle: tree too deep");
@@ -392,6 +402,12 @@ struct HipProver {
                 continue;
             }
             size_t n = (log > 0 ? p.off[log - 1] : p.n_all) - p.off[log];
+            if (p.folded_leaves && log == (int)mk.max_log) {
+                if (p.fold_mode < 0 || p.fold.log != mk.max_log) throw HipError("merkle_run: the fold of the deepest level was not described");
+                fri_fold_leaf(c.stream, mk.layers[log], p.fold, p.fold_mode, c.conv.merkle_node_hash);
+                c.last_proof_flags |= 32u;      // bfhip_ctx_last_proof_flags bit 5
+                continue;
+            }
             const bool share = log >= mk.band_lo && log <= mk.band_hi;
             const u32 per_rank = share ? ((1u << (log - mk.shifts[log])) >> sg.log_count) : 0u;   // in stored slots
             if (poseidon)
@@ -1240,7 +1256,7 @@ struct HipProver {
             tm.fri = (now() - t0) - tm.quotients;
         }
 
-        c.last_proof_flags = (c.last_proof_flags & 16u) | (mb ? 1u : 0u) | (reuse && !shared ? 2u : 0u) | (shared ? 4u : 0u) | (replicate() ? 8u : 0u);
+        c.last_proof_flags = (c.last_proof_flags & 48u) | (mb ? 1u : 0u) | (reuse && !shared ? 2u : 0u) | (shared ? 4u : 0u) | (replicate() ? 8u : 0u);
         tm.total = now() - t_start;
         mark("done");
         print_marks();
@@ -1698,12 +1714,27 @@ struct HipProver {
         std::vector<DSecure> layers(n_inner + 1);
         for (u32 i = 0; i <= n_inner; i++) layers[i] = new_layer(line_log - i);
         std::vector<MerklePlan> plans;                  // [0] first layer, [1 + i] inner layer i
+        // Layers of 2^17 rows and above (the ones neither k_fri_layer nor k_fri_tail takes): the fold that produces layer k runs inside the
+        // leaf launch of layer k's tree (merkle.hip: k_fri_fold_leaf) instead of as a launch of its own in front of it — device channel, one
+        // process, neither the folded layer nor what it is folded from cut into row ranges. Everything else keeps the two launches.
+        auto fold_leaf = [&](u32 k) {
+            return !host_channel && c.shard.count == 1 && k < n_inner && line_log - k >= 17 && layers[k].lc == 0 && (k == 0 ? quotients[0].lc == 0 : layers[k - 1].lc == 0);
+        };
+        // what the fused launch of layer k's tree folds: src (2^(log + 1) rows, or nullptr: the first line layer), the circle evaluation of that
+        // size (or nullptr), alpha_k. It runs on the main stream behind every quotient launch and behind the channel step that draws alpha_k.
+        auto describe_fold = [&](u32 k, const DSecure* src, const DSecure* q) {
+            MerklePlan& p = plans[1 + k];
+            FriFoldLeafArgs& fa = p.fold;
+            for (int w = 0; w < 4; w++) { fa.src[w] = src ? src->c[w] : nullptr; fa.quot[w] = q ? q->c[w] : nullptr; fa.dst[w] = layers[k].c[w]; }
+            fa.alpha8 = d_alpha + 8 * k; fa.itw = c.d_itw; fa.tw_total = 1u << c.tw_root_log; fa.log = line_log - k;
+            p.fold_mode = !src ? FF_CIRCLE : q ? FF_LINE_CIRCLE : FF_LINE;
+        };
         if (!host_channel) {
             c.stage_checkpoint();
             StageBatch sb(c);
             plans.reserve(n_inner + 1);
             plans.push_back(merkle_plan(first_cols));
-            for (u32 i = 0; i < n_inner; i++) plans.push_back(merkle_plan(secure_cols(layers[i])));
+            for (u32 i = 0; i < n_inner; i++) plans.push_back(merkle_plan(secure_cols(layers[i]), fold_leaf(i)));
             sb.end();
         }
         auto commit_step = [&](size_t plan_idx, const std::vector<DCol>& cols, u32 alpha_idx, u32 root_idx) -> DevMerkle {
@@ -1742,8 +1773,11 @@ struct HipProver {
             const DSecure& q = quotients[qi++];
             const u32* src[4] = {q.c[0], q.c[1], q.c[2], q.c[3]};
             u32 first, count; fold_range(q.log_size, q.lc != 0, first, count);
-            fold_circle_into_line(c.stream, layers[0].c, src, d_alpha, c.d_itw, c.tw_root_log, q.log_size, /*fresh=*/true, first, count);
-            if (q.lc != 0 && layers[0].lc == 0) complete(layers[0]);
+            if (fold_leaf(0)) describe_fold(0, nullptr, &q);
+            else {
+                fold_circle_into_line(c.stream, layers[0].c, src, d_alpha, c.d_itw, c.tw_root_log, q.log_size, /*fresh=*/true, first, count);
+                if (q.lc != 0 && layers[0].lc == 0) complete(layers[0]);
+            }
         }
         // inner layers: commit layer k (-> alpha_{k+1}), then ONE launch folds it into layer k + 1 together with the quotient of layer k's
         // size (fold_line, then dst * alpha^2 + fold_circle: both with alpha_{k+1}). Below 2^10 rows the rest of the phase is one launch.
@@ -1782,6 +1816,7 @@ struct HipProver {
             const u32* src[4] = {layers[li].c[0], layers[li].c[1], layers[li].c[2], layers[li].c[3]};
             const u32* qs[4] = {q ? q->c[0] : nullptr, q ? q->c[1] : nullptr, q ? q->c[2] : nullptr, q ? q->c[3] : nullptr};
             if (q && (q->lc != 0) != (layers[li].lc != 0)) throw HipError("FRI: a layer and the quotient of its size are sharded differently");
+            if (fold_leaf(li + 1)) { describe_fold(li + 1, &layers[li], q); continue; }      // the next layer's leaf launch folds this one
             u32 first, count; fold_range(log, layers[li].lc != 0, first, count);
             fold_line_circle(c.stream, next.c, src, q ? qs : nullptr, d_alpha + 8 * (li + 1), c.d_itw, c.tw_root_log, log, first, count);
             if (layers[li].lc != 0 && next.lc == 0) complete(next);
