@@ -108,6 +108,34 @@ impl Context {
         Ok(reports)
     }
 
+    /// stwo's relation tracker for an executed machine (`bfhip_trace_relations`): the counts of the three lookup relations (Memory,
+    /// Instruction, Processor) and, per relation, up to `max_entries` tuples whose multiplicities do not cancel — what lies behind a non-zero
+    /// logUp total of `check_machine`. Table index = component; counts are per table row (16 trace cells each).
+    pub fn relations(&self, trace7: &[u32], program: &[u32], max_entries: u32) -> Result<([sys::BfhipRelationReport; 3], Vec<sys::BfhipRelationEntry>), String> {
+        assert!(trace7.len() % 7 == 0);
+        let mut tr: *mut sys::BfhipTrace = std::ptr::null_mut();
+        let rc = unsafe {
+            sys::bfhip_trace_create_from_registers(self.0, trace7.as_ptr(), trace7.len() / 7, program.as_ptr(), program.len(), &mut tr, std::ptr::null_mut(),
+                                                   std::ptr::null_mut(), std::ptr::null_mut())
+        };
+        if rc != 0 {
+            return Err(last_error());
+        }
+        let mut reports = [sys::BfhipRelationReport::default(); 3];
+        let mut entries = vec![sys::BfhipRelationEntry::default(); 3 * max_entries as usize];
+        let entries_ptr = if max_entries == 0 { std::ptr::null_mut() } else { entries.as_mut_ptr() };
+        let rc = unsafe { sys::bfhip_trace_relations(self.0, tr, reports.as_mut_ptr(), entries_ptr, max_entries) };
+        unsafe { sys::bfhip_trace_destroy(self.0, tr) };
+        if rc != 0 {
+            return Err(last_error());
+        }
+        let mut listed = Vec::new();
+        for (r, rep) in reports.iter().enumerate() {
+            listed.extend_from_slice(&entries[r * max_entries as usize..r * max_entries as usize + rep.n_reported as usize]);
+        }
+        Ok((reports, listed))
+    }
+
     /// Byte-level stwo conventions / Merkle channel of this context (`bfhip_conventions`; all zero = defaults).
     pub fn set_conventions(&self, conv: &sys::BfhipConventions) -> Result<(), String> {
         if unsafe { sys::bfhip_ctx_set_conventions(self.0, conv) } != 0 { Err(last_error()) } else { Ok(()) }

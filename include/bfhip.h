@@ -383,6 +383,63 @@ int32_t bfhip_prove_trace(bfhip_ctx* ctx, const bfhip_trace* trace, uint32_t log
 int32_t bfhip_trace_check(bfhip_ctx* ctx, const bfhip_trace* trace, const uint32_t* lookup_h /* u32[24] or NULL */,
                           bfhip_check_report out[13], uint32_t logup_total_h[4], int32_t* n_bad_components);
 
+/* ---- the lookup tuples that do not cancel: which relation entry is yielded and never used, or used and never yielded ----
+ * stwo's relation tracker (the second debugging tool it ships for AIR authors beside `assert_constraints`) over the row-granular tables.
+ * A non-zero logUp total (bfhip_trace_check; `lookup_sum_valid`, mod.rs:207-226) says that the lookups do not balance, not which
+ * tuple is to blame; a trace can satisfy all 13 AIRs row by row and still fail there (an opcode that is no instruction: the Processor
+ * table yields its row into the Processor relation and no opcode table consumes it). These entry points name the tuples.
+ * The three relations, their tuples and who adds to them (`add_to_relation` of components/<name>/component.rs, restated in csrc/air.h; d = the
+ * table's dummy column; the multiplicity of a table row is its logUp numerator, an M31 value):
+ *   0 Memory      (clk, mp, mv), 3 words               yields (1 - d): Processor cols 0, 4, 5, d = col 7
+ *                                                      uses   (d - 1): Memory cols 0, 1, 2, d = col 3
+ *   1 Instruction (ip, ci, ni), 3 words                yields (1 - d): Processor cols 1, 2, 3; Program cols 0, 1, 2, d = col 3
+ *                                                      uses   (d - 1): Instruction cols 0, 1, 2, d = col 3
+ *   2 Processor   (clk, ip, ci, ni, mp, mv, mvi), 7    yields (1 - d): Processor cols 0..6
+ *                                                      uses   (d - 1): jnz, jz cols 0..6, d = col 11; input, left, minus, output, plus, right
+ *                                                                      cols 0..6, d = col 7; end_of_execution cols 0..6, always -1
+ * A table row with numerator 0 contributes nothing and is no entry. Numerator 1 counts as a yield, p - 1 as a use, anything else (a d that
+ * is not boolean) as "other". net of a tuple = the sum of its numerators in M31, canonical; a tuple is unbalanced iff net != 0. Counts
+ * are per TABLE ROW: every row stands for 16 trace cells (LOG_N_LANES = 4), so the logUp sum sees 16 x net of each tuple.
+ * Layouts (natural alignment, declaration order):
+ *   bfhip_relation_entry   96 bytes: relation 0, n_words 4, tuple 8, net 36, n_yield 40, n_use 48, n_other 56, first_yield_table 64,
+ *                                    first_use_table 68, first_yield_row 72, first_use_row 80, reserved 88
+ *   bfhip_relation_report  48 bytes: relation 0, n_words 4, n_entries 8, n_tuples 16, n_unbalanced 24, n_reported 32, reserved 40
+ *   bfhip_relation_table   16 bytes: component 0, log_size 4, main_rows_h 8 */
+typedef struct bfhip_relation_entry {
+    uint32_t relation, n_words;
+    uint32_t tuple[7];                 /* the tuple's words, zero padded beyond n_words */
+    uint32_t net;                      /* sum of the numerators, canonical M31; never 0 in a reported entry */
+    uint64_t n_yield, n_use, n_other;  /* table rows with numerator 1 / p - 1 / anything else non-zero */
+    int32_t  first_yield_table, first_use_table;   /* index into the table list; -1 if none */
+    uint64_t first_yield_row, first_use_row;       /* table row; UINT64_MAX if none. "first" = the lowest (table index, row) */
+    uint32_t reserved[2];
+} bfhip_relation_entry;
+typedef struct bfhip_relation_report {
+    uint32_t relation, n_words;
+    uint64_t n_entries;                /* table rows with a non-zero numerator */
+    uint64_t n_tuples;                 /* distinct tuples among them */
+    uint64_t n_unbalanced;             /* tuples with net != 0, whatever the cap */
+    uint64_t n_reported;               /* min(n_unbalanced, cap_per_relation) */
+    uint32_t reserved[2];
+} bfhip_relation_report;
+typedef struct bfhip_relation_table {
+    int32_t component;                 /* claim order, 0..12 */
+    uint32_t log_size;                 /* 2^(log_size - 4) table rows */
+    const uint32_t* const* main_rows_h;   /* host array of device pointers to the row-granular main columns: what bfhip_check_constraints takes */
+} bfhip_relation_table;
+/* Any list of 1..64 caller-supplied tables; a component may be absent or repeated (an integrator of the Rust HipBackend builds the tables
+ * outside this library). out[r] = relation r; relation r's entries go to entries_h + r * cap_per_relation: the unbalanced tuples in
+ * lexicographic order of their words (word 0 most significant, unsigned), the first cap_per_relation of them; slots beyond n_reported are not written. entries_h == NULL with
+ * cap_per_relation == 0 gives the counts only. Every field is an integer and the same whatever the schedule. Uses the context's arena
+ * (reset like a proof resets it). Returns 0 whether or not anything is unbalanced, and bfhip_last_error() is not touched by imbalances;
+ * -1 only for bad arguments (unknown component, log_size outside [4, 29], null pointers, more than 2^31 table rows in total, a context
+ * in a shard group) and HIP errors. */
+int32_t bfhip_relation_summary(bfhip_ctx* ctx, const bfhip_relation_table* tables, uint32_t n_tables, bfhip_relation_report out[3],
+                               bfhip_relation_entry* entries_h, uint32_t cap_per_relation);
+/* The 13 tables of a resident trace (bfhip_trace_create*): table index = component. */
+int32_t bfhip_trace_relations(bfhip_ctx* ctx, const bfhip_trace* trace, bfhip_relation_report out[3], bfhip_relation_entry* entries_h,
+                              uint32_t cap_per_relation);
+
 /* ---- proofs in flight: a pool of sub-contexts on one GPU behind ONE caller thread -------------------------------------------------------------
  * The reference's caller is a single thread of control (prove_brainfuck, mod.rs:471-735); a single proof leaves the GPU partly idle in its
  * single-workgroup chains (tree tops, small FRI layers) and at its Fiat-Shamir round trips. A pool proves the proofs of a batch n_in_flight at a

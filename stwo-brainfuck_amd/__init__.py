@@ -195,6 +195,77 @@ class CheckResult(list):
         return lines
 
 
+RELATION_NAMES = ("memory", "instruction", "processor")
+NO_ROW = (1 << 64) - 1
+
+
+class RelationEntry(ctypes.Structure):
+    """include/bfhip.h `bfhip_relation_entry`: one unbalanced tuple of a lookup relation (stwo's relation tracker)."""
+    _fields_ = [("relation", ctypes.c_uint32), ("n_words", ctypes.c_uint32), ("tuple", ctypes.c_uint32 * 7), ("net", ctypes.c_uint32),
+                ("n_yield", ctypes.c_uint64), ("n_use", ctypes.c_uint64), ("n_other", ctypes.c_uint64),
+                ("first_yield_table", ctypes.c_int32), ("first_use_table", ctypes.c_int32), ("first_yield_row", ctypes.c_uint64), ("first_use_row", ctypes.c_uint64),
+                ("reserved", ctypes.c_uint32 * 2)]
+
+    def as_dict(self):
+        """Named fields; tuple cut to n_words; first_yield / first_use = (table index, row) or None."""
+        return {"relation": int(self.relation), "name": RELATION_NAMES[self.relation], "tuple": tuple(int(v) for v in self.tuple[: self.n_words]), "net": int(self.net),
+                "n_yield": int(self.n_yield), "n_use": int(self.n_use), "n_other": int(self.n_other),
+                "first_yield": None if self.first_yield_table < 0 else (int(self.first_yield_table), int(self.first_yield_row)),
+                "first_use": None if self.first_use_table < 0 else (int(self.first_use_table), int(self.first_use_row))}
+
+
+class RelationReport(ctypes.Structure):
+    """include/bfhip.h `bfhip_relation_report`: the counts of one relation."""
+    _fields_ = [("relation", ctypes.c_uint32), ("n_words", ctypes.c_uint32), ("n_entries", ctypes.c_uint64), ("n_tuples", ctypes.c_uint64),
+                ("n_unbalanced", ctypes.c_uint64), ("n_reported", ctypes.c_uint64), ("reserved", ctypes.c_uint32 * 2)]
+
+    def as_dict(self):
+        return {"relation": int(self.relation), "name": RELATION_NAMES[self.relation], "n_words": int(self.n_words), "n_entries": int(self.n_entries),
+                "n_tuples": int(self.n_tuples), "n_unbalanced": int(self.n_unbalanced), "n_reported": int(self.n_reported)}
+
+
+class RelationTable(ctypes.Structure):
+    """include/bfhip.h `bfhip_relation_table`."""
+    _fields_ = [("component", ctypes.c_int32), ("log_size", ctypes.c_uint32), ("main_rows_h", ctypes.POINTER(ctypes.c_void_p))]
+
+
+def format_relation_entry(entry, table_names=None):
+    """One line for an unbalanced tuple (a dict of RelationEntry.as_dict()), e.g.
+    "processor relation: (1, 1, 35, 43, 0, 1, 1) net +1: yielded 1x (first: processor row 1), used 0x". net is printed signed (values above
+    p / 2 read as negative). table_names[i] names table i of the list the summary ran over; None = COMPONENT_NAMES (a resident trace)."""
+    names = COMPONENT_NAMES if table_names is None else table_names
+    net = entry["net"] - P if entry["net"] > P // 2 else entry["net"]
+    where = lambda at: "" if at is None else " (first: %s row %d)" % (names[at[0]], at[1])
+    line = "%s relation: (%s) net %+d: yielded %dx%s, used %dx%s" % (entry["name"], ", ".join(str(v) for v in entry["tuple"]), net, entry["n_yield"],
+                                                                      where(entry["first_yield"]), entry["n_use"], where(entry["first_use"]))
+    return line + (", %d rows with another multiplicity" % entry["n_other"] if entry["n_other"] else "")
+
+
+class RelationResult:
+    """Context.relation_summary() / Trace.relations(): reports = the 3 relations' counts (dicts), entries = the reported unbalanced tuples
+    (dicts, relation by relation, each in lexicographic order of the tuple), balanced = no relation has an unbalanced tuple."""
+
+    def __init__(self, reports, entries, table_names=None):
+        self.reports, self.entries, self.table_names = reports, entries, table_names
+
+    @property
+    def balanced(self):
+        return all(r["n_unbalanced"] == 0 for r in self.reports)
+
+    def lines(self):
+        """One format_relation_entry line per reported tuple, then one line per relation whose report was cut at max_entries."""
+        out = [format_relation_entry(e, self.table_names) for e in self.entries]
+        out += ["%s relation: %d more unbalanced tuples not listed" % (r["name"], r["n_unbalanced"] - r["n_reported"]) for r in self.reports if r["n_unbalanced"] > r["n_reported"]]
+        return out
+
+
+def _relation_result(call, max_entries, table_names=None):
+    reps = (RelationReport * 3)()
+    ents = (RelationEntry * (3 * max_entries))() if max_entries else None
+    _check(call(reps, ents, max_entries))
+    return RelationResult([r.as_dict() for r in reps], [ents[k * max_entries + i].as_dict() for k in range(3) for i in range(reps[k].n_reported)], table_names)
+
+
 class Context:
     """One GPU + one HIP stream + the twiddle tree (mod.rs:480-487: twiddles, channel and commitment scheme setup)."""
 
@@ -462,6 +533,21 @@ class Context:
                                              self._u32s(lookup24), self._u32s(claimed4), ctypes.byref(rep)))
         return rep.as_dict()
 
+    def relation_summary(self, tables, max_entries=64):
+        """bfhip_relation_summary: the lookup tuples that do not cancel over any list of 1..64 tables. tables: (component, log_size,
+        main_row_ptrs) each — the row-granular device columns check_constraints takes; a component may be absent or repeated. Returns a
+        RelationResult whose lines name table i as "<component name>[i]"; imbalances are a result, not an error."""
+        n_main = (8, 8, 4, 9, 13, 13, 11, 11, 11, 11, 11, 11, 7)      # csrc/air.h: n_main_cols; the library reads that many pointers
+        for comp, _, ptrs in tables:
+            if ptrs is not None and 0 <= comp < 13 and len(ptrs) < n_main[comp]:
+                raise BfhipError("relation summary: %s takes %d main columns, got %d" % (COMPONENT_NAMES[comp], n_main[comp], len(ptrs)))
+        keep = [None if ptrs is None else self._ptr_array(ptrs) for _, _, ptrs in tables]
+        arr = (RelationTable * max(1, len(tables)))()
+        for t, ((comp, log_size, _), ptrs) in enumerate(zip(tables, keep)):
+            arr[t] = RelationTable(comp, log_size, None if ptrs is None else ctypes.cast(ptrs, ctypes.POINTER(ctypes.c_void_p)))
+        names = ["%s[%d]" % (COMPONENT_NAMES[c] if 0 <= c < 13 else "?", t) for t, (c, _, _) in enumerate(tables)]
+        return _relation_result(lambda reps, ents, cap: lib().bfhip_relation_summary(self._h, arr, len(tables), reps, ents, cap), max_entries, names)
+
     def accumulate_quotients(self, log_size, col_ptrs, n_samples, sample_points, sample_values, random_coeff4, out_ptrs, col_shifts=None):
         """QuotientOps::accumulate_quotients for the columns of one LDE size."""
         _check(lib().bfhip_accumulate_quotients(self._h, log_size, self._ptr_array(col_ptrs), None if col_shifts is None else self._u32s(col_shifts), len(col_ptrs),
@@ -687,6 +773,12 @@ class Trace:
         res = CheckResult(r.as_dict() for r in reps)
         res.logup_total, res.n_bad_components = tuple(int(v) for v in total), n_bad.value
         return res
+
+    def relations(self, max_entries=64):
+        """bfhip_trace_relations: the lookup tuples of this trace's 13 tables that do not cancel (stwo's relation tracker), as a
+        RelationResult: .balanced, .reports (3 dicts), .entries (at most max_entries per relation), .lines(). Names what a non-zero
+        check().logup_total cannot: which tuple is yielded and never used, or used and never yielded, and by which table row."""
+        return _relation_result(lambda reps, ents, cap: lib().bfhip_trace_relations(self.ctx._h, self._h, reps, ents, cap), max_entries)
 
     def column(self, component, column):
         n = ctypes.c_size_t()

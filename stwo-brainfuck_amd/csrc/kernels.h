@@ -226,6 +226,10 @@ void check_constraints_launch(hipStream_t stream, int comp, const CheckLaunch* d
 // prover.hip — the row-granular main-trace columns and the log sizes of a resident trace (for bfhip_trace_check in api.hip)
 void trace_columns(const bfhip_trace* t, const u32* cols[N_COMPONENTS][13], u32 log_sizes[N_COMPONENTS]);
 
+// tables.hip — u32 exclusive scan over tiles of 2048 (wraps mod 2^32): out[i] = sum_{j<i} in[j], in == out allowed; returns a device pointer
+// to the grand total (inside `totals`, which needs n / 2048 + 2 words). Shared with relations.hip.
+const u32* exclusive_scan_u32(hipStream_t s, const u32* in, u32* out, u32* totals, u32 n);
+
 // quotient.hip
 struct EvalJob { const u32* coeffs; u32 log_n; u32 point; u32 factor_shift; u32 partial_off; u32 out_idx; u32 pad_; };   // result -> out[out_idx]
 void eval_at_points(hipStream_t stream, const EvalJob* d_jobs, u32 n_jobs, u32 total_partials, const void* d_factors, void* d_partials, void* d_out);

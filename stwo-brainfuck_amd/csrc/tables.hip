@@ -63,7 +63,7 @@ __global__ void __launch_bounds__(256) k_scan_u32_add(u32* __restrict__ out, con
     if (i < n) out[i] += totals[i / SC_TILE];
 }
 // out[i] = sum_{j<i} in[j]; returns a device pointer to the grand total (inside `totals`, which needs n/2048 + 2 words)
-static const u32* exclusive_scan_u32(hipStream_t s, const u32* in, u32* out, u32* totals, u32 n) {
+const u32* exclusive_scan_u32(hipStream_t s, const u32* in, u32* out, u32* totals, u32 n) {
     u32 nb = (n + SC_TILE - 1) / SC_TILE;
     hipLaunchKernelGGL(k_scan_u32_local, dim3(nb), dim3(256), 0, s, in, out, totals, n);
     hipLaunchKernelGGL(k_scan_u32_totals, dim3(1), dim3(256), 0, s, totals, nb);

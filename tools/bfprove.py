@@ -1,17 +1,25 @@
 #!/usr/bin/env python3
-"""prove | verify over the C ABI — the two sub-commands of the reference's bin/brainfuck_prover.rs (prove: :79-139, verify: :141-151) — and
-check, the reference's `assert_constraints` (memory/component.rs:201-208, mod.rs:252-396) for a whole execution:
+"""prove | verify over the C ABI — the two sub-commands of the reference's bin/brainfuck_prover.rs (prove: :79-139, verify: :141-151) —, check,
+the reference's `assert_constraints` (memory/component.rs:201-208, mod.rs:252-396) for a whole execution, and relations, stwo's relation
+tracker for it:
 
   bfprove.py prove  (--file prog.bf | --code '++>,<[>+.<-]') [--input-file in.bin] [--ram-size N] [--output proof.json]
                     [--log-max-rows 24] [--conventions a,b,c,d | --poseidon252] [--all-sets DIR] [PCS options]
   bfprove.py verify proof.json [--log-max-rows 24] [--conventions a,b,c,d | --poseidon252 | --try-all] [PCS options]
   bfprove.py check  (--file prog.bf | --code '++>,<[>+.<-]') [--input-file in.bin] [--ram-size N] [--set-register ROW:NAME=VALUE ...]
+  bfprove.py relations (--file prog.bf | --code ...) [--input-file in.bin] [--ram-size N] [--set-register ROW:NAME=VALUE ...]
+                    [--set-word INDEX=VALUE ...] [--max-entries 64]
 
 check runs the program on the host VM, hands the register trace to the GPU (bfhip_trace_create_from_registers) and asserts the 13 AIRs on
 the trace domain (bfhip_trace_check). It prints `ok`, or one line per failing component — e.g.
 "memory: constraint 6 fails at table row 0 (cell 0), value (2, 0, 0, 0); 16 cells violate it" — and exits with 1: what lies behind a proof
 that fails with ConstraintsNotSatisfied. --set-register alters one register (clk, ip, ci, ni, mp, mv, mvi) of one row of the executed
 trace first: what a faulty VM would hand over.
+
+relations builds the same trace and lists the lookup tuples that do not cancel (bfhip_trace_relations): `balanced`, or one line per tuple —
+e.g. "processor relation: (1, 1, 35, 43, 0, 1, 1) net +1: yielded 1x (first: processor row 1), used 0x" — and exit code 1: what lies behind
+a logUp total that is not zero while every component checks `ok`. --set-word alters one word of the compiled program as well (an opcode
+that is no instruction has to appear in the program and in the register rows).
 
 PCS options (stwo's PcsConfig; the defaults are PcsConfig::default()): --pow-bits 5 --log-blowup-factor 1 --n-queries 3. The proof file does
 not record them: verify with the values the proof was made with. prove prints the config and its security bits (pow + blowup x queries).
@@ -100,6 +108,10 @@ def main():
     k = sub.add_parser("check")
     k.add_argument("--file"); k.add_argument("--code"); k.add_argument("--input-file"); k.add_argument("--ram-size", type=int, default=0)
     k.add_argument("--set-register", action="append", default=[], metavar="ROW:NAME=VALUE")
+    r = sub.add_parser("relations")
+    r.add_argument("--file"); r.add_argument("--code"); r.add_argument("--input-file"); r.add_argument("--ram-size", type=int, default=0)
+    r.add_argument("--set-register", action="append", default=[], metavar="ROW:NAME=VALUE")
+    r.add_argument("--set-word", action="append", default=[], metavar="INDEX=VALUE"); r.add_argument("--max-entries", type=int, default=64)
     add_pcs_options(p); add_pcs_options(v)
     a = ap.parse_args()
     pkg = load_package()
@@ -113,10 +125,11 @@ def main():
 REGISTERS = ("clk", "ip", "ci", "ni", "mp", "mv", "mvi")
 
 
-def check(pkg, a, ap):
+def executed_trace(pkg, a, ap):
+    """The program run on the host VM, --set-register / --set-word applied, as a resident trace: (context, trace)."""
     code = open(a.file).read() if a.file else a.code
     if code is None:
-        ap.error("check needs --file or --code")
+        ap.error(f"{a.cmd} needs --file or --code")
     inp = open(a.input_file, "rb").read() if a.input_file else (b"" if sys.stdin.isatty() else sys.stdin.buffer.read())
     _, rows = pkg.host_run(code, inp, ram_size=a.ram_size)
     for spec in a.set_register:
@@ -126,8 +139,19 @@ def check(pkg, a, ap):
             rows[int(row), REGISTERS.index(name)] = int(value)
         except (ValueError, IndexError):
             ap.error(f"--set-register takes ROW:NAME=VALUE with NAME one of {', '.join(REGISTERS)} and ROW < {rows.shape[0]}, got {spec!r}")
-    ctx = pkg.Context(0, max_log_domain=8)       # the check needs no twiddle tree
-    tr = pkg.Trace.from_registers(ctx, rows, pkg.host_compile(code))
+    words = pkg.host_compile(code)
+    for spec in getattr(a, "set_word", []):
+        try:
+            index, value = spec.split("=")
+            words[int(index)] = int(value)
+        except (ValueError, IndexError):
+            ap.error(f"--set-word takes INDEX=VALUE with INDEX < {words.size}, got {spec!r}")
+    ctx = pkg.Context(0, max_log_domain=8)       # neither the check nor the relation summary needs a twiddle tree
+    return ctx, pkg.Trace.from_registers(ctx, rows, words)
+
+
+def check(pkg, a, ap):
+    ctx, tr = executed_trace(pkg, a, ap)
     res = tr.check()
     tr.close(); ctx.close()
     for line in res.failures():
@@ -137,9 +161,22 @@ def check(pkg, a, ap):
     return 0 if res.ok else 1
 
 
+def relations(pkg, a, ap):
+    ctx, tr = executed_trace(pkg, a, ap)
+    res = tr.relations(a.max_entries)
+    tr.close(); ctx.close()
+    for line in res.lines():
+        print(line)
+    if res.balanced:
+        print("balanced")
+    return 0 if res.balanced else 1
+
+
 def run(pkg, a, ap):
     if a.cmd == "check":
         return check(pkg, a, ap)
+    if a.cmd == "relations":
+        return relations(pkg, a, ap)
     if a.cmd == "prove":
         code = open(a.file).read() if a.file else a.code
         if code is None:
