@@ -459,9 +459,25 @@ struct Prover {
             M31 denom_inv[2];
             for (int i = 0; i < 2; i++) denom_inv[i] = inv(coset_vanishing<M31>(CanonicCoset{l.log_size}.coset(), ed.at(i)));
             std::vector<const u32*> tc(l.n_main), ic(l.n_inter);
-            for (u32 k = 0; k < l.n_main; k++) tc[k] = trees[1].evals[l.main_off + k].values.data();
-            for (u32 k = 0; k < l.n_inter; k++) ic[k] = trees[2].evals[l.inter_off + k].values.data();
-            const u32* isf = trees[0].evals[log_max_rows - l.log_size].values.data();
+            const u32* isf;
+            // The constraints are evaluated on CanonicCoset(log_size + 1) (FrameworkComponent::evaluate_constraint_quotients_on_domain: eval
+            // domain = max_constraint_log_degree_bound = log_size + 1, whatever the blowup). At log_blowup 1 that is the committed LDE itself;
+            // above it the columns are evaluated there from the committed polynomials, one component at a time (`own` dies with the iteration).
+            std::vector<EvalCol> own;
+            if (cfg.log_blowup == 1) {
+                for (u32 k = 0; k < l.n_main; k++) tc[k] = trees[1].evals[l.main_off + k].values.data();
+                for (u32 k = 0; k < l.n_inter; k++) ic[k] = trees[2].evals[l.inter_off + k].values.data();
+                isf = trees[0].evals[log_max_rows - l.log_size].values.data();
+            } else {
+                own.resize(l.n_main + l.n_inter + 1);
+#pragma omp parallel for schedule(dynamic)
+                for (u32 k = 0; k < l.n_main + l.n_inter + 1; k++)
+                    own[k] = evaluate_poly(k < l.n_main ? trees[1].polys[l.main_off + k] : k < l.n_main + l.n_inter ? trees[2].polys[l.inter_off + k - l.n_main]
+                                                                                          : trees[0].polys[log_max_rows - l.log_size], eval_log, tw);
+                for (u32 k = 0; k < l.n_main; k++) tc[k] = own[k].values.data();
+                for (u32 k = 0; k < l.n_inter; k++) ic[k] = own[l.n_main + k].values.data();
+                isf = own[l.n_main + l.n_inter].values.data();
+            }
             size_t n = size_t(1) << eval_log;
 #pragma omp parallel for schedule(static)
             for (size_t row = 0; row < n; row++) {

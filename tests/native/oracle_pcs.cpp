@@ -1,8 +1,9 @@
 // Test shim over the CPU oracle (oracle/*.h, the checker): prove and verify under an explicit PcsConfig. The oracle's own C ABI
 // (oracle/oracle_capi.cpp) fixes PcsConfig::default(); tests/test_pcs_config_cpu.py and tests/test_gpu_pcs_config.py build this file with g++
 // into a temporary directory (next to oracle/simd_port.cpp, which the headers call into) and load it with ctypes.
-// The oracle's commitment, FRI, proof-of-work and decommitment code is generic in the config. Its compute_composition reads the trace LDE as
-// the constraint domain, which is CanonicCoset(log_size + 1) at log_blowup_factor 1 only: above that its proofs are exact up to the root2 tap.
+// The oracle's commitment, sampling, quotient, FRI, proof-of-work and decommitment code is generic in the config. Its compute_composition
+// evaluates the constraints on CanonicCoset(log_size + 1): at log_blowup_factor 1 that is the committed LDE, above it the columns are evaluated
+// there from the committed polynomials (oracle/prover.h). Whole proofs are the byte-exact reference at every log_blowup_factor.
 #include "json.h"
 #include <cstdio>
 
@@ -29,7 +30,7 @@ int ops_set_conventions(u32 merkle_node_hash, u32 mix_u64, u32 logup_mask_order,
 }
 
 // The proof (malloc'd JSON) and the transcript taps ("name:hexdigest\n" per tap, malloc'd; optional) under the given config. A proof that
-// fails (at log_blowup_factor > 1 the oracle's composition is not a low-degree polynomial) still returns the taps it reached.
+// fails still returns the taps it reached.
 int ops_prove(const char* code, const u8* input, size_t n_in, u32 log_max_rows, u32 pow_bits, u32 log_blowup, u32 n_queries,
               char** json_out, size_t* json_len, char** transcript_out) {
     std::string transcript;

@@ -1,7 +1,7 @@
 """ctypes view of tests/native/oracle_pcs.cpp: the CPU oracle (the checker) proving and verifying under an explicit PcsConfig.
 Built with g++ into a temporary directory by the `oracle_pcs` fixtures of tests/test_pcs_config_cpu.py and tests/test_gpu_pcs_config.py.
-At log_blowup_factor > 1 the oracle's proofs are exact up to the root2 tap only (its constraint evaluation reads the LDE as the constraint
-domain, see the source's header)."""
+Its proofs are the byte-exact reference at every log_blowup_factor (above 1 the oracle evaluates the constraints on their own domain, see the
+source's header)."""
 import ctypes
 import os
 import subprocess
@@ -43,16 +43,8 @@ class OraclePcs:
         return proof, dict(line.split(":") for line in taps.strip().split("\n"))
 
     def taps(self, code, inp=b"", log_max_rows=20, pow_bits=5, log_blowup_factor=1, n_queries=3):
-        """The transcript taps the oracle reaches under this config, whether or not its proof completes (at log_blowup_factor > 1 it
-        stops at the composition: ConstraintsNotSatisfied)."""
-        js, n, tr = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_void_p()
-        rc = self.L.ops_prove(code.encode(), inp, ctypes.c_size_t(len(inp)), log_max_rows, pow_bits, log_blowup_factor, n_queries,
-                              ctypes.byref(js), ctypes.byref(n), ctypes.byref(tr))
-        taps = ctypes.string_at(tr).decode()
-        self.L.ops_free(tr)
-        if rc == 0:
-            self.L.ops_free(js)
-        return dict(line.split(":") for line in taps.strip().split("\n") if line)
+        """The transcript taps of the oracle's proof under this config."""
+        return self.prove(code, inp, log_max_rows, pow_bits, log_blowup_factor, n_queries)[1]
 
     def verify(self, js, log_max_rows=20, pow_bits=5, log_blowup_factor=1, n_queries=3):
         err = ctypes.create_string_buffer(512)

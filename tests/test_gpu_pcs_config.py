@@ -1,8 +1,10 @@
 """-m gpu: proofs under a configurable PcsConfig (include/bfhip.h `bfhip_pcs_config`). Every non-default config must give the bytes of the CPU
 oracle proving under the same config (tests/native/oracle_pcs.cpp), through a single context, a pool and a kept preprocessed tree, in either
 launch order; the proof-of-work search must find GrindOps' smallest nonce at the larger pow_bits; and what the device prover does not
-support must fail with a clear error and leave the context usable. Above log_blowup_factor 1 the oracle is exact up to the root2 tap only:
-there the proofs are checked by both verifiers, against single-flip corruptions, and against each other across contexts, pools and launch orders."""
+support must fail with a clear error and leave the context usable. That holds above log_blowup_factor 1 too (there the oracle evaluates the
+constraints on CanonicCoset(log_size + 1) from its committed polynomials, as the device prover does): every proof made here at b > 1 is
+compared byte for byte, and tap for tap, with the oracle's, on top of both verifiers, single-flip corruptions and the comparisons across
+contexts, pools and launch orders (fib19 at full size with the digest of the oracle's proof, a committed fixture)."""
 import ctypes
 import hashlib
 import json
@@ -11,6 +13,7 @@ import os
 import pytest
 
 import oracle_pcs
+from bf_fuzz import random_program
 
 pytestmark = pytest.mark.gpu
 
@@ -34,6 +37,34 @@ def shim(_shim, conv):
     _shim.set_conventions(*conv)
     yield _shim
     _shim.set_conventions()
+
+
+@pytest.fixture
+def stwo_shim(_shim):
+    """The shim under the default conventions, for the tests that are not parametrised over `conv`."""
+    _shim.set_conventions()
+    yield _shim
+    _shim.set_conventions()
+
+
+_SHIM_PROOFS = {}     # the oracle's (proof, taps) per (conventions, program, input, log_max_rows, config): each CPU proof is made once per module run
+
+
+def _want(shim, conv, code, inp, lmr, cfg):
+    """The oracle's (proof bytes, taps) under cfg; `shim` is set to `conv` already (the `shim` and `stwo_shim` fixtures)."""
+    key = (tuple(conv), code, inp, lmr, cfg.pow_bits, cfg.log_blowup_factor, cfg.n_queries)
+    if key not in _SHIM_PROOFS:
+        _SHIM_PROOFS[key] = shim.prove(code, inp, lmr, pow_bits=cfg.pow_bits, log_blowup_factor=cfg.log_blowup_factor, n_queries=cfg.n_queries)
+    return _SHIM_PROOFS[key]
+
+
+def _assert_oracle_bytes(got, taps, want, want_taps, what=""):
+    """Taps first: the first one that differs names the phase (root3: composition; sampled: OODS; fri_commit: quotients or folds; equal taps
+    and different bytes: proof of work or decommitment)."""
+    assert set(want_taps) == {"root0", "root1", "root2", "root3", "sampled", "fri_commit"}
+    for k in ("root0", "root1", "root2", "root3", "sampled", "fri_commit"):
+        assert taps[k] == want_taps[k], (k, what)
+    assert got == want, what
 
 
 @pytest.fixture(scope="module")
@@ -120,13 +151,11 @@ def _flip_first_value(proof, *path):
 
 @pytest.mark.parametrize("lmr", [17, 20])
 @pytest.mark.parametrize("b,pw,q", [(2, 12, 20), (3, 8, 24), (4, 10, 20)])
-def test_blowup_above_1_verifies_and_matches_the_oracle_through_root2(pkg, shim, bctx, conv, lmr, b, pw, q):
+def test_blowup_above_1_gives_the_shim_oracle_bytes(pkg, shim, bctx, conv, lmr, b, pw, q):
+    """At log_max_rows 17 and b >= 2 the first FRI line layers have 2^17 rows or more: the fused fold-and-leaf launch runs under these configs."""
     cfg = pkg.PcsConfig(pow_bits=pw, log_blowup_factor=b, n_queries=q)
     got, taps = pkg.prove_brainfuck(CODE, INP, ctx=bctx, log_max_rows=lmr, with_transcript=True, pcs_config=cfg)
-    want_taps = shim.taps(CODE, INP, lmr, pow_bits=pw, log_blowup_factor=b, n_queries=q)
-    # the oracle's composition reads its LDE as the constraint domain: exact up to the interaction root at b > 1
-    for k in ("root0", "root1", "root2"):
-        assert taps[k] == want_taps[k], k
+    _assert_oracle_bytes(got, taps, *_want(shim, conv, CODE, INP, lmr, cfg))
     assert pkg.verify_brainfuck(got, lmr, conventions=conv, pcs_config=cfg) == (True, "")
     assert shim.verify(got, lmr, pow_bits=pw, log_blowup_factor=b, n_queries=q) == (True, "")
     assert not pkg.verify_brainfuck(got, lmr, conventions=conv)[0]
@@ -143,8 +172,8 @@ def test_blowup_above_1_verifies_and_matches_the_oracle_through_root2(pkg, shim,
 def test_large_blowups_the_config_promises(pkg, shim, conv, b, lmr, code, inp):
     """bfhip_pcs_config advertises 1 <= log_blowup_factor <= 16. From 6 up (5 with a 2^5-row component) the row-granular columns of the 2^4- and
     2^5-row components are polynomials of ONE or TWO coefficients extended past 32 cells, which the transform planner used to refuse: every
-    such proof failed. Same assertions as above; the oracle's taps are compared for 5 and 6 (at 8 and 16 the CPU proof is left out: the two
-    verifiers and the rejection under b - 1 carry the check)."""
+    such proof failed. Same assertions as above, whole proofs and all taps against the oracle included (b = 16 at log_max_rows 8 too: its CPU
+    proof, on domains of 2^24 and more cells, took 50 s on 8 cores when this was written)."""
     pw, q = 8, 6
     cfg = pkg.PcsConfig(pow_bits=pw, log_blowup_factor=b, n_queries=q)
     c = pkg.Context(0, max_log_domain=lmr + b + 1)
@@ -152,10 +181,7 @@ def test_large_blowups_the_config_promises(pkg, shim, conv, b, lmr, code, inp):
         got, taps = pkg.prove_brainfuck(code, inp, ctx=c, log_max_rows=lmr, with_transcript=True, pcs_config=cfg)
     finally:
         c.close()
-    if b <= 6:
-        want_taps = shim.taps(code, inp, lmr, pow_bits=pw, log_blowup_factor=b, n_queries=q)
-        for k in ("root0", "root1", "root2"):
-            assert taps[k] == want_taps[k], k
+    _assert_oracle_bytes(got, taps, *_want(shim, conv, code, inp, lmr, cfg))
     assert pkg.verify_brainfuck(got, lmr, conventions=conv, pcs_config=cfg) == (True, "")
     assert shim.verify(got, lmr, pow_bits=pw, log_blowup_factor=b, n_queries=q) == (True, "")
     assert not pkg.verify_brainfuck(got, lmr, conventions=conv)[0]
@@ -163,6 +189,35 @@ def test_large_blowups_the_config_promises(pkg, shim, conv, b, lmr, code, inp):
     bad = _flip_first_value(got, "proof", "queried_values", 1)
     assert not pkg.verify_brainfuck(bad, lmr, conventions=conv, pcs_config=cfg)[0]
     assert not shim.verify(bad, lmr, pow_bits=pw, log_blowup_factor=b, n_queries=q)[0]
+
+
+def _ten_sizes_program():
+    return random_program(40402, 6000, min_steps=300)[:2]      # tests/test_gpu_fuzz.py::test_program_with_ten_distinct_component_sizes
+
+
+SMALL_SHAPES = {
+    "ten_component_sizes": (_ten_sizes_program, 17),      # its memory table has 2^17 rows: the one shape here above 2^14
+    "a-bc": (lambda: (_prog("a-bc.bf"), b"a"), 12),
+    "32_row_component": (lambda: ("++[-]+.", b""), 12),
+    "empty_loops": (lambda: ("[][]+[-]", b""), 14),
+}
+SMALL_SHAPES.update({"fuzz_seed_%d" % s: (lambda s=s: random_program(s, 400, min_steps=20)[:2], 12 + s % 3) for s in range(701, 707)})
+
+
+@pytest.mark.parametrize("b", [2, 3])
+@pytest.mark.parametrize("shape", list(SMALL_SHAPES))
+def test_small_shapes_at_blowup_2_and_3_give_the_shim_oracle_bytes(pkg, shim, bctx, conv, shape, b):
+    """Other component-size patterns than the sweep program's, at log_max_rows 12 to 14: components of 16 and 32 rows under preprocessed
+    columns of 2^12 rows and more, loops that never run, six generated programs — and ten distinct component sizes (ten composition
+    accumulators, each evaluated on its own domain), whose program needs log_max_rows 17."""
+    make, lmr = SMALL_SHAPES[shape]
+    code, inp = make()
+    cfg = pkg.PcsConfig(pow_bits=8, log_blowup_factor=b, n_queries=12)
+    got, taps = pkg.prove_brainfuck(code, inp, ctx=bctx, log_max_rows=lmr, with_transcript=True, pcs_config=cfg)
+    if shape == "ten_component_sizes":
+        assert len({c["log_size"] for c in json.loads(got)["claim"].values()}) >= 10
+    _assert_oracle_bytes(got, taps, *_want(shim, conv, code, inp, lmr, cfg), what=code)
+    assert pkg.verify_brainfuck(got, lmr, conventions=conv, pcs_config=cfg) == (True, "")
 
 
 @pytest.mark.single_conv
@@ -211,11 +266,12 @@ def test_shard_group_keeps_the_default_config(pkg, oracle):
         g.close()
 
 
-def test_pool_batch_gives_the_single_context_bytes(pkg, bctx, conv):
+def test_pool_batch_gives_the_single_context_bytes(pkg, shim, bctx, conv):
     cfg = pkg.PcsConfig(pow_bits=12, log_blowup_factor=2, n_queries=20)
     progs = [(CODE, INP), ("++[-]+.", b""), (_prog("a-bc.bf"), b"a"), ("[][]+[-]", b"")]
     bctx.set_pcs_config(cfg)
     want = [pkg.prove_brainfuck(c, i, ctx=bctx, log_max_rows=18) for c, i in progs]
+    assert want == [_want(shim, conv, c, i, 18, cfg)[0] for c, i in progs]      # ... which are the oracle's: the pool is pinned through them
     pool = pkg.Pool(0, n_in_flight=2, max_log_domain=21)
     try:
         pool.set_conventions(*conv)
@@ -236,11 +292,13 @@ def _fresh_proof(pkg, cfg, lmr=18):
 
 
 @pytest.mark.single_conv
-def test_kept_preprocessed_trees_follow_the_blowup(pkg):
+def test_kept_preprocessed_trees_follow_the_blowup(pkg, stwo_shim):
     """Pool mode 2 and a context that keeps its preprocessed tree, alternating b = 1 -> 2 -> 1 -> 2: every proof is a fresh context's bytes
-    (the IsFirst LDE depends on the blowup: a tree kept from the other blowup must not serve the proof)."""
+    (the IsFirst LDE depends on the blowup: a tree kept from the other blowup must not serve the proof), and those are the oracle's."""
     seq = [pkg.PcsConfig(pow_bits=8, log_blowup_factor=b, n_queries=20) for b in (1, 2, 1, 2)]
     want = {cfg.log_blowup_factor: _fresh_proof(pkg, cfg) for cfg in seq[:2]}
+    for cfg in seq[:2]:
+        assert want[cfg.log_blowup_factor] == _want(stwo_shim, (0, 0, 0, 0), CODE, INP, 18, cfg)[0], cfg
     c = pkg.Context(0, max_log_domain=21)
     pool = pkg.Pool(0, n_in_flight=2, max_log_domain=21, preprocessed=2)
     try:
@@ -261,7 +319,7 @@ def test_kept_preprocessed_trees_follow_the_blowup(pkg):
 
 
 @pytest.mark.single_conv
-def test_mailbox_order_on_and_off_give_the_same_bytes(pkg):
+def test_mailbox_order_on_and_off_give_the_same_bytes(pkg, stwo_shim):
     code = _prog("collatz.bf")
     c = pkg.Context(0, max_log_domain=24)
     try:
@@ -272,6 +330,7 @@ def test_mailbox_order_on_and_off_give_the_same_bytes(pkg):
             got.append(pkg.prove_brainfuck(code, b"7\n", ctx=c, log_max_rows=21))
             assert c.last_proof_flags()["mailbox_order"] == (mode == 1)
         assert got[0] == got[1]
+        assert got[0] == _want(stwo_shim, (0, 0, 0, 0), code, b"7\n", 21, c.pcs_config())[0]
         assert pkg.verify_brainfuck(got[0], 21, pcs_config=c.pcs_config()) == (True, "")
     finally:
         c.close()
@@ -306,7 +365,8 @@ def test_poseidon252_with_a_non_default_config_verifies(pkg, shim, pctx):
     pctx.set_conventions(0, 0, 0, 1)
     shim.set_conventions(0, 0, 0, 1)
     cfg = pkg.PcsConfig(pow_bits=8, log_blowup_factor=2, n_queries=10)
-    got = pkg.prove_brainfuck(CODE, INP, ctx=pctx, log_max_rows=17, pcs_config=cfg)
+    got, taps = pkg.prove_brainfuck(CODE, INP, ctx=pctx, log_max_rows=17, with_transcript=True, pcs_config=cfg)
+    _assert_oracle_bytes(got, taps, *_want(shim, (0, 0, 0, 1), CODE, INP, 17, cfg))
     assert pkg.verify_brainfuck(got, 17, conventions=(0, 0, 0, 1), pcs_config=cfg) == (True, "")
     assert shim.verify(got, 17, pow_bits=8, log_blowup_factor=2, n_queries=10) == (True, "")
     assert not pkg.verify_brainfuck(got, 17, conventions=(0, 0, 0, 1))[0]
@@ -314,6 +374,8 @@ def test_poseidon252_with_a_non_default_config_verifies(pkg, shim, pctx):
 
 @pytest.mark.single_conv
 def test_fib19_full_size_at_b2_pow20_q20_verifies(pkg):
+    """The oracle's proof at this size takes minutes and 56 GiB: its size and SHA-256 are a fixture (tests/golden/make_fib19_b2_proof_digest.py)."""
+    golden = json.load(open(os.path.join(HERE, "golden", "fib19_lmr24_b2_pow20_q20_oracle_proof.json")))["stwo"]
     cfg = pkg.PcsConfig(pow_bits=20, log_blowup_factor=2, n_queries=20)
     c = pkg.Context(0, max_log_domain=27)
     try:
@@ -323,6 +385,8 @@ def test_fib19_full_size_at_b2_pow20_q20_verifies(pkg):
         tr.close()
     finally:
         c.close()
+    assert golden["pcs_config"] == {"pow_bits": cfg.pow_bits, "log_blowup_factor": cfg.log_blowup_factor, "n_queries": cfg.n_queries}
+    assert (len(proof), hashlib.sha256(proof).hexdigest()) == (golden["proof_bytes"], golden["sha256"])
     assert pkg.verify_brainfuck(proof, 24, pcs_config=cfg) == (True, "")
     assert not pkg.verify_brainfuck(proof, 24)[0]
     bad = proof.replace(b'"proof_of_work":', b'"proof_of_work":1', 1)
