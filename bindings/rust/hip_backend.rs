@@ -23,7 +23,7 @@ use stwo_prover::constraint_framework::{FrameworkComponent, FrameworkEval};
 use stwo_prover::core::air::accumulation::{AccumulationOps, DomainEvaluationAccumulator};
 use stwo_prover::core::air::{ComponentProver, Trace};
 use stwo_prover::core::backend::{Backend, BackendForChannel, Col, Column, ColumnOps};
-use stwo_prover::core::channel::Blake2sChannel;
+use stwo_prover::core::channel::{Blake2sChannel, Poseidon252Channel};
 use stwo_prover::core::circle::{CirclePoint, Coset};
 use stwo_prover::core::fields::m31::BaseField;
 use stwo_prover::core::fields::qm31::SecureField;
@@ -370,6 +370,15 @@ impl GrindOps<Blake2sChannel> for HipBackend {
     fn grind(channel: &Blake2sChannel, pow_bits: u32) -> u64 {
         let mut nonce = 0u64;
         check(unsafe { sys::bfhip_grind(ctx().p(), channel.digest().0.as_ptr(), pow_bits, &mut nonce) });
+        nonce
+    }
+}
+impl GrindOps<Poseidon252Channel> for HipBackend {
+    fn grind(channel: &Poseidon252Channel, pow_bits: u32) -> u64 {
+        let mut digest = channel.digest().to_bytes_be();      // the entry point takes the felt252 as canonical little-endian bytes
+        digest.reverse();
+        let mut nonce = 0u64;
+        check(unsafe { sys::bfhip_grind_poseidon252(ctx().p(), digest.as_ptr(), pow_bits, 0, &mut nonce, std::ptr::null_mut()) });
         nonce
     }
 }

@@ -206,6 +206,11 @@ int32_t bfhip_fri_fold_leaf(bfhip_ctx* ctx, const uint32_t* const src_d[4], cons
                             const uint32_t alpha_h[4], void* out_hashes_d);
 /* GrindOps::grind for Blake2sChannel: smallest nonce such that mix_u64(nonce) on `digest_h` (32 bytes) leaves >= pow_bits trailing zeros. */
 int32_t bfhip_grind(bfhip_ctx* ctx, const uint8_t digest_h[32], uint32_t pow_bits, uint64_t* nonce);
+/* GrindOps::grind for Poseidon252Channel: the smallest nonce >= start_nonce such that poseidon_hash(digest, nonce) — the digest after
+ * mix_u64(nonce) — has >= pow_bits trailing zeros in that channel's sense. digest_h: the felt252 digest as its canonical 32
+ * little-endian bytes (a value >= p is refused). tried (may be NULL): nonces scanned = launches x span. */
+int32_t bfhip_grind_poseidon252(bfhip_ctx* ctx, const uint8_t digest_h[32], uint32_t pow_bits, uint64_t start_nonce,
+                                uint64_t* nonce, uint64_t* tried);
 /* Decommitment reads: out_h[j] = col_d[idx_h[j]] for n positions of one column. */
 int32_t bfhip_gather(bfhip_ctx* ctx, const uint32_t* col_d, const uint64_t* idx_h, size_t n, uint32_t* out_h);
 

@@ -499,6 +499,17 @@ class Context:
         _check(lib().bfhip_grind(self._h, bytes(digest32), pow_bits, ctypes.byref(nonce)))
         return nonce.value
 
+    def grind_poseidon252(self, digest32, pow_bits, start_nonce=0, with_tried=False):
+        """GrindOps::grind for Poseidon252Channel: the smallest nonce >= start_nonce whose poseidon_hash(digest, nonce) has >= pow_bits
+        trailing zeros in that channel's sense. digest32: the felt252 digest as 32 canonical little-endian bytes.
+        with_tried: also return the number of nonces scanned (launches x span)."""
+        digest32 = bytes(digest32)
+        if len(digest32) != 32:
+            raise ValueError("grind_poseidon252: the digest is 32 bytes")
+        nonce, tried = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().bfhip_grind_poseidon252(self._h, digest32, ctypes.c_uint32(pow_bits), ctypes.c_uint64(start_nonce), ctypes.byref(nonce), ctypes.byref(tried)))
+        return (nonce.value, tried.value) if with_tried else nonce.value
+
     def gather(self, col_ptr, indices):
         idx = np.ascontiguousarray(indices, dtype=np.uint64)
         out = np.empty(idx.size, dtype=np.uint32)

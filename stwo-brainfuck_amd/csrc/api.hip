@@ -683,6 +683,36 @@ int32_t bfhip_grind(bfhip_ctx* ctx, const uint8_t digest_h[32], uint32_t pow_bit
     return 0;
     API_CATCH
 }
+// Spans start at start_nonce and are scanned in order, so the first span with a hit holds the smallest nonce. Span per launch: 2^clamp(pow_bits - 4, 12, 20)
+// — twice the expected 2^(pow_bits - 5) tries, at least 64 waves, at most ~1.4 ms of the GPU per launch.
+int32_t bfhip_grind_poseidon252(bfhip_ctx* ctx, const uint8_t digest_h[32], uint32_t pow_bits, uint64_t start_nonce, uint64_t* nonce, uint64_t* tried) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    if (!digest_h || !nonce) throw HipError("grind_poseidon252: null argument");
+    if (pow_bits > BFHIP_MAX_POW_BITS) throw HipError("grind_poseidon252: pow_bits must be at most 32, got " + std::to_string(pow_bits));
+    if (!fe252::canonical_bytes_in_range(digest_h)) throw HipError("grind_poseidon252: digest is not a canonical felt252");
+    c.stage_checkpoint();
+    u32* d_digest = (u32*)c.stage(digest_h, 32);
+    unsigned long long init = ~0ull, best = ~0ull;
+    unsigned long long* d_best = c.stage(&init, 1);
+    const u32 log_span = std::min(std::max(pow_bits, 16u) - 4u, 20u);
+    const u64 span = u64(1) << log_span, limit = u64(64) << (std::max(pow_bits, 8u) - 5u);      // a legitimate miss of `limit` nonces: e^-64
+    u64 scanned = 0;
+    while (best == ~0ull) {
+        if (scanned >= limit) throw HipError("grind_poseidon252: no nonce found");
+        const u64 base = start_nonce + scanned;
+        if (base < start_nonce || base + (span - 1) < base) throw HipError("grind_poseidon252: the scan would wrap past 2^64");
+        grind_poseidon_span(c.stream, d_digest, base, (u32)span, pow_bits, d_best);
+        BF_HIP(hipGetLastError());
+        BF_HIP(hipMemcpyAsync(&best, d_best, 8, hipMemcpyDeviceToHost, c.stream));
+        c.sync();
+        scanned += span;
+    }
+    *nonce = best;
+    if (tried) *tried = scanned;
+    return 0;
+    API_CATCH
+}
 int32_t bfhip_gather(bfhip_ctx* ctx, const uint32_t* col_d, const uint64_t* idx_h, size_t n, uint32_t* out_h) {
     API_CTX(ctx)
     Ctx& c = ctx->c;

@@ -174,6 +174,8 @@ void channel_mix_root_draw(hipStream_t stream, u32* d_chan, const u32* d_root, u
 void merkle_layer_poseidon(hipStream_t stream, void* out, const void* prev, const ColDesc* d_cols, u32 ncols, u32 log, u32 out_shift = 0, u32 prev_shift = 0,
                            u32 first = 0, u32 count = 0);
 void hades_once(hipStream_t stream, const u32* d_in24, u32* d_out24);
+// Poseidon252Channel proof of work: scans the nonces [base, base + span) (span a multiple of 128), keeps the smallest hit in *d_best (atomicMin)
+void grind_poseidon_span(hipStream_t stream, const u32* d_digest, u64 base, u32 span, u32 pow_bits, unsigned long long* d_best);
 
 // air.hip
 struct ConstraintLaunch {

@@ -9,6 +9,7 @@
 // 4 full + 83 partial + 4 full rounds, MDS [[3,1,1],[1,-1,1],[1,1,-2]]) is 214 field multiplications ≈ 90 k lane-ops: this hasher
 // is ~90x more VALU work per 64 hashed bytes than Blake2s — firmly VALU-bound. The permutation is pinned by the public Hades([0,0,0])
 // known-answer vector (tests/test_gpu_poseidon.py); the node layout is recalled from stwo (unpinned).
+// Also here, beside the constants block: k_grind_poseidon, the Poseidon252Channel proof-of-work search (bfhip_grind_poseidon252).
 #include "kernels.h"
 #include "poseidon_constants.h"
 #include "poseidon_dev.h"
@@ -63,6 +64,31 @@ __global__ void k_hades_once(const u32* __restrict__ in, u32* __restrict__ out, 
     for (int k = 0; k < 3; k++) { const Fe y = f9_to_canonical(s[k], pc); for (int i = 0; i < 8; i++) out[8 * k + i] = y.l[i]; }
 }
 
+// Proof-of-work search for Poseidon252Channel (GrindOps::grind): the smallest nonce whose poseidon_hash(digest, nonce) = Hades([digest, nonce,
+// 2])[0] — the digest after mix_u64(nonce) — has >= pow_bits trailing zeros in that channel's sense (host/hash.h Channel::trailing_zeros: the
+// first 16 bytes of the big-endian form read as a little-endian u128, i.e. ctz over bswap(w7), bswap(w6), bswap(w5), bswap(w4) taken low to
+// high; 128 when all four are zero). One nonce per lane, the state in registers like tools/ubench_poseidon.hip's k_hades; the minimum hit of
+// the launch is kept. digest: 8 canonical little-endian words. The grid covers the span exactly (a multiple of 128 lanes).
+__global__ void __launch_bounds__(128) k_grind_poseidon(const u32* __restrict__ digest, u64 base, u32 pow_bits, unsigned long long* __restrict__ best,
+                                                        const u32* __restrict__ consts) {
+    const u64 nonce = base + (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    const PoseidonConsts pc(consts);
+    Fe d, n;
+#pragma unroll
+    for (int k = 0; k < 8; k++) { d.l[k] = digest[k]; n.l[k] = 0; }
+    n.l[0] = (u32)nonce; n.l[1] = (u32)(nonce >> 32);
+    F9 s[3];
+    s[0] = f9_from_canonical(d, pc);
+    s[1] = f9_from_canonical(n, pc);
+    s[2] = f9_add_const(f9_load_const(pc.R1), pc.R1);       // 2 in Montgomery form: R1 + R1 limb-wise (< 2 p), swept back to normalised limbs
+    f9_normalise(s[2]);
+    hades(s, pc.table);
+    const Fe h = f9_to_canonical(s[0], pc);
+    const u32 b7 = __builtin_bswap32(h.l[7]), b6 = __builtin_bswap32(h.l[6]), b5 = __builtin_bswap32(h.l[5]), b4 = __builtin_bswap32(h.l[4]);
+    const u32 tz = b7 ? __ffs(b7) - 1 : b6 ? 32 + __ffs(b6) - 1 : b5 ? 64 + __ffs(b5) - 1 : b4 ? 96 + __ffs(b4) - 1 : 128;
+    if (tz >= pow_bits) atomicMin(best, (unsigned long long)nonce);
+}
+
 static u32* g_poseidon_consts[64] = {nullptr};   // per device; tiny (8.8 KB each), kept for the life of the process
 static std::mutex g_poseidon_mutex;
 static const u32* poseidon_consts() {
@@ -94,6 +120,11 @@ void merkle_layer_poseidon(hipStream_t stream, void* out, const void* prev, cons
 }
 void hades_once(hipStream_t stream, const u32* d_in24, u32* d_out24) {
     hipLaunchKernelGGL(k_hades_once, dim3(1), dim3(64), 0, stream, d_in24, d_out24, poseidon_consts());
+}
+
+void grind_poseidon_span(hipStream_t stream, const u32* d_digest, u64 base, u32 span, u32 pow_bits, unsigned long long* d_best) {
+    ProfScope ps(stream, "k_grind_poseidon", 0.0, (double)span);       // units: Hades permutations
+    hipLaunchKernelGGL(k_grind_poseidon, dim3(span / 128), dim3(128), 0, stream, d_digest, base, pow_bits, d_best, poseidon_consts());
 }
 
 }  // namespace bf

@@ -1886,7 +1886,8 @@ struct HipProver {
         tap("fri_commit");
 
         // proof of work (GrindOps): GPU search in spans, smallest nonce wins. Poseidon252Channel: one Hades permutation per nonce and a
-        // 1-in-16 hit rate at pow_bits = 5 (the test reads the top byte of the big-endian digest) — searched on the host.
+        // 1-in-8 hit rate at pow_bits = 5 (the test reads the top byte of the big-endian digest, which is 0..8) — searched on the host: at the
+        // cap of 12 bits that is 128 expected permutations, less than a launch and a read-back of bfhip_grind_poseidon252's kernel.
         if (host_channel) {
             u64 nonce = 0;
             for (;; nonce++) { Channel t = ch; t.mix_u64(nonce); if (t.trailing_zeros() >= cfg.pow_bits) break; if (nonce > (u64(1) << 32)) throw HipError("grind: no nonce found"); }
