@@ -1,6 +1,6 @@
 // C ABI (include/bfhip.h) over the gfx950 kernels. No torch types, plain pointers and sizes.
 #include "../../include/bfhip.h"
-#include "ctx.h"
+#include "api_guard.h"
 #include <cstdlib>
 #include "host/circle.h"
 #include "host/quotients.h"
@@ -14,10 +14,6 @@ using namespace bf;
 
 static thread_local std::string g_err;
 void bfhip_set_error(const std::string& s) { g_err = s; }
-
-#define API_TRY try {
-#define API_CTX(ctx) try { if (!(ctx)) throw HipError("null context"); (ctx)->c.bind();
-#define API_CATCH } catch (const std::exception& e) { g_err = e.what(); return -1; } catch (...) { g_err = "unknown error"; return -1; }
 
 namespace bf {
 
@@ -92,6 +88,7 @@ void Ctx::destroy() {
     if (stream || stream2 || h_stage || h_small || d_stage) (void)hipSetDevice(device);      // may run on any thread (a destructor)
     if (stream) (void)hipStreamSynchronize(stream);
     if (stream2) (void)hipStreamSynchronize(stream2);
+    preprocessed_cache_drop(*this);      // the kept preprocessed tree: nothing reads it any more, and its memory goes before the streams do
     for (auto& a : aux) if (a) { (void)hipStreamSynchronize(a); prof_forget(a); (void)hipStreamDestroy(a); a = nullptr; }
     for (auto& e : evp) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     for (auto& e : reap_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
@@ -268,7 +265,7 @@ int32_t bfhip_ctx_create(int32_t device_id, uint32_t max_log_domain, bfhip_ctx**
     return 0;
     API_CATCH
 }
-int32_t bfhip_ctx_destroy(bfhip_ctx* ctx) { API_TRY if (ctx) { bfhip_ctx_reuse_preprocessed(ctx, 0); delete ctx; } return 0; API_CATCH }
+int32_t bfhip_ctx_destroy(bfhip_ctx* ctx) { API_TRY delete ctx; return 0; API_CATCH }
 // ---- shard groups: one proof over several GPUs (comm.h) ------------------------------------------------------------------------------
 struct bfhip_local_group { std::shared_ptr<LocalGroup> g; uint32_t count; };
 static void join_group(bfhip_ctx* ctx, std::unique_ptr<Comm> comm) {
@@ -287,12 +284,13 @@ static void check_group_size(const bfhip_ctx* ctx, uint32_t rank, uint32_t count
 }
 int32_t bfhip_local_group_create(uint32_t count, bfhip_local_group** out) {
     API_TRY
+    if (!out) throw HipError("null argument");
     check_group_size(nullptr, 0, count);
     *out = new bfhip_local_group{local_group_create(count), count};
     return 0;
     API_CATCH
 }
-int32_t bfhip_local_group_destroy(bfhip_local_group* g) { delete g; return 0; }   // members that have not left yet keep the rendezvous alive
+int32_t bfhip_local_group_destroy(bfhip_local_group* g) { API_TRY delete g; return 0; API_CATCH }   // members that have not left yet keep the rendezvous alive
 int32_t bfhip_ctx_join_local_group(bfhip_ctx* ctx, bfhip_local_group* group, uint32_t rank) {
     API_CTX(ctx)
     if (!group) throw HipError("null group");
@@ -302,7 +300,7 @@ int32_t bfhip_ctx_join_local_group(bfhip_ctx* ctx, bfhip_local_group* group, uin
     return 0;
     API_CATCH
 }
-int32_t bfhip_rccl_unique_id(uint8_t id[128]) { API_TRY rccl_unique_id(id); return 0; API_CATCH }
+int32_t bfhip_rccl_unique_id(uint8_t id[128]) { API_TRY if (!id) throw HipError("null argument"); rccl_unique_id(id); return 0; API_CATCH }
 int32_t bfhip_ctx_join_rccl_group(bfhip_ctx* ctx, const uint8_t id[128], uint32_t rank, uint32_t count) {
     API_CTX(ctx)
     check_group_size(ctx, rank, count);
@@ -313,6 +311,7 @@ int32_t bfhip_ctx_join_rccl_group(bfhip_ctx* ctx, const uint8_t id[128], uint32_
 }
 int32_t bfhip_ctx_group_stats(bfhip_ctx* ctx, uint64_t out[4]) {
     API_CTX(ctx)
+    if (!out) throw HipError("null argument");
     const Comm* m = ctx->c.shard.comm.get();
     out[0] = m ? m->n_all_gather : 0; out[1] = m ? m->n_all_reduce : 0; out[2] = m ? m->n_exchange : 0; out[3] = m ? m->bytes_sent : 0;
     return 0;
@@ -320,6 +319,7 @@ int32_t bfhip_ctx_group_stats(bfhip_ctx* ctx, uint64_t out[4]) {
 }
 int32_t bfhip_ctx_group_times(bfhip_ctx* ctx, double out_ms[3]) {
     API_CTX(ctx)
+    if (!out_ms) throw HipError("null argument");
     out_ms[0] = out_ms[1] = out_ms[2] = 0.0;
     if (Comm* m = ctx->c.shard.comm.get()) { ctx->c.sync(); m->times_ms(out_ms); }
     return 0;
@@ -411,7 +411,7 @@ int32_t bfhip_ctx_set_conventions(bfhip_ctx* ctx, const bfhip_conventions* conv)
         cv.merkle_node_hash = conv->merkle_node_hash; cv.mix_u64 = conv->mix_u64; cv.logup_mask_order = conv->logup_mask_order; cv.merkle_channel = conv->merkle_channel;
     }
     ctx->c.sync();
-    // a kept preprocessed tree is keyed on the hasher it was built with (prover.hip: PreprocessedCache::matches) and dropped here as well
+    // a kept preprocessed tree is keyed on the hasher it was built with (prover.h: PreprocessedCache::matches) and dropped here as well
     if (cv.merkle_node_hash != ctx->c.conv.merkle_node_hash || cv.merkle_channel != ctx->c.conv.merkle_channel) preprocessed_cache_invalidate(&ctx->c);
     ctx->c.conv = cv;
     return 0;
@@ -422,7 +422,7 @@ int32_t bfhip_ctx_set_pcs_config(bfhip_ctx* ctx, const bfhip_pcs_config* pcs) {
     PcsConfig cfg = pcs_config_from(pcs);
     if (ctx->c.shard.count > 1 && !cfg.is_default()) throw HipError("bfhip_ctx_set_pcs_config: a context in a shard group keeps the default config");
     ctx->c.sync();
-    // a kept preprocessed tree is keyed on the blowup it was built with (prover.hip: PreprocessedCache::matches)
+    // a kept preprocessed tree is keyed on the blowup it was built with (prover.h: PreprocessedCache::matches)
     ctx->c.pcs = cfg;
     return 0;
     API_CATCH
@@ -472,6 +472,7 @@ int32_t bfhip_ctx_memory(bfhip_ctx* ctx, uint64_t out[4]) {
 }
 int32_t bfhip_ctx_get_conventions(bfhip_ctx* ctx, bfhip_conventions* out) {
     API_CTX(ctx)
+    if (!out) throw HipError("null argument");
     bfhip_conventions r{};
     r.merkle_node_hash = ctx->c.conv.merkle_node_hash; r.mix_u64 = ctx->c.conv.mix_u64; r.logup_mask_order = ctx->c.conv.logup_mask_order; r.merkle_channel = ctx->c.conv.merkle_channel;
     *out = r;
@@ -491,7 +492,7 @@ int32_t bfhip_download(bfhip_ctx* ctx, void* dst_h, const void* src_d, size_t by
 int32_t bfhip_memset_zero(bfhip_ctx* ctx, void* dst_d, size_t bytes) { API_CTX(ctx) BF_HIP(hipMemsetAsync(dst_d, 0, bytes, ctx->c.stream)); return 0; API_CATCH }
 
 int32_t bfhip_twiddles(bfhip_ctx* ctx, const uint32_t** tw_d, const uint32_t** itw_d, uint32_t* root_log) {
-    API_CTX(ctx) *tw_d = ctx->c.d_tw; *itw_d = ctx->c.d_itw; *root_log = ctx->c.tw_root_log; return 0; API_CATCH
+    API_CTX(ctx) if (!tw_d || !itw_d || !root_log) throw HipError("null argument"); *tw_d = ctx->c.d_tw; *itw_d = ctx->c.d_itw; *root_log = ctx->c.tw_root_log; return 0; API_CATCH
 }
 
 int32_t bfhip_interpolate(bfhip_ctx* ctx, uint32_t* const* src_cols_h, uint32_t* const* dst_cols_h, uint32_t n_cols, uint32_t log_size, int32_t replicated) {

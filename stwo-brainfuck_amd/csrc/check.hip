@@ -3,7 +3,7 @@
 // Replaces stwo's `assert_constraints` (constraint_framework/assert.rs: AssertEvaluator over every row of the trace), which the reference's
 // component tests are built on — the positive cases at memory/component.rs:163-209 and brainfuck_air/mod.rs:252-396 (all 13 components),
 // the ten negative cases at memory/component.rs:211-609, whose panic texts quote the failing row and value. The prover only says
-// "ConstraintsNotSatisfied" after a whole proof (prover.hip, the out-of-domain check); this pass names the component, the constraint
+// "ConstraintsNotSatisfied" after a whole proof (prover.hip: HipProver::prove, the out-of-domain check); this pass names the component, the constraint
 // and the row: one streaming read of the columns, no transform, no hashing.
 //
 // A lane owns one domain cell (storage index, bit-reversed circle-domain order) and evaluates the component's AIR body of air.h with

@@ -96,6 +96,9 @@ struct Ctx {
     bool owns_tables = true;
     // Set by a pool for the duration of a batch (pool.hip): the preprocessed tree every proof of the batch takes instead of committing its own.
     const struct SharedPreprocessed* shared_pre = nullptr;
+    // The preprocessed tree this context keeps across proofs (bfhip_ctx_reuse_preprocessed; prover.h: PreprocessedCache). Owned: created by
+    // preprocessed_cache_of(), released by preprocessed_cache_drop() (destroy() does, behind its stream synchronisations).
+    struct PreprocessedCache* pre_cache = nullptr;
     uint2* d_tlo = nullptr; uint2* d_thi = nullptr;   // G^a (a < 2^16) and G^(b << 16) (b < 2^15) point tables
     Arena arena;
     // pinned staging for pointer arrays / small parameter blocks
@@ -242,9 +245,12 @@ struct Ctx {
     }
 };
 
-// Scope of one staging batch: blocks staged inside are moved by one copy at end(); an exception unwinds the batch without copying.
-void preprocessed_cache_invalidate(Ctx* c);   // prover.hip: called when the context joins or leaves a shard group
-// prover.hip, for pool.hip: the preprocessed tree a pool's builder context commits once for all proofs of a batch (Ctx::shared_pre)
+// prover_commit.hip: the preprocessed tree a context keeps (Ctx::pre_cache)
+struct PreprocessedCache;
+PreprocessedCache& preprocessed_cache_of(Ctx& c);   // created on first use
+void preprocessed_cache_drop(Ctx& c);               // frees the kept tree; the caller has waited for the streams that may read it
+void preprocessed_cache_invalidate(Ctx* c);         // called when the context joins or leaves a shard group
+// prover_commit.hip, for pool.hip: the preprocessed tree a pool's builder context commits once for all proofs of a batch (Ctx::shared_pre)
 struct SharedPreprocessed;
 SharedPreprocessed* shared_preprocessed_create(Ctx& builder);
 void shared_preprocessed_destroy(SharedPreprocessed* sp);
@@ -300,6 +306,7 @@ struct Mailbox {
     ~Mailbox() { if (open) c.stage_batch_depth = 0; post(); }
 };
 
+// Scope of one staging batch: blocks staged inside are moved by one copy at end(); an exception unwinds the batch without copying.
 struct StageBatch {
     Ctx& c; bool open = true;
     explicit StageBatch(Ctx& c_) : c(c_) { c.stage_begin(); }

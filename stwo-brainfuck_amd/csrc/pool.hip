@@ -9,11 +9,11 @@
 //   - the twiddle tree and the circle-point tables of sub-context 0 (read-only after creation; 2 x 2^(max_log_domain - 1) words not held k times);
 //   - by default ONE preprocessed commitment per batch (IsFirst(LOG_MAX_ROWS ..= 4): trace independent, mod.rs:495-500 recommits it in every
 //     prove_brainfuck call): a builder context enqueues it before the workers start and every proof of the batch reads that tree
-//     (prover.hip: SharedPreprocessed). With it a worker needs ONE stream, so k workers + the builder stay within the 4 hardware queues a
+//     (prover.h: SharedPreprocessed). With it a worker needs ONE stream, so k workers + the builder stay within the 4 hardware queues a
 //     process gets by default (ctx.h: ensure_aux / ensure_side).
 // Everything else is per sub-context as before: arena, staging ring, pinned slots, streams.
 #include "../../include/bfhip.h"
-#include "ctx.h"
+#include "api_guard.h"
 #include <atomic>
 #include <condition_variable>
 #include <mutex>
@@ -120,17 +120,14 @@ struct bfhip_pool {
     }
 };
 
-#define POOL_TRY try { if (!pool) throw HipError("null pool");
-#define POOL_CATCH } catch (const std::exception& e) { bfhip_set_error(e.what()); return -1; } catch (...) { bfhip_set_error("unknown error"); return -1; }
-
 extern "C" {
 
 int32_t bfhip_pool_create(int32_t device_id, uint32_t n_in_flight, uint32_t max_log_domain, bfhip_pool** out) {
-    bfhip_pool* pool = nullptr;
+    API_TRY
+    if (!out) throw HipError("null argument");
+    if (n_in_flight < 1 || n_in_flight > 16) throw HipError("bfhip_pool_create: n_in_flight must be in [1, 16]");
+    bfhip_pool* pool = new bfhip_pool();
     try {
-        if (!out) throw HipError("null argument");
-        if (n_in_flight < 1 || n_in_flight > 16) throw HipError("bfhip_pool_create: n_in_flight must be in [1, 16]");
-        pool = new bfhip_pool();
         pool->device = device_id; pool->k = n_in_flight; pool->max_log_domain = max_log_domain;
         for (uint32_t i = 0; i < n_in_flight; i++) {
             pool->subs.push_back(new bfhip_ctx());
@@ -140,67 +137,68 @@ int32_t bfhip_pool_create(int32_t device_id, uint32_t n_in_flight, uint32_t max_
         pool->builder->c.init(device_id, max_log_domain, &pool->subs[0]->c);
         pool->shared = shared_preprocessed_create(pool->builder->c);
         for (uint32_t w = 0; w < n_in_flight; w++) pool->threads.emplace_back([pool, w] { pool->worker(w); });
-        *out = pool;
-        return 0;
-    } catch (const std::exception& e) { delete pool; bfhip_set_error(e.what()); return -1; } catch (...) { delete pool; bfhip_set_error("unknown error"); return -1; }
+    } catch (...) { delete pool; throw; }      // ~bfhip_pool joins the workers and releases whatever exists
+    *out = pool;
+    return 0;
+    API_CATCH
 }
 
-int32_t bfhip_pool_destroy(bfhip_pool* pool) { try { delete pool; return 0; } catch (...) { bfhip_set_error("unknown error"); return -1; } }
+int32_t bfhip_pool_destroy(bfhip_pool* pool) { API_TRY delete pool; return 0; API_CATCH }
 
-int32_t bfhip_pool_size(bfhip_pool* pool, uint32_t* n_in_flight) { POOL_TRY if (!n_in_flight) throw HipError("null argument"); *n_in_flight = pool->k; return 0; POOL_CATCH }
+int32_t bfhip_pool_size(bfhip_pool* pool, uint32_t* n_in_flight) { API_POOL(pool) if (!n_in_flight) throw HipError("null argument"); *n_in_flight = pool->k; return 0; API_CATCH }
 
 int32_t bfhip_pool_ctx(bfhip_pool* pool, uint32_t i, bfhip_ctx** out) {
-    POOL_TRY
+    API_POOL(pool)
     if (!out) throw HipError("null argument");
     if (i >= pool->k) throw HipError("bfhip_pool_ctx: index out of range");
     *out = pool->subs[i];
     return 0;
-    POOL_CATCH
+    API_CATCH
 }
 
 int32_t bfhip_pool_set_conventions(bfhip_pool* pool, const bfhip_conventions* conv) {
-    POOL_TRY
+    API_POOL(pool)
     std::lock_guard<std::mutex> call(pool->call_mu);
     for (auto* s : pool->subs) if (bfhip_ctx_set_conventions(s, conv) != 0) return -1;
     if (bfhip_ctx_set_conventions(pool->builder, conv) != 0) return -1;
     shared_preprocessed_invalidate(pool->shared);
     return 0;
-    POOL_CATCH
+    API_CATCH
 }
 
 int32_t bfhip_pool_set_pcs_config(bfhip_pool* pool, const bfhip_pcs_config* pcs) {
-    POOL_TRY
+    API_POOL(pool)
     std::lock_guard<std::mutex> call(pool->call_mu);
     for (auto* s : pool->subs) if (bfhip_ctx_set_pcs_config(s, pcs) != 0) return -1;
     if (bfhip_ctx_set_pcs_config(pool->builder, pcs) != 0) return -1;
     shared_preprocessed_invalidate(pool->shared);
     return 0;
-    POOL_CATCH
+    API_CATCH
 }
 
 int32_t bfhip_pool_set_preprocessed(bfhip_pool* pool, int32_t mode) {
-    POOL_TRY
+    API_POOL(pool)
     if (mode < 0 || mode > 2) throw HipError("bfhip_pool_set_preprocessed: 0 = per proof, 1 = per batch, 2 = kept across batches");
     std::lock_guard<std::mutex> call(pool->call_mu);
     pool->pre_mode = mode;
     if (mode != 2) shared_preprocessed_invalidate(pool->shared);
     return 0;
-    POOL_CATCH
+    API_CATCH
 }
 
 int32_t bfhip_prove_batch(bfhip_pool* pool, const bfhip_trace* const* traces, uint32_t n, uint32_t log_max_rows, char** proofs_json, size_t* proof_lens,
                           int32_t* statuses, double* seconds) {
-    POOL_TRY
+    API_POOL(pool)
     if (n && !traces) throw HipError("null argument");
     for (uint32_t i = 0; i < n; i++) if (!traces[i]) throw HipError("null trace in the batch");
     Job j; j.traces = traces; j.n = n; j.log_max_rows = log_max_rows; j.json = proofs_json; j.len = proof_lens; j.status = statuses; j.seconds = seconds;
     return pool->run(j);
-    POOL_CATCH
+    API_CATCH
 }
 
 int32_t bfhip_prove_batch_brainfuck(bfhip_pool* pool, const char* const* codes, const uint8_t* const* inputs_h, const size_t* n_inputs, uint32_t n,
                                     uint32_t log_max_rows, char** proofs_json, size_t* proof_lens, int32_t* statuses, double* seconds) {
-    POOL_TRY
+    API_POOL(pool)
     if (n && !codes) throw HipError("null argument");
     if (inputs_h && !n_inputs) throw HipError("inputs without their lengths");
     for (uint32_t i = 0; i < n; i++) {
@@ -210,7 +208,7 @@ int32_t bfhip_prove_batch_brainfuck(bfhip_pool* pool, const char* const* codes, 
     Job j; j.codes = codes; j.inputs = inputs_h; j.n_inputs = n_inputs; j.n = n; j.log_max_rows = log_max_rows; j.json = proofs_json; j.len = proof_lens;
     j.status = statuses; j.seconds = seconds;
     return pool->run(j);
-    POOL_CATCH
+    API_CATCH
 }
 
 }  // extern "C"

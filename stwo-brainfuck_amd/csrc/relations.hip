@@ -18,7 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 #include "kernels.h"
-#include "ctx.h"
+#include "api_guard.h"
 #include "air.h"
 
 namespace bf {
@@ -327,23 +327,20 @@ static void relations_run(Ctx& c, const RelTable* tables, u32 n_tables, bfhip_re
 
 using namespace bf;
 
-#define REL_API_CTX(ctx) try { if (!(ctx)) throw HipError("null context"); (ctx)->c.bind();
-#define REL_API_CATCH } catch (const std::exception& e) { bfhip_set_error(e.what()); return -1; } catch (...) { bfhip_set_error("unknown error"); return -1; }
-
 int32_t bfhip_relation_summary(bfhip_ctx* ctx, const bfhip_relation_table* tables, uint32_t n_tables, bfhip_relation_report out[3],
                                bfhip_relation_entry* entries_h, uint32_t cap_per_relation) {
-    REL_API_CTX(ctx)
+    API_CTX(ctx)
     if (!tables || !out || (!entries_h && cap_per_relation)) throw HipError("null argument");
     if (n_tables < 1 || n_tables > 64) throw HipError("relation summary: 1 to 64 tables");
     RelTable t[64];
     for (u32 i = 0; i < n_tables; i++) t[i] = RelTable{tables[i].component, tables[i].log_size, tables[i].main_rows_h};
     relations_run(ctx->c, t, n_tables, out, entries_h, cap_per_relation);
     return 0;
-    REL_API_CATCH
+    API_CATCH
 }
 
 int32_t bfhip_trace_relations(bfhip_ctx* ctx, const bfhip_trace* trace, bfhip_relation_report out[3], bfhip_relation_entry* entries_h, uint32_t cap_per_relation) {
-    REL_API_CTX(ctx)
+    API_CTX(ctx)
     if (!trace || !out || (!entries_h && cap_per_relation)) throw HipError("null argument");
     const u32* rows[N_COMPONENTS][13] = {};
     u32 log_sizes[N_COMPONENTS];
@@ -352,5 +349,5 @@ int32_t bfhip_trace_relations(bfhip_ctx* ctx, const bfhip_trace* trace, bfhip_re
     for (int k = 0; k < N_COMPONENTS; k++) t[k] = RelTable{k, log_sizes[k], rows[k]};
     relations_run(ctx->c, t, N_COMPONENTS, out, entries_h, cap_per_relation);
     return 0;
-    REL_API_CATCH
+    API_CATCH
 }

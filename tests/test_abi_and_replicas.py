@@ -156,6 +156,8 @@ def test_host_entries_survive_null_and_invalid_arguments():
     signal exit code): all return, with -1 / 1 where the reference would panic."""
     import subprocess, sys, textwrap
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    messages = {"compile_null_count": "null argument", "compile_null_out": "null argument", "run_null_input": "null argument", "table_null_counts": "null argument",
+                "local_group_null_out": "null argument", "reuse_preprocessed_null": "null context"}
     prog = textwrap.dedent("""
         import ctypes, sys
         sys.path.insert(0, %r)
@@ -182,18 +184,58 @@ def test_host_entries_survive_null_and_invalid_arguments():
             "pool_batch_null": lambda: L.bfhip_prove_batch(None, None, 0, 20, None, None, None, None),
             "pool_programs_null": lambda: L.bfhip_prove_batch_brainfuck(None, None, None, None, 0, 20, None, None, None, None),
             "pool_ctx_null": lambda: L.bfhip_pool_ctx(None, 0, None),
+            # partly-null arguments: the valid ones take the call past its first checks
+            "compile_null_count": lambda: L.bfhip_host_compile(b"+", None, z, None),
+            "compile_null_out": lambda: L.bfhip_host_compile(b"+", None, ctypes.c_size_t(8), ctypes.byref(n)),
+            "run_null_input": lambda: L.bfhip_host_run(b",", None, ctypes.c_size_t(1), None, z, ctypes.byref(n), None, z, ctypes.byref(m)),
+            "table_null_counts": lambda: L.bfhip_host_table((ctypes.c_uint32 * 7)(), ctypes.c_size_t(1), (ctypes.c_uint32 * 1)(43), ctypes.c_size_t(1), 0, None, z, None, None),
+            "local_group_null_out": lambda: L.bfhip_local_group_create(2, None),
+            "reuse_preprocessed_null": lambda: L.bfhip_ctx_reuse_preprocessed(None, 1),
         }
-        print(calls[sys.argv[1]]())
-    """) % os.path.join(root, "tests")
+        rc = calls[sys.argv[1]]()
+        if sys.argv[1] in %r:
+            print(L.bfhip_last_error().decode())
+        print(rc)
+    """) % (os.path.join(root, "tests"), sorted(messages))
     expect = {"compile_null": -1, "run_null_code": -1, "table_bad_component": -1, "verify_null": 1, "verify_no_error_buffer": 1, "ctx_create_null_out": -1,
               "pool_create_null_out": -1, "pool_create_zero": -1, "pool_destroy_null": 0, "pool_batch_null": -1, "pool_programs_null": -1, "pool_ctx_null": -1}
+    expect.update({name: -1 for name in messages})
     for name in ["compile_null", "run_null_code", "run_null_counts", "table_null", "table_bad_component", "verify_null", "verify_no_error_buffer",
                  "ctx_destroy_null", "trace_destroy_null", "free_host_null", "component_shape_null", "ctx_create_null_out", "pool_create_null_out",
-                 "pool_create_zero", "pool_destroy_null", "pool_batch_null", "pool_programs_null", "pool_ctx_null"]:
+                 "pool_create_zero", "pool_destroy_null", "pool_batch_null", "pool_programs_null", "pool_ctx_null"] + sorted(messages):
         r = subprocess.run([sys.executable, "-c", prog, name], capture_output=True, text=True, timeout=120)
         assert r.returncode == 0, (name, r.returncode, r.stderr[-300:])
         if name in expect:
             assert int(r.stdout.strip().splitlines()[-1]) == expect[name], (name, r.stdout)
+        if name in messages:
+            assert r.stdout.strip().splitlines()[-2] == messages[name], (name, r.stdout)
+
+
+def test_every_entry_point_survives_all_null_arguments():
+    """Every function include/bfhip.h declares, called with twelve null / zero arguments in ONE child process: each returns (the shared
+    error boundary of the C ABI, csrc/api_guard.h, and the null checks in front of it). The name is printed before the call, so a crash
+    names its culprit."""
+    import subprocess, sys, textwrap
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    prog = textwrap.dedent("""
+        import ctypes, sys
+        sys.path.insert(0, %r)
+        from conftest import load_package
+        L = load_package().lib()
+        for name in sys.argv[1:]:
+            print(name, flush=True)
+            f = getattr(L, name)
+            if name == "bfhip_free_host":
+                f.restype = None
+            f(*([None] * 12))
+        print("survived", len(sys.argv) - 1)
+    """) % os.path.join(root, "tests")
+    syms = declared_symbols()
+    assert len(syms) >= 91
+    r = subprocess.run([sys.executable, "-c", prog] + syms, capture_output=True, text=True, timeout=120)
+    lines = r.stdout.strip().splitlines()
+    assert r.returncode == 0, ("died in", lines[-1] if lines else None, r.returncode, r.stderr[-300:])
+    assert "survived %d" % len(syms) in lines      # (a library the sweep made the process load may still write a line of its own at exit)
 
 
 def test_rccl_exchange_bookkeeping_through_a_mock_library(tmp_path):

@@ -1,4 +1,4 @@
-"""Counts the Blake2s compressions k_merkle_layer performs for one proof (same layer/shift rules as prover.hip::merkle_commit),
+"""Counts the Blake2s compressions k_merkle_layer performs for one proof (same layer/shift rules as prover_commit.hip: HipProver::merkle_plan),
 given the 13 component log sizes and LOG_MAX_ROWS. Used for the VALU roofline of the Merkle kernel in bench.py / DESIGN.md."""
 import sys
 
@@ -16,7 +16,7 @@ def shape_of(has_prev, n_cols):
 def tree(cols, fused_top_limit=10, census=None):
     """cols: list of (log_size, shift). Returns (compressions in k_merkle_layer, compressions in k_merkle_top).
     census: dict shape -> [first-block compressions, later-block compressions] of the levels hashed by single k_merkle_layer launches (>= 2^18 stored
-    nodes; the smaller levels above `fused` in this count are hashed by k_merkle_subtree, which prover.hip accounts under its own name)."""
+    nodes; the smaller levels above `fused` in this count are hashed by k_merkle_subtree, which prover_commit.hip accounts under its own name)."""
     cols = sorted(cols, key=lambda c: -c[0])
     max_log, min_log = cols[0][0], cols[-1][0]
     shifts = {}
