@@ -54,20 +54,16 @@ impl Context {
     }
 
     /// `prove_brainfuck(&Machine)` as the reference receives it (`mod.rs:471-473`): the executed machine's register trace
-    /// (`inputs.trace()`, `mod.rs:508`; 7 words per row: clk, ip, ci, ni, mp, mv, mvi) and its program words — no re-execution.
+    /// (`inputs.trace()`, `mod.rs:508`; 7 words per row: clk, ip, ci, ni, mp, mv, mvi) and its program words — no re-execution, and ONE
+    /// call (`bfhip_prove_registers`): the rows are transposed and checked on the GPU while it already commits the preprocessed tree, and no
+    /// resident trace is created. A non-canonical register is an `Err` that names its (row, register).
     pub fn prove_machine(&self, trace7: &[u32], program: &[u32], log_max_rows: u32) -> Result<Vec<u8>, String> {
         assert!(trace7.len() % 7 == 0);
-        let mut tr: *mut sys::BfhipTrace = std::ptr::null_mut();
-        let rc = unsafe {
-            sys::bfhip_trace_create_from_registers(self.0, trace7.as_ptr(), trace7.len() / 7, program.as_ptr(), program.len(), &mut tr, std::ptr::null_mut(),
-                                                   std::ptr::null_mut(), std::ptr::null_mut())
-        };
-        if rc != 0 {
-            return Err(last_error());
-        }
         let (mut js, mut len): (*mut c_char, usize) = (std::ptr::null_mut(), 0);
-        let rc = unsafe { sys::bfhip_prove_trace(self.0, tr, log_max_rows, &mut js, &mut len, std::ptr::null_mut(), std::ptr::null_mut()) };
-        unsafe { sys::bfhip_trace_destroy(self.0, tr) };
+        let rc = unsafe {
+            sys::bfhip_prove_registers(self.0, trace7.as_ptr(), trace7.len() / 7, program.as_ptr(), program.len(), log_max_rows, &mut js, &mut len,
+                                       std::ptr::null_mut(), std::ptr::null_mut())
+        };
         if rc != 0 {
             return Err(last_error());
         }
@@ -156,6 +152,112 @@ impl Context {
 impl Drop for Context {
     fn drop(&mut self) {
         unsafe { sys::bfhip_ctx_destroy(self.0) };
+    }
+}
+
+/// What `prove_brainfuck(&Machine)` reads of an executed machine (`mod.rs:471-473`, `:508`): `inputs.trace()` flattened to 7 words per row
+/// (clk, ip, ci, ni, mp, mv, mvi) and `inputs.program()` as words. Build it once per machine; a pool borrows it until the result is taken.
+pub struct Machine {
+    pub trace7: Vec<u32>,
+    pub program: Vec<u32>,
+}
+
+/// One finished job of a pool's queue (`bfhip_pool_result`).
+pub struct JobResult {
+    pub ticket: u64,
+    pub tag: u64,
+    /// the sub-context that ran the job
+    pub worker: u32,
+    /// `bfhip_ctx_last_proof_flags` of that proof (bit 2: it read the pool's shared preprocessed tree)
+    pub flags: u32,
+    pub seconds_queued: f64,
+    pub seconds_proving: f64,
+    /// the proof's serde-JSON bytes, or the job's own error text ("job <ticket>: ..."; `cancelled` tells a cancelled job from a failed one)
+    pub proof: Result<Vec<u8>, String>,
+    pub cancelled: bool,
+}
+
+/// `bfhip_pool_*`: k proofs in flight on one GPU behind a queue. `submit_machine` returns at once with a ticket, `wait` hands out results in
+/// completion order. The lifetime ties every submitted machine to the pool: the library borrows the register rows until the job's result
+/// has been taken, and dropping the pool lets running jobs finish first.
+pub struct Pool<'a> {
+    ptr: *mut sys::BfhipPool,
+    log_max_rows: u32,
+    _machines: std::marker::PhantomData<&'a Machine>,
+}
+
+// One producer thread may submit while one consumer thread waits (include/bfhip.h).
+unsafe impl<'a> Send for Pool<'a> {}
+unsafe impl<'a> Sync for Pool<'a> {}
+
+impl<'a> Pool<'a> {
+    pub fn new(device_id: i32, n_in_flight: u32, log_max_rows: u32) -> Result<Self, String> {
+        let mut p = std::ptr::null_mut();
+        if unsafe { sys::bfhip_pool_create(device_id, n_in_flight, log_max_rows + 2, &mut p) } != 0 {
+            return Err(last_error());
+        }
+        Ok(Pool { ptr: p, log_max_rows, _machines: std::marker::PhantomData })
+    }
+
+    /// `bfhip_pool_submit_registers`: queues the proof of an executed machine and returns its ticket. `Err` = the submit itself was refused
+    /// (empty trace, 4096 jobs outstanding); everything else comes back as that job's result.
+    pub fn submit_machine(&self, machine: &'a Machine, tag: u64) -> Result<u64, String> {
+        assert!(machine.trace7.len() % 7 == 0);
+        let mut ticket = 0u64;
+        let rc = unsafe {
+            sys::bfhip_pool_submit_registers(self.ptr, machine.trace7.as_ptr(), machine.trace7.len() / 7, machine.program.as_ptr(), machine.program.len(),
+                                             self.log_max_rows, tag, &mut ticket)
+        };
+        if rc != 0 { Err(last_error()) } else { Ok(ticket) }
+    }
+
+    /// `bfhip_pool_wait`: `Ok(Some(result))`, `Ok(None)` when nothing is outstanding, `Err("timeout")` when `timeout_ms` (`u32::MAX` = no
+    /// limit, 0 = poll) ran out with jobs outstanding.
+    pub fn wait(&self, timeout_ms: u32) -> Result<Option<JobResult>, String> {
+        let mut r = std::mem::MaybeUninit::<sys::BfhipPoolResult>::zeroed();
+        match unsafe { sys::bfhip_pool_wait(self.ptr, timeout_ms, r.as_mut_ptr()) } {
+            0 => {
+                let r = unsafe { r.assume_init() };
+                let proof = if r.status == 0 {
+                    Ok(unsafe { std::slice::from_raw_parts(r.proof_json as *const u8, r.proof_len) }.to_vec())
+                } else if r.error.is_null() {
+                    Err(format!("job {}: failed", r.ticket))
+                } else {
+                    Err(unsafe { CStr::from_ptr(r.error) }.to_string_lossy().into_owned())
+                };
+                unsafe {
+                    sys::bfhip_free_host(r.proof_json as *mut c_void);
+                    sys::bfhip_free_host(r.error as *mut c_void);
+                }
+                Ok(Some(JobResult { ticket: r.ticket, tag: r.user_tag, worker: r.worker, flags: r.flags, seconds_queued: r.seconds_queued,
+                                    seconds_proving: r.seconds_proving, proof, cancelled: r.status == sys::BFHIP_JOB_CANCELLED }))
+            }
+            1 => Err("timeout".to_string()),
+            2 => Ok(None),
+            _ => Err(last_error()),
+        }
+    }
+
+    /// `bfhip_pool_cancel`: `Ok(true)` = the job was still queued and will be delivered as cancelled.
+    pub fn cancel(&self, ticket: u64) -> Result<bool, String> {
+        match unsafe { sys::bfhip_pool_cancel(self.ptr, ticket) } {
+            0 => Ok(true),
+            1 => Ok(false),
+            _ => Err(last_error()),
+        }
+    }
+
+    /// `bfhip_pool_outstanding`: (queued, running, finished and not yet taken).
+    pub fn outstanding(&self) -> (u32, u32, u32) {
+        let (mut q, mut r, mut f) = (0u32, 0u32, 0u32);
+        unsafe { sys::bfhip_pool_outstanding(self.ptr, &mut q, &mut r, &mut f) };
+        (q, r, f)
+    }
+}
+
+impl<'a> Drop for Pool<'a> {
+    fn drop(&mut self) {
+        unsafe { sys::bfhip_pool_destroy(self.ptr) };
     }
 }
 

@@ -364,7 +364,8 @@ int32_t bfhip_trace_create_ram(bfhip_ctx* ctx, const char* code, const uint8_t* 
 /* What prove_brainfuck(&Machine) actually receives (mod.rs:471-473): an EXECUTED machine — its register trace (`inputs.trace()`, mod.rs:508;
  * n_rows rows of 7 u32: clk, ip, ci, ni, mp, mv, mvi, the final ci = ni = 0 row included) and its compiled program (`inputs.program()`,
  * n_code words incl. the jump-target words). No re-execution: the rows are uploaded as they are and the 13 tables are built from them.
- * Values must be canonical M31 (< 2^31 - 1); the trace must be non-empty. */
+ * Values must be canonical M31 (< 2^31 - 1); the trace must be non-empty. With the GPU table builder (the default) the rows reach the device
+ * in one copy and are transposed and checked by one kernel (bfhip_prove_registers names the offending row; this entry keeps its text). */
 int32_t bfhip_trace_create_from_registers(bfhip_ctx* ctx, const uint32_t* trace7_h, size_t n_rows, const uint32_t* code_words_h, size_t n_code,
                                           bfhip_trace** out, uint32_t log_sizes[13], uint64_t* main_cells, uint64_t* interaction_cells);
 int32_t bfhip_trace_destroy(bfhip_ctx* ctx, bfhip_trace* trace);
@@ -375,6 +376,15 @@ int32_t bfhip_ctx_set_table_builder(bfhip_ctx* ctx, int32_t on_gpu);
 int32_t bfhip_trace_column(bfhip_ctx* ctx, const bfhip_trace* trace, uint32_t component, uint32_t column, uint32_t* out_h, size_t cap, size_t* n_rows);
 int32_t bfhip_prove_trace(bfhip_ctx* ctx, const bfhip_trace* trace, uint32_t log_max_rows, char** proof_json, size_t* proof_len,
                           char** transcript, double* phase_seconds);
+/* prove_brainfuck(&Machine) (mod.rs:471-473) in ONE call: the executed machine's register rows (`inputs.trace()`, mod.rs:508) and program words
+ * in, the proof out — the bytes of bfhip_trace_create_from_registers followed by bfhip_prove_trace. The rows go to the device in one copy
+ * and are transposed into columns and checked there; that and the table build are enqueued while the GPU already works on the preprocessed
+ * commitment (what bfhip_prove_brainfuck does for a program text), and the tables live in the proof's arena: no resident trace.
+ * A non-canonical register is reported with its place: "register value is not a canonical M31 (row R, register K)", the lowest
+ * (row, register) of the trace, register K in the order clk, ip, ci, ni, mp, mv, mvi. n_rows >= 2^31 is refused. Outputs as for
+ * bfhip_prove_brainfuck. */
+int32_t bfhip_prove_registers(bfhip_ctx* ctx, const uint32_t* trace7_h, size_t n_rows, const uint32_t* code_words_h, size_t n_code,
+                              uint32_t log_max_rows, char** proof_json, size_t* proof_len, char** transcript, double* phase_seconds);
 
 /* The 13 components of a resident trace (bfhip_trace_create*): for each the logUp columns are generated with the prover's own logUp kernels
  * into the context's arena (which is reset like a proof resets it) and bfhip_check_constraints' pass runs over them; out[k] = component k.
@@ -478,6 +488,58 @@ int32_t bfhip_prove_batch(bfhip_pool* pool, const bfhip_trace* const* traces, ui
  * inputs_h may be NULL (no program reads input); n_inputs[i] bytes at inputs_h[i] otherwise. Outputs as above. */
 int32_t bfhip_prove_batch_brainfuck(bfhip_pool* pool, const char* const* codes, const uint8_t* const* inputs_h, const size_t* n_inputs, uint32_t n,
                                     uint32_t log_max_rows, char** proofs_json, size_t* proof_lens, int32_t* statuses, double* seconds);
+
+/* ---- the pool as a QUEUE: submit returns at once, results come back as they complete ---------------------------------------------------
+ * A batch call returns when its LAST proof is done and nothing can be added while it runs; a deployment with a stream of executed machines
+ * (the caller of prove_brainfuck(&Machine), mod.rs:471-473) wants the first proof's bytes as soon as they exist and the workers never idle.
+ *   submit    returns at once with a ticket (1, 2, 3, ... per pool). Jobs START in ticket order on whichever worker is free; results are
+ *             delivered in COMPLETION order, each exactly once. Program text, input bytes and program words are copied at submit; register
+ *             rows and traces are BORROWED until that ticket's result has been taken. What needs no GPU to check fails the submit itself
+ *             (-1, no ticket): null pointers, zero rows, n_rows >= 2^31, more than BFHIP_POOL_MAX_OUTSTANDING jobs outstanding (queued +
+ *             running + finished and not taken), a batch call in progress. Everything else fails the JOB.
+ *   traces    for bfhip_pool_submit_trace may come from ANY context on the pool's device, e.g. one the caller owns: a trace is plain device
+ *             memory (bfhip_trace_destroy ignores its context argument). The pool's sub-contexts stay off limits to the caller while
+ *             anything is outstanding.
+ *   wait      timeout_ms 0 polls, UINT32_MAX waits without limit. Returns 0 = *out holds a result, 1 = timed out with jobs outstanding,
+ *             2 = nothing outstanding, -1 = error (null pool or null out: returned without blocking; the pool is being destroyed).
+ *             The result owns proof_json and error: release both with bfhip_free_host.
+ *   failures  a failed job is a result with status -1 and its own text, "job <ticket>: <message>"; whatever a job throws ends as that job's
+ *             result, and the other jobs and the pool are unaffected.
+ *   cancel    0 = the job was still queued: it is removed and delivered with status BFHIP_JOB_CANCELLED; 1 = already running or finished (a
+ *             running job is never interrupted); -1 = no such ticket was issued.
+ *   destroy   bfhip_pool_destroy with jobs outstanding drops the queued jobs, lets the running ones finish and frees the untaken results.
+ *   threads   one producer thread may submit while one consumer thread waits; destroy waits for calls in progress to return.
+ *   shared preprocessed tree (bfhip_pool_set_preprocessed): 0 as for batches; in queue use 1 and 2 both mean "kept while LOG_MAX_ROWS, the
+ *             hasher and log_blowup_factor match". The pool keeps up to two such trees (two values of LOG_MAX_ROWS interleaved in one
+ *             stream both find theirs) and recommits one only when no running job uses it; a job that matches neither meanwhile commits its
+ *             own. Proof bytes are the same either way; flags bit 2 says what a proof did. The queue creates no stream of its own.
+ *   batches   bfhip_prove_batch*, bfhip_pool_set_conventions, bfhip_pool_set_pcs_config and bfhip_pool_set_preprocessed return -1
+ *             ("jobs outstanding") while anything is queued, running or not yet taken; otherwise they behave as before.
+ * Layout (natural alignment, declaration order):
+ *   bfhip_pool_result  88 bytes: ticket 0, user_tag 8, status 16, worker 20, flags 24, log_max_rows 28, proof_json 32, proof_len 40,
+ *                                error 48, seconds_queued 56, seconds_proving 64, reserved 72 */
+enum { BFHIP_JOB_CANCELLED = -2, BFHIP_POOL_MAX_OUTSTANDING = 4096 };
+typedef struct bfhip_pool_result {
+    uint64_t ticket, user_tag;
+    int32_t  status;                 /* 0 ok; -1 that proof's error; BFHIP_JOB_CANCELLED */
+    uint32_t worker;                 /* the sub-context that ran it (0 for a cancelled job) */
+    uint32_t flags;                  /* bfhip_ctx_last_proof_flags of that proof (0 unless status == 0) */
+    uint32_t log_max_rows;
+    char*    proof_json; size_t proof_len;   /* malloc'd (bfhip_free_host); NULL unless status == 0 */
+    char*    error;                  /* malloc'd text when status != 0, else NULL */
+    double   seconds_queued, seconds_proving;   /* submit -> start on a worker; start -> done */
+    uint64_t reserved[2];
+} bfhip_pool_result;
+int32_t bfhip_pool_submit_trace(bfhip_pool* pool, const bfhip_trace* trace, uint32_t log_max_rows, uint64_t user_tag, uint64_t* ticket);
+int32_t bfhip_pool_submit_brainfuck(bfhip_pool* pool, const char* code, const uint8_t* input_h, size_t n_input, uint32_t log_max_rows, uint64_t user_tag,
+                                    uint64_t* ticket);
+/* What bfhip_prove_registers takes, as a job: rows borrowed, program words copied. */
+int32_t bfhip_pool_submit_registers(bfhip_pool* pool, const uint32_t* trace7_h, size_t n_rows, const uint32_t* code_words_h, size_t n_code,
+                                    uint32_t log_max_rows, uint64_t user_tag, uint64_t* ticket);
+int32_t bfhip_pool_wait(bfhip_pool* pool, uint32_t timeout_ms, bfhip_pool_result* out);
+/* Jobs queued, running, and finished but not yet taken by bfhip_pool_wait (any pointer may be NULL). */
+int32_t bfhip_pool_outstanding(bfhip_pool* pool, uint32_t* queued, uint32_t* running, uint32_t* finished_not_taken);
+int32_t bfhip_pool_cancel(bfhip_pool* pool, uint64_t ticket);
 
 /* verify_brainfuck (mod.rs:738-797): replays the channel, checks the logUp sum (mod.rs:207-227), the OODS consistency, the proof of work,
  * every Merkle decommitment and FRI. Host only (the reference verifies on the CPU as well). Returns 0 = accepted, 1 = rejected with the

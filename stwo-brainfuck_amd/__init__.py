@@ -571,9 +571,44 @@ class Context:
         return tw.value, itw.value, rl.value
 
 
+JOB_CANCELLED = -2
+POOL_MAX_OUTSTANDING = 4096
+
+
+class PoolResult(ctypes.Structure):
+    """include/bfhip.h `bfhip_pool_result`: one finished job of a pool's queue (88 bytes)."""
+    _fields_ = [("ticket", ctypes.c_uint64), ("user_tag", ctypes.c_uint64), ("status", ctypes.c_int32), ("worker", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("log_max_rows", ctypes.c_uint32), ("proof_json", ctypes.c_void_p), ("proof_len", ctypes.c_size_t), ("error", ctypes.c_void_p),
+                ("seconds_queued", ctypes.c_double), ("seconds_proving", ctypes.c_double), ("reserved", ctypes.c_uint64 * 2)]
+
+
+class JobResult:
+    """What Pool.wait() returns: ticket, tag, status (0 ok, -1 failed, JOB_CANCELLED), worker, flags (Context.last_proof_flags bits of that
+    proof), log_max_rows, proof (bytes, None unless ok), error (str, None when ok), seconds_queued, seconds_proving."""
+
+    def __init__(self, r):
+        self.ticket, self.tag, self.status, self.worker, self.flags = int(r.ticket), int(r.user_tag), int(r.status), int(r.worker), int(r.flags)
+        self.log_max_rows, self.seconds_queued, self.seconds_proving = int(r.log_max_rows), float(r.seconds_queued), float(r.seconds_proving)
+        self.proof = ctypes.string_at(r.proof_json, r.proof_len) if r.proof_json else None
+        self.error = ctypes.string_at(r.error).decode() if r.error else None
+        if r.proof_json:
+            lib().bfhip_free_host(ctypes.c_void_p(r.proof_json))
+        if r.error:
+            lib().bfhip_free_host(ctypes.c_void_p(r.error))
+
+    ok = property(lambda self: self.status == 0)
+    cancelled = property(lambda self: self.status == JOB_CANCELLED)
+    shared_preprocessed = property(lambda self: bool(self.flags & 4))
+
+    def __repr__(self):
+        return "JobResult(ticket=%d, tag=%d, status=%d, worker=%d, %s)" % (self.ticket, self.tag, self.status, self.worker,
+                                                                             "%d proof bytes" % len(self.proof) if self.ok else self.error)
+
+
 class Pool:
     """bfhip_pool_create: `n_in_flight` sub-contexts on one GPU behind ONE caller thread — prove_batch() hands the library a batch of resident
-    traces and returns when all are proved, n_in_flight at a time on the library's own worker threads. The sub-contexts share one twiddle
+    traces and returns when all are proved, n_in_flight at a time on the library's own worker threads; submit_trace / submit_program /
+    submit_registers + wait() / as_completed() use the same workers as a queue (results as they complete; not while a batch runs). The sub-contexts share one twiddle
     tree and (preprocessed=1, default) one preprocessed commitment per batch; 0 = every proof recommits it like the reference
     (mod.rs:495-500), 2 = kept across batches."""
 
@@ -582,6 +617,7 @@ class Pool:
         _check(lib().bfhip_pool_create(device_id, n_in_flight, max_log_domain, ctypes.byref(self._h)))
         self.n_in_flight, self.max_log_domain = n_in_flight, max_log_domain
         self._subs = {}
+        self._borrowed = {}                       # ticket -> the arrays / trace the library borrows until that result is taken
         if preprocessed != 1:
             self.set_preprocessed(preprocessed)
         if _default_conventions != (0, 0, 0, 0):
@@ -591,14 +627,77 @@ class Pool:
         if self._h:
             for c in self._subs.values():
                 c._h = ctypes.c_void_p()          # borrowed handles die with the pool
-            lib().bfhip_pool_destroy(self._h)
+            lib().bfhip_pool_destroy(self._h)             # running jobs finish before this returns: the borrowed arrays outlive them
             self._h = ctypes.c_void_p()
+            self._borrowed.clear()
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+    # -- the queue: submit returns a ticket at once, wait() hands out results in completion order -------------------------------------
+    def _submitted(self, rc, ticket, keep):
+        _check(rc)
+        self._borrowed[ticket.value] = keep
+        return ticket.value
+
+    def submit_trace(self, trace, log_max_rows=24, tag=0):
+        """bfhip_pool_submit_trace: a resident trace of ANY context on the pool's device. The pool keeps a reference to it until its result is taken."""
+        t = ctypes.c_uint64()
+        return self._submitted(lib().bfhip_pool_submit_trace(self._h, trace._h, log_max_rows, ctypes.c_uint64(tag), ctypes.byref(t)), t, trace)
+
+    def submit_program(self, code, input_bytes=b"", log_max_rows=24, tag=0):
+        """bfhip_pool_submit_brainfuck: program text and input are copied; VM run, table build and upload happen inside the worker."""
+        t = ctypes.c_uint64()
+        return self._submitted(lib().bfhip_pool_submit_brainfuck(self._h, code.encode(), bytes(input_bytes), ctypes.c_size_t(len(input_bytes)), log_max_rows,
+                                                                 ctypes.c_uint64(tag), ctypes.byref(t)), t, None)
+
+    def submit_registers(self, rows, code_words, log_max_rows=24, tag=0):
+        """bfhip_pool_submit_registers: an executed machine's register rows (n x 7 u32) and program words — what prove_registers takes, as a job.
+        The rows are borrowed by the library: the pool holds the array until the result is taken."""
+        tr = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, 7)
+        code = np.ascontiguousarray(code_words, dtype=np.uint32)
+        t = ctypes.c_uint64()
+        return self._submitted(lib().bfhip_pool_submit_registers(self._h, tr.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(tr.shape[0]), code.ctypes.data_as(ctypes.c_void_p),
+                                                                 ctypes.c_size_t(code.size), log_max_rows, ctypes.c_uint64(tag), ctypes.byref(t)), t, tr)
+
+    def wait(self, timeout_s=None):
+        """bfhip_pool_wait: the next finished job as a JobResult; None when nothing is outstanding; TimeoutError when timeout_s (None = no limit,
+        0 = poll) ran out with jobs outstanding."""
+        ms = 0xFFFFFFFF if timeout_s is None else min(0xFFFFFFFE, max(0, int(round(timeout_s * 1000))))
+        r = PoolResult()
+        rc = lib().bfhip_pool_wait(self._h, ctypes.c_uint32(ms), ctypes.byref(r))
+        if rc == 0:
+            self._borrowed.pop(int(r.ticket), None)
+            return JobResult(r)
+        if rc == 1:
+            raise TimeoutError("no job of the pool finished within %s s" % timeout_s)
+        if rc == 2:
+            return None
+        raise BfhipError(lib().bfhip_last_error().decode())
+
+    def as_completed(self, timeout_s=None):
+        """Yields JobResults in completion order until nothing is outstanding (jobs submitted meanwhile included); timeout_s is per result."""
+        while True:
+            r = self.wait(timeout_s)
+            if r is None:
+                return
+            yield r
+
+    def outstanding(self):
+        """bfhip_pool_outstanding: {queued, running, finished} — finished = done and not yet taken by wait()."""
+        q, r, f = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        _check(lib().bfhip_pool_outstanding(self._h, ctypes.byref(q), ctypes.byref(r), ctypes.byref(f)))
+        return {"queued": q.value, "running": r.value, "finished": f.value}
+
+    def cancel(self, ticket):
+        """bfhip_pool_cancel: True = the job was still queued (its result arrives with status JOB_CANCELLED), False = already running or finished."""
+        rc = lib().bfhip_pool_cancel(self._h, ctypes.c_uint64(ticket))
+        if rc < 0:
+            raise BfhipError(lib().bfhip_last_error().decode())
+        return rc == 0
 
     def ctx(self, i=0):
         """Sub-context i as a (borrowed) Context: for Trace(...) on the pool's device between batches, per-context settings, memory()."""
@@ -687,6 +786,36 @@ def prove_brainfuck(code, input_bytes=b"", ctx=None, log_max_rows=24, with_trans
             t = ctypes.string_at(tr).decode()
             lib().bfhip_free_host(tr)
             out.append(dict(line.split(":") for line in t.strip().split("\n")))
+        if with_timings:
+            out.append(dict(zip(PHASES, list(times))))
+        return out[0] if len(out) == 1 else tuple(out)
+    finally:
+        if own:
+            ctx.close()
+
+
+def prove_registers(rows, code_words, ctx=None, log_max_rows=24, with_transcript=False, with_timings=False):
+    """bfhip_prove_registers — prove_brainfuck(&Machine) (mod.rs:471-473) in one call: an executed machine's register rows (n x 7 u32: clk, ip,
+    ci, ni, mp, mv, mvi) and program words in, the proof's serde_json bytes out. Same bytes as Trace.from_registers(...).prove(...); no
+    resident trace. A non-canonical register raises with its (row, register)."""
+    own = ctx is None
+    if own:
+        ctx = Context(0, max_log_domain=log_max_rows + 2)
+    try:
+        tr = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, 7)
+        code = np.ascontiguousarray(code_words, dtype=np.uint32)
+        js, n, t = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_void_p()
+        times = (ctypes.c_double * 10)()
+        _check(lib().bfhip_prove_registers(ctx._h, tr.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(tr.shape[0]), code.ctypes.data_as(ctypes.c_void_p),
+                                           ctypes.c_size_t(code.size), log_max_rows, ctypes.byref(js), ctypes.byref(n),
+                                           ctypes.byref(t) if with_transcript else None, times))
+        proof = ctypes.string_at(js, n.value)
+        lib().bfhip_free_host(js)
+        out = [proof]
+        if with_transcript:
+            text = ctypes.string_at(t).decode()
+            lib().bfhip_free_host(t)
+            out.append(dict(line.split(":") for line in text.strip().split("\n")))
         if with_timings:
             out.append(dict(zip(PHASES, list(times))))
         return out[0] if len(out) == 1 else tuple(out)

@@ -87,15 +87,14 @@ extern "C" int32_t bfhip_trace_create_from_registers(bfhip_ctx* ctx, const uint3
     if (!out) throw HipError("null argument");
     if (!trace7 || n_rows == 0) throw HipError("EmptyTrace");
     if (!code_words || n_code == 0) throw HipError("empty program");
-    std::vector<Registers> tr(n_rows);
-    for (size_t i = 0; i < n_rows; i++) {
-        const u32* v = trace7 + 7 * i;
-        for (int k = 0; k < 7; k++) if (v[k] >= P31) throw HipError("register value is not a canonical M31");
-        tr[i] = Registers{v[0], v[1], v[2], v[3], v[4], v[5], v[6]};
-    }
-    std::vector<u32> ins(code_words, code_words + n_code);
-    for (u32 w : ins) if (w >= P31) throw HipError("program word is not a canonical M31");
-    return trace_create_common(ctx, tr, ins, out, log_sizes, nullptr, main_cells, interaction_cells);
+    // GPU table builder (default): the rows are transposed and checked on the device (ingest.hip); otherwise the host path as it was
+    auto* t = new bfhip_trace();
+    try { HipProver::upload_registers(ctx->c, trace7, n_rows, code_words, n_code, t->in, /*use_arena=*/false, /*with_place=*/false); } catch (...) { t->in.release(); delete t; throw; }
+    if (log_sizes) memcpy(log_sizes, t->in.log_sizes, sizeof(u32) * N_COMPONENTS);
+    if (main_cells) *main_cells = t->in.main_cells;
+    if (interaction_cells) *interaction_cells = t->in.interaction_cells;
+    *out = t;
+    return 0;
     API_CATCH
 }
 extern "C" int32_t bfhip_trace_destroy(bfhip_ctx* ctx, bfhip_trace* t) { API_TRY (void)ctx; if (t) { t->in.release(); delete t; } return 0; API_CATCH }
@@ -133,6 +132,30 @@ extern "C" int32_t bfhip_prove_brainfuck(bfhip_ctx* ctx, const char* code, const
             Machine m(ins, std::vector<u8>(input, input + n_input));
             m.execute();
             HipProver::upload_trace(ctx->c, m.trace, ins, in, /*use_arena=*/true, /*on_gpu=*/ctx->c.tables_on_gpu);
+            return in;
+        });
+        fill_outputs(pv, bp, proof_json, proof_len, transcript, phase_seconds);
+        in.release();
+        return 0;
+    } catch (...) { release_group_after_failure(ctx); in.release(); throw; }
+    API_CATCH
+}
+// prove_brainfuck(&Machine) in one call: the executed machine's register rows and program words in, the proof out. Ingestion and table build
+// are enqueued by the lazy producer, i.e. behind the preprocessed commitment the GPU is already working on; the tables live in the proof's arena.
+extern "C" int32_t bfhip_prove_registers(bfhip_ctx* ctx, const uint32_t* trace7_h, size_t n_rows, const uint32_t* code_words_h, size_t n_code,
+                                          uint32_t log_max_rows, char** proof_json, size_t* proof_len, char** transcript, double* phase_seconds) {
+    API_TRY
+    TraceInput in;
+    try {
+        if (!ctx) throw HipError("null context");
+        if (!trace7_h || n_rows == 0) throw HipError("EmptyTrace");
+        if (n_rows >= (size_t(1) << 31)) throw HipError("bfhip_prove_registers: n_rows >= 2^31");
+        if (!code_words_h || n_code == 0) throw HipError("empty program");
+        ctx->c.bind();
+        HipProver pv(ctx->c, log_max_rows);
+        pv.want_transcript = transcript != nullptr;
+        BrainfuckProof bp = pv.prove([&]() -> const TraceInput& {
+            HipProver::upload_registers(ctx->c, trace7_h, n_rows, code_words_h, n_code, in, /*use_arena=*/true, /*with_place=*/true);
             return in;
         });
         fill_outputs(pv, bp, proof_json, proof_len, transcript, phase_seconds);

@@ -270,4 +270,12 @@ void batch_inverse_qm31(hipStream_t stream, const u32* const src[4], u32* const 
 void bit_reverse(hipStream_t stream, const u32* src, u32* dst, u32 log);
 void one_hot(hipStream_t stream, u32* dst, u32 n);
 
+// The VM's register trace on the device, one column per register (what the table builders of tables.hip read).
+struct TraceSoA { const u32 *clk, *ip, *ci, *ni, *mp, *mv, *mvi; u32 n; };
+// ingest.hip — n_rows register rows (7 u32 each, row-major, host memory) -> TraceSoA in the context's arena: one upload, one launch that
+// transposes through LDS and checks every word against 2^31 - 1. *first_bad = row * 8 + register of the lowest non-canonical word
+// (UINT64_MAX: none); the host has waited for the launch on return. Refuses n_rows == 0 and n_rows >= 2^31.
+struct Ctx;
+TraceSoA ingest_registers(Ctx& c, const u32* trace7_h, size_t n_rows, u64* first_bad);
+
 }  // namespace bf

@@ -18,6 +18,9 @@ namespace bf {
 // tables.hip
 void build_tables_device(Ctx& c, const std::vector<u32> trace7_soa[7], u32 n, const std::vector<u32>& code, const std::function<u32*(size_t)>& alloc,
                          std::vector<std::vector<u32*>>& cols_out, u32 log_sizes_out[13]);
+// the same from a register trace that is already on the device (ingest.hip); the host-vector form uploads and calls this one
+void build_tables_device(Ctx& c, const TraceSoA& t, const std::vector<u32>& code, const std::function<u32*(size_t)>& alloc,
+                         std::vector<std::vector<u32*>>& cols_out, u32 log_sizes_out[13]);
 
 static constexpr u32 OWNER_ALL = 0xFFFFFFFFu;   // a polynomial every rank of a shard group holds and transforms itself
 
@@ -92,6 +95,7 @@ struct SharedPreprocessed {
     DTree tree;                         // storage: the builder context's arena (not reset while a batch can read it)
     hipEvent_t ready = nullptr;         // recorded on the builder's stream behind the tree (and the root's copy into pinned memory)
     const Hash32* pinned_root = nullptr;
+    u32 root_slot = 0;                  // which 32-byte slot of the builder's pinned block receives the root (a pool keeps two trees)
     bool matches(const Ctx& c, u32 log_max_rows) const {
         return valid && lmr == log_max_rows && node_conv == c.conv.merkle_node_hash && channel == c.conv.merkle_channel && log_blowup == c.pcs.log_blowup &&
                c.shard.count == 1;
@@ -199,6 +203,9 @@ struct HipProver {
     void commit_tree(DTree& t, Hash32* pinned_root = nullptr, bool with_prev = false);
     void commit_tree_overlapped(DTree& t, Hash32* pinned_root, const std::vector<DCol>* interp_src = nullptr, int stamp_slot = -1);
     static void upload_trace(Ctx& c, const std::vector<Registers>& vm_trace, const std::vector<u32>& code, TraceInput& in, bool use_arena = false, bool on_gpu = true);
+    // The same from the caller's register rows (n_rows x 7 u32) and program words: device-side ingestion (ingest.hip) + GPU table builders, or
+    // with c.tables_on_gpu off the host path above. with_place: a non-canonical register is reported with its (row, register).
+    static void upload_registers(Ctx& c, const u32* trace7_h, size_t n_rows, const u32* code_words_h, size_t n_code, TraceInput& in, bool use_arena, bool with_place);
     void build_preprocessed(DTree& tree, Hash32* pinned_root);
     void build_shared_preprocessed(SharedPreprocessed& sp);
 

@@ -447,6 +447,52 @@ void HipProver::upload_trace(Ctx& c, const std::vector<Registers>& vm_trace, con
     c.sync();
 }
 
+// Prover-input preparation from the caller's register rows (bfhip_trace_create_from_registers, bfhip_prove_registers, the pool's register
+// jobs): the rows go to the device in one copy and are transposed and checked there (ingest.hip); the table kernels read the result.
+// Which error wins when several apply: a non-canonical register, then a non-canonical program word, then the table builders' refusals.
+void HipProver::upload_registers(Ctx& c, const u32* trace7_h, size_t n_rows, const u32* code_words_h, size_t n_code, TraceInput& in, bool use_arena, bool with_place) {
+    auto bad_register = [&](size_t row, int reg) {
+        std::string m = "register value is not a canonical M31";
+        if (with_place) m += " (row " + std::to_string(row) + ", register " + std::to_string(reg) + ")";
+        return HipError(m);
+    };
+    auto check_code = [&]() {
+        std::vector<u32> ins(code_words_h, code_words_h + n_code);
+        for (u32 w : ins) if (w >= P31) throw HipError("program word is not a canonical M31");
+        return ins;
+    };
+    if (!c.tables_on_gpu) {
+        std::vector<Registers> tr(n_rows);
+        for (size_t i = 0; i < n_rows; i++) {
+            const u32* v = trace7_h + 7 * i;
+            for (int k = 0; k < 7; k++) if (v[k] >= P31) throw bad_register(i, k);
+            tr[i] = Registers{v[0], v[1], v[2], v[3], v[4], v[5], v[6]};
+        }
+        upload_trace(c, tr, check_code(), in, use_arena, /*on_gpu=*/false);
+        return;
+    }
+    c.stage_checkpoint();
+    u64 first_bad = ~u64(0);
+    TraceSoA t = ingest_registers(c, trace7_h, n_rows, &first_bad);
+    if (first_bad != ~u64(0)) throw bad_register(size_t(first_bad >> 3), int(first_bad & 7));
+    std::vector<u32> ins = check_code();
+    in.rows.assign(N_COMPONENTS, {});
+    in.n_steps = n_rows;
+    in.main_cells = in.interaction_cells = 0;
+    auto alloc = [&](size_t words) -> u32* {
+        if (use_arena) return c.alloc_u32(words);
+        u32* p = nullptr; BF_HIP(hipMalloc((void**)&p, (words ? words : 1) * sizeof(u32))); in.owned.push_back(p); return p;
+    };
+    std::vector<std::vector<u32*>> cols;
+    build_tables_device(c, t, ins, alloc, cols, in.log_sizes);
+    for (int k = 0; k < N_COMPONENTS; k++) {
+        for (u32 j = 0; j < n_main_cols(k); j++) { DCol r; r.log_size = in.log_sizes[k]; r.shift = LOG_N_LANES; r.ptr = cols[k][j]; in.rows[k].push_back(r); }
+        in.main_cells += (u64)n_main_cols(k) << in.log_sizes[k];
+        in.interaction_cells += (u64)(4 * n_logup_cols(k)) << in.log_sizes[k];
+    }
+    c.sync();
+}
+
 // Phase 0 of prove_brainfuck: the preprocessed tree IsFirst(LOG_MAX_ROWS ..= LOG_N_LANES) (mod.rs:495-500) — polynomials in closed form,
 // LDE, Merkle tree; the root goes to *pinned_root behind the tree (no host wait). Storage from the context's current arena.
 void HipProver::build_preprocessed(DTree& tree, Hash32* pinned_root) {
@@ -480,7 +526,7 @@ void HipProver::build_shared_preprocessed(SharedPreprocessed& sp) {
     c.arena.reset(); c.stage_used = 0; c.use_mailbox = false;
     BF_HIP(hipMemsetAsync(c.d_counters, 0, 4 * 64 * sizeof(u32), c.stream));
     sp.tree = DTree();
-    Hash32* root = reinterpret_cast<Hash32*>(c.h_small);
+    Hash32* root = reinterpret_cast<Hash32*>(c.h_small) + sp.root_slot;
     build_preprocessed(sp.tree, root);
     BF_HIP(hipEventRecord(sp.ready, c.stream));
     sp.pinned_root = root; sp.lmr = log_max_rows; sp.node_conv = c.conv.merkle_node_hash; sp.channel = c.conv.merkle_channel; sp.log_blowup = cfg.log_blowup; sp.valid = true;

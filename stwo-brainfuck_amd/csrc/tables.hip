@@ -14,8 +14,6 @@
 
 namespace bf {
 
-struct TraceSoA { const u32 *clk, *ip, *ci, *ni, *mp, *mv, *mvi; u32 n; };
-
 // ---- generic u32 exclusive scan (block-local + totals) -----------------------------------------------------------------------------
 static constexpr u32 SC_TILE = 2048;   // 256 lanes x 8
 __global__ void __launch_bounds__(256) k_scan_u32_local(const u32* __restrict__ in, u32* __restrict__ out, u32* __restrict__ totals, u32 n) {
@@ -209,21 +207,38 @@ __global__ void __launch_bounds__(256) k_memory_entries(TraceSoA t, const u32* _
     else { u32 kp = order[i - 1]; e_clk[j] = m_add(t.clk[kp], (1 + (j - pos[i])) % P31); e_mp[j] = t.mp[kp]; e_mv[j] = t.mv[kp]; e_d[j] = 1; }
 }
 
+// end of execution: the rows with ci == 0 — how many, and the highest of them (one row in a trace the EndOfExecution table accepts)
+__global__ void __launch_bounds__(256) k_eoe_find(TraceSoA t, u32* __restrict__ hits_at) {
+    u32 k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < t.n && t.ci[k] == 0) { atomicAdd(hits_at, 1u); atomicMax(hits_at + 1, k); }
+}
+
 static u32 next_pow2_u32(u32 x) { u32 p = 1; while (p < x) p <<= 1; return p; }
 static u32 log2_u32(u32 x) { u32 l = 0; while ((1u << l) < x) l++; return l; }
 
+void build_tables_device(Ctx& c, const TraceSoA& t, const std::vector<u32>& code, const std::function<u32*(size_t)>& alloc,
+                         std::vector<std::vector<u32*>>& cols_out, u32 log_sizes_out[13]);
+
 // Builds all 13 row-granular tables on the device. `alloc(words)` provides output storage (stable device memory).
 // cols_out[k][j] = device pointer of column j of component k; log_sizes_out[k] = log2(rows) + 4.
+// The register trace as seven host vectors: uploaded column by column, then the device-resident form below.
 void build_tables_device(Ctx& c, const std::vector<u32> trace7_soa[7], u32 n, const std::vector<u32>& code, const std::function<u32*(size_t)>& alloc,
                          std::vector<std::vector<u32*>>& cols_out, u32 log_sizes_out[13]) {
+    if (n == 0) throw HipError("EmptyTrace");
+    c.stage_checkpoint();
+    u32* d_tr[7];
+    for (int k = 0; k < 7; k++) { d_tr[k] = c.alloc_u32(n); BF_HIP(hipMemcpyAsync(d_tr[k], trace7_soa[k].data(), n * sizeof(u32), hipMemcpyHostToDevice, c.stream)); }
+    build_tables_device(c, TraceSoA{d_tr[0], d_tr[1], d_tr[2], d_tr[3], d_tr[4], d_tr[5], d_tr[6], n}, code, alloc, cols_out, log_sizes_out);
+}
+
+void build_tables_device(Ctx& c, const TraceSoA& t, const std::vector<u32>& code, const std::function<u32*(size_t)>& alloc,
+                         std::vector<std::vector<u32*>>& cols_out, u32 log_sizes_out[13]) {
     hipStream_t s = c.stream;
+    const u32 n = t.n;
     if (n == 0) throw HipError("EmptyTrace");
     c.stage_checkpoint();
     // scratch from the arena (only the outputs need to outlive the proof when the caller says so)
     auto tmp_u32 = [&](size_t words) { return c.alloc_u32(words); };
-    u32* d_tr[7];
-    for (int k = 0; k < 7; k++) { d_tr[k] = tmp_u32(n); BF_HIP(hipMemcpyAsync(d_tr[k], trace7_soa[k].data(), n * sizeof(u32), hipMemcpyHostToDevice, s)); }
-    TraceSoA t{d_tr[0], d_tr[1], d_tr[2], d_tr[3], d_tr[4], d_tr[5], d_tr[6], n};
     u32 L = (u32)code.size();
     u32* d_code = tmp_u32(L + 1);
     BF_HIP(hipMemcpyAsync(d_code, code.data(), L * sizeof(u32), hipMemcpyHostToDevice, s));
@@ -253,6 +268,9 @@ void build_tables_device(Ctx& c, const std::vector<u32> trace7_soa[7], u32 n, co
     u32* mem_counts = tmp_u32(n); u32* mem_pos = tmp_u32(n); u32* mem_tot = tmp_u32(nb + 2);
     unsigned long long* d_mem_total64 = (unsigned long long*)c.arena.alloc(256);
     BF_HIP(hipMemsetAsync(d_mem_total64, 0, 8, s));
+    u32* d_eoe = tmp_u32(2);                        // {rows with ci == 0, the highest of them}
+    BF_HIP(hipMemsetAsync(d_eoe, 0, 2 * sizeof(u32), s));
+    hipLaunchKernelGGL(k_eoe_find, dim3((n + 255) / 256), dim3(256), 0, s, t, d_eoe);
     hipLaunchKernelGGL(k_memory_counts, dim3((n + 255) / 256), dim3(256), 0, s, t, mem_order, mem_counts, d_mem_total64);
     const u32* d_mem_total = exclusive_scan_u32(s, mem_counts, mem_pos, mem_tot, n);
     // instruction: sort by (ip, clk)
@@ -264,6 +282,8 @@ void build_tables_device(Ctx& c, const std::vector<u32> trace7_soa[7], u32 n, co
     BF_HIP(hipMemcpyAsync(&h_counts[8], d_mem_total, 4, hipMemcpyDeviceToHost, s));
     unsigned long long h_mem_total64 = 0;
     BF_HIP(hipMemcpyAsync(&h_mem_total64, d_mem_total64, 8, hipMemcpyDeviceToHost, s));
+    u32 h_eoe[2] = {0, 0};
+    BF_HIP(hipMemcpyAsync(h_eoe, d_eoe, sizeof h_eoe, hipMemcpyDeviceToHost, s));
     c.sync();
     if (h_mem_total64 > (1ull << 28)) throw HipError("the Memory table would have more than 2^28 rows (2^32 domain rows): not a provable trace");
 
@@ -332,14 +352,10 @@ void build_tables_device(Ctx& c, const std::vector<u32> trace7_soa[7], u32 n, co
     }
     // ---- end of execution (component 12): exactly one row with ci == 0 (end_of_execution/table.rs:71-111) ------------------------------------
     {
-        u32 hits = 0, at = 0;
-        for (u32 i = 0; i < n; i++) if (trace7_soa[2][i] == 0) { hits++; at = i; }
-        if (hits != 1) throw HipError("InvalidEndOfExecution");
+        if (h_eoe[0] != 1) throw HipError("InvalidEndOfExecution");
         make_cols(C_EOE, 7, 1);
-        u32 v[7];
-        for (int j = 0; j < 7; j++) v[j] = trace7_soa[j][at];
-        const u32* st = c.stage(v, 7);
-        for (int j = 0; j < 7; j++) BF_HIP(hipMemcpyAsync(cols_out[C_EOE][j], st + j, sizeof(u32), hipMemcpyDeviceToDevice, s));
+        const u32* src[7] = {t.clk, t.ip, t.ci, t.ni, t.mp, t.mv, t.mvi};
+        for (int j = 0; j < 7; j++) BF_HIP(hipMemcpyAsync(cols_out[C_EOE][j], src[j] + h_eoe[1], sizeof(u32), hipMemcpyDeviceToDevice, s));
     }
     BF_HIP(hipGetLastError());
 }

@@ -5,6 +5,8 @@ tracker for it:
 
   bfprove.py prove  (--file prog.bf | --code '++>,<[>+.<-]') [--input-file in.bin] [--ram-size N] [--output proof.json]
                     [--log-max-rows 24] [--conventions a,b,c,d | --poseidon252] [--all-sets DIR] [PCS options]
+  bfprove.py prove  --queue N --programs a.bf b.bf ... --output-dir DIR [--input-file in.bin] [--ram-size N] [--log-max-rows 24]
+                    [--conventions a,b,c,d | --poseidon252] [PCS options]
   bfprove.py verify proof.json [--log-max-rows 24] [--conventions a,b,c,d | --poseidon252 | --try-all] [PCS options]
   bfprove.py check  (--file prog.bf | --code '++>,<[>+.<-]') [--input-file in.bin] [--ram-size N] [--set-register ROW:NAME=VALUE ...]
   bfprove.py relations (--file prog.bf | --code ...) [--input-file in.bin] [--ram-size N] [--set-register ROW:NAME=VALUE ...]
@@ -20,6 +22,11 @@ relations builds the same trace and lists the lookup tuples that do not cancel (
 e.g. "processor relation: (1, 1, 35, 43, 0, 1, 1) net +1: yielded 1x (first: processor row 1), used 0x" — and exit code 1: what lies behind
 a logUp total that is not zero while every component checks `ok`. --set-word alters one word of the compiled program as well (an opcode
 that is no instruction has to appear in the program and in the register rows).
+
+prove --queue N proves a list of programs N at a time through the pool's queue (bfhip_pool_submit_registers / bfhip_pool_wait): every program
+is run on the host VM, its executed machine is submitted, and each proof is written to DIR/<program name>.proof.json as it completes — in
+completion order, one line per proof on stdout. A program that fails (too large for --log-max-rows, input exhausted) is reported with its
+own error and does not stop the others; the exit code is 1 if any failed.
 
 PCS options (stwo's PcsConfig; the defaults are PcsConfig::default()): --pow-bits 5 --log-blowup-factor 1 --n-queries 3. The proof file does
 not record them: verify with the values the proof was made with. prove prints the config and its security bits (pow + blowup x queries).
@@ -102,6 +109,8 @@ def main():
     p.add_argument("--file"); p.add_argument("--code"); p.add_argument("--input-file"); p.add_argument("--ram-size", type=int, default=0)
     p.add_argument("--output"); p.add_argument("--log-max-rows", type=int, default=24); p.add_argument("--poseidon252", action="store_true")
     p.add_argument("--conventions"); p.add_argument("--all-sets", metavar="DIR")
+    p.add_argument("--queue", type=int, default=0, metavar="N", help="prove --programs through the pool's queue, N proofs in flight")
+    p.add_argument("--programs", nargs="+", default=[], metavar="FILE"); p.add_argument("--output-dir", metavar="DIR")
     v = sub.add_parser("verify")
     v.add_argument("proof"); v.add_argument("--log-max-rows", type=int, default=24); v.add_argument("--poseidon252", action="store_true")
     v.add_argument("--conventions"); v.add_argument("--try-all", action="store_true")
@@ -172,7 +181,47 @@ def relations(pkg, a, ap):
     return 0 if res.balanced else 1
 
 
+def prove_queue(pkg, a, ap):
+    """prove --queue N: the programs' executed machines through bfhip_pool_submit_registers, each proof written as it completes."""
+    if not a.programs or not a.output_dir:
+        ap.error("prove --queue needs --programs FILE... and --output-dir DIR")
+    if not 1 <= a.queue <= 16:
+        ap.error("--queue takes 1..16 proofs in flight")
+    inp = open(a.input_file, "rb").read() if a.input_file else (b"" if sys.stdin.isatty() else sys.stdin.buffer.read())
+    os.makedirs(a.output_dir, exist_ok=True)
+    pcs = parse_pcs(pkg, a)
+    pool = pkg.Pool(0, n_in_flight=a.queue, max_log_domain=a.log_max_rows + pcs.log_blowup_factor + 1)
+    failed = 0
+    try:
+        pool.set_pcs_config(pcs)
+        pool.set_conventions(*parse_conventions(a))
+        t0 = time.time()
+        for i, path in enumerate(a.programs):
+            code = open(path).read()
+            try:
+                _, rows = pkg.host_run(code, inp, ram_size=a.ram_size)
+                pool.submit_registers(rows, pkg.host_compile(code), a.log_max_rows, tag=i)
+            except pkg.BfhipError as e:            # the VM refused the program: nothing was submitted
+                failed += 1
+                print(f"{path}: error: {e}", file=sys.stderr)
+        for r in pool.as_completed(timeout_s=3600.0):
+            path = a.programs[r.tag]
+            if not r.ok:
+                failed += 1
+                print(f"{path}: error: {r.error}", file=sys.stderr)
+                continue
+            out = os.path.join(a.output_dir, os.path.splitext(os.path.basename(path))[0] + ".proof.json")
+            open(out, "wb").write(r.proof)
+            print(f"{out}  {len(r.proof)} bytes; queued {1e3 * r.seconds_queued:.1f} ms, proving {1e3 * r.seconds_proving:.1f} ms on worker {r.worker}; "
+                  f"{time.time() - t0:.3f}s after the first submit", flush=True)
+    finally:
+        pool.close()
+    return 1 if failed else 0
+
+
 def run(pkg, a, ap):
+    if a.cmd == "prove" and a.queue:
+        return prove_queue(pkg, a, ap)
     if a.cmd == "check":
         return check(pkg, a, ap)
     if a.cmd == "relations":
