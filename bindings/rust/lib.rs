@@ -142,6 +142,14 @@ impl Context {
         unsafe { sys::bfhip_ctx_reuse_preprocessed(self.0, on as i32) };
     }
 
+    /// The proof's own filter (`bfhip_ctx_set_preflight`): every later `prove_*` of this context first asserts the 13 AIRs and the logUp total
+    /// on its tables and fails with the rejection lines ("TraceRejected: ...", then component / row / tuple) — the C status is
+    /// `sys::BFHIP_TRACE_REJECTED`, `bfhip_ctx_last_preflight` has the report — instead of proving a trace that cannot be proved. A filter,
+    /// not a soundness gate: its lookup elements are fixed and public. Refused for a context in a shard group.
+    pub fn set_preflight(&self, on: bool) -> Result<(), String> {
+        if unsafe { sys::bfhip_ctx_set_preflight(self.0, on as i32) } != 0 { Err(last_error()) } else { Ok(()) }
+    }
+
     /// Device memory of this context in bytes: [reserved by the per-proof arena, its peak use, the twiddle trees, in use now] (`bfhip_ctx_memory`).
     pub fn memory(&self) -> Result<[u64; 4], String> {
         let mut out = [0u64; 4];

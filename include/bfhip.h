@@ -286,7 +286,8 @@ void bfhip_free_host(void* p);
  * (bfhip_ctx_reuse_preprocessed), bit 2 = it took a pool's shared preprocessed tree (bfhip_pool_set_preprocessed), bit 3 = shard group: the transforms were replicated
  * (bfhip_ctx_set_shard_policy), bit 4 = the decommitment's gather request table outgrew a quarter of the staging ring and was split over
  * several launches (many queries at a large LOG_MAX_ROWS), bit 5 = FRI layers were folded inside the leaf launch of their Merkle tree
- * (bfhip_fri_fold_leaf's kernel: layers of 2^17 rows and above, device channel, one process). Tests and tools read it so that
+ * (bfhip_fri_fold_leaf's kernel: layers of 2^17 rows and above, device channel, one process), bit 6 = the preflight ran and passed
+ * (bfhip_ctx_set_preflight). Tests and tools read it so that
  * a setting that silently did not apply is visible. */
 int32_t bfhip_ctx_last_proof_flags(bfhip_ctx* ctx, uint32_t* flags);
 /* ---- one proof over several GPUs (shard group) ------------------------------------------------------------------------------------------
@@ -455,6 +456,55 @@ int32_t bfhip_relation_summary(bfhip_ctx* ctx, const bfhip_relation_table* table
 int32_t bfhip_trace_relations(bfhip_ctx* ctx, const bfhip_trace* trace, bfhip_relation_report out[3], bfhip_relation_entry* entries_h,
                               uint32_t cap_per_relation);
 
+/* ---- preflight: a proof that first rejects a trace it cannot prove, naming row and tuple ---------------------------------------------------
+ * A trace that is canonical but is not an execution costs a whole proof before it fails at the out-of-domain check with
+ * "ConstraintsNotSatisfied"; one whose 13 AIRs hold row by row but whose lookups do not balance is not stopped by the prover at all (it has
+ * no `lookup_sum_valid` check, mod.rs:207-226: a verifier rejects the proof). With the preflight on, every proving entry point of the
+ * context (bfhip_prove_trace, bfhip_prove_brainfuck, bfhip_prove_registers, and through them a pool's jobs) runs bfhip_trace_check's
+ * assertion on its row-granular tables — a resident trace's columns, or the tables just built in the proof's arena — before anything of the
+ * main-trace phase is enqueued: the logUp pass (4 launches), the cells of all 13 components in ONE launch, one launch of 13 + 1 waves
+ * (first failing constraint of each component; the QM31 sum of the 13 claimed sums), ONE read-back. Each component's total is read on the
+ * device from the slot the logUp pass wrote. The lookup elements are the fixed defaults of bfhip_trace_check(.., NULL, ..), so the 13
+ * reports and the total are those of that call on the same tables. Scratch comes from the proof's arena and is given back before the
+ * main-trace phase allocates.
+ *   pass    the proof goes on exactly as without the preflight (same launches, bytes and transcript); bit 6 of bfhip_ctx_last_proof_flags.
+ *   fail    (a component with n_bad_cells != 0, or a non-zero total) nothing further of the proof is enqueued, the side stream is joined
+ *           as at the other early exits, and the call returns BFHIP_TRACE_REJECTED with the text of bfhip_format_preflight in
+ *           bfhip_last_error(). If the total is non-zero, bfhip_relation_summary's pass runs over the same 13 tables with a cap of 4
+ *           entries per relation. The context stays usable; the next proof starts clean.
+ * A FILTER, NOT A SOUNDNESS GATE: the elements are fixed and public, so a trace built to cancel under them passes — and then ends as it does
+ * without the preflight. A context in a shard group is not supported: bfhip_ctx_set_preflight(ctx, 1) on a member is refused
+ * (bfhip_ctx_leave_group first), and a context with the preflight on cannot join (bfhip_ctx_set_preflight(ctx, 0) first).
+ * Layout (natural alignment, declaration order):
+ *   bfhip_preflight_report  4064 bytes: ran 0, rejected 4, n_bad_components 8, n_entries 12, logup_total 16, components 32, relations 2736,
+ *                                       entries 2880, seconds 4032, reserved 4040 */
+enum { BFHIP_TRACE_REJECTED = -3 };
+/* default 0; takes effect at the next proof */
+int32_t bfhip_ctx_set_preflight(bfhip_ctx* ctx, int32_t on);
+int32_t bfhip_ctx_get_preflight(bfhip_ctx* ctx, int32_t* on);
+typedef struct bfhip_preflight_report {
+    uint32_t ran, rejected;            /* of the last proof call of this context that reached the preflight */
+    int32_t  n_bad_components; uint32_t n_entries;       /* entries[] slots in use: the sum of relations[r].n_reported */
+    uint32_t logup_total[4];
+    bfhip_check_report    components[13];
+    bfhip_relation_report relations[3];                  /* zero unless the relation summary ran */
+    bfhip_relation_entry  entries[12];                   /* relation r at entries[4 r ..], n_reported of them */
+    double   seconds;                                    /* host wall time of the preflight */
+    uint64_t reserved[3];
+} bfhip_preflight_report;
+/* All zero before the first proof of the context that reached the preflight. */
+int32_t bfhip_ctx_last_preflight(bfhip_ctx* ctx, bfhip_preflight_report* out);
+/* Host only, no GPU: the text a rejection carries, lines joined by '\n':
+ *   "TraceRejected: <n> of 13 components violate their constraints", "TraceRejected: the logUp total is not zero", or both joined by " and ";
+ *   one line per failing component: "<name>: constraint <j> fails at table row <r> (cell <i>), value (a, b, c, d); <n> cells violate it";
+ *   "logUp: the 13 claimed sums add up to (a, b, c, d), not zero" when they do;
+ *   one line per reported tuple: "<relation> relation: (<words>) net <+n>: yielded <n>x (first: <table> row <r>), used <n>x (first: ..)"
+ *   [", <n> rows with another multiplicity"], then "<relation> relation: <n> more unbalanced tuples not listed" per cut relation.
+ * A report that was not rejected gives "preflight: ok" (ran) or "preflight: did not run". *need (may be NULL) = bytes needed, the
+ * terminating NUL included. Returns 0, or -2 ("capacity") when cap < *need: buf then holds the first cap - 1 bytes, NUL-terminated
+ * (buf may be NULL with cap 0: size query). */
+int32_t bfhip_format_preflight(const bfhip_preflight_report* rep, char* buf, size_t cap, size_t* need);
+
 /* ---- proofs in flight: a pool of sub-contexts on one GPU behind ONE caller thread -------------------------------------------------------------
  * The reference's caller is a single thread of control (prove_brainfuck, mod.rs:471-735); a single proof leaves the GPU partly idle in its
  * single-workgroup chains (tree tops, small FRI layers) and at its Fiat-Shamir round trips. A pool proves the proofs of a batch n_in_flight at a
@@ -478,10 +528,13 @@ int32_t bfhip_pool_set_conventions(bfhip_pool* pool, const bfhip_conventions* co
 int32_t bfhip_pool_set_preprocessed(bfhip_pool* pool, int32_t mode);
 /* bfhip_ctx_set_pcs_config on every sub-context and on the builder of the shared preprocessed tree (pcs == NULL: the defaults). */
 int32_t bfhip_pool_set_pcs_config(bfhip_pool* pool, const bfhip_pcs_config* pcs);
+/* bfhip_ctx_set_preflight on every sub-context: a job whose trace is rejected ends with status BFHIP_TRACE_REJECTED and the rejection text
+ * (a queued job's behind its "job <ticket>: " prefix); the other jobs and the pool are unaffected. Refused while jobs are outstanding. */
+int32_t bfhip_pool_set_preflight(bfhip_pool* pool, int32_t on);
 /* n x bfhip_prove_trace. Outputs are arrays of n entries, each optional (NULL): proofs_json[i] (malloc'd, bfhip_free_host; NULL when proof i failed),
  * proof_lens[i], statuses[i] (0 = ok, < 0 = that proof's error). seconds (optional) has n + 1 entries: each proof's own wall time from its start on
  * its worker, then the wall time of the whole batch. Returns 0 when every proof succeeded, -1 otherwise (bfhip_last_error: the first failed
- * proof's message); the other proofs of the batch are still delivered. */
+ * proof's message); the other proofs of the batch are still delivered. statuses[i] = BFHIP_TRACE_REJECTED for a trace the preflight rejected. */
 int32_t bfhip_prove_batch(bfhip_pool* pool, const bfhip_trace* const* traces, uint32_t n, uint32_t log_max_rows, char** proofs_json, size_t* proof_lens,
                           int32_t* statuses, double* seconds);
 /* n x bfhip_prove_brainfuck: VM run, table build and upload of proof i happen inside its worker, beside the other workers' GPU work.
@@ -504,7 +557,8 @@ int32_t bfhip_prove_batch_brainfuck(bfhip_pool* pool, const char* const* codes, 
  *             2 = nothing outstanding, -1 = error (null pool or null out: returned without blocking; the pool is being destroyed).
  *             The result owns proof_json and error: release both with bfhip_free_host.
  *   failures  a failed job is a result with status -1 and its own text, "job <ticket>: <message>"; whatever a job throws ends as that job's
- *             result, and the other jobs and the pool are unaffected.
+ *             result, and the other jobs and the pool are unaffected. With bfhip_pool_set_preflight on, a job whose trace the preflight
+ *             rejects has status BFHIP_TRACE_REJECTED instead: bad input, not an internal failure.
  *   cancel    0 = the job was still queued: it is removed and delivered with status BFHIP_JOB_CANCELLED; 1 = already running or finished (a
  *             running job is never interrupted); -1 = no such ticket was issued.
  *   destroy   bfhip_pool_destroy with jobs outstanding drops the queued jobs, lets the running ones finish and frees the untaken results.
@@ -513,7 +567,7 @@ int32_t bfhip_prove_batch_brainfuck(bfhip_pool* pool, const char* const* codes, 
  *             hasher and log_blowup_factor match". The pool keeps up to two such trees (two values of LOG_MAX_ROWS interleaved in one
  *             stream both find theirs) and recommits one only when no running job uses it; a job that matches neither meanwhile commits its
  *             own. Proof bytes are the same either way; flags bit 2 says what a proof did. The queue creates no stream of its own.
- *   batches   bfhip_prove_batch*, bfhip_pool_set_conventions, bfhip_pool_set_pcs_config and bfhip_pool_set_preprocessed return -1
+ *   batches   bfhip_prove_batch*, bfhip_pool_set_conventions, bfhip_pool_set_pcs_config, bfhip_pool_set_preflight and bfhip_pool_set_preprocessed return -1
  *             ("jobs outstanding") while anything is queued, running or not yet taken; otherwise they behave as before.
  * Layout (natural alignment, declaration order):
  *   bfhip_pool_result  88 bytes: ticket 0, user_tag 8, status 16, worker 20, flags 24, log_max_rows 28, proof_json 32, proof_len 40,
@@ -521,7 +575,7 @@ int32_t bfhip_prove_batch_brainfuck(bfhip_pool* pool, const char* const* codes, 
 enum { BFHIP_JOB_CANCELLED = -2, BFHIP_POOL_MAX_OUTSTANDING = 4096 };
 typedef struct bfhip_pool_result {
     uint64_t ticket, user_tag;
-    int32_t  status;                 /* 0 ok; -1 that proof's error; BFHIP_JOB_CANCELLED */
+    int32_t  status;                 /* 0 ok; -1 that proof's error; BFHIP_JOB_CANCELLED; BFHIP_TRACE_REJECTED */
     uint32_t worker;                 /* the sub-context that ran it (0 for a cancelled job) */
     uint32_t flags;                  /* bfhip_ctx_last_proof_flags of that proof (0 unless status == 0) */
     uint32_t log_max_rows;

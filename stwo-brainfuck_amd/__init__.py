@@ -35,9 +35,30 @@ def lib():
     return _lib
 
 
+TRACE_REJECTED = -3
+
+
+class TraceRejected(BfhipError):
+    """BFHIP_TRACE_REJECTED: a proof's preflight (Context.set_preflight) refused the trace before proving it. str() = the rejection lines
+    (bfhip_format_preflight); .check = the CheckResult of the 13 components, .relations = the RelationResult of the tuples that do not
+    cancel (empty unless the logUp total is not zero)."""
+
+    def __init__(self, text, check=None, relations=None):
+        super().__init__(text)
+        self.check, self.relations = check, relations
+
+
 def _check(rc):
     if rc != 0:
         raise BfhipError(lib().bfhip_last_error().decode())
+
+
+def _check_proof(rc, ctx):
+    """_check for the proving entry points: BFHIP_TRACE_REJECTED raises TraceRejected with the context's preflight report."""
+    if rc == TRACE_REJECTED:
+        text = lib().bfhip_last_error().decode()
+        raise TraceRejected(text, *ctx.last_preflight())
+    _check(rc)
 
 
 def device_count():
@@ -259,6 +280,48 @@ class RelationResult:
         return out
 
 
+class PreflightReport(ctypes.Structure):
+    """include/bfhip.h `bfhip_preflight_report` (4064 bytes): what the last proof of a context that reached the preflight found."""
+    _fields_ = [("ran", ctypes.c_uint32), ("rejected", ctypes.c_uint32), ("n_bad_components", ctypes.c_int32), ("n_entries", ctypes.c_uint32),
+                ("logup_total", ctypes.c_uint32 * 4), ("components", CheckReport * 13), ("relations", RelationReport * 3), ("entries", RelationEntry * 12),
+                ("seconds", ctypes.c_double), ("reserved", ctypes.c_uint64 * 3)]
+
+    def results(self):
+        """(CheckResult, RelationResult): the CheckResult also carries ran, rejected and seconds."""
+        check = CheckResult(r.as_dict() for r in self.components)
+        check.logup_total, check.n_bad_components = tuple(int(v) for v in self.logup_total), int(self.n_bad_components)
+        check.ran, check.rejected, check.seconds = bool(self.ran), bool(self.rejected), float(self.seconds)
+        ents = [self.entries[4 * k + i].as_dict() for k in range(3) for i in range(min(4, self.relations[k].n_reported))]
+        reps = [self.relations[k].as_dict() if self.relations[k].n_words else dict(RelationReport(k, (3, 3, 7)[k]).as_dict()) for k in range(3)]
+        return check, RelationResult(reps, ents)
+
+
+def format_preflight_lines(check, relations):
+    """The lines of a rejection (what bfhip_format_preflight joins by "\\n"): the headline, CheckResult.failures(), RelationResult.lines().
+    check: a CheckResult with .ran / .rejected (PreflightReport.results())."""
+    if not getattr(check, "ran", True):
+        return ["preflight: did not run"]
+    if not getattr(check, "rejected", not check.ok):
+        return ["preflight: ok"]
+    what = []
+    if check.n_bad_components:
+        what.append("%d of 13 components violate their constraints" % check.n_bad_components)
+    if any(check.logup_total):
+        what.append("the logUp total is not zero")
+    return ["TraceRejected: " + " and ".join(what)] + check.failures() + (relations.lines() if relations is not None else [])
+
+
+def format_preflight(report):
+    """bfhip_format_preflight of a PreflightReport (host only, no GPU): the text a rejection carries."""
+    need = ctypes.c_size_t()
+    rc = lib().bfhip_format_preflight(ctypes.byref(report), None, ctypes.c_size_t(0), ctypes.byref(need))
+    if rc not in (0, -2):
+        raise BfhipError(lib().bfhip_last_error().decode())
+    buf = ctypes.create_string_buffer(need.value)
+    _check(lib().bfhip_format_preflight(ctypes.byref(report), buf, ctypes.c_size_t(need.value), None))
+    return buf.value.decode()
+
+
 def _relation_result(call, max_entries, table_names=None):
     reps = (RelationReport * 3)()
     ents = (RelationEntry * (3 * max_entries))() if max_entries else None
@@ -325,12 +388,34 @@ class Context:
         _check(lib().bfhip_ctx_set_mailbox(self._h, int(mode), int(timeout_ms), int(test_delay_ms)))
 
     def last_proof_flags(self):
-        """bfhip_ctx_last_proof_flags: {mailbox_order, kept_preprocessed, shared_preprocessed, replicated_transforms, split_gather, fri_fold_leaf} of the last
-        completed proof."""
+        """bfhip_ctx_last_proof_flags: {mailbox_order, kept_preprocessed, shared_preprocessed, replicated_transforms, split_gather, fri_fold_leaf, preflight}
+        of the last completed proof."""
         f = ctypes.c_uint32()
         _check(lib().bfhip_ctx_last_proof_flags(self._h, ctypes.byref(f)))
         return {"mailbox_order": bool(f.value & 1), "kept_preprocessed": bool(f.value & 2), "shared_preprocessed": bool(f.value & 4), "replicated_transforms": bool(f.value & 8),
-                "split_gather": bool(f.value & 16), "fri_fold_leaf": bool(f.value & 32)}
+                "split_gather": bool(f.value & 16), "fri_fold_leaf": bool(f.value & 32), "preflight": bool(f.value & 64)}
+
+    def set_preflight(self, on=True):
+        """bfhip_ctx_set_preflight: every later proof of this context first asserts the 13 AIRs and the logUp total on its tables (one batched
+        launch pair, one read-back) and raises TraceRejected — naming component, constraint, row and unbalanced tuple — instead of proving a
+        trace that cannot be proved. A filter, not a soundness gate: the lookup elements are the fixed public ones of Trace.check()."""
+        _check(lib().bfhip_ctx_set_preflight(self._h, 1 if on else 0))
+
+    def preflight(self):
+        on = ctypes.c_int32()
+        _check(lib().bfhip_ctx_get_preflight(self._h, ctypes.byref(on)))
+        return bool(on.value)
+
+    def last_preflight_report(self):
+        """bfhip_ctx_last_preflight as the raw PreflightReport."""
+        rep = PreflightReport()
+        _check(lib().bfhip_ctx_last_preflight(self._h, ctypes.byref(rep)))
+        return rep
+
+    def last_preflight(self):
+        """bfhip_ctx_last_preflight: (CheckResult, RelationResult) of the last proof of this context that reached the preflight. The
+        CheckResult also has .ran, .rejected and .seconds (host wall time of the preflight)."""
+        return self.last_preflight_report().results()
 
     def clock_probe(self, seconds=0.6):
         """bfhip_clock_probe: {ghz (median over workgroups), ghz_min, ghz_max, G_compressions_per_s, launches, ms_per_launch} of a register-only
@@ -583,7 +668,7 @@ class PoolResult(ctypes.Structure):
 
 
 class JobResult:
-    """What Pool.wait() returns: ticket, tag, status (0 ok, -1 failed, JOB_CANCELLED), worker, flags (Context.last_proof_flags bits of that
+    """What Pool.wait() returns: ticket, tag, status (0 ok, -1 failed, JOB_CANCELLED, TRACE_REJECTED), worker, flags (Context.last_proof_flags bits of that
     proof), log_max_rows, proof (bytes, None unless ok), error (str, None when ok), seconds_queued, seconds_proving."""
 
     def __init__(self, r):
@@ -598,6 +683,8 @@ class JobResult:
 
     ok = property(lambda self: self.status == 0)
     cancelled = property(lambda self: self.status == JOB_CANCELLED)
+    rejected = property(lambda self: self.status == TRACE_REJECTED)      # Pool.set_preflight: bad input, not an internal failure
+    preflight = property(lambda self: bool(self.flags & 64))
     shared_preprocessed = property(lambda self: bool(self.flags & 4))
 
     def __repr__(self):
@@ -717,6 +804,11 @@ class Pool:
     def set_preprocessed(self, mode):
         _check(lib().bfhip_pool_set_preprocessed(self._h, int(mode)))
 
+    def set_preflight(self, on=True):
+        """bfhip_pool_set_preflight: Context.set_preflight on every sub-context. A job whose trace is rejected comes back with
+        status TRACE_REJECTED (JobResult.rejected) and the rejection lines as its error; refused while jobs are outstanding."""
+        _check(lib().bfhip_pool_set_preflight(self._h, 1 if on else 0))
+
     def set_pcs_config(self, pcs_config=None):
         """bfhip_pool_set_pcs_config: the PcsConfig of every sub-context and of the shared preprocessed tree's builder (None = the default)."""
         _check(lib().bfhip_pool_set_pcs_config(self._h, _pcs_ref(pcs_config)))
@@ -765,7 +857,8 @@ PHASES = ("preprocessed", "tables_host", "main_trace", "interaction", "compositi
 
 
 def prove_brainfuck(code, input_bytes=b"", ctx=None, log_max_rows=24, with_transcript=False, with_timings=False, pcs_config=None):
-    """prove_brainfuck (mod.rs:471): returns the proof as serde_json bytes of BrainfuckProof. GPU only.
+    """prove_brainfuck (mod.rs:471): returns the proof as serde_json bytes of BrainfuckProof. GPU only. With ctx.set_preflight() a trace
+    that cannot be proved raises TraceRejected (so do prove_registers and Trace.prove).
     pcs_config: a PcsConfig for this proof (None: the context's own, PcsConfig::default() for a new context). A context passed in keeps it
     afterwards."""
     own = ctx is None
@@ -777,8 +870,8 @@ def prove_brainfuck(code, input_bytes=b"", ctx=None, log_max_rows=24, with_trans
             ctx.set_pcs_config(pcs_config)
         js, n, tr = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_void_p()
         times = (ctypes.c_double * 10)()
-        _check(lib().bfhip_prove_brainfuck(ctx._h, code.encode(), input_bytes, ctypes.c_size_t(len(input_bytes)), log_max_rows,
-                                           ctypes.byref(js), ctypes.byref(n), ctypes.byref(tr) if with_transcript else None, times))
+        _check_proof(lib().bfhip_prove_brainfuck(ctx._h, code.encode(), input_bytes, ctypes.c_size_t(len(input_bytes)), log_max_rows,
+                                                 ctypes.byref(js), ctypes.byref(n), ctypes.byref(tr) if with_transcript else None, times), ctx)
         proof = ctypes.string_at(js, n.value)
         lib().bfhip_free_host(js)
         out = [proof]
@@ -806,9 +899,9 @@ def prove_registers(rows, code_words, ctx=None, log_max_rows=24, with_transcript
         code = np.ascontiguousarray(code_words, dtype=np.uint32)
         js, n, t = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_void_p()
         times = (ctypes.c_double * 10)()
-        _check(lib().bfhip_prove_registers(ctx._h, tr.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(tr.shape[0]), code.ctypes.data_as(ctypes.c_void_p),
-                                           ctypes.c_size_t(code.size), log_max_rows, ctypes.byref(js), ctypes.byref(n),
-                                           ctypes.byref(t) if with_transcript else None, times))
+        _check_proof(lib().bfhip_prove_registers(ctx._h, tr.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(tr.shape[0]), code.ctypes.data_as(ctypes.c_void_p),
+                                                 ctypes.c_size_t(code.size), log_max_rows, ctypes.byref(js), ctypes.byref(n),
+                                                 ctypes.byref(t) if with_transcript else None, times), ctx)
         proof = ctypes.string_at(js, n.value)
         lib().bfhip_free_host(js)
         out = [proof]
@@ -895,7 +988,7 @@ class Trace:
     def prove(self, log_max_rows=24, want_json=True):
         js, n = ctypes.c_void_p(), ctypes.c_size_t()
         times = (ctypes.c_double * 10)()
-        _check(lib().bfhip_prove_trace(self.ctx._h, self._h, log_max_rows, ctypes.byref(js) if want_json else None, ctypes.byref(n), None, times))
+        _check_proof(lib().bfhip_prove_trace(self.ctx._h, self._h, log_max_rows, ctypes.byref(js) if want_json else None, ctypes.byref(n), None, times), self.ctx)
         proof = None
         if want_json:
             proof = ctypes.string_at(js, n.value)

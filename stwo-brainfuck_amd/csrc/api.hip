@@ -1,6 +1,7 @@
 // C ABI (include/bfhip.h) over the gfx950 kernels. No torch types, plain pointers and sizes.
 #include "../../include/bfhip.h"
 #include "api_guard.h"
+#include "prover.h"
 #include <cstdlib>
 #include "host/circle.h"
 #include "host/quotients.h"
@@ -279,6 +280,7 @@ static void join_group(bfhip_ctx* ctx, std::unique_ptr<Comm> comm) {
 // checked before the rendezvous: prev_row_copy and the row exchanges of a shard group assume blowup 1, and every rank must prove under one config
 static void check_group_size(const bfhip_ctx* ctx, uint32_t rank, uint32_t count) {
     if (ctx && !ctx->c.pcs.is_default()) throw HipError("a context with a non-default PcsConfig cannot join a shard group (bfhip_ctx_set_pcs_config(ctx, NULL) first)");
+    if (ctx && ctx->c.preflight) throw HipError("a context with the preflight on cannot join a shard group (bfhip_ctx_set_preflight(ctx, 0) first)");
     if (count < 2 || (count & (count - 1)) != 0 || count > 64) throw HipError("shard count must be a power of two in [2, 64]");
     if (rank >= count) throw HipError("shard rank out of range");
 }
@@ -808,25 +810,7 @@ int32_t bfhip_eval_constraints(bfhip_ctx* ctx, int32_t component, uint32_t log_s
     API_CATCH
 }
 // ---- the AIRs asserted on the trace domain (check.hip) -------------------------------------------------------------------------------
-static CheckReportDev check_report_init() { CheckReportDev r{}; r.first_bad_cell = ~u64(0); r.first_bad_constraint = 0xffffffffu; return r; }
-static void check_report_fill(bfhip_check_report& out, const CheckReportDev& r, int component, u32 log_size, Q31 claimed) {
-    out = bfhip_check_report{};
-    out.component = (u32)component; out.log_size = log_size;
-    out.n_bad_cells = r.n_bad_cells; out.first_bad_cell = r.first_bad_cell; out.first_bad_constraint = (int32_t)r.first_bad_constraint;
-    for (int w = 0; w < 4; w++) out.first_bad_value[w] = r.first_bad_value[w];
-    for (int j = 0; j < 16; j++) out.bad_per_constraint[j] = r.bad_per_constraint[j];
-    out.claimed_sum[0] = claimed.a.a; out.claimed_sum[1] = claimed.a.b; out.claimed_sum[2] = claimed.b.a; out.claimed_sum[3] = claimed.b.b;
-}
-// main: row-granular; logup: 4 coordinate columns per logUp column, the last logUp column full size, earlier ones row-granular
-static CheckLaunch check_launch_of(int component, u32 log_size, const u32* const* main_rows, const u32* const* logup_cols, const Lookups& el, Q31 total_sum,
-                                   CheckReportDev* d_report) {
-    CheckLaunch L{};
-    const u32 n_inter = 4 * n_logup_cols(component);
-    for (u32 j = 0; j < n_main_cols(component); j++) L.trace[j] = ColDesc{main_rows[j], LOG_N_LANES, 0};
-    for (u32 j = 0; j < n_inter; j++) L.inter[j] = ColDesc{logup_cols[j], j + 4 < n_inter ? LOG_N_LANES : 0u, 0};
-    L.el = el; L.total_sum = total_sum; L.log_size = log_size; L.report = d_report;
-    return L;
-}
+// check_report_init / check_report_fill / check_launch_of / default_check_lookups: prover.h (shared with a proof's preflight)
 static void check_not_sharded(const Ctx& c) {
     if (c.shard.count > 1) throw HipError("constraint check: a context in a shard group is not supported (bfhip_ctx_leave_group first)");
 }
@@ -866,11 +850,7 @@ int32_t bfhip_trace_check(bfhip_ctx* ctx, const bfhip_trace* trace, const uint32
     Lookups el;
     if (lookup_h) el = lookups_from_h(lookup_h);
     else {
-        // MemoryElements::draw, InstructionElements::draw, ProcessorElements::draw (mod.rs:589-597) on Blake2sChannel::default()
-        Channel ch;
-        { Q31 z, a; ch.draw_two_felts(z, a); el.memory = make_lookup(z, a); }
-        { Q31 z, a; ch.draw_two_felts(z, a); el.instruction = make_lookup(z, a); }
-        { Q31 z, a; ch.draw_two_felts(z, a); el.processor = make_lookup(z, a); }
+        el = default_check_lookups();
     }
     const u32* rows[N_COMPONENTS][13] = {};
     u32 log_sizes[N_COMPONENTS];
@@ -1022,5 +1002,19 @@ extern "C" int32_t bfhip_test_constraint_group_rows(int32_t component, uint32_t 
     for (u32 j = 0; j + 4 < 4 * n_logup_cols(component); j++) L.inter[j].shift = main_shift;
     L.log_size = log_size;
     return (int32_t)constraint_group_rows(L, component);
+}
+// Overwrites one row-granular main column of a resident trace with n_rows host words (n_rows = the column's stored rows): the tests of the trace
+// checks and of a proof's preflight build tables no register trace produces — one component corrupted alone, a chosen cell of a chosen table.
+extern "C" int32_t bfhip_test_trace_set_column(bfhip_ctx* ctx, bfhip_trace* trace, uint32_t component, uint32_t column, const uint32_t* src_h, size_t n_rows) {
+    API_CTX(ctx)
+    if (!trace || !src_h) throw HipError("null argument");
+    if (component >= (uint32_t)N_COMPONENTS || column >= trace->in.rows[component].size()) throw HipError("bad component/column");
+    const DCol& col = trace->in.rows[component][column];
+    if (n_rows != col.stored()) throw HipError("bfhip_test_trace_set_column: n_rows differs from the column's stored rows");
+    ctx->c.sync();
+    BF_HIP(hipMemcpyAsync(col.ptr, src_h, n_rows * sizeof(u32), hipMemcpyHostToDevice, ctx->c.stream));
+    ctx->c.sync();
+    return 0;
+    API_CATCH
 }
 #endif

@@ -53,21 +53,23 @@ static constexpr u32 CHECK_SLOTS = 17;
 // cell order, so its first bad cell is the lowest set bit. Such waves first clear the four presence flags (all write the same zeros), then
 // publish flag, counts and first cell; the lowest of them adds the workgroup's sums to the report: one 64-bit atomicAdd per non-zero
 // counter and one 64-bit atomicMin. Integer atomics only: the report does not depend on the order in which workgroups arrive.
+struct CheckShared { u32 flag[4], first[4], cnt[4][CHECK_SLOTS]; };
+
+// The body shared by k_check_cells and k_check_batch: workgroup `block` of component COMP's cells, closing on `total_sum`.
 template <int COMP>
-__global__ void __launch_bounds__(256) k_check_cells(const CheckLaunch* __restrict__ ap) {
-    __shared__ u32 s_flag[4], s_first[4], s_cnt[4][CHECK_SLOTS];
-    const CheckLaunch& a = *ap;
+__device__ __forceinline__ void check_cells_body(const CheckLaunch& a, CheckShared& sh, u32 block, Q31 total_sum) {
     const u32 n = 1u << a.log_size;
-    const u32 cell = blockIdx.x * 256u + threadIdx.x;
+    const u32 cell = block * 256u + threadIdx.x;
     const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     u32 mask = 0;
     if (cell < n) {
         CheckEval<false> e(a, cell);
+        e.total_sum = total_sum;
         air_eval<COMP>(e, a.el);
         mask = e.mask;
     }
     const u64 bad = __ballot(mask != 0);
-    if (bad && lane < 4) s_flag[lane] = 0;
+    if (bad && lane < 4) sh.flag[lane] = 0;
     __syncthreads();
     if (bad) {
         u32 mine = 0;
@@ -77,33 +79,39 @@ __global__ void __launch_bounds__(256) k_check_cells(const CheckLaunch* __restri
             if (lane == j) mine = cnt;
         }
         if (lane == 16) mine = (u32)__popcll(bad);
-        if (lane < CHECK_SLOTS) s_cnt[wave][lane] = mine;
-        if (lane == 0) { s_flag[wave] = 1; s_first[wave] = blockIdx.x * 256u + wave * 64u + (u32)(__ffsll((long long)bad) - 1); }
+        if (lane < CHECK_SLOTS) sh.cnt[wave][lane] = mine;
+        if (lane == 0) { sh.flag[wave] = 1; sh.first[wave] = block * 256u + wave * 64u + (u32)(__ffsll((long long)bad) - 1); }
     }
     __syncthreads();
     if (!bad) return;
     u32 leader = 0;
-    while (!s_flag[leader]) leader++;       // this wave's own flag is set: leader <= wave
+    while (!sh.flag[leader]) leader++;       // this wave's own flag is set: leader <= wave
     if (wave != leader) return;
     CheckReportDev* rep = a.report;
     if (lane < CHECK_SLOTS) {
         u32 sum = 0;
-        for (u32 w = leader; w < 4; w++) if (s_flag[w]) sum += s_cnt[w][lane];
+        for (u32 w = leader; w < 4; w++) if (sh.flag[w]) sum += sh.cnt[w][lane];
         if (sum) atomicAdd(reinterpret_cast<unsigned long long*>(lane == 16 ? &rep->n_bad_cells : &rep->bad_per_constraint[lane]), (unsigned long long)sum);
     }
-    if (lane == 0) atomicMin(reinterpret_cast<unsigned long long*>(&rep->first_bad_cell), (unsigned long long)s_first[leader]);   // waves are in cell order too
+    if (lane == 0) atomicMin(reinterpret_cast<unsigned long long*>(&rep->first_bad_cell), (unsigned long long)sh.first[leader]);   // waves are in cell order too
 }
 
-// One wave re-evaluates the AIR at the first bad cell (known once k_check_cells has completed: same stream) and writes the lowest failing
+template <int COMP>
+__global__ void __launch_bounds__(256) k_check_cells(const CheckLaunch* __restrict__ ap) {
+    __shared__ CheckShared sh;
+    check_cells_body<COMP>(*ap, sh, blockIdx.x, ap->total_sum);
+}
+
+// One wave re-evaluates the AIR at the first bad cell (known once the cells pass has completed: same stream) and writes the lowest failing
 // constraint and its value; -1 and zeros for a trace without violations.
 template <int COMP>
-__global__ void __launch_bounds__(64) k_check_first(const CheckLaunch* __restrict__ ap) {
-    const CheckLaunch& a = *ap;
+__device__ __forceinline__ void check_first_body(const CheckLaunch& a, Q31 total_sum) {
     CheckReportDev* rep = a.report;
     const u64 cell = rep->first_bad_cell;
     u32 first = 0xffffffffu; Q31 v = q_zero();
     if (cell < ((u64)1 << a.log_size)) {
         CheckEval<true> e(a, (u32)cell);
+        e.total_sum = total_sum;
         air_eval<COMP>(e, a.el);
         first = e.first; v = e.first_value;
     }
@@ -111,6 +119,64 @@ __global__ void __launch_bounds__(64) k_check_first(const CheckLaunch* __restric
         rep->first_bad_constraint = first;
         rep->first_bad_value[0] = v.a.a; rep->first_bad_value[1] = v.a.b; rep->first_bad_value[2] = v.b.a; rep->first_bad_value[3] = v.b.b;
     }
+}
+
+template <int COMP>
+__global__ void __launch_bounds__(64) k_check_first(const CheckLaunch* __restrict__ ap) { check_first_body<COMP>(*ap, ap->total_sum); }
+
+// ---- the 13 components in one launch pair (a proof's preflight) ---------------------------------------------------------------------------
+// A workgroup finds its component from the workgroup offsets (uniform: scalar loads, as k_constraints_batch and k_rel_flags do) and branches
+// on it once, so no wave mixes components; the component's total_sum is the claimed sum the logUp pass left in out->claimed[k].
+#define CHECK_DISPATCH(k, CALL) \
+    switch (k) { \
+        case C_MEMORY: { constexpr int C = C_MEMORY; CALL; } break; case C_INSTRUCTION: { constexpr int C = C_INSTRUCTION; CALL; } break; \
+        case C_PROGRAM: { constexpr int C = C_PROGRAM; CALL; } break; case C_PROCESSOR: { constexpr int C = C_PROCESSOR; CALL; } break; \
+        case C_JNZ: { constexpr int C = C_JNZ; CALL; } break; case C_JZ: { constexpr int C = C_JZ; CALL; } break; \
+        case C_INPUT: { constexpr int C = C_INPUT; CALL; } break; case C_LEFT: { constexpr int C = C_LEFT; CALL; } break; \
+        case C_MINUS: { constexpr int C = C_MINUS; CALL; } break; case C_OUTPUT: { constexpr int C = C_OUTPUT; CALL; } break; \
+        case C_PLUS: { constexpr int C = C_PLUS; CALL; } break; case C_RIGHT: { constexpr int C = C_RIGHT; CALL; } break; \
+        default: { constexpr int C = C_EOE; CALL; } break; \
+    }
+__device__ __forceinline__ Q31 claimed_of(const CheckReadback* out, u32 k) { const uint4 v = out->claimed[k]; return q_make(v.x, v.y, v.z, v.w); }
+
+__global__ void __launch_bounds__(256) k_check_batch(const CheckBatch* __restrict__ bp, const CheckLaunch* __restrict__ launches) {
+    __shared__ CheckShared sh;
+    const CheckBatch& b = *bp;
+    u32 k = 0;
+    while (k + 1 < (u32)N_COMPONENTS && b.blk0[k + 1] <= blockIdx.x) k++;
+    const CheckLaunch& a = launches[k];
+    const u32 block = blockIdx.x - b.blk0[k];
+    const Q31 total_sum = claimed_of(b.out, k);
+    CHECK_DISPATCH(k, check_cells_body<C>(a, sh, block, total_sum))
+}
+
+// Workgroup k < 13 (one wave): k_check_first of component k. Workgroup 13: the QM31 sum of the 13 claimed sums -> out->total.
+__global__ void __launch_bounds__(64) k_check_first_batch(const CheckBatch* __restrict__ bp, const CheckLaunch* __restrict__ launches) {
+    const CheckBatch& b = *bp;
+    const u32 k = blockIdx.x;
+    if (k >= (u32)N_COMPONENTS) {
+        if (threadIdx.x != 0) return;
+        Q31 t = q_zero();
+        for (u32 j = 0; j < (u32)N_COMPONENTS; j++) t = q_add(t, claimed_of(b.out, j));
+        b.out->total = make_uint4(t.a.a, t.a.b, t.b.a, t.b.b);
+        return;
+    }
+    const CheckLaunch& a = launches[k];
+    const Q31 total_sum = claimed_of(b.out, k);
+    CHECK_DISPATCH(k, check_first_body<C>(a, total_sum))
+}
+#undef CHECK_DISPATCH
+
+void check_batch_init(CheckBatch& b, const u32 log_sizes[N_COMPONENTS], CheckReadback* d_out) {
+    b = CheckBatch{};
+    u32 blocks = 0;
+    for (int k = 0; k < N_COMPONENTS; k++) { b.blk0[k] = blocks; blocks += ((1u << log_sizes[k]) + 255u) / 256u; }      // log_size <= 29: at most 13 * 2^21 workgroups
+    b.blk0[N_COMPONENTS] = blocks;
+    b.out = d_out;
+}
+void check_batch_run(hipStream_t stream, const CheckBatch* d_batch, const CheckBatch& h_batch, const CheckLaunch* d_launches) {
+    hipLaunchKernelGGL(k_check_batch, dim3(h_batch.blk0[N_COMPONENTS]), dim3(256), 0, stream, d_batch, d_launches);
+    hipLaunchKernelGGL(k_check_first_batch, dim3(N_COMPONENTS + 1), dim3(64), 0, stream, d_batch, d_launches);
 }
 
 template <int COMP>

@@ -11,9 +11,16 @@
 #include <stdexcept>
 #include <cstring>
 
+struct bfhip_preflight_report;
+struct bfhip_relation_report;
+struct bfhip_relation_entry;
+
 namespace bf {
 
 struct HipError : std::runtime_error { using std::runtime_error::runtime_error; };
+// A proof's preflight refused the trace (prover_preflight.hip): the one error the C ABI returns as BFHIP_TRACE_REJECTED instead of -1
+// (api_guard.h), so that a caller can tell bad input from an internal failure. what() = the text of bfhip_format_preflight.
+struct TraceRejected : HipError { using HipError::HipError; };
 // A failed runtime call also leaves its code in the thread's "last error"; it is cleared here, or the next BF_HIP(hipGetLastError()) behind a perfectly
 // good launch would report it (r06: an out-of-memory context creation made the NEXT creation on that thread fail with "out of memory").
 #define BF_HIP(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { (void)hipGetLastError(); throw bf::HipError(std::string(#expr) + ": " + hipGetErrorString(e__)); } } while (0)
@@ -35,6 +42,10 @@ struct Arena {
         return p;
     }
     void reset() { for (auto& c : chunks) c.used = 0; total_used = 0; }
+    // mark() / rewind(): what was allocated after the mark is given back (chunks obtained meanwhile stay reserved, empty); the peak keeps it
+    struct Mark { std::vector<size_t> used; size_t total_used; };
+    Mark mark() const { Mark m; for (auto& c : chunks) m.used.push_back(c.used); m.total_used = total_used; return m; }
+    void rewind(const Mark& m) { for (size_t i = 0; i < chunks.size(); i++) chunks[i].used = i < m.used.size() ? m.used[i] : 0; total_used = m.total_used; }
     void release() { for (auto& c : chunks) (void)hipFree(c.base); chunks.clear(); total_used = 0; }
 };
 
@@ -53,6 +64,10 @@ struct Ctx {
     ShardGroup shard;
     int shard_policy = -1;          // bfhip_ctx_set_shard_policy: -1 automatic, 0 exchange columns -> rows (column-sharded transforms), 1 replicate the transforms
     bool shard_replicate = false;   // the decision for the proof in progress (HipProver::prove)
+    // bfhip_ctx_set_preflight: every proof of this context first asserts the 13 AIRs and the logUp total on its tables (prover_preflight.hip);
+    // preflight_last = the report of the last proof that reached it (bfhip_ctx_last_preflight), created by the first such proof
+    bool preflight = false;
+    std::shared_ptr<bfhip_preflight_report> preflight_last;
     hipStream_t stream = nullptr;
     // side stream: the trace-independent preprocessed commitment runs here, beside the main-trace phase. Created by the first proof that uses it
     // (ensure_side): a pool worker whose proofs take the pool's shared preprocessed tree never does, and every stream a process creates takes a
@@ -257,6 +272,11 @@ void shared_preprocessed_destroy(SharedPreprocessed* sp);
 bool shared_preprocessed_matches(const SharedPreprocessed* sp, const Ctx& c, u32 log_max_rows);
 void shared_preprocessed_build(SharedPreprocessed* sp, Ctx& builder, u32 log_max_rows);      // enqueues, records sp->ready, returns without waiting
 void shared_preprocessed_invalidate(SharedPreprocessed* sp);
+
+// relations.hip: bfhip_relation_summary's pass over the 13 tables of a proof in progress — arena memory is taken above the current mark and
+// given back, nothing is reset (the tables themselves may sit in the arena)
+void relations_in_proof(Ctx& c, const u32* const* const cols[N_COMPONENTS], const u32 log_sizes[N_COMPONENTS], bfhip_relation_report* out,
+                        bfhip_relation_entry* entries_h, u32 cap);
 
 void mailbox_launch(hipStream_t s, const u32* d_flag, u32 expect, const void* src_pinned_alias, void* dst, size_t bytes, u32* d_err, double timeout_seconds);
 void post_stamp_launch(hipStream_t s, u32* d_stamp, u32 value);

@@ -224,6 +224,15 @@ struct CheckReportDev { u64 n_bad_cells, first_bad_cell; u64 bad_per_constraint[
 struct CheckLaunch { ColDesc trace[13]; ColDesc inter[12]; Lookups el; Q31 total_sum; u32 log_size; u32 pad_; CheckReportDev* report; };
 // k_check_cells (counters, first bad cell) followed by k_check_first (constraint index and value at that cell) on `stream`
 void check_constraints_launch(hipStream_t stream, int comp, const CheckLaunch* d_args, u32 log_size);
+// The 13 components as ONE launch pair (a proof's preflight, prover_preflight.hip). Everything the host reads afterwards is one block:
+// the reports, the claimed sums the logUp pass wrote (LogupLaunch::claimed = &out->claimed[k]) and their QM31 sum. The kernels take each
+// component's total_sum from out->claimed[k], so nothing is read back between the logUp pass and the check (CheckLaunch::total_sum is
+// ignored; CheckLaunch::report = &out->report[k]). The host initialises the reports as for check_constraints_launch.
+struct CheckReadback { CheckReportDev report[N_COMPONENTS]; uint4 claimed[N_COMPONENTS]; uint4 total; };
+struct CheckBatch { u32 blk0[N_COMPONENTS + 1]; u32 pad_[2]; CheckReadback* out; };      // blk0[k] = first workgroup of component k, blk0[13] = the grid
+void check_batch_init(CheckBatch& b, const u32 log_sizes[N_COMPONENTS], CheckReadback* d_out);
+// k_check_batch (cells of all 13 components) followed by k_check_first_batch (13 waves + one for the total); d_launches: 13 CheckLaunch
+void check_batch_run(hipStream_t stream, const CheckBatch* d_batch, const CheckBatch& h_batch, const CheckLaunch* d_launches);
 
 // prover.hip — the row-granular main-trace columns and the log sizes of a resident trace (for bfhip_trace_check in api.hip)
 void trace_columns(const bfhip_trace* t, const u32* cols[N_COMPONENTS][13], u32 log_sizes[N_COMPONENTS]);

@@ -137,7 +137,7 @@ struct bfhip_pool {
             else if (q.kind == 1) rc = bfhip_prove_brainfuck(subs[w], q.code.c_str(), q.input.data(), q.input.size(), q.log_max_rows, &js, &n, nullptr, nullptr);
             else rc = bfhip_prove_registers(subs[w], q.rows, q.n_rows, q.words.data(), q.words.size(), q.log_max_rows, &js, &n, nullptr, nullptr);
             if (rc == 0) { r.status = 0; r.proof_json = js; r.proof_len = n; r.flags = subs[w]->c.last_proof_flags; js = nullptr; }
-            else err = bfhip_last_error();
+            else { if (rc == BFHIP_TRACE_REJECTED) r.status = rc; err = bfhip_last_error(); }      // bad input, not an internal failure
         } catch (const std::exception& e) { err = e.what(); } catch (...) { err = "unknown error"; }
         subs[w]->c.shared_pre = nullptr;
         try { release_tree(tree); } catch (...) {}
@@ -308,6 +308,15 @@ int32_t bfhip_pool_set_pcs_config(bfhip_pool* pool, const bfhip_pcs_config* pcs)
     for (auto* s : pool->subs) if (bfhip_ctx_set_pcs_config(s, pcs) != 0) return -1;
     if (bfhip_ctx_set_pcs_config(pool->builder, pcs) != 0) return -1;
     pool->invalidate_trees();
+    return 0;
+    API_CATCH
+}
+
+int32_t bfhip_pool_set_preflight(bfhip_pool* pool, int32_t on) {
+    API_POOL(pool)
+    std::lock_guard<std::mutex> call(pool->call_mu);
+    pool->require_idle("bfhip_pool_set_preflight");
+    for (auto* s : pool->subs) if (bfhip_ctx_set_preflight(s, on) != 0) return -1;
     return 0;
     API_CATCH
 }

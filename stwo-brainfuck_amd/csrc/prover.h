@@ -102,6 +102,38 @@ struct SharedPreprocessed {
     }
 };
 
+// ---- the AIRs asserted on the trace domain (check.hip): what bfhip_check_constraints / bfhip_trace_check (api.hip) and a proof's preflight
+// (prover_preflight.hip) share --------------------------------------------------------------------------------------------------------------
+inline CheckReportDev check_report_init() { CheckReportDev r{}; r.first_bad_cell = ~u64(0); r.first_bad_constraint = 0xffffffffu; return r; }
+inline void check_report_fill(bfhip_check_report& out, const CheckReportDev& r, int component, u32 log_size, Q31 claimed) {
+    out = bfhip_check_report{};
+    out.component = (u32)component; out.log_size = log_size;
+    out.n_bad_cells = r.n_bad_cells; out.first_bad_cell = r.first_bad_cell; out.first_bad_constraint = (int32_t)r.first_bad_constraint;
+    for (int w = 0; w < 4; w++) out.first_bad_value[w] = r.first_bad_value[w];
+    for (int j = 0; j < 16; j++) out.bad_per_constraint[j] = r.bad_per_constraint[j];
+    out.claimed_sum[0] = claimed.a.a; out.claimed_sum[1] = claimed.a.b; out.claimed_sum[2] = claimed.b.a; out.claimed_sum[3] = claimed.b.b;
+}
+// main: row-granular; logup: 4 coordinate columns per logUp column, the last logUp column full size, earlier ones row-granular
+inline CheckLaunch check_launch_of(int component, u32 log_size, const u32* const* main_rows, const u32* const* logup_cols, const Lookups& el, Q31 total_sum,
+                                   CheckReportDev* d_report) {
+    CheckLaunch L{};
+    const u32 n_inter = 4 * n_logup_cols(component);
+    for (u32 j = 0; j < n_main_cols(component); j++) L.trace[j] = ColDesc{main_rows[j], LOG_N_LANES, 0};
+    for (u32 j = 0; j < n_inter; j++) L.inter[j] = ColDesc{logup_cols[j], j + 4 < n_inter ? LOG_N_LANES : 0u, 0};
+    L.el = el; L.total_sum = total_sum; L.log_size = log_size; L.report = d_report;
+    return L;
+}
+// The lookup elements of bfhip_trace_check(.., NULL, ..): MemoryElements::draw, InstructionElements::draw, ProcessorElements::draw
+// (mod.rs:589-597) on Blake2sChannel::default()
+inline Lookups default_check_lookups() {
+    Lookups el;
+    Channel ch;
+    { Q31 z, a; ch.draw_two_felts(z, a); el.memory = make_lookup(z, a); }
+    { Q31 z, a; ch.draw_two_felts(z, a); el.instruction = make_lookup(z, a); }
+    { Q31 z, a; ch.draw_two_felts(z, a); el.processor = make_lookup(z, a); }
+    return el;
+}
+
 // waits for the context's main, side and partner streams
 inline void sync_both(Ctx& c) { c.sync(); if (c.stream2) BF_HIP(hipStreamSynchronize(c.stream2)); for (auto a : c.aux) if (a) BF_HIP(hipStreamSynchronize(a)); }
 
@@ -131,6 +163,9 @@ struct HipProver {
     void check_config() const;      // prover.hip: what every proof and the pool's preprocessed build check first
     BrainfuckProof prove(const TraceInput& in) { return prove([&]() -> const TraceInput& { return in; }); }
     BrainfuckProof prove(const std::function<const TraceInput&()>& get_input);      // prover.hip
+    // prover_preflight.hip (bfhip_ctx_set_preflight): the 13 AIRs and the logUp total asserted on the proof's tables before its main-trace
+    // phase; fills c.preflight_last, throws TraceRejected for a trace that cannot be proved
+    void preflight(const TraceInput& in);
 
     // ---- prover_commit.hip: transforms, Merkle trees, tree commitments, the preprocessed tree ------------------------------------------------
     FftPlan fft_prepare(bool inverse, const std::vector<DCol>& src, const std::vector<DCol>& dst);

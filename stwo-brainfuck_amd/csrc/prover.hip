@@ -144,6 +144,10 @@ BrainfuckProof HipProver::prove(const std::function<const TraceInput&()>& get_in
     const TraceInput* in_p = nullptr;
     try { in_p = &get_input(); } catch (...) { join_side(); throw; }
     const TraceInput& in = *in_p;
+    // bfhip_ctx_set_preflight: a trace that cannot be proved is refused here, before anything of the main-trace phase is enqueued — the
+    // side stream's commitment is joined as at the other early exits, and a pool's shared tree has not been awaited yet
+    const bool preflight_ran = c.preflight && !sharded();
+    if (preflight_ran) { try { preflight(in); } catch (...) { join_side(); throw; } }
 
     // ---- Phase 1: main trace (mod.rs:506-583) -----------------------------------------------------------------------------
     const std::vector<std::vector<DCol>>& rows = in.rows;   // row-granular table columns (also feed the logUp pass)
@@ -501,7 +505,7 @@ BrainfuckProof HipProver::prove(const std::function<const TraceInput&()>& get_in
         tm.fri = (now() - t0) - tm.quotients;
     }
 
-    c.last_proof_flags = (c.last_proof_flags & 48u) | (mb ? 1u : 0u) | (reuse && !shared ? 2u : 0u) | (shared ? 4u : 0u) | (replicate() ? 8u : 0u);
+    c.last_proof_flags = (c.last_proof_flags & 48u) | (mb ? 1u : 0u) | (reuse && !shared ? 2u : 0u) | (shared ? 4u : 0u) | (replicate() ? 8u : 0u) | (preflight_ran ? 64u : 0u);
     tm.total = now() - t_start;
     mark("done");
     print_marks();

@@ -272,7 +272,9 @@ static void relation_run(Ctx& c, u32 relation, const RelSources& S, u32 N, u32 c
 
 struct RelTable { int component; u32 log_size; const u32* const* cols; };
 
-static void relations_run(Ctx& c, const RelTable* tables, u32 n_tables, bfhip_relation_report out[3], bfhip_relation_entry* entries_h, u32 cap) {
+// in_proof: called from inside a proof (its preflight) — the arena holds the proof's tables, so each relation's scratch is taken above a mark
+// and given back instead of resetting the arena, and the staging ring is left alone
+static void relations_run(Ctx& c, const RelTable* tables, u32 n_tables, bfhip_relation_report out[3], bfhip_relation_entry* entries_h, u32 cap, bool in_proof = false) {
     if (c.shard.count > 1) throw HipError("relation summary: a context in a shard group is not supported (bfhip_ctx_leave_group first)");
     u64 total_rows = 0;
     for (u32 t = 0; t < n_tables; t++) {
@@ -286,6 +288,7 @@ static void relations_run(Ctx& c, const RelTable* tables, u32 n_tables, bfhip_re
     }
     if (total_rows > (u64(1) << 31)) throw HipError("more than 2^31 table rows in total");
     static const u32 N_WORDS[3] = {3, 3, 7};
+    const Arena::Mark arena_mark = c.arena.mark();
     for (u32 r = 0; r < 3; r++) {
         RelSources S{};
         S.n_words = N_WORDS[r];
@@ -316,11 +319,19 @@ static void relations_run(Ctx& c, const RelTable* tables, u32 n_tables, bfhip_re
         }
         // like a proof: nothing of this context is in flight, and its per-proof memory starts empty
         c.sync();
-        c.arena.reset();
-        c.stage_checkpoint();
+        if (in_proof) c.arena.rewind(arena_mark);
+        else { c.arena.reset(); c.stage_checkpoint(); }
         relation_run(c, r, S, N, cap, out[r], entries_h ? entries_h + size_t(r) * cap : nullptr);
     }
+    if (in_proof) { c.sync(); c.arena.rewind(arena_mark); }
     BF_HIP(hipGetLastError());
+}
+
+void relations_in_proof(Ctx& c, const u32* const* const cols[N_COMPONENTS], const u32 log_sizes[N_COMPONENTS], bfhip_relation_report* out,
+                        bfhip_relation_entry* entries_h, u32 cap) {
+    RelTable t[N_COMPONENTS];
+    for (int k = 0; k < N_COMPONENTS; k++) t[k] = RelTable{k, log_sizes[k], cols[k]};
+    relations_run(c, t, N_COMPONENTS, out, entries_h, cap, /*in_proof=*/true);
 }
 
 }  // namespace bf

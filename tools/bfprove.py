@@ -5,8 +5,9 @@ tracker for it:
 
   bfprove.py prove  (--file prog.bf | --code '++>,<[>+.<-]') [--input-file in.bin] [--ram-size N] [--output proof.json]
                     [--log-max-rows 24] [--conventions a,b,c,d | --poseidon252] [--all-sets DIR] [PCS options]
+                    [--preflight] [--set-register ROW:NAME=VALUE ...] [--set-word INDEX=VALUE ...]
   bfprove.py prove  --queue N --programs a.bf b.bf ... --output-dir DIR [--input-file in.bin] [--ram-size N] [--log-max-rows 24]
-                    [--conventions a,b,c,d | --poseidon252] [PCS options]
+                    [--conventions a,b,c,d | --poseidon252] [PCS options] [--preflight] [--set-register ...]
   bfprove.py verify proof.json [--log-max-rows 24] [--conventions a,b,c,d | --poseidon252 | --try-all] [PCS options]
   bfprove.py check  (--file prog.bf | --code '++>,<[>+.<-]') [--input-file in.bin] [--ram-size N] [--set-register ROW:NAME=VALUE ...]
   bfprove.py relations (--file prog.bf | --code ...) [--input-file in.bin] [--ram-size N] [--set-register ROW:NAME=VALUE ...]
@@ -27,6 +28,12 @@ prove --queue N proves a list of programs N at a time through the pool's queue (
 is run on the host VM, its executed machine is submitted, and each proof is written to DIR/<program name>.proof.json as it completes — in
 completion order, one line per proof on stdout. A program that fails (too large for --log-max-rows, input exhausted) is reported with its
 own error and does not stop the others; the exit code is 1 if any failed.
+
+prove --preflight switches on the proof's own filter (bfhip_ctx_set_preflight / bfhip_pool_set_preflight): the 13 AIRs and the logUp total
+are asserted on the tables before the proof starts, and a trace that cannot be proved is refused with the lines check and relations would
+print — "TraceRejected: 1 of 13 components violate their constraints ..." on stdout, exit code 1 — instead of a proof's worth of GPU time and
+"ConstraintsNotSatisfied". In --queue mode a rejected program is reported with those lines and does not stop the others. --set-register /
+--set-word hand the prover the executed machine with one register / program word altered (in --queue mode: of every program).
 
 PCS options (stwo's PcsConfig; the defaults are PcsConfig::default()): --pow-bits 5 --log-blowup-factor 1 --n-queries 3. The proof file does
 not record them: verify with the values the proof was made with. prove prints the config and its security bits (pow + blowup x queries).
@@ -111,6 +118,8 @@ def main():
     p.add_argument("--conventions"); p.add_argument("--all-sets", metavar="DIR")
     p.add_argument("--queue", type=int, default=0, metavar="N", help="prove --programs through the pool's queue, N proofs in flight")
     p.add_argument("--programs", nargs="+", default=[], metavar="FILE"); p.add_argument("--output-dir", metavar="DIR")
+    p.add_argument("--preflight", action="store_true", help="reject a trace that cannot be proved before proving it, naming row and tuple")
+    p.add_argument("--set-register", action="append", default=[], metavar="ROW:NAME=VALUE"); p.add_argument("--set-word", action="append", default=[], metavar="INDEX=VALUE")
     v = sub.add_parser("verify")
     v.add_argument("proof"); v.add_argument("--log-max-rows", type=int, default=24); v.add_argument("--poseidon252", action="store_true")
     v.add_argument("--conventions"); v.add_argument("--try-all", action="store_true")
@@ -134,12 +143,8 @@ def main():
 REGISTERS = ("clk", "ip", "ci", "ni", "mp", "mv", "mvi")
 
 
-def executed_trace(pkg, a, ap):
-    """The program run on the host VM, --set-register / --set-word applied, as a resident trace: (context, trace)."""
-    code = open(a.file).read() if a.file else a.code
-    if code is None:
-        ap.error(f"{a.cmd} needs --file or --code")
-    inp = open(a.input_file, "rb").read() if a.input_file else (b"" if sys.stdin.isatty() else sys.stdin.buffer.read())
+def executed_machine(pkg, a, ap, code, inp):
+    """The program run on the host VM, --set-register / --set-word applied: (register rows, program words)."""
     _, rows = pkg.host_run(code, inp, ram_size=a.ram_size)
     for spec in a.set_register:
         try:
@@ -155,6 +160,16 @@ def executed_trace(pkg, a, ap):
             words[int(index)] = int(value)
         except (ValueError, IndexError):
             ap.error(f"--set-word takes INDEX=VALUE with INDEX < {words.size}, got {spec!r}")
+    return rows, words
+
+
+def executed_trace(pkg, a, ap):
+    """The executed machine of --file / --code as a resident trace: (context, trace)."""
+    code = open(a.file).read() if a.file else a.code
+    if code is None:
+        ap.error(f"{a.cmd} needs --file or --code")
+    inp = open(a.input_file, "rb").read() if a.input_file else (b"" if sys.stdin.isatty() else sys.stdin.buffer.read())
+    rows, words = executed_machine(pkg, a, ap, code, inp)
     ctx = pkg.Context(0, max_log_domain=8)       # neither the check nor the relation summary needs a twiddle tree
     return ctx, pkg.Trace.from_registers(ctx, rows, words)
 
@@ -195,17 +210,23 @@ def prove_queue(pkg, a, ap):
     try:
         pool.set_pcs_config(pcs)
         pool.set_conventions(*parse_conventions(a))
+        if a.preflight:
+            pool.set_preflight(True)
         t0 = time.time()
         for i, path in enumerate(a.programs):
             code = open(path).read()
             try:
-                _, rows = pkg.host_run(code, inp, ram_size=a.ram_size)
-                pool.submit_registers(rows, pkg.host_compile(code), a.log_max_rows, tag=i)
+                rows, words = executed_machine(pkg, a, ap, code, inp)
+                pool.submit_registers(rows, words, a.log_max_rows, tag=i)
             except pkg.BfhipError as e:            # the VM refused the program: nothing was submitted
                 failed += 1
                 print(f"{path}: error: {e}", file=sys.stderr)
         for r in pool.as_completed(timeout_s=3600.0):
             path = a.programs[r.tag]
+            if r.rejected:                         # --preflight: the rejection lines, "job <ticket>: TraceRejected: ..." first
+                failed += 1
+                print(f"{path}: {r.error}", flush=True)
+                continue
             if not r.ok:
                 failed += 1
                 print(f"{path}: error: {r.error}", file=sys.stderr)
@@ -237,15 +258,24 @@ def run(pkg, a, ap):
         pcs = parse_pcs(pkg, a)
         ctx = pkg.Context(0, max_log_domain=a.log_max_rows + pcs.log_blowup_factor + 1)
         ctx.set_pcs_config(pcs)
+        ctx.set_preflight(a.preflight)
         print(f"PcsConfig: pow_bits={pcs.pow_bits} log_blowup_factor={pcs.log_blowup_factor} n_queries={pcs.n_queries} "
               f"log_last_layer_degree_bound={pcs.log_last_layer_degree_bound}; security {pkg.security_bits(pcs)} bits", file=sys.stderr)
         t0 = time.time()
-        tr = pkg.Trace(ctx, code, inp, ram_size=a.ram_size)
+        if a.set_register or a.set_word:
+            tr = pkg.Trace.from_registers(ctx, *executed_machine(pkg, a, ap, code, inp))
+        else:
+            tr = pkg.Trace(ctx, code, inp, ram_size=a.ram_size)
         t_prep = time.time() - t0           # VM run + table build + upload, once, whatever the number of convention sets
         for conv in sets:
             ctx.set_conventions(*conv)
             t_start = time.time()
-            proof, _ = tr.prove(a.log_max_rows)
+            try:
+                proof, _ = tr.prove(a.log_max_rows)
+            except pkg.TraceRejected as e:          # --preflight: the lines check / relations would print
+                print(e)
+                tr.close(); ctx.close()
+                return 1
             t_proof = time.time() - t_start
             print(f"Steps: {tr.n_steps}; trace preparation {1e3 * t_prep:.1f} ms; proof generation time: {t_proof:.3f}s; {len(proof)} bytes; {describe(conv)}", file=sys.stderr)
             if a.all_sets:
