@@ -292,8 +292,20 @@ struct HipProver {
     static std::vector<DCol> secure_cols(const DSecure& s);
     // what the commit phase hands to the decommitment: the first-layer tree over the coordinate columns of every quotient, and every inner
     // layer's evaluation with its tree
-    struct FriCommitted { struct Inner { DSecure ev; DevMerkle tree; }; DevMerkle first_tree; std::vector<DCol> first_cols; std::vector<Inner> inner; };
-    FriCommitted fri_commit(std::vector<DSecure>& quotients, StarkProof& pf, const std::vector<LevelWait>& q_waits, const std::function<void()>& while_the_commit_phase_runs);
+    // layers, path, d_alpha, d_chan: what the test hook of the commit phase (bfhip_test_fri_commit) reads back — every line layer (the last one
+    // included), alpha || alpha^2 per channel step, the device channel, and per layer who produced it: path[k] = who folded layer k (FRI_BY_*),
+    // | FRI_QUOTIENT when a circle evaluation was folded in, | who hashed its tree << 4 (FRI_NO_TREE: the last layer). Written by the driver
+    // where it takes each decision.
+    enum : u32 { FRI_BY_LAUNCHES = 0, FRI_BY_FOLD_LEAF = 1, FRI_BY_LAYER_KERNEL = 2, FRI_BY_TAIL = 3, FRI_QUOTIENT = 4, FRI_NO_TREE = 15 };
+    static constexpr size_t FRI_MAX_LAYERS = 40;
+    struct FriCommitted {
+        struct Inner { DSecure ev; DevMerkle tree; }; DevMerkle first_tree; std::vector<DCol> first_cols; std::vector<Inner> inner;
+        std::vector<DSecure> layers; std::vector<u32> path; u32* d_alpha = nullptr; u32* d_chan = nullptr;
+    };
+    // last_layer_poly = false (the test hook: arbitrary columns have no low degree): the 2^b evaluations of the last layer are left as they
+    // are — no degree check, no coefficient mixed into the channel, pf untouched
+    FriCommitted fri_commit(std::vector<DSecure>& quotients, StarkProof& pf, const std::vector<LevelWait>& q_waits, const std::function<void()>& while_the_commit_phase_runs,
+                            bool last_layer_poly = true);
     void grind(StarkProof& pf);
     void decommit_queries(std::vector<DTree>& trees, const std::vector<DSecure>& quotients, const FriCommitted& fc, StarkProof& pf);
 };

@@ -134,7 +134,7 @@ std::vector<DCol> HipProver::secure_cols(const DSecure& s) {
 }
 
 HipProver::FriCommitted HipProver::fri_commit(std::vector<DSecure>& quotients, StarkProof& pf, const std::vector<LevelWait>& q_waits,
-                                              const std::function<void()>& while_the_commit_phase_runs) {
+                                              const std::function<void()>& while_the_commit_phase_runs, bool last_layer_poly) {
     // FriProver::commit — first layer: one Merkle tree over the coordinate columns of every quotient.
     // The channel is stepped on the device through the whole commit phase (k_channel_mix_root_draw): per layer mix_root(root) and
     // draw_felt() run as a one-lane kernel and the folds read alpha from device memory, so the ~25 layers are enqueued back to back
@@ -143,7 +143,7 @@ HipProver::FriCommitted HipProver::fri_commit(std::vector<DSecure>& quotients, S
     FriCommitted out;
     std::vector<DCol>& first_cols = out.first_cols;
     for (auto& q : quotients) for (auto& col : secure_cols(q)) first_cols.push_back(col);
-    const size_t max_layers = 40;
+    const size_t max_layers = FRI_MAX_LAYERS;
     Hash32* pinned_roots = reinterpret_cast<Hash32*>(c.h_small + 64);                       // [0] first layer, [1 + i] inner layer i
     u32* pinned_chan = reinterpret_cast<u32*>(c.h_small + 64 + 32 * (max_layers + 1));      // digest[8] || n_sent
     u32* d_chan = c.alloc_u32(16);
@@ -174,7 +174,11 @@ HipProver::FriCommitted HipProver::fri_commit(std::vector<DSecure>& quotients, S
     // Every layer's storage and (device channel) every tree's layout exist before the first launch: the column descriptors and level
     // tables of all ~26 trees reach the device in ONE staging copy instead of one in front of every layer of the serial chain.
     const u32 n_inner = line_log > last_log ? line_log - last_log : 0;
-    std::vector<DSecure> layers(n_inner + 1);
+    std::vector<DSecure>& layers = out.layers;
+    layers.resize(n_inner + 1);
+    out.path.assign(n_inner + 1, 0u); out.path[n_inner] = FRI_NO_TREE << 4; out.d_alpha = d_alpha; out.d_chan = d_chan;
+    auto folded_by = [&](u32 k, u32 who, bool quotient) { out.path[k] |= who | (quotient ? (u32)FRI_QUOTIENT : 0u); };
+    auto hashed_by = [&](u32 k, u32 who) { out.path[k] |= who << 4; };
     for (u32 i = 0; i <= n_inner; i++) layers[i] = new_layer(line_log - i);
     std::vector<MerklePlan> plans;                  // [0] first layer, [1 + i] inner layer i
     // Layers of 2^17 rows and above (the ones neither k_fri_layer nor k_fri_tail takes): the fold that produces layer k runs inside the
@@ -236,6 +240,7 @@ HipProver::FriCommitted HipProver::fri_commit(std::vector<DSecure>& quotients, S
         const DSecure& q = quotients[qi++];
         const u32* src[4] = {q.c[0], q.c[1], q.c[2], q.c[3]};
         u32 first, count; fold_range(q.log_size, q.lc != 0, first, count);
+        folded_by(0, fold_leaf(0) ? FRI_BY_FOLD_LEAF : FRI_BY_LAUNCHES, true);
         if (fold_leaf(0)) describe_fold(0, nullptr, &q);
         else {
             fold_circle_into_line(c.stream, layers[0].c, src, d_alpha, c.d_itw, c.tw_root_log, q.log_size, /*fresh=*/true, first, count);
@@ -271,7 +276,8 @@ HipProver::FriCommitted HipProver::fri_commit(std::vector<DSecure>& quotients, S
             fa.counter = d_counter; fa.chan = d_chan; fa.alpha_out = d_alpha + 8 * (li + 1); fa.root_out = d_roots + 8 * (1 + li);
             fri_layer(c.stream, fa);
             in.tree = mk;
-        } else in.tree = commit_step(1 + li, secure_cols(layers[li]), li + 1, 1 + li);
+            folded_by(li, FRI_BY_LAYER_KERNEL, q != nullptr); hashed_by(li, FRI_BY_LAYER_KERNEL);
+        } else { in.tree = commit_step(1 + li, secure_cols(layers[li]), li + 1, 1 + li); hashed_by(li, fold_leaf(li) ? FRI_BY_FOLD_LEAF : FRI_BY_LAUNCHES); }
         inner.push_back(in);
         if (fused(li + 1)) continue;                           // the next layer folds this one itself
         const DSecure* q = take_quotient(log);
@@ -279,6 +285,7 @@ HipProver::FriCommitted HipProver::fri_commit(std::vector<DSecure>& quotients, S
         const u32* src[4] = {layers[li].c[0], layers[li].c[1], layers[li].c[2], layers[li].c[3]};
         const u32* qs[4] = {q ? q->c[0] : nullptr, q ? q->c[1] : nullptr, q ? q->c[2] : nullptr, q ? q->c[3] : nullptr};
         if (q && (q->lc != 0) != (layers[li].lc != 0)) throw HipError("FRI: a layer and the quotient of its size are sharded differently");
+        folded_by(li + 1, fold_leaf(li + 1) ? FRI_BY_FOLD_LEAF : FRI_BY_LAUNCHES, q != nullptr);
         if (fold_leaf(li + 1)) { describe_fold(li + 1, &layers[li], q); continue; }      // the next layer's leaf launch folds this one
         u32 first, count; fold_range(log, layers[li].lc != 0, first, count);
         fold_line_circle(c.stream, next.c, src, q ? qs : nullptr, d_alpha + 8 * (li + 1), c.d_itw, c.tw_root_log, log, first, count);
@@ -295,6 +302,7 @@ HipProver::FriCommitted HipProver::fri_commit(std::vector<DSecure>& quotients, S
             FriTailLayer& L = ta.layer[k];
             for (int w = 0; w < 4; w++) L.ev[w] = layers[li + k].c[w];
             if (qi < quotients.size() && quotients[qi].log_size == log) { for (int w = 0; w < 4; w++) L.quot[w] = quotients[qi].c[w]; qi++; }
+            folded_by(li + k + 1, FRI_BY_TAIL, L.quot[0] != nullptr); hashed_by(li + k, FRI_BY_TAIL);
             const DevMerkle& mk = plans[1 + li + k].mk;
             if (mk.max_log != log) throw HipError("FRI tail: tree layout");
             for (u32 lg = 0; lg <= log; lg++) { if (mk.shifts[lg] != 0) throw HipError("FRI tail: replicated level"); L.tree[lg] = (uint4*)mk.layers[lg]; }
@@ -340,11 +348,13 @@ HipProver::FriCommitted HipProver::fri_commit(std::vector<DSecure>& quotients, S
         }
         // bound 0: the 2^b evaluations are those of a constant line polynomial — all equal, and line_ifft's only nonzero coefficient is
         // that value (at b = 1: c0 = (v0 + v1) / 2 = v0, c1 = (v0 - v1) / (2 x0) = 0)
-        for (const Q31& x : v) if (!q_eq(x, v[0])) throw HipError("invalid degree");
-        Q31 c0 = v[0];
-        pf.fri_proof.last_layer_coeffs = {c0};
-        pf.fri_proof.last_layer_log_size = 0;
-        ch.mix_felts(&c0, 1);
+        if (last_layer_poly) {
+            for (const Q31& x : v) if (!q_eq(x, v[0])) throw HipError("invalid degree");
+            Q31 c0 = v[0];
+            pf.fri_proof.last_layer_coeffs = {c0};
+            pf.fri_proof.last_layer_log_size = 0;
+            ch.mix_felts(&c0, 1);
+        }
     }
     tap("fri_commit");
     return out;
@@ -454,3 +464,76 @@ void HipProver::decommit_queries(std::vector<DTree>& trees, const std::vector<DS
 }
 
 }  // namespace bf
+
+#ifdef BFHIP_TEST_HOOKS
+#include "api_guard.h"
+// libbfhip_testhooks.so only (Makefile); not declared in include/bfhip.h. Runs HipProver::fri_commit — the driver above, nothing of it restated — on the
+// caller's columns, from a caller-given channel digest (n_sent 0), and hands back everything the commit phase leaves in HBM, so that
+// tests/test_gpu_fri_commit.py can compare each fused path with tests/fri_commit_model.py layer by layer: tree nodes no query of a proof opens, layers
+// folded without a quotient, the channel's rejected draws. The columns need no low degree: the last layer is returned as it is (last_layer_poly = false).
+//   log_sizes[n_cols] distinct and descending, cols_h[4 * n_cols] host arrays of 2^log_sizes[k] words (the 4 coordinates of column k).
+//   With line_log = log_sizes[0] - 1 and n_inner = line_log - log_blowup_factor:
+//   layers_out  layer 0 .. n_inner, each its 4 coordinate columns of 2^(line_log - k) words
+//   trees_out   the first-layer tree, then the tree of layer 0 .. n_inner - 1: every level, deepest first, 8 words per node
+//   roots_out, alphas_out   8 words per channel step (first-layer tree, layer 0 .. n_inner - 1): the root mixed, alpha || alpha^2 drawn
+//   chan_out    digest[8] || n_sent of the device channel at the end (Poseidon252 channel: of the host channel, the only one there is)
+//   paths_out   n_inner + 1 words, HipProver::FriCommitted::path
+extern "C" int32_t bfhip_test_fri_commit(bfhip_ctx* ctx, const uint8_t* digest32, uint32_t n_cols, const uint32_t* log_sizes, const uint32_t* const* cols_h,
+                                          uint32_t* layers_out, uint32_t* trees_out, uint32_t* roots_out, uint32_t* alphas_out, uint32_t* chan_out, uint32_t* paths_out) {
+    using namespace bf;
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    if (!digest32 || !log_sizes || !cols_h || !layers_out || !trees_out || !roots_out || !alphas_out || !chan_out || !paths_out) throw HipError("null argument");
+    if (c.shard.count > 1) throw HipError("bfhip_test_fri_commit: the context is in a shard group");
+    if (n_cols == 0) throw HipError("bfhip_test_fri_commit: no columns");
+    for (u32 k = 0; k < 4 * n_cols; k++) if (!cols_h[k]) throw HipError("null argument");
+    for (u32 k = 1; k < n_cols; k++) if (log_sizes[k] >= log_sizes[k - 1]) throw HipError("bfhip_test_fri_commit: the column sizes must be distinct and descending");
+    HipProver pv(c, 0);
+    const u32 last_log = pv.cfg.log_last_layer_degree_bound + pv.cfg.log_blowup;
+    if (pv.cfg.log_last_layer_degree_bound != 0) throw HipError("only log_last_layer_degree_bound 0 is supported");
+    if (log_sizes[n_cols - 1] < last_log + 1) throw HipError("bfhip_test_fri_commit: the smallest column lies below log_blowup_factor + 1");
+    if (log_sizes[n_cols - 1] < 3) throw HipError("bfhip_test_fri_commit: a circle evaluation has at least 8 rows");
+    if (log_sizes[0] > c.tw_root_log) throw HipError("bfhip_test_fri_commit: context twiddle tree too small for the largest column");
+    const u32 line_log = log_sizes[0] - 1;
+    if (line_log > last_log + HipProver::FRI_MAX_LAYERS) throw HipError("bfhip_test_fri_commit: more layers than the commit phase allows");
+    sync_both(c);
+    c.arena.reset();
+    c.use_mailbox = false;
+    c.stage_checkpoint();
+    pv.ch = Channel(c.conv);
+    memcpy(pv.ch.digest.b, digest32, 32); pv.ch.n_sent = 0;
+    std::vector<DSecure> quotients(n_cols);
+    for (u32 k = 0; k < n_cols; k++) {
+        quotients[k].log_size = log_sizes[k];
+        for (int w = 0; w < 4; w++) {
+            quotients[k].c[w] = c.alloc_u32(size_t(1) << log_sizes[k]);
+            BF_HIP(hipMemcpyAsync(quotients[k].c[w], cols_h[4 * k + w], sizeof(u32) << log_sizes[k], hipMemcpyHostToDevice, c.stream));
+        }
+    }
+    StarkProof pf;
+    HipProver::FriCommitted fc;
+    try { fc = pv.fri_commit(quotients, pf, {}, [] {}, /*last_layer_poly=*/false); } catch (...) { (void)hipStreamSynchronize(c.stream); throw; }
+    sync_both(c);
+    const u32 n_inner = (u32)fc.inner.size();
+    if (fc.layers.size() != n_inner + 1 || fc.path.size() != n_inner + 1) throw HipError("bfhip_test_fri_commit: layer count");
+    for (u32 k = 0; k <= n_inner; k++) {
+        const DSecure& l = fc.layers[k];
+        for (int w = 0; w < 4; w++) { BF_HIP(hipMemcpy(layers_out, l.c[w], sizeof(u32) << l.log_size, hipMemcpyDeviceToHost)); layers_out += size_t(1) << l.log_size; }
+        paths_out[k] = fc.path[k];
+    }
+    for (u32 t = 0; t <= n_inner; t++) {
+        const DevMerkle& mk = t == 0 ? fc.first_tree : fc.inner[t - 1].tree;
+        for (int lg = (int)mk.max_log; lg >= 0; lg--) {
+            if (mk.shifts[lg] != 0) throw HipError("bfhip_test_fri_commit: replicated tree level");
+            BF_HIP(hipMemcpy(trees_out, mk.layers[lg], size_t(32) << lg, hipMemcpyDeviceToHost));
+            trees_out += size_t(8) << lg;
+        }
+        memcpy(roots_out + 8 * t, mk.root.b, 32);
+    }
+    BF_HIP(hipMemcpy(alphas_out, fc.d_alpha, 32 * (n_inner + 1), hipMemcpyDeviceToHost));
+    if (c.conv.merkle_channel == 1) { memcpy(chan_out, pv.ch.digest.b, 32); chan_out[8] = pv.ch.n_sent; }
+    else BF_HIP(hipMemcpy(chan_out, fc.d_chan, 36, hipMemcpyDeviceToHost));
+    return 0;
+    API_CATCH
+}
+#endif

@@ -27,15 +27,15 @@ def test_library_exports_every_declared_symbol(pkg):
 
 def test_default_library_has_no_test_hooks():
     """The release build must not contain the test hooks: no lookup of a mock's symbol, no environment variable that makes it
-    dlopen an arbitrary path, no host delay for the mailboxes. The hooks build (same sources, -DBFHIP_TEST_HOOKS in api.hip / comm.hip) has them and
+    dlopen an arbitrary path, no host delay for the mailboxes. The hooks build (same sources, -DBFHIP_TEST_HOOKS in api.hip / comm.hip / prover_fri.hip) has them and
     exports the same entry points."""
     pkg_dir = os.path.join(ROOT, "stwo-brainfuck_amd")
     blob = open(os.path.join(pkg_dir, "libbfhip.so"), "rb").read()
-    for needle in (b"bfhip_mock_self_copy", b"BFHIP_RCCL_LIBRARY", b"BFHIP_MAILBOX_TEST_DELAY_MS", b"bfhip_test_field_op", b"bfhip_test_constraint_group_rows"):
+    for needle in (b"bfhip_mock_self_copy", b"BFHIP_RCCL_LIBRARY", b"BFHIP_MAILBOX_TEST_DELAY_MS", b"bfhip_test_field_op", b"bfhip_test_constraint_group_rows", b"bfhip_test_fri_commit"):
         assert needle not in blob, f"the default libbfhip.so contains the test hook {needle!r}"
     assert b"mock" not in blob.lower().replace(b"mockingbird", b""), "the default libbfhip.so mentions a mock"
     hooks = open(TESTHOOKS_LIBRARY, "rb").read()
-    for needle in (b"bfhip_mock_self_copy", b"BFHIP_RCCL_LIBRARY", b"BFHIP_MAILBOX_TEST_DELAY_MS", b"bfhip_test_field_op", b"bfhip_test_constraint_group_rows"):
+    for needle in (b"bfhip_mock_self_copy", b"BFHIP_RCCL_LIBRARY", b"BFHIP_MAILBOX_TEST_DELAY_MS", b"bfhip_test_field_op", b"bfhip_test_constraint_group_rows", b"bfhip_test_fri_commit"):
         assert needle in hooks
     H = ctypes.CDLL(TESTHOOKS_LIBRARY)
     for s in declared_symbols():

@@ -188,6 +188,38 @@ def test_channel_primitives(oracle, conv):
     oracle.L.orc_channel_free(ch)
 
 
+def test_channel_draw_felt_redraws_a_rejected_draw(oracle, conv):
+    """Fixture R0 of tests/golden/channel_redraw.json (found by search, make_channel_redraw_fixtures.py): behind mix_root(root) on a fresh channel
+    the first draw has a word >= 2P. draw_felt must throw it away and return the SECOND draw (counter 1) reduced mod P — the branch a proof
+    takes once in ~10^7 and the guarded assertion of test_channel_primitives never sees."""
+    import json
+    import os
+    fx = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "channel_redraw.json")))["R0"]
+    root = bytes.fromhex(fx["root"])
+    ch = ctypes.c_void_p(oracle.L.orc_channel_new())
+    d = (ctypes.c_ubyte * 32)()
+    oracle.L.orc_channel_mix_root(ch, root)
+    oracle.L.orc_channel_digest(ch, d)
+    digest = bytes(d)
+    assert digest == hashlib.blake2s(bytes(32) + root).digest()
+    first = np.frombuffer(hashlib.blake2s(digest + bytes(32)).digest(), dtype=np.uint32)                                   # counter 0
+    second = np.frombuffer(hashlib.blake2s(digest + (1).to_bytes(4, "little") + bytes(28)).digest(), dtype=np.uint32)      # counter 1
+    assert first.tolist() == fx["first_draw"] and np.any(first >= 2 * P), "the fixture's first draw is not rejected: the retry is not taken"
+    assert np.all(second < 2 * P)
+    out = (ctypes.c_uint32 * 4)()
+    oracle.L.orc_channel_draw_felt(ch, out)
+    assert list(out) == [int(w % P) for w in second[:4]] == fx["alpha"]
+    assert list(out) != [int(w % P) for w in first[:4]]
+    oracle.L.orc_channel_digest(ch, d)
+    assert bytes(d) == digest                                   # a draw leaves the digest alone
+    # the counter went to 2: the next draw_felt hashes counter 2
+    third = np.frombuffer(hashlib.blake2s(digest + (2).to_bytes(4, "little") + bytes(28)).digest(), dtype=np.uint32)
+    assert np.all(third < 2 * P)
+    oracle.L.orc_channel_draw_felt(ch, out)
+    assert list(out) == [int(w % P) for w in third[:4]]
+    oracle.L.orc_channel_free(ch)
+
+
 # ---- the circle-FFT conventions restated from their DEFINITION in pure Python (SURVEY.md Appendix B) --------------------------------------
 # Independent of the oracle's and the product's code: circle group law on the generator (2, 1268011823), CanonicCoset(n) = odds(n) with
 # circle_domain() = half_odds(n - 1) followed by its conjugates, evaluations stored bit-reversed, monomial basis y^b0 x^b1 pi(x)^b2 ...
