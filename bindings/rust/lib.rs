@@ -281,3 +281,173 @@ pub fn verify_brainfuck(proof_json: &[u8], log_max_rows: u32) -> Result<(), Stri
         _ => Err(last_error()),                                                                                // internal error
     }
 }
+
+// ---- commitment-scheme session (`include/bfhip.h` "Commitment-scheme session"): commit and open ANY AIR's columns -------------------------
+// stwo's `CommitmentSchemeProver` / `CommitmentSchemeVerifier` over trees of arbitrary columns, on the fused launches of a Brainfuck proof.
+// An AIR that is not the snapshot's computes its traces and constraints itself and keeps everything else.
+
+/// A secure-field element: 4 canonical M31 words. A point of the circle over it: x then y.
+pub type Felt = [u32; 4];
+pub type Point = [u32; 8];
+
+fn check(rc: i32) -> Result<(), String> {
+    if rc != 0 { Err(last_error()) } else { Ok(()) }
+}
+
+/// `bfhip_circle_point_offset`: `p + offset * CanonicCoset(log_size).step()` — the mask point of a column of 2^log_size rows at a row offset.
+pub fn circle_point_offset(p: &Point, log_size: u32, offset: i32) -> Result<Point, String> {
+    let mut out = [0u32; 8];
+    check(unsafe { sys::bfhip_circle_point_offset(p.as_ptr(), log_size, offset, out.as_mut_ptr()) })?;
+    Ok(out)
+}
+
+/// `Blake2sChannel::default()` / `Poseidon252Channel::default()` (by `conv.merkle_channel`): what stwo passes as `channel`. Host only.
+pub struct Channel(*mut sys::BfhipChannel);
+
+impl Channel {
+    pub fn new(conv: Option<&sys::BfhipConventions>) -> Result<Self, String> {
+        let mut p = std::ptr::null_mut();
+        check(unsafe { sys::bfhip_channel_create(conv.map_or(std::ptr::null(), |c| c as *const _), &mut p) })?;
+        Ok(Channel(p))
+    }
+    pub fn mix_root(&mut self, root: &[u8; 32]) -> Result<(), String> {
+        check(unsafe { sys::bfhip_channel_mix_root(self.0, root.as_ptr()) })
+    }
+    pub fn mix_u64(&mut self, v: u64) -> Result<(), String> {
+        check(unsafe { sys::bfhip_channel_mix_u64(self.0, v) })
+    }
+    pub fn mix_felts(&mut self, felts: &[Felt]) -> Result<(), String> {
+        check(unsafe { sys::bfhip_channel_mix_felts(self.0, felts.as_ptr() as *const u32, felts.len()) })
+    }
+    /// stwo's `draw_felts(n)`: n = 1 is `draw_felt`, n = 2 a lookup element's (z, alpha).
+    pub fn draw_felts(&mut self, n: usize) -> Result<Vec<Felt>, String> {
+        let mut out = vec![[0u32; 4]; n];
+        check(unsafe { sys::bfhip_channel_draw_felts(self.0, n, out.as_mut_ptr() as *mut u32) })?;
+        Ok(out)
+    }
+    /// `CirclePoint::get_random_point`.
+    pub fn draw_point(&mut self) -> Result<Point, String> {
+        let mut out = [0u32; 8];
+        check(unsafe { sys::bfhip_channel_draw_point(self.0, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+    /// (digest, n_sent)
+    pub fn state(&self) -> Result<([u8; 32], u32), String> {
+        let (mut d, mut n) = ([0u8; 32], 0u32);
+        check(unsafe { sys::bfhip_channel_state(self.0, d.as_mut_ptr(), &mut n) })?;
+        Ok((d, n))
+    }
+    pub fn trailing_zeros(&self) -> Result<u32, String> {
+        let mut n = 0u32;
+        check(unsafe { sys::bfhip_channel_trailing_zeros(self.0, &mut n) })?;
+        Ok(n)
+    }
+}
+
+impl Drop for Channel {
+    fn drop(&mut self) {
+        unsafe { sys::bfhip_channel_destroy(self.0) };
+    }
+}
+
+/// The sample description of `prove_values` / `verify_values`: for every column of every tree, in commit order, the indices into `points`
+/// of the points it is opened at, in the order its sampled values are to appear.
+pub struct Samples<'a> {
+    pub points: &'a [Point],
+    pub per_column: &'a [Vec<u32>],
+}
+
+impl<'a> Samples<'a> {
+    fn flat(&self) -> (Vec<u32>, Vec<u32>) {
+        (self.per_column.iter().map(|c| c.len() as u32).collect(), self.per_column.iter().flatten().copied().collect())
+    }
+}
+
+/// `CommitmentSchemeProver` on one context (`bfhip_pcs_*`). One open session per context; while it lives the context refuses its proving,
+/// checking and trace-building entries. The lifetime ties the session to its context: the context cannot be dropped first.
+pub struct PcsProver<'a> {
+    h: *mut sys::BfhipPcs,
+    _ctx: std::marker::PhantomData<&'a Context>,
+}
+
+impl<'a> PcsProver<'a> {
+    pub fn new(ctx: &'a Context) -> Result<Self, String> {
+        let mut p = std::ptr::null_mut();
+        check(unsafe { sys::bfhip_pcs_create(ctx.0, &mut p) })?;
+        Ok(PcsProver { h: p, _ctx: std::marker::PhantomData })
+    }
+    /// `tree_builder.extend_evals` (`coefficients = false`) / `extend_polys` (`true`) + `commit(channel)`: device columns, column k of
+    /// 2^log_sizes[k] words. Returns the root, which is mixed into `channel`.
+    ///
+    /// # Safety
+    /// Every pointer must be a device allocation of this context's GPU holding 2^log_sizes[k] canonical words.
+    pub unsafe fn commit(&mut self, channel: &mut Channel, cols: &[*const u32], log_sizes: &[u32], coefficients: bool) -> Result<[u8; 32], String> {
+        assert_eq!(cols.len(), log_sizes.len());
+        let mut root = [0u8; 32];
+        check(sys::bfhip_pcs_commit(self.h, channel.0, cols.as_ptr(), log_sizes.as_ptr(), cols.len() as u32, coefficients as i32, root.as_mut_ptr()))?;
+        Ok(root)
+    }
+    /// (coefficient pointers, LDE pointers) of a committed tree's columns — what the caller's constraint sweep reads; valid while `self` lives.
+    pub fn tree_columns(&self, tree: u32) -> Result<(Vec<*const u32>, Vec<*const u32>), String> {
+        let mut n = 0u32;
+        check(unsafe { sys::bfhip_pcs_tree_columns(self.h, tree, std::ptr::null_mut(), std::ptr::null_mut(), 0, &mut n) })?;
+        let (mut co, mut ev) = (vec![std::ptr::null(); n as usize], vec![std::ptr::null(); n as usize]);
+        check(unsafe { sys::bfhip_pcs_tree_columns(self.h, tree, co.as_mut_ptr(), ev.as_mut_ptr(), n, &mut n) })?;
+        Ok((co, ev))
+    }
+    /// `prove_values`: (the serde-JSON bytes of the `CommitmentSchemeProof`, the sampled values in the order of the description).
+    /// Ends the session's proving life.
+    pub fn prove_values(&mut self, channel: &mut Channel, samples: &Samples) -> Result<(Vec<u8>, Vec<Felt>), String> {
+        let (counts, idx) = samples.flat();
+        let mut sampled = vec![[0u32; 4]; idx.len()];
+        let (mut js, mut len): (*mut c_char, usize) = (std::ptr::null_mut(), 0);
+        check(unsafe {
+            sys::bfhip_pcs_prove_values(self.h, channel.0, samples.points.as_ptr() as *const u32, samples.points.len() as u32, counts.as_ptr(), idx.as_ptr(),
+                                        sampled.as_mut_ptr() as *mut u32, &mut js, &mut len)
+        })?;
+        let out = unsafe { std::slice::from_raw_parts(js as *const u8, len) }.to_vec();
+        unsafe { sys::bfhip_free_host(js as *mut c_void) };
+        Ok((out, sampled))
+    }
+}
+
+impl<'a> Drop for PcsProver<'a> {
+    fn drop(&mut self) {
+        unsafe { sys::bfhip_pcs_destroy(self.h) };
+    }
+}
+
+/// `CommitmentSchemeVerifier` (`bfhip_pcs_verifier_*`). Host only.
+pub struct PcsVerifier(*mut sys::BfhipPcsVerifier);
+
+impl PcsVerifier {
+    pub fn new(conv: Option<&sys::BfhipConventions>, config: Option<&sys::BfhipPcsConfig>) -> Result<Self, String> {
+        let mut p = std::ptr::null_mut();
+        check(unsafe { sys::bfhip_pcs_verifier_create(conv.map_or(std::ptr::null(), |c| c as *const _), config.map_or(std::ptr::null(), |c| c as *const _), &mut p) })?;
+        Ok(PcsVerifier(p))
+    }
+    /// `commit`: the trace-domain log sizes of the tree's columns; mixes the root into `channel`.
+    pub fn commit(&mut self, channel: &mut Channel, root: &[u8; 32], log_sizes: &[u32]) -> Result<(), String> {
+        check(unsafe { sys::bfhip_pcs_verifier_commit(self.0, channel.0, root.as_ptr(), log_sizes.as_ptr(), log_sizes.len() as u32) })
+    }
+    /// `verify_values`: `Ok(Ok(()))` accepted, `Ok(Err(name))` rejected with the `VerificationError` name, `Err` = bad arguments.
+    pub fn verify_values(&mut self, channel: &mut Channel, samples: &Samples, proof_json: &[u8]) -> Result<Result<(), String>, String> {
+        let (counts, idx) = samples.flat();
+        let mut err = [0 as c_char; 512];
+        let rc = unsafe {
+            sys::bfhip_pcs_verifier_verify_values(self.0, channel.0, samples.points.as_ptr() as *const u32, samples.points.len() as u32, counts.as_ptr(), idx.as_ptr(),
+                                                  proof_json.as_ptr() as *const c_char, proof_json.len(), err.as_mut_ptr(), err.len())
+        };
+        match rc {
+            0 => Ok(Ok(())),
+            1 => Ok(Err(unsafe { CStr::from_ptr(err.as_ptr()) }.to_string_lossy().into_owned())),
+            _ => Err(last_error()),
+        }
+    }
+}
+
+impl Drop for PcsVerifier {
+    fn drop(&mut self) {
+        unsafe { sys::bfhip_pcs_verifier_destroy(self.0) };
+    }
+}

@@ -606,6 +606,114 @@ int32_t bfhip_verify_brainfuck_conv(const char* proof_json, size_t proof_len, ui
 int32_t bfhip_verify_brainfuck_pcs(const char* proof_json, size_t proof_len, uint32_t log_max_rows, const bfhip_conventions* conv,
                                    const bfhip_pcs_config* pcs, char* err, size_t err_cap);
 
+/* ---- Commitment-scheme session: commit and open ANY AIR's columns on the fused PCS path ---------------------------------------------------
+ * bfhip_prove_* prove the 13 components of one snapshot of the reference. An AIR that differs from it (another column, another component)
+ * computes its traces and constraints with its own kernels, or with bfhip_logup_generate / bfhip_eval_constraints, and keeps everything else:
+ * the session below is stwo's CommitmentSchemeProver / CommitmentSchemeVerifier over trees of arbitrary columns opened at arbitrary points,
+ * run by the same driver and the same fused launches as a Brainfuck proof (subtree / top Merkle kernels, batched sampling, one quotient launch
+ * per size group, the device-stepped channel of the FRI commit phase with k_fri_fold_leaf / k_fri_layer / k_fri_tail, one gather for the
+ * whole decommitment). INTEGRATION.md section 2e assembles the Brainfuck protocol from it.
+ *   stwo                                                         here
+ *   Blake2sChannel::default() / Poseidon252Channel::default()    bfhip_channel_create
+ *   channel.mix_* / draw_felts / CirclePoint::get_random_point   bfhip_channel_mix_* / _draw_felts / _draw_point
+ *   CommitmentSchemeProver::new(config, twiddles)                bfhip_pcs_create (the context's PcsConfig and twiddle tree)
+ *   tree_builder.extend_evals / extend_polys + commit(channel)   bfhip_pcs_commit (form 0 / form 1)
+ *   commitment_scheme.trees[t].polynomials / .evaluations        bfhip_pcs_tree_columns
+ *   commitment_scheme.prove_values(sample_points, channel)       bfhip_pcs_prove_values
+ *   CommitmentSchemeVerifier::new / commit / verify_values       bfhip_pcs_verifier_create / _commit / _verify_values
+ *
+ * The channel (host only, no GPU): created under a bfhip_conventions (NULL = defaults): merkle_channel selects Blake2sChannel or
+ * Poseidon252Channel, mix_u64 the Blake2s form of mix_u64. Felts are 4 canonical words each, a point is x (4 words) then y (4 words); a
+ * non-canonical word (>= 2^31 - 1) is refused, and so is a root that is no canonical felt252 under the Poseidon252 channel.
+ * draw_felts(n) is stwo's: ceil(n / 2) draws of 8 base felts, two secure felts per draw (n = 1 is draw_felt, n = 2 a lookup element's draw).
+ * draw_point is CirclePoint::get_random_point: t = draw_felt(), ((1 - t^2) / (1 + t^2), 2 t / (1 + t^2)). */
+typedef struct bfhip_channel bfhip_channel;
+int32_t bfhip_channel_create(const bfhip_conventions* conv, bfhip_channel** out);
+int32_t bfhip_channel_destroy(bfhip_channel* ch);
+int32_t bfhip_channel_mix_root(bfhip_channel* ch, const uint8_t hash32[32]);
+int32_t bfhip_channel_mix_u64(bfhip_channel* ch, uint64_t v);
+int32_t bfhip_channel_mix_felts(bfhip_channel* ch, const uint32_t* felts_h, size_t n);
+int32_t bfhip_channel_draw_felts(bfhip_channel* ch, size_t n, uint32_t* out_h);
+int32_t bfhip_channel_draw_point(bfhip_channel* ch, uint32_t point_out[8]);
+/* digest (32 bytes; Poseidon252: the felt252 as canonical little-endian bytes) and the draw counter; either pointer may be NULL */
+int32_t bfhip_channel_state(bfhip_channel* ch, uint8_t digest[32], uint32_t* n_sent);
+/* Channel::trailing_zeros of the digest: what a proof of work is checked against */
+int32_t bfhip_channel_trailing_zeros(bfhip_channel* ch, uint32_t* out);
+/* Mask points: out = p + offset * CanonicCoset(log_size).step(), the point at which a column of 2^log_size rows is opened for the row
+ * offset `offset` of a constraint (offset -1: the previous row). 1 <= log_size <= 30. Host only. */
+int32_t bfhip_circle_point_offset(const uint32_t p[8], uint32_t log_size, int32_t offset, uint32_t out[8]);
+/* The one AIR-dependent step of a VERIFIER of the snapshot's AIR assembled from the session: Components::eval_composition_polynomial_at_point
+ * at `point_h`, which stwo's verify() compares with the sampled value of the composition polynomial (its four coordinate columns combined)
+ * before it calls verify_values. n_cols_h[3] / n_samples_h / sampled_h: the sampled values of the preprocessed, main-trace and interaction
+ * trees in the description of bfhip_pcs_prove_values (columns in commit order, n_samples_h[] per column, values flat, 4 words each).
+ * lookup_h: 24 words as for bfhip_logup_generate. Host only. */
+int32_t bfhip_brainfuck_composition_at_point(const uint32_t log_sizes_h[13], const uint32_t* claimed_sums_h, uint32_t log_max_rows, const uint32_t lookup_h[24],
+                                             const uint32_t point_h[8], const uint32_t n_cols_h[3], const uint32_t* n_samples_h, const uint32_t* sampled_h,
+                                             const uint32_t random_coeff_h[4], const bfhip_conventions* conv, uint32_t out_h[4]);
+
+/* The prover session. One open session per context: bfhip_pcs_create waits for the context's streams and resets its arena as a proof does;
+ * the session's polynomials, LDE columns, Merkle layers, quotients and FRI layers live in the arena until bfhip_pcs_destroy, which puts the
+ * arena's bookkeeping (bfhip_ctx_memory out[3]) back to what it was. Conventions, hasher and PcsConfig are the context's at creation.
+ * While a session is open these entry points of its context return -1 with "a commitment-scheme session is open" — they reset, or borrow
+ * from, the arena, or change what the session was created under:
+ *   bfhip_prove_trace, bfhip_prove_brainfuck, bfhip_prove_registers (and every pool job or batch that lands on the context),
+ *   bfhip_trace_create, bfhip_trace_create_ram, bfhip_trace_create_from_registers (the GPU table builders' scratch),
+ *   bfhip_trace_check, bfhip_check_constraints, bfhip_relation_summary, bfhip_trace_relations,
+ *   bfhip_ctx_set_conventions, bfhip_ctx_set_pcs_config, bfhip_ctx_join_local_group, bfhip_ctx_join_rccl_group, bfhip_ctx_destroy,
+ *   and a second bfhip_pcs_create.
+ * Everything else keeps working, which is what the caller's constraint sweep needs: bfhip_malloc / bfhip_free / bfhip_upload / bfhip_download /
+ * bfhip_memset_zero, bfhip_interpolate, bfhip_evaluate, bfhip_is_first_coeffs, bfhip_eval_at_point, bfhip_logup_generate, bfhip_eval_constraints,
+ * bfhip_accumulate, the Merkle / fold / grind / gather single operations, resident traces' getters and the profiler.
+ * Not supported: a context in a shard group (create refuses; joining refuses while a session is open); a pool's sub-context while anything
+ * is queued, running or not yet taken on the pool.
+ * Launch order: the plain one only (wait, draw, copy, launch). No mailbox order, and the overlap mask (bfhip_ctx_set_overlap) is ignored.
+ * Columns are full size: 2^log_size words each (no row-granular storage).
+ *
+ * bfhip_pcs_commit: n_cols device columns, column k of 2^log_sizes_h[k] words, in the caller's order; sizes in any order, repeats allowed.
+ *   form 0: evaluations on CanonicCoset(log_size).circle_domain() in bit-reversed order (interpolated here); form 1: coefficients, what
+ *   bfhip_interpolate produces (stwo commits the composition polynomial this way). The columns are borrowed for the call and not modified.
+ *   The root is mixed into ch and returned (Poseidon252: canonical little-endian bytes of the felt252).
+ * bfhip_pcs_tree_columns: per column of committed tree `tree` the device pointers of its coefficients (2^log_size words) and of its LDE
+ *   (2^(log_size + log_blowup_factor) words, bit-reversed), valid until bfhip_pcs_destroy; either array may be NULL, both NULL: *n_cols only;
+ *   -2 = cap too small.
+ * bfhip_pcs_prove_values: points_h = n_points points (8 words each). For every column of every tree, in commit order, n_samples_h[] counts
+ *   its samples and point_idx_h lists them as indices into points_h, in the order the sampled values are to appear. It samples every
+ *   (column, point), mixes the sampled values, draws the quotient coefficient, accumulates the quotients per LDE size, runs the FRI commit
+ *   phase, grinds, draws the queries and decommits. *proof_json = the serde form of CommitmentSchemeProof {commitments, sampled_values,
+ *   decommitments, queried_values, proof_of_work, fri_proof} — byte for byte the "proof" member of a BrainfuckProof — malloc'd, release
+ *   with bfhip_free_host. sampled_out_h (optional): the sampled values flat, 4 words each, same order. A column without samples is
+ *   committed and decommitted but enters no quotient. The call ends the session's proving life, also when it fails after its checks:
+ *   only bfhip_pcs_tree_columns and bfhip_pcs_destroy remain. A failure waits for the context's streams before it returns.
+ * Caps (each refused with a message that names it; none grows a kernel):
+ *   log_size                 4 <= log_size <= max_log_domain - log_blowup_factor (the twiddle tree; the Brainfuck path uses every size from 4)
+ *   samples per column       <= 2 = BFHIP_PCS_MAX_SAMPLES_PER_COLUMN (the quotient tables hold two (point, value) pairs per column)
+ *   points                   <= 64 = BFHIP_PCS_MAX_POINTS (fixed tables of the batch builder); two indices may name equal points: one batch
+ *   columns per tree         <= 4096 = BFHIP_PCS_MAX_COLUMNS (descriptors, pointer arrays and pass tables of one commitment share the 8 MiB staging ring)
+ *   trees                    <= 64 = BFHIP_PCS_MAX_TREES
+ *   FRI layers               <= 40 (FRI_MAX_LAYERS of the commit phase): cannot be exceeded, the largest LDE has at most 2^29 rows
+ *   quotient columns         one per distinct LDE size by construction: "two quotient columns of one size" cannot arise
+ *   at least one tree and one column per tree; log_last_layer_degree_bound 0; Poseidon252 channel: pow_bits <= 12 (refused at prove_values). */
+enum { BFHIP_PCS_MAX_SAMPLES_PER_COLUMN = 2, BFHIP_PCS_MAX_POINTS = 64, BFHIP_PCS_MAX_COLUMNS = 4096, BFHIP_PCS_MAX_TREES = 64 };
+typedef struct bfhip_pcs bfhip_pcs;
+int32_t bfhip_pcs_create(bfhip_ctx* ctx, bfhip_pcs** out);
+int32_t bfhip_pcs_destroy(bfhip_pcs* pcs);
+int32_t bfhip_pcs_commit(bfhip_pcs* pcs, bfhip_channel* ch, const uint32_t* const* cols_h, const uint32_t* log_sizes_h, uint32_t n_cols, int32_t form, uint8_t root_out[32]);
+int32_t bfhip_pcs_tree_columns(bfhip_pcs* pcs, uint32_t tree, const uint32_t** coeffs_d_out, const uint32_t** lde_d_out, uint32_t cap, uint32_t* n_cols);
+int32_t bfhip_pcs_prove_values(bfhip_pcs* pcs, bfhip_channel* ch, const uint32_t* points_h, uint32_t n_points, const uint32_t* n_samples_h,
+                               const uint32_t* point_idx_h, uint32_t* sampled_out_h, char** proof_json, size_t* proof_len);
+
+/* The verifier session (host only). create: the conventions and PcsConfig the proof was made under (NULL = defaults).
+ * commit = CommitmentSchemeVerifier::commit: the TRACE-domain log sizes of the tree's columns (the blowup is added inside, 1 <= log_size <=
+ * 30 - log_blowup_factor); mixes the root into ch. verify_values: the same point / index description as bfhip_pcs_prove_values;
+ * 0 = accepted, 1 = rejected (VerificationError name in err, the names of bfhip_verify_brainfuck), -1 = internal / bad arguments.
+ * The proof's commitments must equal the roots committed above. */
+typedef struct bfhip_pcs_verifier bfhip_pcs_verifier;
+int32_t bfhip_pcs_verifier_create(const bfhip_conventions* conv, const bfhip_pcs_config* pcs, bfhip_pcs_verifier** out);
+int32_t bfhip_pcs_verifier_destroy(bfhip_pcs_verifier* v);
+int32_t bfhip_pcs_verifier_commit(bfhip_pcs_verifier* v, bfhip_channel* ch, const uint8_t root[32], const uint32_t* log_sizes_h, uint32_t n_cols);
+int32_t bfhip_pcs_verifier_verify_values(bfhip_pcs_verifier* v, bfhip_channel* ch, const uint32_t* points_h, uint32_t n_points, const uint32_t* n_samples_h,
+                                         const uint32_t* point_idx_h, const char* proof_json, size_t proof_len, char* err, size_t err_cap);
+
 /* Host-only pieces of the drop-in (usable without a GPU): the Brainfuck compiler (crates/brainfuck_vm/src/compiler.rs:17-37), the VM
  * (crates/brainfuck_vm/src/machine.rs:141-238; trace rows are 7 u32: clk, ip, ci, ni, mp, mv, mvi) and the 13 table builders
  * (`XTable::from`, the table.rs files under crates/brainfuck_prover/src/components; component index = claim order of mod.rs:85-99), row-major out. */

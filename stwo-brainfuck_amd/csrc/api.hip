@@ -115,20 +115,7 @@ void Ctx::destroy() {
 
 }  // namespace bf
 
-// include/bfhip.h `bfhip_pcs_config`: the accepted ranges (the same for a context and for the verifier).
-PcsConfig pcs_config_from(const bfhip_pcs_config* p) {
-    PcsConfig cfg;
-    if (!p) return cfg;
-    for (uint32_t r : p->reserved) if (r) throw HipError("bfhip_pcs_config: reserved fields must be zero");
-    if (p->log_blowup_factor < 1 || p->log_blowup_factor > BFHIP_MAX_LOG_BLOWUP)
-        throw HipError("bfhip_pcs_config: log_blowup_factor must be in [1, 16], got " + std::to_string(p->log_blowup_factor));
-    if (p->n_queries < 1 || p->n_queries > BFHIP_MAX_QUERIES) throw HipError("bfhip_pcs_config: n_queries must be in [1, 256], got " + std::to_string(p->n_queries));
-    if (p->pow_bits > BFHIP_MAX_POW_BITS) throw HipError("bfhip_pcs_config: pow_bits must be at most 32, got " + std::to_string(p->pow_bits));
-    if (p->log_last_layer_degree_bound != 0)
-        throw HipError("bfhip_pcs_config: only log_last_layer_degree_bound 0 is supported, got " + std::to_string(p->log_last_layer_degree_bound));
-    cfg.pow_bits = p->pow_bits; cfg.log_blowup = p->log_blowup_factor; cfg.log_last_layer_degree_bound = 0; cfg.n_queries = p->n_queries;
-    return cfg;
-}
+// pcs_config_from (ctx.h): pcs_host.hip, with the other host-only checks of the commitment scheme's settings
 
 extern "C" {
 
@@ -266,10 +253,11 @@ int32_t bfhip_ctx_create(int32_t device_id, uint32_t max_log_domain, bfhip_ctx**
     return 0;
     API_CATCH
 }
-int32_t bfhip_ctx_destroy(bfhip_ctx* ctx) { API_TRY delete ctx; return 0; API_CATCH }
+int32_t bfhip_ctx_destroy(bfhip_ctx* ctx) { API_TRY if (ctx) ctx->c.refuse_in_session("bfhip_ctx_destroy"); delete ctx; return 0; API_CATCH }
 // ---- shard groups: one proof over several GPUs (comm.h) ------------------------------------------------------------------------------
 struct bfhip_local_group { std::shared_ptr<LocalGroup> g; uint32_t count; };
 static void join_group(bfhip_ctx* ctx, std::unique_ptr<Comm> comm) {
+    ctx->c.refuse_in_session("joining a shard group");
     u32 count = comm->count, lc = 0;
     while ((1u << lc) < count) lc++;
     ctx->c.sync();
@@ -412,6 +400,7 @@ int32_t bfhip_ctx_set_conventions(bfhip_ctx* ctx, const bfhip_conventions* conv)
         if (conv->merkle_node_hash > 1 || conv->mix_u64 > 1 || conv->logup_mask_order > 1 || conv->merkle_channel > 1) throw HipError("unknown convention value");
         cv.merkle_node_hash = conv->merkle_node_hash; cv.mix_u64 = conv->mix_u64; cv.logup_mask_order = conv->logup_mask_order; cv.merkle_channel = conv->merkle_channel;
     }
+    ctx->c.refuse_in_session("bfhip_ctx_set_conventions");
     ctx->c.sync();
     // a kept preprocessed tree is keyed on the hasher it was built with (prover.h: PreprocessedCache::matches) and dropped here as well
     if (cv.merkle_node_hash != ctx->c.conv.merkle_node_hash || cv.merkle_channel != ctx->c.conv.merkle_channel) preprocessed_cache_invalidate(&ctx->c);
@@ -423,6 +412,7 @@ int32_t bfhip_ctx_set_pcs_config(bfhip_ctx* ctx, const bfhip_pcs_config* pcs) {
     API_CTX(ctx)
     PcsConfig cfg = pcs_config_from(pcs);
     if (ctx->c.shard.count > 1 && !cfg.is_default()) throw HipError("bfhip_ctx_set_pcs_config: a context in a shard group keeps the default config");
+    ctx->c.refuse_in_session("bfhip_ctx_set_pcs_config");
     ctx->c.sync();
     // a kept preprocessed tree is keyed on the blowup it was built with (prover.h: PreprocessedCache::matches)
     ctx->c.pcs = cfg;
@@ -468,7 +458,8 @@ int32_t bfhip_ctx_memory(bfhip_ctx* ctx, uint64_t out[4]) {
     if (!out) throw HipError("null argument");
     uint64_t reserved = 0;
     for (auto& ch : ctx->c.arena.chunks) reserved += ch.size;
-    out[0] = reserved; out[1] = ctx->c.arena.peak; out[2] = ctx->c.owns_tables ? (uint64_t)(2 * sizeof(u32)) << ctx->c.tw_root_log : 0;      // a pool's sub-contexts borrow the first one's out[3] = ctx->c.arena.total_used;
+    out[0] = reserved; out[1] = ctx->c.arena.peak; out[2] = ctx->c.owns_tables ? (uint64_t)(2 * sizeof(u32)) << ctx->c.tw_root_log : 0;      // a pool's sub-contexts borrow the first one's
+    out[3] = ctx->c.arena.total_used;
     return 0;
     API_CATCH
 }
@@ -825,6 +816,7 @@ int32_t bfhip_check_constraints(bfhip_ctx* ctx, int32_t component, uint32_t log_
     for (u32 j = 0; j < n_main_cols(component); j++) if (!main_rows_h[j]) throw HipError("null main column pointer");
     for (u32 j = 0; j < 4 * n_logup_cols(component); j++) if (!logup_cols_h[j]) throw HipError("null logUp column pointer");
     check_not_sharded(c);
+    c.refuse_in_session("bfhip_check_constraints");
     const Q31 claimed = q_from_h(claimed_sum_h);
     const CheckReportDev init = check_report_init();
     c.stage_checkpoint();
@@ -847,6 +839,7 @@ int32_t bfhip_trace_check(bfhip_ctx* ctx, const bfhip_trace* trace, const uint32
     Ctx& c = ctx->c;
     if (!trace || !out || !logup_total_h) throw HipError("null argument");
     check_not_sharded(c);
+    c.refuse_in_session("bfhip_trace_check");
     Lookups el;
     if (lookup_h) el = lookups_from_h(lookup_h);
     else {

@@ -5,6 +5,7 @@
 #include <chrono>
 #include "kernels.h"
 #include "comm.h"
+#include <functional>
 #include <memory>
 #include <vector>
 #include <string>
@@ -116,6 +117,17 @@ struct Ctx {
     struct PreprocessedCache* pre_cache = nullptr;
     uint2* d_tlo = nullptr; uint2* d_thi = nullptr;   // G^a (a < 2^16) and G^(b << 16) (b < 2^15) point tables
     Arena arena;
+    // A commitment-scheme session (include/bfhip.h: bfhip_pcs_*; pcs.hip) keeps its polynomials, LDE columns and trees in the arena from
+    // bfhip_pcs_create to bfhip_pcs_destroy: meanwhile every entry point that resets or borrows the arena refuses (refuse_in_session).
+    bool pcs_session_open = false;
+    void refuse_in_session(const char* what) const {
+        if (pcs_session_open) throw HipError(std::string(what) + ": a commitment-scheme session is open on this context (bfhip_pcs_destroy first)");
+    }
+    // set by a pool on its sub-contexts: is anything queued, running or not yet taken on that pool? (a session on a sub-context needs it idle)
+    std::function<bool()> pool_busy;
+    // test-hooks build only (prover_commit.hip: bfhip_test_capture_polys): where the next proof's polynomials are copied to; always null in
+    // the default library. A member of every build so that the two builds share one layout of this struct.
+    struct PolyCapture* capture = nullptr;
     // pinned staging for pointer arrays / small parameter blocks
     // Pinned scratch for device->host results. [0, 4096): fixed slots for deferred tiny results (tree roots, FRI roots, channel
     // state); [4096, h_small_bytes): bounce buffer of read_back(). A pageable destination would make every such copy a blocking,

@@ -57,6 +57,21 @@ inline void fri_layer(std::string& s, const FriLayerProof& l, bool felt) {
 }
 }  // namespace json
 
+// CommitmentSchemeProof on its own: the "proof" member below, and what a commitment-scheme session returns (bfhip_pcs_prove_values)
+inline void stark_proof_to_json(std::string& s, const StarkProof& p, bool felt) {
+    using namespace json;
+    s += "{\"commitments\":"; arr(s, p.commitments, [&](const Hash32& h) { hash(s, h, felt); });
+    s += ",\"sampled_values\":";
+    arr(s, p.sampled_values, [&](const std::vector<std::vector<Q31>>& t) { arr(s, t, [&](const std::vector<Q31>& c) { arr(s, c, [&](const Q31& q) { qm31(s, q); }); }); });
+    s += ",\"decommitments\":"; arr(s, p.decommitments, [&](const MerkleDecommitment& d) { decommitment(s, d, felt); });
+    s += ",\"queried_values\":"; arr(s, p.queried_values, [&](const std::vector<u32>& v) { arr(s, v, [&](u32 x) { num(s, x); }); });
+    s += ",\"proof_of_work\":"; num(s, p.proof_of_work);
+    s += ",\"fri_proof\":{\"first_layer\":"; fri_layer(s, p.fri_proof.first_layer, felt);
+    s += ",\"inner_layers\":"; arr(s, p.fri_proof.inner_layers, [&](const FriLayerProof& l) { fri_layer(s, l, felt); });
+    s += ",\"last_layer_poly\":{\"coeffs\":"; arr(s, p.fri_proof.last_layer_coeffs, [&](const Q31& q) { qm31(s, q); });
+    s += ",\"log_size\":"; num(s, p.fri_proof.last_layer_log_size); s += "}}}";
+}
+
 // felt_hashes: the proof was made with Poseidon252MerkleChannel (hashes are felt252 values)
 inline std::string proof_to_json(const BrainfuckProof& bp, bool felt_hashes = false) {
     using namespace json;
@@ -67,17 +82,9 @@ inline std::string proof_to_json(const BrainfuckProof& bp, bool felt_hashes = fa
     for (int c = 0; c < N_COMPONENTS; c++) { if (c) s += ','; s += '"'; s += COMPONENT_NAMES[c]; s += "\":{\"log_size\":"; num(s, bp.log_sizes[c]); s += ",\"_marker\":null}"; }
     s += "},\"interaction_claim\":{";
     for (int c = 0; c < N_COMPONENTS; c++) { if (c) s += ','; s += '"'; s += COMPONENT_NAMES[c]; s += "\":{\"claimed_sum\":"; qm31(s, bp.claimed_sums[c]); s += '}'; }
-    const StarkProof& p = bp.proof;
-    s += "},\"proof\":{\"commitments\":"; arr(s, p.commitments, [&](const Hash32& h) { hash(s, h, felt); });
-    s += ",\"sampled_values\":";
-    arr(s, p.sampled_values, [&](const std::vector<std::vector<Q31>>& t) { arr(s, t, [&](const std::vector<Q31>& c) { arr(s, c, [&](const Q31& q) { qm31(s, q); }); }); });
-    s += ",\"decommitments\":"; arr(s, p.decommitments, [&](const MerkleDecommitment& d) { decommitment(s, d, felt); });
-    s += ",\"queried_values\":"; arr(s, p.queried_values, [&](const std::vector<u32>& v) { arr(s, v, [&](u32 x) { num(s, x); }); });
-    s += ",\"proof_of_work\":"; num(s, p.proof_of_work);
-    s += ",\"fri_proof\":{\"first_layer\":"; fri_layer(s, p.fri_proof.first_layer, felt);
-    s += ",\"inner_layers\":"; arr(s, p.fri_proof.inner_layers, [&](const FriLayerProof& l) { fri_layer(s, l, felt); });
-    s += ",\"last_layer_poly\":{\"coeffs\":"; arr(s, p.fri_proof.last_layer_coeffs, [&](const Q31& q) { qm31(s, q); });
-    s += ",\"log_size\":"; num(s, p.fri_proof.last_layer_log_size); s += "}}}}";
+    s += "},\"proof\":";
+    stark_proof_to_json(s, bp.proof, felt);
+    s += '}';
     return s;
 }
 

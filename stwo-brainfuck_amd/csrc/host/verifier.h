@@ -105,20 +105,10 @@ inline FriLayerProof jv_fri_layer(const JVal& v, bool felt) {
     l.commitment = jv_hash(v.get("commitment"), felt);
     return l;
 }
-inline BrainfuckProof proof_from_json(const char* s, size_t len, bool felt = false) {
-    JsonReader jr{s, s + len};
-    JVal root = jr.parse();
-    jr.ws();
-    if (jr.p != jr.end) throw std::runtime_error("json: trailing characters");
-    BrainfuckProof bp;
-    for (int c = 0; c < N_COMPONENTS; c++) {
-        const JVal& ls = root.get("claim").get(COMPONENT_NAMES[c]).get("log_size");
-        if (ls.kind != JVal::NUM || ls.num > 31) throw std::runtime_error("bad log_size");
-        bp.log_sizes[c] = (u32)ls.num;
-        bp.claimed_sums[c] = jv_qm31(root.get("interaction_claim").get(COMPONENT_NAMES[c]).get("claimed_sum"));
-    }
-    const JVal& p = root.get("proof");
-    StarkProof& sp = bp.proof;
+// CommitmentSchemeProof {commitments, sampled_values, decommitments, queried_values, proof_of_work, fri_proof}: the "proof" member of a
+// BrainfuckProof, and the whole of what a commitment-scheme session (bfhip_pcs_prove_values) returns
+inline StarkProof stark_proof_from_jval(const JVal& p, bool felt) {
+    StarkProof sp;
     for (auto& h : jv_list(p.get("commitments"))) sp.commitments.push_back(jv_hash(h, felt));
     for (auto& t : jv_list(p.get("sampled_values"))) {
         std::vector<std::vector<Q31>> tv;
@@ -134,6 +124,26 @@ inline BrainfuckProof proof_from_json(const char* s, size_t len, bool felt = fal
     for (auto& l : jv_list(f.get("inner_layers"))) sp.fri_proof.inner_layers.push_back(jv_fri_layer(l, felt));
     for (auto& q : jv_list(f.get("last_layer_poly").get("coeffs"))) sp.fri_proof.last_layer_coeffs.push_back(jv_qm31(q));
     { const JVal& ll = f.get("last_layer_poly").get("log_size"); if (ll.kind != JVal::NUM || ll.num > 31) throw std::runtime_error("bad last layer log_size"); sp.fri_proof.last_layer_log_size = (u32)ll.num; }
+    return sp;
+}
+inline JVal json_document(const char* s, size_t len) {
+    JsonReader jr{s, s + len};
+    JVal root = jr.parse();
+    jr.ws();
+    if (jr.p != jr.end) throw std::runtime_error("json: trailing characters");
+    return root;
+}
+inline StarkProof stark_proof_from_json(const char* s, size_t len, bool felt = false) { return stark_proof_from_jval(json_document(s, len), felt); }
+inline BrainfuckProof proof_from_json(const char* s, size_t len, bool felt = false) {
+    JVal root = json_document(s, len);
+    BrainfuckProof bp;
+    for (int c = 0; c < N_COMPONENTS; c++) {
+        const JVal& ls = root.get("claim").get(COMPONENT_NAMES[c]).get("log_size");
+        if (ls.kind != JVal::NUM || ls.num > 31) throw std::runtime_error("bad log_size");
+        bp.log_sizes[c] = (u32)ls.num;
+        bp.claimed_sums[c] = jv_qm31(root.get("interaction_claim").get(COMPONENT_NAMES[c]).get("claimed_sum"));
+    }
+    bp.proof = stark_proof_from_jval(root.get("proof"), felt);
     return bp;
 }
 
@@ -261,6 +271,164 @@ inline std::vector<size_t> v_fold_queries(const std::vector<size_t>& q, u32 n) {
     return o;
 }
 
+// CommitmentSchemeVerifier::verify_values: everything of a verification that does not depend on the AIR. ch = the channel after the
+// out-of-domain point was drawn; col_logs[t][c] = LDE-domain log size of column c of tree t (trace log + log_blowup_factor); sp[t][c] = the
+// sample points of that column, in the order of pf.sampled_values[t][c]. The caller has checked that pf has one commitment, decommitment,
+// sampled-value and queried-value list per tree and one sampled value per sample point. Returns "" when the openings verify, else the reason;
+// may throw (a caller's boundary turns that into "InvalidStructure: ...").
+inline std::string verify_values(Channel& ch, const std::vector<std::vector<u32>>& col_logs, const std::vector<std::vector<std::vector<PtQ>>>& sp, const StarkProof& pf,
+                                 const VerifierConfig& cfg, const Conventions& cv) {
+    const size_t n_trees = col_logs.size();
+    { std::vector<Q31> flat; for (auto& t : pf.sampled_values) for (auto& c : t) for (auto& v : c) flat.push_back(v); ch.mix_felts(flat.data(), flat.size()); }
+    Q31 q_coeff = ch.draw_felt();
+    std::set<u32, std::greater<u32>> logs_set;
+    for (auto& t : col_logs) for (u32 l : t) logs_set.insert(l);
+    std::vector<u32> dom_logs(logs_set.begin(), logs_set.end());
+    // FriVerifier::commit
+    const FriProof& fp = pf.fri_proof;
+    ch.mix_root(fp.first_layer.commitment);
+    Q31 first_alpha = ch.draw_felt();
+    u32 layer_bound = dom_logs[0] - cfg.log_blowup - 1;
+    std::vector<Q31> alphas;
+    for (auto& lp : fp.inner_layers) { ch.mix_root(lp.commitment); alphas.push_back(ch.draw_felt()); if (layer_bound == 0) return "InvalidNumFriLayers"; layer_bound--; }
+    if (layer_bound != cfg.log_last_layer_degree_bound) return "InvalidNumFriLayers";
+    if (fp.last_layer_coeffs.size() > (size_t(1) << cfg.log_last_layer_degree_bound)) return "LastLayerDegreeInvalid";
+    // LinePoly::eval_at_point folds the coefficients over log_size doublings and asserts len == 2^log_size (stwo utils::fold): a proof
+    // whose log_size does not match its coefficient count makes the reference's verifier panic
+    if (fp.last_layer_log_size > 31 || fp.last_layer_coeffs.size() != (size_t(1) << fp.last_layer_log_size)) return "LastLayerDegreeInvalid";
+    ch.mix_felts(fp.last_layer_coeffs.data(), fp.last_layer_coeffs.size());
+    ch.mix_u64(pf.proof_of_work);
+    if (ch.trailing_zeros() < cfg.pow_bits) return "ProofOfWork";
+    u32 max_log = dom_logs[0];
+    std::vector<size_t> queries;
+    {
+        std::set<size_t> qs; u32 cnt = 0; u32 maskq = (u32)((u64(1) << max_log) - 1);
+        while (cnt < cfg.n_queries) {   // Queries::generate: chunks_exact(4) of the drawn bytes (32 per draw for Blake2s, 31 for Poseidon252)
+            std::vector<u8> r = ch.draw_random_bytes();
+            for (size_t k = 0; 4 * k + 4 <= r.size() && cnt < cfg.n_queries; k++) { u32 w; memcpy(&w, r.data() + 4 * k, 4); qs.insert(w & maskq); cnt++; }
+        }
+        queries.assign(qs.begin(), qs.end());
+    }
+    std::map<u32, std::vector<size_t>> positions_by_log;
+    for (u32 l : dom_logs) positions_by_log[l] = v_fold_queries(queries, max_log - l);
+    for (size_t t = 0; t < n_trees; t++) { std::string e = merkle_verify(pf.commitments[t], col_logs[t], positions_by_log, pf.queried_values[t], pf.decommitments[t], cv); if (!e.empty()) return "MerkleVerification tree " + std::to_string(t) + ": " + e; }
+    // fri_answers: per LDE size (descending), the quotient value at every query position
+    struct Flat { size_t t; size_t c; u32 log; };
+    std::vector<Flat> flat;
+    for (size_t t = 0; t < n_trees; t++) for (size_t c = 0; c < sp[t].size(); c++) flat.push_back({t, c, col_logs[t][c]});
+    std::stable_sort(flat.begin(), flat.end(), [](const Flat& a, const Flat& b) { return a.log > b.log; });
+    std::vector<size_t> qv_pos(n_trees, 0), ncols(n_trees, 0);
+    std::vector<std::vector<Q31>> answers;
+    for (size_t i = 0; i < flat.size();) {
+        size_t j = i; u32 log = flat[i].log;
+        while (j < flat.size() && flat[j].log == log) j++;
+        std::map<PtQ, std::vector<std::pair<u32, Q31>>, PointLessV> by_point;
+        for (size_t k = i; k < j; k++) for (size_t s = 0; s < sp[flat[k].t][flat[k].c].size(); s++)
+            by_point[sp[flat[k].t][flat[k].c][s]].push_back({(u32)(k - i), pf.sampled_values[flat[k].t][flat[k].c][s]});
+        for (size_t t = 0; t < n_trees; t++) { ncols[t] = 0; for (u32 l : col_logs[t]) if (l == log) ncols[t]++; }
+        std::vector<Q31> ans;
+        for (size_t qpos : positions_by_log[log]) {
+            PtM dp = canonic_domain_at(log, bit_rev((u32)qpos, log));
+            std::vector<u32> vals;
+            for (size_t t = 0; t < n_trees; t++) for (size_t k = 0; k < ncols[t]; k++) { if (qv_pos[t] >= pf.queried_values[t].size()) return "InvalidStructure: queried_values"; vals.push_back(pf.queried_values[t][qv_pos[t]++]); }
+            Q31 row = q_zero();
+            for (auto& kv : by_point) {
+                const PtQ& pt = kv.first;
+                Q31 alpha = q_one(), num = q_zero();
+                Q31 cc = q_sub(q_conj(pt.y), pt.y);
+                for (auto& cv : kv.second) {
+                    alpha = q_mul(alpha, q_coeff);
+                    Q31 a = q_sub(q_conj(cv.second), cv.second);
+                    Q31 b = q_sub(q_mul(cv.second, cc), q_mul(a, pt.y));
+                    Q31 value = q_mulm(q_mul(alpha, cc), vals.at(cv.first));
+                    Q31 linear = q_add(q_mulm(q_mul(alpha, a), dp.y), q_mul(alpha, b));
+                    num = q_add(num, q_sub(value, linear));
+                }
+                C31 dx = pt.x.a; dx.a = m_sub(dx.a, dp.x);
+                C31 dy = pt.y.a; dy.a = m_sub(dy.a, dp.y);
+                C31 den = c_sub(c_mul(dx, pt.y.b), c_mul(dy, pt.x.b));
+                row = q_add(q_mul(row, q_pow(q_coeff, kv.second.size())), q_mulc(num, c_inv(den)));
+            }
+            ans.push_back(row);
+        }
+        answers.push_back(ans);
+        i = j;
+    }
+    if (answers.size() != dom_logs.size()) return "InvalidStructure: fri answers";
+    // FriVerifier::decommit
+    struct Sparse { std::vector<std::array<Q31, 2>> evals; std::vector<size_t> starts; };
+    auto rebuild = [&](const std::vector<size_t>& q, const std::vector<Q31>& qevals, const std::vector<Q31>& wit, size_t& wi, std::vector<size_t>& positions, Sparse& out) -> bool {
+        size_t i = 0, ei = 0;
+        while (i < q.size()) {
+            size_t j = i; while (j < q.size() && (q[j] >> 1) == (q[i] >> 1)) j++;
+            size_t start = (q[i] >> 1) << 1, qi2 = i;
+            std::array<Q31, 2> ev;
+            for (size_t pos = start; pos < start + 2; pos++) {
+                positions.push_back(pos);
+                if (qi2 < j && q[qi2] == pos) { qi2++; if (ei >= qevals.size()) return false; ev[pos - start] = qevals[ei++]; }
+                else { if (wi >= wit.size()) return false; ev[pos - start] = wit[wi++]; }
+            }
+            out.evals.push_back(ev); out.starts.push_back(start);
+            i = j;
+        }
+        return true;
+    };
+    auto words_of = [](const Sparse& s) { std::vector<u32> v; for (auto& ev : s.evals) for (auto& q : ev) { v.push_back(q.a.a); v.push_back(q.a.b); v.push_back(q.b.a); v.push_back(q.b.b); } return v; };
+    std::vector<Sparse> first_sparse(dom_logs.size());
+    {
+        size_t wi = 0; std::map<u32, std::vector<size_t>> dpos; std::vector<u32> dvals, mlogs;
+        for (size_t k = 0; k < dom_logs.size(); k++) {
+            std::vector<size_t> pos;
+            if (!rebuild(v_fold_queries(queries, max_log - dom_logs[k]), answers[k], fp.first_layer.fri_witness, wi, pos, first_sparse[k])) return "FirstLayerEvaluationsInvalid";
+            dpos[dom_logs[k]] = pos;
+            auto w = words_of(first_sparse[k]); dvals.insert(dvals.end(), w.begin(), w.end());
+            for (int c = 0; c < 4; c++) mlogs.push_back(dom_logs[k]);
+        }
+        if (wi != fp.first_layer.fri_witness.size()) return "FirstLayerEvaluationsInvalid";
+        std::string e = merkle_verify(fp.first_layer.commitment, mlogs, dpos, dvals, fp.first_layer.decommitment, cv);
+        if (!e.empty()) return "FirstLayerCommitmentInvalid: " + e;
+    }
+    auto lq = v_fold_queries(queries, 1);
+    std::vector<Q31> lev(lq.size(), q_zero());
+    size_t fk = 0; Q31 prev_alpha = first_alpha; u32 line_log = max_log - 1;
+    for (size_t li = 0; li < fp.inner_layers.size(); li++) {
+        while (fk < dom_logs.size() && dom_logs[fk] - 1 == line_log) {
+            if (first_sparse[fk].evals.size() != lev.size()) return "InvalidStructure: sparse evals";
+            Q31 a2 = q_mul(prev_alpha, prev_alpha);
+            for (size_t s = 0; s < lev.size(); s++) {
+                PtM p = canonic_domain_at(dom_logs[fk], bit_rev((u32)first_sparse[fk].starts[s], dom_logs[fk]));
+                Q31 fpv = first_sparse[fk].evals[s][0], fnv = first_sparse[fk].evals[s][1];
+                Q31 f0 = q_add(fpv, fnv), f1 = q_mulm(q_sub(fpv, fnv), m_inv(p.y));
+                lev[s] = q_add(q_mul(lev[s], a2), q_add(f0, q_mul(prev_alpha, f1)));
+            }
+            fk++;
+        }
+        const FriLayerProof& lp = fp.inner_layers[li];
+        size_t wi = 0; std::vector<size_t> pos; Sparse sps;
+        if (!rebuild(lq, lev, lp.fri_witness, wi, pos, sps) || wi != lp.fri_witness.size()) return "InnerLayerEvaluationsInvalid";
+        std::map<u32, std::vector<size_t>> dpos; dpos[line_log] = pos;
+        std::string e = merkle_verify(lp.commitment, std::vector<u32>(4, line_log), dpos, words_of(sps), lp.decommitment, cv);
+        if (!e.empty()) return "InnerLayerCommitmentInvalid: " + e;
+        std::vector<Q31> nev;
+        for (size_t s = 0; s < sps.evals.size(); s++) {
+            // LineDomain(Coset::half_odds(line_log)).at(bit_reverse(start)): x-coordinate
+            u32 idx = subgroup_gen(line_log + 2) + subgroup_gen(line_log) * bit_rev((u32)sps.starts[s], line_log);
+            u32 x = index_to_point(idx).x;
+            Q31 fx = sps.evals[s][0], fn = sps.evals[s][1];
+            Q31 f0 = q_add(fx, fn), f1 = q_mulm(q_sub(fx, fn), m_inv(x));
+            nev.push_back(q_add(f0, q_mul(alphas[li], f1)));
+        }
+        lq = v_fold_queries(lq, 1); lev = nev; prev_alpha = alphas[li]; line_log--;
+    }
+    if (fk != dom_logs.size()) return "InvalidStructure: unconsumed first-layer columns";
+    if (cfg.log_last_layer_degree_bound != 0) return "unsupported last layer bound";
+    for (size_t i = 0; i < lq.size(); i++) {
+        Q31 expect = fp.last_layer_coeffs.empty() ? q_zero() : fp.last_layer_coeffs[0];
+        if (!q_eq(lev.at(i), expect)) return "LastLayerEvaluationsInvalid";
+    }
+    return "";
+}
+
 // Returns "" when the proof verifies, else the reason.
 inline std::string verify_brainfuck(const BrainfuckProof& bp, u32 log_max_rows, const Conventions& cv = Conventions(), VerifierConfig cfg = VerifierConfig()) {
     try {
@@ -317,155 +485,7 @@ inline std::string verify_brainfuck(const BrainfuckProof& bp, u32 log_max_rows, 
             Q31 want = eval_composition_at_point(bp.log_sizes, bp.claimed_sums, log_max_rows, el, oods, pf.sampled_values, random_coeff, cv);
             if (!q_eq(HostPointEval::combine(ce, 0), want)) return "OodsNotMatching";
         }
-        { std::vector<Q31> flat; for (auto& t : pf.sampled_values) for (auto& c : t) for (auto& v : c) flat.push_back(v); ch.mix_felts(flat.data(), flat.size()); }
-        Q31 q_coeff = ch.draw_felt();
-        std::set<u32, std::greater<u32>> logs_set;
-        for (auto& t : col_logs) for (u32 l : t) logs_set.insert(l);
-        std::vector<u32> dom_logs(logs_set.begin(), logs_set.end());
-        // FriVerifier::commit
-        const FriProof& fp = pf.fri_proof;
-        ch.mix_root(fp.first_layer.commitment);
-        Q31 first_alpha = ch.draw_felt();
-        u32 layer_bound = dom_logs[0] - cfg.log_blowup - 1;
-        std::vector<Q31> alphas;
-        for (auto& lp : fp.inner_layers) { ch.mix_root(lp.commitment); alphas.push_back(ch.draw_felt()); if (layer_bound == 0) return "InvalidNumFriLayers"; layer_bound--; }
-        if (layer_bound != cfg.log_last_layer_degree_bound) return "InvalidNumFriLayers";
-        if (fp.last_layer_coeffs.size() > (size_t(1) << cfg.log_last_layer_degree_bound)) return "LastLayerDegreeInvalid";
-        // LinePoly::eval_at_point folds the coefficients over log_size doublings and asserts len == 2^log_size (stwo utils::fold): a proof
-        // whose log_size does not match its coefficient count makes the reference's verifier panic
-        if (fp.last_layer_log_size > 31 || fp.last_layer_coeffs.size() != (size_t(1) << fp.last_layer_log_size)) return "LastLayerDegreeInvalid";
-        ch.mix_felts(fp.last_layer_coeffs.data(), fp.last_layer_coeffs.size());
-        ch.mix_u64(pf.proof_of_work);
-        if (ch.trailing_zeros() < cfg.pow_bits) return "ProofOfWork";
-        u32 max_log = dom_logs[0];
-        std::vector<size_t> queries;
-        {
-            std::set<size_t> qs; u32 cnt = 0; u32 maskq = (u32)((u64(1) << max_log) - 1);
-            while (cnt < cfg.n_queries) {   // Queries::generate: chunks_exact(4) of the drawn bytes (32 per draw for Blake2s, 31 for Poseidon252)
-                std::vector<u8> r = ch.draw_random_bytes();
-                for (size_t k = 0; 4 * k + 4 <= r.size() && cnt < cfg.n_queries; k++) { u32 w; memcpy(&w, r.data() + 4 * k, 4); qs.insert(w & maskq); cnt++; }
-            }
-            queries.assign(qs.begin(), qs.end());
-        }
-        std::map<u32, std::vector<size_t>> positions_by_log;
-        for (u32 l : dom_logs) positions_by_log[l] = v_fold_queries(queries, max_log - l);
-        for (int t = 0; t < 4; t++) { std::string e = merkle_verify(pf.commitments[t], col_logs[t], positions_by_log, pf.queried_values[t], pf.decommitments[t], cv); if (!e.empty()) return "MerkleVerification tree " + std::to_string(t) + ": " + e; }
-        // fri_answers: per LDE size (descending), the quotient value at every query position
-        struct Flat { int t; size_t c; u32 log; };
-        std::vector<Flat> flat;
-        for (int t = 0; t < 4; t++) for (size_t c = 0; c < sp[t].size(); c++) flat.push_back({t, c, col_logs[t][c]});
-        std::stable_sort(flat.begin(), flat.end(), [](const Flat& a, const Flat& b) { return a.log > b.log; });
-        size_t qv_pos[4] = {0, 0, 0, 0};
-        std::vector<std::vector<Q31>> answers;
-        for (size_t i = 0; i < flat.size();) {
-            size_t j = i; u32 log = flat[i].log;
-            while (j < flat.size() && flat[j].log == log) j++;
-            std::map<PtQ, std::vector<std::pair<u32, Q31>>, PointLessV> by_point;
-            for (size_t k = i; k < j; k++) for (size_t s = 0; s < sp[flat[k].t][flat[k].c].size(); s++)
-                by_point[sp[flat[k].t][flat[k].c][s]].push_back({(u32)(k - i), pf.sampled_values[flat[k].t][flat[k].c][s]});
-            size_t ncols[4] = {0, 0, 0, 0};
-            for (int t = 0; t < 4; t++) for (u32 l : col_logs[t]) if (l == log) ncols[t]++;
-            std::vector<Q31> ans;
-            for (size_t qpos : positions_by_log[log]) {
-                PtM dp = canonic_domain_at(log, bit_rev((u32)qpos, log));
-                std::vector<u32> vals;
-                for (int t = 0; t < 4; t++) for (size_t k = 0; k < ncols[t]; k++) { if (qv_pos[t] >= pf.queried_values[t].size()) return "InvalidStructure: queried_values"; vals.push_back(pf.queried_values[t][qv_pos[t]++]); }
-                Q31 row = q_zero();
-                for (auto& kv : by_point) {
-                    const PtQ& pt = kv.first;
-                    Q31 alpha = q_one(), num = q_zero();
-                    Q31 cc = q_sub(q_conj(pt.y), pt.y);
-                    for (auto& cv : kv.second) {
-                        alpha = q_mul(alpha, q_coeff);
-                        Q31 a = q_sub(q_conj(cv.second), cv.second);
-                        Q31 b = q_sub(q_mul(cv.second, cc), q_mul(a, pt.y));
-                        Q31 value = q_mulm(q_mul(alpha, cc), vals.at(cv.first));
-                        Q31 linear = q_add(q_mulm(q_mul(alpha, a), dp.y), q_mul(alpha, b));
-                        num = q_add(num, q_sub(value, linear));
-                    }
-                    C31 dx = pt.x.a; dx.a = m_sub(dx.a, dp.x);
-                    C31 dy = pt.y.a; dy.a = m_sub(dy.a, dp.y);
-                    C31 den = c_sub(c_mul(dx, pt.y.b), c_mul(dy, pt.x.b));
-                    row = q_add(q_mul(row, q_pow(q_coeff, kv.second.size())), q_mulc(num, c_inv(den)));
-                }
-                ans.push_back(row);
-            }
-            answers.push_back(ans);
-            i = j;
-        }
-        if (answers.size() != dom_logs.size()) return "InvalidStructure: fri answers";
-        // FriVerifier::decommit
-        struct Sparse { std::vector<std::array<Q31, 2>> evals; std::vector<size_t> starts; };
-        auto rebuild = [&](const std::vector<size_t>& q, const std::vector<Q31>& qevals, const std::vector<Q31>& wit, size_t& wi, std::vector<size_t>& positions, Sparse& out) -> bool {
-            size_t i = 0, ei = 0;
-            while (i < q.size()) {
-                size_t j = i; while (j < q.size() && (q[j] >> 1) == (q[i] >> 1)) j++;
-                size_t start = (q[i] >> 1) << 1, qi2 = i;
-                std::array<Q31, 2> ev;
-                for (size_t pos = start; pos < start + 2; pos++) {
-                    positions.push_back(pos);
-                    if (qi2 < j && q[qi2] == pos) { qi2++; if (ei >= qevals.size()) return false; ev[pos - start] = qevals[ei++]; }
-                    else { if (wi >= wit.size()) return false; ev[pos - start] = wit[wi++]; }
-                }
-                out.evals.push_back(ev); out.starts.push_back(start);
-                i = j;
-            }
-            return true;
-        };
-        auto words_of = [](const Sparse& s) { std::vector<u32> v; for (auto& ev : s.evals) for (auto& q : ev) { v.push_back(q.a.a); v.push_back(q.a.b); v.push_back(q.b.a); v.push_back(q.b.b); } return v; };
-        std::vector<Sparse> first_sparse(dom_logs.size());
-        {
-            size_t wi = 0; std::map<u32, std::vector<size_t>> dpos; std::vector<u32> dvals, mlogs;
-            for (size_t k = 0; k < dom_logs.size(); k++) {
-                std::vector<size_t> pos;
-                if (!rebuild(v_fold_queries(queries, max_log - dom_logs[k]), answers[k], fp.first_layer.fri_witness, wi, pos, first_sparse[k])) return "FirstLayerEvaluationsInvalid";
-                dpos[dom_logs[k]] = pos;
-                auto w = words_of(first_sparse[k]); dvals.insert(dvals.end(), w.begin(), w.end());
-                for (int c = 0; c < 4; c++) mlogs.push_back(dom_logs[k]);
-            }
-            if (wi != fp.first_layer.fri_witness.size()) return "FirstLayerEvaluationsInvalid";
-            std::string e = merkle_verify(fp.first_layer.commitment, mlogs, dpos, dvals, fp.first_layer.decommitment, cv);
-            if (!e.empty()) return "FirstLayerCommitmentInvalid: " + e;
-        }
-        auto lq = v_fold_queries(queries, 1);
-        std::vector<Q31> lev(lq.size(), q_zero());
-        size_t fk = 0; Q31 prev_alpha = first_alpha; u32 line_log = max_log - 1;
-        for (size_t li = 0; li < fp.inner_layers.size(); li++) {
-            while (fk < dom_logs.size() && dom_logs[fk] - 1 == line_log) {
-                if (first_sparse[fk].evals.size() != lev.size()) return "InvalidStructure: sparse evals";
-                Q31 a2 = q_mul(prev_alpha, prev_alpha);
-                for (size_t s = 0; s < lev.size(); s++) {
-                    PtM p = canonic_domain_at(dom_logs[fk], bit_rev((u32)first_sparse[fk].starts[s], dom_logs[fk]));
-                    Q31 fpv = first_sparse[fk].evals[s][0], fnv = first_sparse[fk].evals[s][1];
-                    Q31 f0 = q_add(fpv, fnv), f1 = q_mulm(q_sub(fpv, fnv), m_inv(p.y));
-                    lev[s] = q_add(q_mul(lev[s], a2), q_add(f0, q_mul(prev_alpha, f1)));
-                }
-                fk++;
-            }
-            const FriLayerProof& lp = fp.inner_layers[li];
-            size_t wi = 0; std::vector<size_t> pos; Sparse sps;
-            if (!rebuild(lq, lev, lp.fri_witness, wi, pos, sps) || wi != lp.fri_witness.size()) return "InnerLayerEvaluationsInvalid";
-            std::map<u32, std::vector<size_t>> dpos; dpos[line_log] = pos;
-            std::string e = merkle_verify(lp.commitment, std::vector<u32>(4, line_log), dpos, words_of(sps), lp.decommitment, cv);
-            if (!e.empty()) return "InnerLayerCommitmentInvalid: " + e;
-            std::vector<Q31> nev;
-            for (size_t s = 0; s < sps.evals.size(); s++) {
-                // LineDomain(Coset::half_odds(line_log)).at(bit_reverse(start)): x-coordinate
-                u32 idx = subgroup_gen(line_log + 2) + subgroup_gen(line_log) * bit_rev((u32)sps.starts[s], line_log);
-                u32 x = index_to_point(idx).x;
-                Q31 fx = sps.evals[s][0], fn = sps.evals[s][1];
-                Q31 f0 = q_add(fx, fn), f1 = q_mulm(q_sub(fx, fn), m_inv(x));
-                nev.push_back(q_add(f0, q_mul(alphas[li], f1)));
-            }
-            lq = v_fold_queries(lq, 1); lev = nev; prev_alpha = alphas[li]; line_log--;
-        }
-        if (fk != dom_logs.size()) return "InvalidStructure: unconsumed first-layer columns";
-        if (cfg.log_last_layer_degree_bound != 0) return "unsupported last layer bound";
-        for (size_t i = 0; i < lq.size(); i++) {
-            Q31 expect = fp.last_layer_coeffs.empty() ? q_zero() : fp.last_layer_coeffs[0];
-            if (!q_eq(lev.at(i), expect)) return "LastLayerEvaluationsInvalid";
-        }
-        return "";
+        return verify_values(ch, col_logs, sp, pf, cfg, cv);
     } catch (const std::exception& e) { return std::string("InvalidStructure: ") + e.what(); }
 }
 

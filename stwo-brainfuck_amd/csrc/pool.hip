@@ -266,6 +266,7 @@ int32_t bfhip_pool_create(int32_t device_id, uint32_t n_in_flight, uint32_t max_
         for (uint32_t i = 0; i < n_in_flight; i++) {
             pool->subs.push_back(new bfhip_ctx());
             pool->subs.back()->c.init(device_id, max_log_domain, i ? &pool->subs[0]->c : nullptr);
+            pool->subs.back()->c.pool_busy = [pool] { std::lock_guard<std::mutex> lk(pool->mu); return pool->batch_active || pool->outstanding() != 0; };
         }
         pool->builder = new bfhip_ctx();
         pool->builder->c.init(device_id, max_log_domain, &pool->subs[0]->c);

@@ -56,6 +56,7 @@ void HipProver::check_config() const {
 BrainfuckProof HipProver::prove(const std::function<const TraceInput&()>& get_input) {
     double t_start = now();
     mark_t0 = t_start;
+    c.refuse_in_session("proof");
     check_config();
     struct SpinScope { Ctx& c; double saved; ~SpinScope() { c.spin_seconds = saved; } } spin_scope{c, c.spin_seconds};
     if (!c.sync_blocking) c.spin_seconds = 8e-3;      // bfhip_ctx_set_sync_policy(blocking): hosts with more contexts than cores keep the short poll

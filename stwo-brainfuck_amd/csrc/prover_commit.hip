@@ -6,6 +6,28 @@
 
 namespace bf {
 
+#ifdef BFHIP_TEST_HOOKS
+// libbfhip_testhooks.so only (see the end of this file): with the capture on, every tree commitment of a proof leaves a copy of its
+// polynomials on the host, in commit order. The copies are enqueued behind the launches that produce the coefficients; the reader waits.
+struct PolyCapture {
+    struct Poly { u32 log_size, shift; std::vector<u32> stored; };
+    bool on = false; int saved_mailbox_mode = -1;
+    std::vector<std::vector<Poly>> trees;
+};
+static void capture_tree(Ctx& c, const DTree& t) {
+    if (!c.capture || !c.capture->on) return;
+    c.capture->trees.emplace_back();
+    auto& out = c.capture->trees.back();
+    out.resize(t.polys.size());
+    for (size_t i = 0; i < t.polys.size(); i++) {
+        const DCol& p = t.polys[i];
+        if (!p.ptr || p.sliced()) throw HipError("bfhip_test_capture_polys: a polynomial this rank does not hold whole");
+        out[i].log_size = p.log_size; out[i].shift = p.shift; out[i].stored.resize(p.stored());
+        BF_HIP(hipMemcpyAsync(out[i].stored.data(), p.ptr, p.stored() * sizeof(u32), hipMemcpyDeviceToHost, c.stream));
+    }
+}
+#endif
+
 // ---- batched FFT over heterogeneous columns: group by (size, storage) --------------------------------------------------
 // Two steps so that a caller can put the plan's staging into a batch shared with what follows (fft_prepare inside a StageBatch,
 // fft_launch after its end()): pointer arrays and the pass table of every size group reach the device in one copy.
@@ -338,6 +360,9 @@ void HipProver::commit_tree(DTree& t, Hash32* pinned_root, bool with_prev) {
     BF_HIP(hipGetLastError());
     t.mk = merkle_commit(t.evals, pinned_root);
     if (!pinned_root) ch.mix_root(t.mk.root);
+#ifdef BFHIP_TEST_HOOKS
+    capture_tree(c, t);
+#endif
 }
 
 // One process per proof: the same commitment with its two bounds overlapped. The transforms are HBM-bound, the Blake2s layers
@@ -403,6 +428,9 @@ void HipProver::commit_tree_overlapped(DTree& t, Hash32* pinned_root, const std:
         if (stamp_slot >= 0) c.post_stamp(stamp_slot);
     }
     if (!pinned_root) ch.mix_root(t.mk.root);
+#ifdef BFHIP_TEST_HOOKS
+    capture_tree(c, t);
+#endif
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -412,6 +440,7 @@ void HipProver::commit_tree_overlapped(DTree& t, Hash32* pinned_root, const std:
 // use_arena: take the column storage from the per-proof arena (no hipMalloc, which would synchronise the device) — only valid for
 // the duration of the current proof; otherwise the columns live in their own device allocations owned by `in`.
 void HipProver::upload_trace(Ctx& c, const std::vector<Registers>& vm_trace, const std::vector<u32>& code, TraceInput& in, bool use_arena, bool on_gpu) {
+    c.refuse_in_session("trace upload");      // the GPU table builders take their scratch from the arena
     in.rows.assign(N_COMPONENTS, {});
     in.n_steps = vm_trace.size();
     in.main_cells = in.interaction_cells = 0;
@@ -456,6 +485,7 @@ void HipProver::upload_registers(Ctx& c, const u32* trace7_h, size_t n_rows, con
         if (with_place) m += " (row " + std::to_string(row) + ", register " + std::to_string(reg) + ")";
         return HipError(m);
     };
+    c.refuse_in_session("trace upload");
     auto check_code = [&]() {
         std::vector<u32> ins(code_words_h, code_words_h + n_code);
         for (u32 w : ins) if (w >= P31) throw HipError("program word is not a canonical M31");
@@ -519,6 +549,7 @@ void HipProver::build_preprocessed(DTree& tree, Hash32* pinned_root) {
 // without waiting — sp.ready is recorded behind the tree and the root's store into pinned memory.
 void HipProver::build_shared_preprocessed(SharedPreprocessed& sp) {
     if (sharded()) throw HipError("pool: the builder context must not be a member of a shard group");
+    c.refuse_in_session("pool: preprocessed commitment");
     if (log_max_rows < LOG_N_LANES) throw HipError("log_max_rows must be at least LOG_N_LANES (4)");
     check_config();
     sp.valid = false;
@@ -566,3 +597,48 @@ void shared_preprocessed_build(SharedPreprocessed* sp, Ctx& builder, u32 log_max
 void shared_preprocessed_invalidate(SharedPreprocessed* sp) { if (sp) sp->valid = false; }
 
 }  // namespace bf
+
+#ifdef BFHIP_TEST_HOOKS
+#include "api_guard.h"
+// libbfhip_testhooks.so only (Makefile); not declared in include/bfhip.h. What tests/test_gpu_pcs_session.py feeds a commitment-scheme session
+// with: the four trees of a Brainfuck proof as plain coefficient columns.
+// bfhip_test_capture_polys(ctx, on): on = the proofs of this context from now on copy, behind each tree commitment, every polynomial of the
+// tree to host memory (commit order: preprocessed, main trace, interaction, composition); the list starts empty at every call. While the
+// capture is on the context proves in the plain launch order (a copy to host memory cannot be enqueued behind a waiting mailbox kernel);
+// off restores the mailbox mode and drops the copies.
+// bfhip_test_captured_poly(ctx, tree, col, out_h, cap, &log_size): polynomial `col` of captured tree `tree` as a full-size coefficient
+// column of 2^log_size words; a row-granular polynomial (stored at one word per 16 cells: its coefficients of index 0 mod 16) is expanded
+// with zeros. out_h == NULL: the size only. -2 = cap too small.
+extern "C" int32_t bfhip_test_capture_polys(bfhip_ctx* ctx, int32_t on) {
+    using namespace bf;
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    if (c.shard.count > 1) throw HipError("bfhip_test_capture_polys: the context is in a shard group");
+    sync_both(c);
+    if (!c.capture) { c.capture = new PolyCapture(); c.capture->saved_mailbox_mode = c.mailbox_mode; }
+    if (on && !c.capture->on) { c.capture->saved_mailbox_mode = c.mailbox_mode; c.mailbox_mode = 0; }
+    if (!on && c.capture->on) c.mailbox_mode = c.capture->saved_mailbox_mode;
+    c.capture->on = on != 0;
+    c.capture->trees.clear();
+    if (!on) { delete c.capture; c.capture = nullptr; }
+    return 0;
+    API_CATCH
+}
+extern "C" int32_t bfhip_test_captured_poly(bfhip_ctx* ctx, uint32_t tree, uint32_t col, uint32_t* out_h, size_t cap, uint32_t* log_size) {
+    using namespace bf;
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    if (!log_size) throw HipError("null argument");
+    if (!c.capture) throw HipError("bfhip_test_captured_poly: the capture is off");
+    sync_both(c);
+    if (tree >= c.capture->trees.size() || col >= c.capture->trees[tree].size()) throw HipError("bfhip_test_captured_poly: no such captured polynomial");
+    const PolyCapture::Poly& p = c.capture->trees[tree][col];
+    *log_size = p.log_size;
+    if (!out_h) return 0;
+    if (cap < (size_t(1) << p.log_size)) { bfhip_set_error("capacity"); return -2; }
+    memset(out_h, 0, sizeof(u32) << p.log_size);
+    for (size_t i = 0; i < p.stored.size(); i++) out_h[i << p.shift] = p.stored[i];
+    return 0;
+    API_CATCH
+}
+#endif

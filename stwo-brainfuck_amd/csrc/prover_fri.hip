@@ -485,6 +485,7 @@ extern "C" int32_t bfhip_test_fri_commit(bfhip_ctx* ctx, const uint8_t* digest32
     Ctx& c = ctx->c;
     if (!digest32 || !log_sizes || !cols_h || !layers_out || !trees_out || !roots_out || !alphas_out || !chan_out || !paths_out) throw HipError("null argument");
     if (c.shard.count > 1) throw HipError("bfhip_test_fri_commit: the context is in a shard group");
+    c.refuse_in_session("bfhip_test_fri_commit");
     if (n_cols == 0) throw HipError("bfhip_test_fri_commit: no columns");
     for (u32 k = 0; k < 4 * n_cols; k++) if (!cols_h[k]) throw HipError("null argument");
     for (u32 k = 1; k < n_cols; k++) if (log_sizes[k] >= log_sizes[k - 1]) throw HipError("bfhip_test_fri_commit: the column sizes must be distinct and descending");

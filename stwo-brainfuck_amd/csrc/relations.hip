@@ -288,6 +288,7 @@ static void relations_run(Ctx& c, const RelTable* tables, u32 n_tables, bfhip_re
     }
     if (total_rows > (u64(1) << 31)) throw HipError("more than 2^31 table rows in total");
     static const u32 N_WORDS[3] = {3, 3, 7};
+    if (!in_proof) c.refuse_in_session("relation summary");
     const Arena::Mark arena_mark = c.arena.mark();
     for (u32 r = 0; r < 3; r++) {
         RelSources S{};
