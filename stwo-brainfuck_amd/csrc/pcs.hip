@@ -18,6 +18,9 @@ struct bfhip_pcs {
     std::vector<DTree> trees;
     bool proved = false;                 // prove_values was called: only tree_columns and destroy remain
     Arena::Mark before;                  // the arena's bookkeeping when the session was created, put back by destroy
+#ifdef BFHIP_TEST_HOOKS
+    std::vector<u32> fri_path;           // HipProver::FriCommitted::path of prove_values (bfhip_test_pcs_fri_path)
+#endif
     explicit bfhip_pcs(bfhip_ctx* x) : ctx(x), pv(x->c, 0), conv(x->c.conv) {}
 };
 
@@ -151,6 +154,9 @@ int32_t bfhip_pcs_prove_values(bfhip_pcs* pcs, bfhip_channel* ch, const uint32_t
         const Q31 q_coeff = pv.ch.draw_felt();
         std::vector<DSecure> quotients = pv.compute_quotients(pcs->trees, mask, points, &pf, q_coeff, nullptr).out;
         const HipProver::FriCommitted fri = pv.fri_commit(quotients, pf, {}, [] {});
+#ifdef BFHIP_TEST_HOOKS
+        pcs->fri_path = fri.path;
+#endif
         pv.grind(pf);
         pv.decommit_queries(pcs->trees, quotients, fri, pf);
         if (sampled_out_h) for (size_t i = 0; i < flat.size(); i++) q31_words(flat[i], sampled_out_h + 4 * i);
@@ -166,5 +172,21 @@ int32_t bfhip_pcs_prove_values(bfhip_pcs* pcs, bfhip_channel* ch, const uint32_t
     return 0;
     API_CATCH
 }
+
+#ifdef BFHIP_TEST_HOOKS
+// libbfhip_testhooks.so only (Makefile); not declared in include/bfhip.h. Which launch folded and which hashed each line layer of the
+// session's FRI commit phase: HipProver::FriCommitted::path (prover.h), one word per layer, the last layer included. *n = the number of
+// layers (0 before bfhip_pcs_prove_values); out may be NULL to ask for it.
+int32_t bfhip_test_pcs_fri_path(bfhip_pcs* pcs, uint32_t* out, uint32_t cap, uint32_t* n) {
+    API_TRY
+    if (!pcs || !n) throw HipError("null argument");
+    *n = (uint32_t)pcs->fri_path.size();
+    if (!out) return 0;
+    if (cap < pcs->fri_path.size()) { bfhip_set_error("capacity"); return -2; }
+    for (size_t k = 0; k < pcs->fri_path.size(); k++) out[k] = pcs->fri_path[k];
+    return 0;
+    API_CATCH
+}
+#endif
 
 }  // extern "C"

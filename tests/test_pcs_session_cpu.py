@@ -27,7 +27,7 @@ NEW_ENTRIES = ["bfhip_channel_create", "bfhip_channel_destroy", "bfhip_channel_m
                "bfhip_brainfuck_composition_at_point", "bfhip_pcs_create", "bfhip_pcs_destroy", "bfhip_pcs_commit", "bfhip_pcs_tree_columns",
                "bfhip_pcs_prove_values", "bfhip_pcs_verifier_create", "bfhip_pcs_verifier_destroy", "bfhip_pcs_verifier_commit",
                "bfhip_pcs_verifier_verify_values"]
-HOOKS = ["bfhip_test_capture_polys", "bfhip_test_captured_poly"]
+HOOKS = ["bfhip_test_capture_polys", "bfhip_test_captured_poly", "bfhip_test_pcs_fri_path"]
 
 
 def test_entries_are_declared_exported_and_bound(pkg):
