@@ -20,7 +20,7 @@ from conftest import P
 
 STWO, RFC7693, MIX_U64, FLIPPED, POSEIDON = (0, 0, 0, 0), (1, 0, 0, 0), (0, 1, 0, 0), (1, 1, 1, 0), (0, 0, 0, 1)
 OODS = (1, 0)            # a point description (log, offset): the drawn point itself
-MAX_LOG_DOMAIN = 18      # the largest LDE of the matrix: 17 + 1 and 16 + 2 (the `deep` cases)
+MAX_LOG_DOMAIN = 20      # the largest LDE of the matrix: 19 + 1 (`wide20`); the `deep` cases end at 17 + 1 and 16 + 2
 
 
 def column(log, family, seed):
@@ -170,6 +170,16 @@ def _points64():
     return trees, [flat[:15], flat[15:]], pts
 
 
+def _wide20():
+    """One tree above LDE level 18: 17 columns of 2^19 rows (tests/fft_plan_model.py: the count at which a workgroup of the LDE walks 2 columns
+    and the last one 1) among the smaller sizes of tests/test_gpu_pcs_commit_large.py, in shuffled caller order. Every third column is opened
+    at both points, the others at one of the two."""
+    cols = [19] * 17 + [5, 9, 13, (16, "edge"), (13, "max"), (9, "zero"), (16, "const")]
+    cols[1], cols[16] = (19, "max"), (19, "edge")
+    random.Random(20).shuffle(cols)
+    return [cols], [[[0, 1] if k % 3 == 0 else [1] if k % 3 == 1 else [0] for k in range(len(cols))]]
+
+
 def _mid(name, cfg=None, conv=STWO, reaches=""):
     """The mid-size case of the `conventions` and `configs` rows: largest log 11, three sizes, two points. One seed: the same columns."""
     trees = [[11, 9, 9], [7, 11, 9]]
@@ -197,6 +207,10 @@ def _cases():
     c.append(Case("deep_b1", t, _all(t), reaches="single-level launches above the subtree; first FRI layer through the leaf launch"))
     t = [[16, 6]]
     c.append(Case("deep_b2", t, _all(t), cfg=dict(log_blowup_factor=2), reaches="the same at log_blowup_factor 2"))
+    t, s = _wide20()
+    c.append(Case("wide20", t, s, points=[OODS, (19, -1)],
+                  reaches="17 columns of 2^19 rows: 2 columns per workgroup with a shorter last block in the LDE to level 20 (wide strided pass), "
+                          "sampling and quotients over a many-column class of 2^20 rows, the FRI commit from 2^19; oracle: commit 0.36 s, prove_values 0.60 s on 8 threads"))
     for n in range(1, 14):
         t = [[6] * n + [8]]
         c.append(Case("batch%02d" % n, t, _all(t), reaches="%d columns in one batch: residue %d of the three-at-a-time loop" % (n, n % 3)))

@@ -8,7 +8,7 @@ The shim itself is anchored to bytes the oracle's full prover is known to produc
 coefficient columns (bfhip_test_capture_polys, test-hooks build), go through the shim under the replay of tests/pcs_replay.py and give the
 proof's own "proof" member.
 Measured on an MI355X host with 16 cores, oracle / session per case: 1 to 10 ms / 1 to 9 ms for every case but sub17, ladder, deep_b1 and
-deep_b2 (39 to 50 ms / 2 ms) and conv_poseidon252 (0.49 s / 25 ms); the module takes 5 s, 3.6 s of which build the shim."""
+deep_b2 (39 to 50 ms / 2 ms), wide20 (0.29 s / 42 ms) and conv_poseidon252 (0.49 s / 25 ms); the module takes 5 s, 3.6 s of which build the shim."""
 import ctypes
 import json
 import time
@@ -24,7 +24,7 @@ from conftest import P
 pytestmark = pytest.mark.gpu
 
 CODE, INP = "+++>,<[>+.<-]", b"\x01"
-ANCHOR_LMR = 15      # log_max_rows 15 at log_blowup_factor 2 needs max_log_domain 15 + 2 + 1 = 18: the context of the matrix
+ANCHOR_LMR = 15      # log_max_rows 15 at log_blowup_factor 2 needs max_log_domain 15 + 2 + 1 = 18: within the context of the matrix (20)
 
 
 @pytest.fixture(scope="module")

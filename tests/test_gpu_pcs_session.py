@@ -6,7 +6,7 @@ launches of a Brainfuck proof. Everything is compared as integers and bytes:
  3. columns without any Brainfuck structure: roots against a chain of single operations (the only check of roots against them), sampled values
     against bfhip_eval_at_point, the proof against the generic verifier, which rejects a flipped queried or sampled value. The bytes of
     such proofs — quotients, FRI layers, nonce, queried values, decommitments — are held to the CPU oracle's generic prover in
-    tests/test_gpu_pcs_generic_oracle.py, over the matrix of tests/pcs_generic_cases.py (LDE levels 5 to 18, up to 302 columns, 64 points);
+    tests/test_gpu_pcs_generic_oracle.py, over the matrix of tests/pcs_generic_cases.py (LDE levels 5 to 20, up to 302 columns, 64 points);
  4. a tree whose largest column makes line layers from 2^17 down: k_fri_fold_leaf, k_fri_layer and k_fri_tail in one commit phase;
  5. what is refused, and that a destroyed session leaves the context as it was."""
 import ctypes
