@@ -451,3 +451,61 @@ impl Drop for PcsVerifier {
         unsafe { sys::bfhip_pcs_verifier_destroy(self.0) };
     }
 }
+
+// ---- constraint programs (`include/bfhip.h` "Constraint programs"): evaluate ANY AIR's constraints ------------------------------------------
+// What a `ComponentProver<HipBackend>` of an AIR the library has never seen calls: the AIR's `FrameworkEval::evaluate`, recorded once as a
+// bytecode of four u32 words {op, dst, a, b} per instruction (opcodes `sys::BFHIP_AIR_*`), runs on the constraint domain in one gfx950 kernel
+// and at the out-of-domain point on the host.
+
+/// `bfhip_air_shape`.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct AirShape { pub n_cols: u32, pub n_params: u32, pub n_constraints: u32, pub n_instr: u32, pub m_regs: u32, pub q_regs: u32, pub min_offset: i32, pub max_offset: i32 }
+
+/// A validated constraint program (`bfhip_air`). Host only to create, inspect and evaluate at a point.
+pub struct AirProgram(*mut sys::BfhipAir);
+
+impl AirProgram {
+    /// `bfhip_air_create`: a refusal names the instruction index and the rule.
+    pub fn new(code: &[u32], n_cols: u32, n_params: u32) -> Result<Self, String> {
+        let mut p = std::ptr::null_mut();
+        check(unsafe { sys::bfhip_air_create(code.as_ptr(), code.len(), n_cols, n_params, &mut p) })?;
+        Ok(AirProgram(p))
+    }
+    pub fn shape(&self) -> Result<AirShape, String> {
+        let mut o = [0u32; 8];
+        check(unsafe { sys::bfhip_air_shape(self.0, o.as_mut_ptr()) })?;
+        Ok(AirShape { n_cols: o[0], n_params: o[1], n_constraints: o[2], n_instr: o[3], m_regs: o[4], q_regs: o[5], min_offset: o[6] as i32, max_offset: o[7] as i32 })
+    }
+    /// `bfhip_air_mask`: (column, offset) by column, within a column by first use — the order of a column's samples for `PcsProver::prove_values`.
+    pub fn mask(&self) -> Result<Vec<(u32, i32)>, String> {
+        let mut n = 0u32;
+        check(unsafe { sys::bfhip_air_mask(self.0, std::ptr::null_mut(), std::ptr::null_mut(), 0, &mut n) })?;
+        let (mut cols, mut offs) = (vec![0u32; n as usize], vec![0i32; n as usize]);
+        if n > 0 { check(unsafe { sys::bfhip_air_mask(self.0, cols.as_mut_ptr(), offs.as_mut_ptr(), n, &mut n) })?; }
+        Ok(cols.into_iter().zip(offs).collect())
+    }
+    /// `bfhip_air_eval_domain`: `evaluate_constraint_quotients_on_domain` on CanonicCoset(log_size + log_expand).circle_domain(), added into `acc`.
+    /// `cols`: one device column per program column (`shifts`: its storage shift, empty = all 0); `params` / `coeffs`: one QM31 per parameter / constraint.
+    pub fn eval_domain(&self, ctx: &Context, log_size: u32, log_expand: u32, cols: &[*const u32], shifts: &[u32], params: &[Felt], coeffs: &[Felt], acc: &[*mut u32; 4]) -> Result<(), String> {
+        if !shifts.is_empty() && shifts.len() != cols.len() { return Err("one shift per column".into()); }
+        check(unsafe {
+            sys::bfhip_air_eval_domain(ctx.0, self.0, log_size, log_expand, cols.as_ptr(), if shifts.is_empty() { std::ptr::null() } else { shifts.as_ptr() },
+                                       params.as_ptr() as *const u32, params.len() as u32, coeffs.as_ptr() as *const u32, coeffs.len() as u32, acc.as_ptr())
+        })
+    }
+    /// `bfhip_air_eval_at_point`: stwo's PointEvaluator over the program; `mask_values` in `mask()` order.
+    pub fn eval_at_point(&self, log_size: u32, point: &Point, mask_values: &[Felt], params: &[Felt], coeffs: &[Felt]) -> Result<Felt, String> {
+        let mut out = [0u32; 4];
+        check(unsafe {
+            sys::bfhip_air_eval_at_point(self.0, log_size, point.as_ptr(), mask_values.as_ptr() as *const u32, mask_values.len() as u32, params.as_ptr() as *const u32,
+                                         params.len() as u32, coeffs.as_ptr() as *const u32, coeffs.len() as u32, out.as_mut_ptr())
+        })?;
+        Ok(out)
+    }
+}
+
+impl Drop for AirProgram {
+    fn drop(&mut self) {
+        unsafe { sys::bfhip_air_destroy(self.0) };
+    }
+}

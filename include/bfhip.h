@@ -608,7 +608,7 @@ int32_t bfhip_verify_brainfuck_pcs(const char* proof_json, size_t proof_len, uin
 
 /* ---- Commitment-scheme session: commit and open ANY AIR's columns on the fused PCS path ---------------------------------------------------
  * bfhip_prove_* prove the 13 components of one snapshot of the reference. An AIR that differs from it (another column, another component)
- * computes its traces and constraints with its own kernels, or with bfhip_logup_generate / bfhip_eval_constraints, and keeps everything else:
+ * computes its constraints from a constraint program (bfhip_air_*, below) or with bfhip_logup_generate / bfhip_eval_constraints, and keeps everything else:
  * the session below is stwo's CommitmentSchemeProver / CommitmentSchemeVerifier over trees of arbitrary columns opened at arbitrary points,
  * run by the same driver and the same fused launches as a Brainfuck proof (subtree / top Merkle kernels, batched sampling, one quotient launch
  * per size group, the device-stepped channel of the FRI commit phase with k_fri_fold_leaf / k_fri_layer / k_fri_tail, one gather for the
@@ -663,7 +663,7 @@ int32_t bfhip_brainfuck_composition_at_point(const uint32_t log_sizes_h[13], con
  *   and a second bfhip_pcs_create.
  * Everything else keeps working, which is what the caller's constraint sweep needs: bfhip_malloc / bfhip_free / bfhip_upload / bfhip_download /
  * bfhip_memset_zero, bfhip_interpolate, bfhip_evaluate, bfhip_is_first_coeffs, bfhip_eval_at_point, bfhip_logup_generate, bfhip_eval_constraints,
- * bfhip_accumulate, the Merkle / fold / grind / gather single operations, resident traces' getters and the profiler.
+ * bfhip_air_eval_domain, bfhip_accumulate, the Merkle / fold / grind / gather single operations, resident traces' getters and the profiler.
  * Not supported: a context in a shard group (create refuses; joining refuses while a session is open); a pool's sub-context while anything
  * is queued, running or not yet taken on the pool.
  * Launch order: the plain one only (wait, draw, copy, launch). No mailbox order, and the overlap mask (bfhip_ctx_set_overlap) is ignored.
@@ -713,6 +713,64 @@ int32_t bfhip_pcs_verifier_destroy(bfhip_pcs_verifier* v);
 int32_t bfhip_pcs_verifier_commit(bfhip_pcs_verifier* v, bfhip_channel* ch, const uint8_t root[32], const uint32_t* log_sizes_h, uint32_t n_cols);
 int32_t bfhip_pcs_verifier_verify_values(bfhip_pcs_verifier* v, bfhip_channel* ch, const uint32_t* points_h, uint32_t n_points, const uint32_t* n_samples_h,
                                          const uint32_t* point_idx_h, const char* proof_json, size_t proof_len, char* err, size_t err_cap);
+
+/* ---- Constraint programs: evaluate ANY AIR's constraints, on the GPU over the constraint domain and on the host at a point ------------------
+ * bfhip_eval_constraints runs one of 13 compiled-in kernels. stwo's `FrameworkEval::evaluate` hands a backend an expression, not a kernel; a
+ * program is that expression as data: a flat, straight-line bytecode for one component. It is evaluated two ways:
+ *   bfhip_air_eval_domain    ONE gfx950 kernel for every program, on the constraint domain: what
+ *                            `ComponentProver::evaluate_constraint_quotients_on_domain` does for a FrameworkComponent (reached from mod.rs:732);
+ *   bfhip_air_eval_at_point  the host evaluator at the out-of-domain point: stwo's PointEvaluator, the composition check of verify (mod.rs:738-797).
+ * With the session above, bfhip_pcs_* + bfhip_air_* prove and verify an AIR this library has never seen.
+ *
+ * A program is n_instr instructions of four u32 words {op, dst, a, b}. Two register files: m[] holds M31 values (one word), q[] QM31 values
+ * (four words). No branches; a register must be written before it is read; words an instruction does not use are ignored.
+ *   BFHIP_AIR_M_COL    dst, col, off   m[dst] = column `col` at the row at trace offset `off` (b is an int32, |off| <= 16)
+ *   BFHIP_AIR_M_CONST  dst, v          m[dst] = v, v < 2^31 - 1
+ *   BFHIP_AIR_M_ADD / _M_SUB / _M_MUL  dst, a, b     M31 arithmetic on m[a], m[b]
+ *   BFHIP_AIR_M_NEG    dst, a          m[dst] = -m[a]
+ *   BFHIP_AIR_Q_COL    dst, col, off   q[dst] = the secure value whose coordinates are columns col..col+3 at offset off
+ *   BFHIP_AIR_Q_PARAM  dst, i          q[dst] = params[i]: the caller's QM31 values (lookup z, alpha powers, claimed sums)
+ *   BFHIP_AIR_Q_FROM_M dst, a          q[dst] = (m[a], 0, 0, 0)
+ *   BFHIP_AIR_Q_ADD / _Q_SUB / _Q_MUL  dst, a, b     QM31 arithmetic on q[a], q[b]
+ *   BFHIP_AIR_Q_MULM   dst, a, b       q[dst] = q[a] * m[b]
+ *   BFHIP_AIR_C_BASE   -, a            the next constraint is m[a]     } constraints are numbered in program order
+ *   BFHIP_AIR_C_EXT    -, a            the next constraint is q[a]     }
+ * "The row at offset off" is the point of this row plus off * CanonicCoset(log_size).step(), on whichever domain is evaluated; at a point it
+ * is bfhip_circle_point_offset. IsFirst is just a column the caller passes.
+ * The mask of a program: the distinct (col, off) pairs it reads, ordered by column and, within a column, by first use; a Q_COL contributes its
+ * four columns at the same offset. This is the order in which a caller lists a column's samples for bfhip_pcs_prove_values, and the order of
+ * mask_values_h below.
+ * Caps (a program beyond one is refused): 96 m registers, 24 q registers, 4096 instructions, 256 columns, 64 parameters, 64 constraints.
+ *
+ * bfhip_air_create (host only): validates everything — opcode, register range, read before write, col (and col + 3) within n_cols, parameter
+ *   index, offset range, v < p, at least one constraint, the caps. Each refusal is -1 and names the instruction index and the rule:
+ *   "bfhip_air_create: instruction <i>: <rule>" (rules about the program as a whole name the instruction count).
+ * bfhip_air_shape: out = {columns, parameters, constraints, instructions, m registers used, q registers used, minimum offset, maximum offset
+ *   (both int32 stored in a u32)}.
+ * bfhip_air_mask: the mask in the order above; *n = its length. -2 ("capacity") when cap < *n; all of cols_out, offs_out NULL with cap 0: size query.
+ * bfhip_air_eval_domain: column k of cols_h holds 2^(log_size + log_expand) cells on CanonicCoset(log_size + log_expand).circle_domain(),
+ *   bit-reversed; with col_shifts_h[k] = s (0 or >= 2, as elsewhere; NULL = all 0) it holds 2^(log_size + log_expand - s) cells and is read at
+ *   row >> s. A shifted column that the program reads at a non-zero offset is refused. For every row
+ *       acc[row] += (sum_j coeffs[j] * C_j(row)) * 1 / coset_vanishing(CanonicCoset(log_size).coset, point(row)).
+ *   params_h = 4 * n_params words, coeffs_h = 4 * n_coeffs words; the counts must be the program's. 1 <= log_expand <= 3, log_size >= 1 and
+ *   log_size + log_expand <= max_log_domain. With log_expand = 1 this is bfhip_eval_constraints' contract, to the bit. Whole domains only. A
+ *   context in a shard group is refused. Works while a session is open, like bfhip_eval_constraints.
+ * bfhip_air_eval_at_point (host only): the same program over QM31. mask_values_h = n_mask values of 4 words in mask order; a Q_COL combines
+ *   its four sampled coordinates as SecureField::from_partial_evals does; the result is multiplied by 1 / coset_vanishing at the point. */
+enum { BFHIP_AIR_M_COL = 0, BFHIP_AIR_M_CONST = 1, BFHIP_AIR_M_ADD = 2, BFHIP_AIR_M_SUB = 3, BFHIP_AIR_M_MUL = 4, BFHIP_AIR_M_NEG = 5, BFHIP_AIR_Q_COL = 6,
+       BFHIP_AIR_Q_PARAM = 7, BFHIP_AIR_Q_FROM_M = 8, BFHIP_AIR_Q_ADD = 9, BFHIP_AIR_Q_SUB = 10, BFHIP_AIR_Q_MUL = 11, BFHIP_AIR_Q_MULM = 12, BFHIP_AIR_C_BASE = 13,
+       BFHIP_AIR_C_EXT = 14 };
+enum { BFHIP_AIR_MAX_M_REGS = 96, BFHIP_AIR_MAX_Q_REGS = 24, BFHIP_AIR_MAX_INSTRUCTIONS = 4096, BFHIP_AIR_MAX_COLUMNS = 256, BFHIP_AIR_MAX_PARAMS = 64,
+       BFHIP_AIR_MAX_CONSTRAINTS = 64, BFHIP_AIR_MAX_OFFSET = 16 };
+typedef struct bfhip_air bfhip_air;
+int32_t bfhip_air_create(const uint32_t* code, size_t n_words, uint32_t n_cols, uint32_t n_params, bfhip_air** out);
+int32_t bfhip_air_destroy(bfhip_air* air);
+int32_t bfhip_air_shape(const bfhip_air* air, uint32_t out[8]);
+int32_t bfhip_air_mask(const bfhip_air* air, uint32_t* cols_out, int32_t* offs_out, uint32_t cap, uint32_t* n);
+int32_t bfhip_air_eval_domain(bfhip_ctx* ctx, const bfhip_air* air, uint32_t log_size, uint32_t log_expand, const uint32_t* const* cols_h, const uint32_t* col_shifts_h,
+                              const uint32_t* params_h, uint32_t n_params, const uint32_t* coeffs_h, uint32_t n_coeffs, uint32_t* const acc_d[4]);
+int32_t bfhip_air_eval_at_point(const bfhip_air* air, uint32_t log_size, const uint32_t point_h[8], const uint32_t* mask_values_h, uint32_t n_mask,
+                                const uint32_t* params_h, uint32_t n_params, const uint32_t* coeffs_h, uint32_t n_coeffs, uint32_t out_h[4]);
 
 /* Host-only pieces of the drop-in (usable without a GPU): the Brainfuck compiler (crates/brainfuck_vm/src/compiler.rs:17-37), the VM
  * (crates/brainfuck_vm/src/machine.rs:141-238; trace rows are 7 u32: clk, ip, ci, ni, mp, mv, mvi) and the 13 table builders

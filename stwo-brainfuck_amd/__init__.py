@@ -620,6 +620,22 @@ class Context:
                                             None if inter_shifts is None else self._u32s(inter_shifts), self._u32s(lookup24), self._u32s(claimed4),
                                             self._u32s(coeffs), self._ptr_array(acc_ptrs)))
 
+    def air_eval_domain(self, program, log_size, log_expand, col_ptrs, params, coeffs, acc_ptrs, col_shifts=None):
+        """bfhip_air_eval_domain: the constraints of an AirProgram on CanonicCoset(log_size + log_expand).circle_domain(), each times its
+        coefficient, the sum times 1 / vanishing, added into the 4 coordinate columns acc_ptrs. col_ptrs: one device column per program column
+        (2^(log_size + log_expand - shift) cells); params / coeffs: QM31 values (4 words each), one per parameter / constraint."""
+        params, coeffs = [list(q) for q in params], [list(q) for q in coeffs]
+        if any(len(q) != 4 for q in params + coeffs):
+            raise ValueError("a parameter or coefficient is 4 words")
+        if len(col_ptrs) != program.shape["n_cols"] or (col_shifts is not None and len(col_shifts) != len(col_ptrs)):
+            raise ValueError("one column pointer (and shift) per program column")
+        if len(acc_ptrs) != 4:
+            raise ValueError("the accumulator is 4 coordinate columns")
+        _check(lib().bfhip_air_eval_domain(self._h, program._h, int(log_size), int(log_expand), self._ptr_array(col_ptrs) if col_ptrs else None,
+                                           None if col_shifts is None or not col_ptrs else self._u32s(col_shifts),
+                                           self._u32s([w for q in params for w in q]) if params else None, len(params),
+                                           self._u32s([w for q in coeffs for w in q]) if coeffs else None, len(coeffs), self._ptr_array(acc_ptrs)))
+
     def check_constraints(self, component, log_size, main_row_ptrs, logup_col_ptrs, lookup24, claimed4):
         """bfhip_check_constraints: one component's AIR asserted on its trace domain (stwo's assert_constraints). main_row_ptrs: row-granular
         main columns; logup_col_ptrs: what logup_generate wrote (the last four full size). Returns CheckReport.as_dict(); violations are
@@ -1236,3 +1252,316 @@ class PcsVerifier:
         if rc < 0:
             raise BfhipError(lib().bfhip_last_error().decode())
         return rc == 0, err.value.decode()
+
+
+# ---- constraint programs (include/bfhip.h "Constraint programs") ------------------------------------------------------------------------
+AIR_OPS = ("M_COL", "M_CONST", "M_ADD", "M_SUB", "M_MUL", "M_NEG", "Q_COL", "Q_PARAM", "Q_FROM_M", "Q_ADD", "Q_SUB", "Q_MUL", "Q_MULM", "C_BASE", "C_EXT")
+(AIR_M_COL, AIR_M_CONST, AIR_M_ADD, AIR_M_SUB, AIR_M_MUL, AIR_M_NEG, AIR_Q_COL, AIR_Q_PARAM, AIR_Q_FROM_M, AIR_Q_ADD, AIR_Q_SUB, AIR_Q_MUL, AIR_Q_MULM,
+ AIR_C_BASE, AIR_C_EXT) = range(15)
+AIR_MAX_M_REGS, AIR_MAX_Q_REGS, AIR_MAX_INSTRUCTIONS, AIR_MAX_COLUMNS, AIR_MAX_PARAMS, AIR_MAX_CONSTRAINTS, AIR_MAX_OFFSET = 96, 24, 4096, 256, 64, 64, 16
+
+
+class AirProgram:
+    """bfhip_air: a validated constraint program. code = the bytecode, four u32 words {op, dst, a, b} per instruction (what bindings pass;
+    AirBuilder writes it from expressions). Host only: creating, shape, mask and eval_at_point need no GPU; Context.air_eval_domain runs it
+    on the constraint domain. A refused program raises BfhipError naming the instruction index and the rule."""
+
+    def __init__(self, code, n_cols, n_params):
+        self.code = [int(w) & 0xFFFFFFFF for w in code]
+        self._h = ctypes.c_void_p()
+        arr = (ctypes.c_uint32 * max(1, len(self.code)))(*self.code)
+        _check(lib().bfhip_air_create(arr, ctypes.c_size_t(len(self.code)), int(n_cols), int(n_params), ctypes.byref(self._h)))
+        out = (ctypes.c_uint32 * 8)()
+        _check(lib().bfhip_air_shape(self._h, out))
+        signed = lambda v: v - (1 << 32) if v >= 1 << 31 else v
+        self.shape = {"n_cols": out[0], "n_params": out[1], "n_constraints": out[2], "n_instr": out[3], "m_regs": out[4], "q_regs": out[5],
+                      "min_offset": signed(out[6]), "max_offset": signed(out[7])}
+
+    def close(self):
+        if self._h:
+            lib().bfhip_air_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def mask(self):
+        """bfhip_air_mask: [(column, offset)] — by column, within a column by first use. The order of a column's samples for
+        PcsSession.prove_values and of eval_at_point's mask values."""
+        n = ctypes.c_uint32()
+        _check(lib().bfhip_air_mask(self._h, None, None, 0, ctypes.byref(n)))
+        cols, offs = (ctypes.c_uint32 * max(1, n.value))(), (ctypes.c_int32 * max(1, n.value))()
+        _check(lib().bfhip_air_mask(self._h, cols, offs, n.value, ctypes.byref(n)))
+        return [(int(cols[i]), int(offs[i])) for i in range(n.value)]
+
+    def eval_at_point(self, log_size, point8, mask_values, params, coeffs):
+        """bfhip_air_eval_at_point: (sum_j coeffs[j] C_j) / coset_vanishing at a point, from the sampled mask values (QM31 each, mask order)."""
+        flat = lambda qs: Context._u32s([w for q in qs for w in q]) if len(qs) else None
+        for qs in (mask_values, params, coeffs):
+            if any(len(q) != 4 for q in qs):
+                raise ValueError("a QM31 value is 4 words")
+        out = (ctypes.c_uint32 * 4)()
+        _check(lib().bfhip_air_eval_at_point(self._h, int(log_size), Context._u32s(point8), flat(mask_values), len(mask_values), flat(params), len(params),
+                                             flat(coeffs), len(coeffs), out))
+        return [int(v) for v in out]
+
+
+class AirExpr:
+    """A value of an AirBuilder: kind 'm' (M31, a base-field column expression) or 'q' (QM31). Operators + - * and unary -; a Python int
+    stands for const(int). m op q promotes the m side (Q_FROM_M), except a product, which is Q_MULM."""
+    __slots__ = ("builder", "id", "kind")
+
+    def __init__(self, builder, vid, kind):
+        self.builder, self.id, self.kind = builder, vid, kind
+
+    def __add__(self, other): return self.builder._binary("add", self, other)
+    def __radd__(self, other): return self.builder._binary("add", other, self)
+    def __sub__(self, other): return self.builder._binary("sub", self, other)
+    def __rsub__(self, other): return self.builder._binary("sub", other, self)
+    def __mul__(self, other): return self.builder._binary("mul", self, other)
+    def __rmul__(self, other): return self.builder._binary("mul", other, self)
+    def __neg__(self): return self.builder._negate(self)
+
+
+class AirBuilder:
+    """Writes a constraint program from expressions — what a user writes; the bytecode is what bindings pass.
+        b = AirBuilder(); a, x = b.col(0), b.col(1); b.constraint(a * a - x); prog = b.program()
+    col(i, off) / secure_col(i, off) (coordinates in columns i..i+3) / param(i) / const(v) give values; every value is computed once, in
+    the order it was created (so the order of first use of a column's offsets — the mask order — is the order of the col() calls that are
+    used); other values no constraint depends on are dropped, but a column read stays (like stwo's next_trace_mask, it is part of the mask
+    whether or not a constraint uses it); a register is reused after its value's last use."""
+
+    def __init__(self):
+        self._ops = []        # [op, kind of the result or None, sources (value ids), immediates]
+        self._memo = {}
+
+    def _emit(self, op, kind, srcs=(), imm=(), key=None):
+        if key is not None and key in self._memo:
+            return self._memo[key]
+        self._ops.append((op, kind, tuple(srcs), tuple(imm)))
+        e = AirExpr(self, len(self._ops) - 1, kind) if kind else None
+        if key is not None:
+            self._memo[key] = e
+        return e
+
+    def col(self, i, off=0):
+        return self._emit(AIR_M_COL, "m", imm=(int(i), int(off)), key=("col", int(i), int(off)))
+
+    def secure_col(self, i, off=0):
+        return self._emit(AIR_Q_COL, "q", imm=(int(i), int(off)), key=("qcol", int(i), int(off)))
+
+    def param(self, i):
+        return self._emit(AIR_Q_PARAM, "q", imm=(int(i),), key=("param", int(i)))
+
+    def const(self, v):
+        return self._emit(AIR_M_CONST, "m", imm=(int(v) % P,), key=("const", int(v) % P))
+
+    def _value(self, x):
+        if isinstance(x, AirExpr):
+            if x.builder is not self:
+                raise ValueError("a value of another AirBuilder")
+            return x
+        if isinstance(x, (int, np.integer)):
+            return self.const(int(x))
+        raise TypeError("an AirBuilder value or an int, got %r" % (x,))
+
+    def _to_q(self, x):
+        return x if x.kind == "q" else self._emit(AIR_Q_FROM_M, "q", (x.id,), key=("from_m", x.id))
+
+    def _binary(self, what, x, y):
+        x, y = self._value(x), self._value(y)
+        if x.kind == "m" and y.kind == "m":
+            return self._emit({"add": AIR_M_ADD, "sub": AIR_M_SUB, "mul": AIR_M_MUL}[what], "m", (x.id, y.id))
+        if what == "mul" and x.kind != y.kind:
+            qv, mv = (x, y) if x.kind == "q" else (y, x)
+            return self._emit(AIR_Q_MULM, "q", (qv.id, mv.id))
+        return self._emit({"add": AIR_Q_ADD, "sub": AIR_Q_SUB, "mul": AIR_Q_MUL}[what], "q", (self._to_q(x).id, self._to_q(y).id))
+
+    def _negate(self, x):
+        if x.kind == "m":
+            return self._emit(AIR_M_NEG, "m", (x.id,))
+        return self._emit(AIR_Q_MULM, "q", (x.id, self.const(P - 1).id))
+
+    def constraint(self, expr):
+        expr = self._value(expr)
+        self._emit(AIR_C_BASE if expr.kind == "m" else AIR_C_EXT, None, (expr.id,))
+
+    def code(self):
+        """The bytecode (a flat list of u32 words). Raises ValueError if the program needs more registers than the caps."""
+        import heapq
+        ops = self._ops
+        live = [kind is None or op in (AIR_M_COL, AIR_Q_COL) for op, kind, _, _ in ops]
+        for i in range(len(ops) - 1, -1, -1):
+            if live[i]:
+                for s in ops[i][2]:
+                    live[s] = True
+        last_use = {}
+        for i, (_, _, srcs, _) in enumerate(ops):
+            if live[i]:
+                for s in srcs:
+                    last_use[s] = i
+        free = {"m": list(range(AIR_MAX_M_REGS + 1)), "q": list(range(AIR_MAX_Q_REGS + 1))}
+        reg, words = {}, []
+        for i, (op, kind, srcs, imm) in enumerate(ops):
+            if not live[i]:
+                continue
+            regs = [reg[s] for s in srcs]
+            for s in set(srcs):
+                if last_use[s] == i:
+                    heapq.heappush(free[ops[s][1]], reg[s])
+            dst = 0
+            if kind:
+                dst = reg[i] = heapq.heappop(free[kind])
+                if dst >= (AIR_MAX_M_REGS if kind == "m" else AIR_MAX_Q_REGS):
+                    raise ValueError("the program needs more than %d %s registers" % ((AIR_MAX_M_REGS, "m") if kind == "m" else (AIR_MAX_Q_REGS, "q")))
+                if i not in last_use:         # a column read no constraint uses: it stays for the mask, its register is free at once
+                    heapq.heappush(free[kind], dst)
+            if op in (AIR_M_COL, AIR_Q_COL):
+                words += [op, dst, imm[0], imm[1] & 0xFFFFFFFF]
+            elif op in (AIR_M_CONST, AIR_Q_PARAM):
+                words += [op, dst, imm[0], 0]
+            elif op in (AIR_C_BASE, AIR_C_EXT):
+                words += [op, 0, regs[0], 0]
+            else:
+                words += [op, dst, regs[0], regs[1] if len(regs) > 1 else 0]
+        return words
+
+    def program(self, n_cols=None, n_params=None):
+        """AirProgram of the bytecode; n_cols / n_params default to one more than the highest column / parameter any col() / param() named."""
+        cols = [imm[0] + (4 if op == AIR_Q_COL else 1) for op, _, _, imm in self._ops if op in (AIR_M_COL, AIR_Q_COL)]
+        pars = [imm[0] + 1 for op, _, _, imm in self._ops if op == AIR_Q_PARAM]
+        return AirProgram(self.code(), max(cols, default=0) if n_cols is None else n_cols, max(pars, default=0) if n_params is None else n_params)
+
+
+def _q_mul(x, y):
+    """QM31 product of two 4-word values: (a + b u)(c + d u), u^2 = 2 + i, over CM31 = M31[i]."""
+    cm = lambda p, q: ((p[0] * q[0] - p[1] * q[1]) % P, (p[0] * q[1] + p[1] * q[0]) % P)
+    a, b, c, d = (x[0], x[1]), (x[2], x[3]), (y[0], y[1]), (y[2], y[3])
+    bd, ac, ad, bc = cm(b, d), cm(a, c), cm(a, d), cm(b, c)
+    e = cm(bd, (2, 1))
+    return [(ac[0] + e[0]) % P, (ac[1] + e[1]) % P, (ad[0] + bc[0]) % P, (ad[1] + bc[1]) % P]
+
+
+BRAINFUCK_AIR_N_PARAMS = 25
+_BF_N_MAIN = (8, 8, 4, 9, 13, 13, 11, 11, 11, 11, 11, 11, 7)
+
+
+def brainfuck_air_params(lookup24, claimed4):
+    """The 25 parameters of a brainfuck_air_program: for each of the Memory, Instruction and Processor relations z, alpha^0 .. alpha^6
+    (8 values), then the component's claimed sum. lookup24: (z, alpha) of the three relations, as for logup_generate."""
+    out = []
+    for r in range(3):
+        z, alpha = [int(v) for v in lookup24[8 * r: 8 * r + 4]], [int(v) for v in lookup24[8 * r + 4: 8 * r + 8]]
+        out.append(z)
+        cur = [1, 0, 0, 0]
+        for _ in range(7):
+            out.append(cur)
+            cur = _q_mul(cur, alpha)
+    return out + [[int(v) for v in claimed4]]
+
+
+def brainfuck_air_program(component, logup_mask_order=0):
+    """The constraints of component 0..12 of the Brainfuck AIR as a program — restated from csrc/air.h (the `FrameworkEval::evaluate` bodies
+    of components/**/component.rs), logUp constraints included; the worked example of INTEGRATION.md section 2e.
+    Returns (AirProgram, parameter names, column names). Columns: the n_main main-trace columns, then 4 coordinate columns per logUp column,
+    then IsFirst — n_main + 4 n_logup + 1. Parameters: brainfuck_air_params. Constraints in bfhip_eval_constraints' order. The last logUp
+    column is read at offsets [0, -1], or [-1, 0] under logup_mask_order = LOGUP_MASK_PREV_CUR."""
+    if not 0 <= component < 13:
+        raise ValueError("component 0..12")
+    b = AirBuilder()
+    n_main, n_logup = _BF_N_MAIN[component], 3 if component == 3 else 1
+    t = [b.col(j) for j in range(n_main)]
+    first_col = n_main + 4 * n_logup
+    is_first, one = b.col(first_col), b.const(1)
+    REL = {"memory": 0, "instruction": 1, "processor": 2}
+    total = b.param(24)
+
+    def combine(rel, values):
+        base = 8 * REL[rel]
+        acc = None
+        for i, v in enumerate(values):
+            term = b.param(base + 1 + i) * v
+            acc = term if acc is None else acc + term
+        return acc - b.param(base)
+
+    state = {"col": 0, "prev": None}
+
+    def logup_mid(num, den):
+        cur = b.secure_col(n_main + 4 * state["col"])
+        diff = cur if state["prev"] is None else cur - state["prev"]
+        state["col"], state["prev"] = state["col"] + 1, cur
+        b.constraint(diff * den - b._to_q(num))
+
+    def logup_last(num, den):
+        at = n_main + 4 * state["col"]
+        if logup_mask_order == LOGUP_MASK_PREV_CUR:
+            prev_row, cur = b.secure_col(at, -1), b.secure_col(at)
+        else:
+            cur, prev_row = b.secure_col(at), b.secure_col(at, -1)
+        diff = cur - (prev_row - total * is_first)
+        if state["prev"] is not None:
+            diff = diff - state["prev"]
+        b.constraint(diff * den - b._to_q(num))
+
+    c = b.constraint
+    if component == 0:        # memory/component.rs:62-137
+        clk, mp, mv, d, n_clk, n_mp, n_mv, n_d = t
+        c(is_first * clk); c(is_first * mp); c(is_first * mv); c(is_first * d)
+        c(d * (d - one)); c(n_d * (n_d - one))
+        c((n_mp - mp) * (n_mp - mp - one)); c((n_mp - mp - one) * (n_clk - clk - one)); c((n_mp - mp) * n_mv)
+        c(d * (n_mp - mp)); c(d * (n_mv - mv))
+        logup_last(d - one, combine("memory", (clk, mp, mv)))
+    elif component == 1:      # instruction/component.rs:65-142
+        ip, ci, ni, d, n_ip, n_ci, n_ni, n_d = t
+        c(is_first * ip); c(d * (d - one)); c(n_d * (n_d - one)); c(d * ci); c(d * ni); c(n_d * n_ci); c(n_d * n_ni)
+        c((n_ip - ip) * (n_ip - ip - one)); c((n_ip - ip - one) * (n_ci - ci)); c((n_ip - ip - one) * (n_ni - ni))
+        logup_last(d - one, combine("instruction", (ip, ci, ni)))
+    elif component == 2:      # program/component.rs:60-104
+        ip, ci, ni, d = t
+        c(is_first * ip); c(d * (d - one)); c(d * ci); c(d * ni)
+        logup_last(one - d, combine("instruction", (ip, ci, ni)))
+    elif component == 3:      # processor/component.rs:79-153 — three relation entries: Processor, Instruction, Memory
+        clk, ip, ci, ni, mp, mv, mvi, d, n_clk = t
+        c(is_first * clk); c(is_first * ip); c(is_first * mp); c(is_first * mv)
+        c(mv * (mv * mvi - one)); c(mvi * (mv * mvi - one)); c(n_clk - clk - one)
+        num = one - d
+        den_p, den_i, den_m = combine("processor", (clk, ip, ci, ni, mp, mv, mvi)), combine("instruction", (ip, ci, ni)), combine("memory", (clk, mp, mv))
+        logup_mid(num, den_p); logup_mid(num, den_i); logup_last(num, den_m)
+    elif component in (4, 5):   # jump/jump_if_not_zero_component.rs:61-130, jump/jump_if_zero_component.rs:61-130
+        clk, ip, ci, ni, mp, mv, mvi, n_clk, n_ip, n_mp, n_mv, d, is_mv_zero = t
+        two = b.const(2)
+        c(ci * (ci - b.const(ord("[") if component == 5 else ord("]"))))
+        c(n_clk - clk - one); c(d * (d - one)); c(d * mv); c(d * ci)
+        if component == 5:
+            c((d - one) * (mv * (n_ip - ip - two) + is_mv_zero * (n_ip - (ni + one))))
+        else:
+            c((d - one) * (is_mv_zero * (n_ip - ip - two) + mv * (n_ip - ni)))
+        c(n_mp - mp); c(n_mv - mv)
+        logup_last(d - one, combine("processor", (clk, ip, ci, ni, mp, mv, mvi)))
+    elif component == 12:     # end_of_execution/component.rs:61-90
+        clk, ip, ci, ni, mp, mv, mvi = t
+        c(ci)
+        logup_last(b.const(P - 1), combine("processor", (clk, ip, ci, ni, mp, mv, mvi)))
+    else:                     # processor/instructions/{input,left,minus,output,plus,right}_component.rs:62-122
+        clk, ip, ci, ni, mp, mv, mvi, d, n_ip, n_mp, n_mv = t
+        opcode = {6: ",", 7: "<", 8: "-", 9: ".", 10: "+", 11: ">"}[component]
+        c(ci * (ci - b.const(ord(opcode)))); c(d * (d - one)); c(d * mv); c(d * ci); c((one - d) * (n_ip - ip - one))
+        if opcode == "+":
+            c(n_mp - mp); c((one - d) * (n_mv - mv - one))
+        elif opcode == "-":
+            c(n_mp - mp); c((one - d) * (n_mv - mv + one))
+        elif opcode == "<":
+            c((one - d) * (n_mp - mp + one))
+        elif opcode == ">":
+            c((one - d) * (n_mp - mp - one))
+        elif opcode == ",":
+            c(n_mp - mp)
+        else:
+            c(n_mp - mp); c(n_mv - mv)
+        logup_last(d - one, combine("processor", (clk, ip, ci, ni, mp, mv, mvi)))
+    names = ["%s.%s" % (r, p) for r in ("memory", "instruction", "processor") for p in ["z"] + ["alpha^%d" % i for i in range(7)]] + ["claimed_sum"]
+    columns = ["main%d" % j for j in range(n_main)] + ["logup%d.%d" % (k, w) for k in range(n_logup) for w in range(4)] + ["is_first"]
+    return b.program(n_cols=n_main + 4 * n_logup + 1, n_params=BRAINFUCK_AIR_N_PARAMS), names, columns

@@ -1,0 +1,39 @@
+// The constraint program (include/bfhip.h "Constraint programs"): a flat, straight-line bytecode that describes one component's constraints,
+// as air_program_host.hip (validator, mask, out-of-domain evaluator; host only) and air_program.hip (the gfx950 interpreter kernel on the
+// constraint domain) share it. What stwo's `FrameworkEval::evaluate` hands a backend is an expression, not a kernel: this is that expression
+// for a backend whose kernels are compiled ahead of time. Internal to the library.
+#pragma once
+#include "m31.h"
+#include <cstdint>
+#include <vector>
+
+namespace bf {
+
+// {op, dst, a, b}: four u32 words per instruction. The numbering is that of include/bfhip.h (BFHIP_AIR_*).
+enum AirOp : u32 {
+    AIR_M_COL = 0, AIR_M_CONST, AIR_M_ADD, AIR_M_SUB, AIR_M_MUL, AIR_M_NEG,
+    AIR_Q_COL, AIR_Q_PARAM, AIR_Q_FROM_M, AIR_Q_ADD, AIR_Q_SUB, AIR_Q_MUL, AIR_Q_MULM,
+    AIR_C_BASE, AIR_C_EXT, AIR_N_OPS
+};
+// Caps (include/bfhip.h states them). The register file of the kernel is LDS, [register][lane] over the 64 lanes of a one-wave workgroup:
+// (96 + 4 x 24) words x 64 lanes x 4 bytes = 48 KiB at the caps, below the 64 KiB a workgroup gets without asking.
+constexpr u32 AIR_MAX_M_REGS = 96, AIR_MAX_Q_REGS = 24, AIR_MAX_INSTRUCTIONS = 4096, AIR_MAX_COLUMNS = 256, AIR_MAX_PARAMS = 64, AIR_MAX_CONSTRAINTS = 64;
+constexpr int AIR_MAX_OFFSET = 16;
+
+}  // namespace bf
+
+// A validated program. Everything the evaluators index with was checked by bfhip_air_create: they do no bounds checks of their own.
+struct bfhip_air {
+    std::vector<uint32_t> code;              // 4 words per instruction
+    uint32_t n_cols = 0, n_params = 0, n_constraints = 0, n_instr = 0, n_m = 0, n_q = 0;
+    int32_t min_off = 0, max_off = 0;
+    std::vector<uint32_t> mask_cols;         // the mask: by column, within a column by first use
+    std::vector<int32_t> mask_offs;
+    std::vector<uint32_t> mask_first;        // n_cols + 1: the mask entries of column c are [mask_first[c], mask_first[c + 1])
+    std::vector<uint8_t> col_read_shifted;   // per column: 1 if some instruction reads it at a non-zero offset
+    // index into the mask of (col, off); the pair is in the mask
+    uint32_t mask_index(uint32_t col, int32_t off) const {
+        for (uint32_t i = mask_first[col]; i < mask_first[col + 1]; i++) if (mask_offs[i] == off) return i;
+        return mask_first[col];
+    }
+};

@@ -1,0 +1,193 @@
+// The constraint program on the constraint domain (include/bfhip.h "Constraint programs": bfhip_air_eval_domain) — what
+// `ComponentProver::evaluate_constraint_quotients_on_domain` does for any `FrameworkEval` (reached from prover::prove, mod.rs:732), as ONE
+// gfx950 kernel that interprets the program instead of one compiled kernel per AIR (air.hip: k_constraints<COMP>).
+//
+// One lane per row of CanonicCoset(log_size + log_expand).circle_domain(), one wave per workgroup. The instruction stream, the column
+// descriptors, the parameters and the coefficients are the same for every lane: they live in HBM and are fetched through scalar loads
+// (address space 4, like ConstraintArgs), and the opcode dispatch is a scalar branch. The two register files would be runtime-indexed private
+// arrays, which the compiler puts in scratch; they live in LDS instead, laid out [register][lane] so that the 64 lanes of an access hit 64
+// consecutive banks, and sized at launch from the registers the program uses (a small program keeps its occupancy). No barrier: a lane only
+// ever touches its own slot of each register.
+#include "api_guard.h"
+#include "air_program.h"
+#include "host/circle.h"
+#include "../../include/bfhip.h"
+#include <cstddef>
+
+namespace bf {
+
+constexpr u32 AIR_LANES = 64;
+
+// Staged in HBM. Addresses are kept as integers: read from address space 4 they arrive in SGPRs and are cast to global pointers.
+struct AirLaunch {
+    u64 code;            // bf_u32x4[n_instr]
+    u64 cols;            // bf_u32x4[n_cols]: {pointer low, pointer high, shift, 0}
+    u64 params, coeffs;  // bf_u32x4[n_params], bf_u32x4[n_constraints]
+    u64 acc[4];
+    u32 n_instr, n_m, log_size, log_expand;
+    u32 denom_inv[8];    // 1 / coset_vanishing, indexed by row >> log_size
+};
+
+// Storage index of the row at trace offset `off` from `row` on the 2^log_expand blowup (prev_lde_row of air.hip is off = -1, log_expand = 1):
+// a trace step is 2^(log_expand - 1) steps of the half coset; in circle-domain order the first half moves with the offset, the conjugate
+// half against it (-P + T = -(P - T)), each cyclically.
+__device__ __forceinline__ u32 air_offset_row(u32 row, int off, u32 log_size, u32 log_expand) {
+    const u32 el = log_size + log_expand, half = 1u << (el - 1);
+    const u32 d = bit_rev(row, el);
+    const u32 step = (u32)off * (1u << (log_expand - 1));      // modulo 2^32, of which half is a divisor
+    const u32 pd = d < half ? ((d + step) & (half - 1)) : (((d - half - step) & (half - 1)) + half);
+    return bit_rev(pd, el);
+}
+
+__device__ __forceinline__ u32 air_ld_cell(const bf_u32x4 col, u32 idx) {
+    const unsigned long long base = ((unsigned long long)col.y << 32) | col.x;
+    return *(g_cu32p)((const BF_GLOBAL char*)base + (idx << 2));
+}
+
+__global__ void __launch_bounds__(AIR_LANES) k_air_program(const AirLaunch* __restrict__ ap) {
+    extern __shared__ u32 s_regs[];
+    const BF_CONSTANT AirLaunch* a = (const BF_CONSTANT AirLaunch*)(unsigned long long)ap;
+    const u32 log_size = a->log_size, log_expand = a->log_expand;
+    const u32 row = blockIdx.x * AIR_LANES + threadIdx.x;
+    if (row >= (1u << (log_size + log_expand))) return;
+    u32* const m = s_regs + threadIdx.x;                           // m[r] = m[r * AIR_LANES]
+    u32* const q = s_regs + a->n_m * AIR_LANES + threadIdx.x;      // coordinate k of q[r] = q[(4 r + k) * AIR_LANES]
+    const BF_CONSTANT bf_u32x4* code = (const BF_CONSTANT bf_u32x4*)a->code;
+    const BF_CONSTANT bf_u32x4* cols = (const BF_CONSTANT bf_u32x4*)a->cols;
+    const BF_CONSTANT bf_u32x4* params = (const BF_CONSTANT bf_u32x4*)a->params;
+    const BF_CONSTANT bf_u32x4* coeffs = (const BF_CONSTANT bf_u32x4*)a->coeffs;
+    // sum_j coeff_j * c_j as DomainEval::constraint(Fm) of air.hip keeps it: four 64-bit dot products with lazy reduction for the base-field
+    // constraints (four products of canonical values on top of a folded accumulator stay below 2^64), a QM31 sum for the others
+    u64 acc[4] = {0, 0, 0, 0};
+    u32 pending = 0, ci = 0;
+    Q31 ext = q_zero();
+    const u32 n_instr = a->n_instr;
+#pragma unroll 1
+    for (u32 pc = 0; pc < n_instr; pc++) {
+        const bf_u32x4 ins = code[pc];
+        const u32 dst = ins.y * AIR_LANES, ra = ins.z * AIR_LANES, rb = ins.w * AIR_LANES;
+        switch (ins.x) {
+            case AIR_M_COL: {
+                const bf_u32x4 col = cols[ins.z];
+                const int off = (int)ins.w;
+                m[dst] = air_ld_cell(col, off ? air_offset_row(row, off, log_size, log_expand) : row >> col.z);
+                break;
+            }
+            case AIR_M_CONST: m[dst] = ins.z; break;
+            case AIR_M_ADD: m[dst] = m_add(m[ra], m[rb]); break;
+            case AIR_M_SUB: m[dst] = m_sub(m[ra], m[rb]); break;
+            case AIR_M_MUL: m[dst] = m_mul(m[ra], m[rb]); break;
+            case AIR_M_NEG: m[dst] = m_neg(m[ra]); break;
+            case AIR_Q_COL: {
+                const int off = (int)ins.w;
+                const u32 orow = off ? air_offset_row(row, off, log_size, log_expand) : row;
+#pragma unroll
+                for (u32 k = 0; k < 4; k++) {
+                    const bf_u32x4 col = cols[ins.z + k];
+                    q[4 * dst + k * AIR_LANES] = air_ld_cell(col, off ? orow : orow >> col.z);
+                }
+                break;
+            }
+            case AIR_Q_PARAM: {
+                const bf_u32x4 v = params[ins.z];
+                q[4 * dst] = v.x; q[4 * dst + AIR_LANES] = v.y; q[4 * dst + 2 * AIR_LANES] = v.z; q[4 * dst + 3 * AIR_LANES] = v.w;
+                break;
+            }
+            case AIR_Q_FROM_M: q[4 * dst] = m[ra]; q[4 * dst + AIR_LANES] = 0; q[4 * dst + 2 * AIR_LANES] = 0; q[4 * dst + 3 * AIR_LANES] = 0; break;
+            case AIR_Q_ADD: case AIR_Q_SUB: case AIR_Q_MUL: {
+                const Q31 x = q_make(q[4 * ra], q[4 * ra + AIR_LANES], q[4 * ra + 2 * AIR_LANES], q[4 * ra + 3 * AIR_LANES]);
+                const Q31 y = q_make(q[4 * rb], q[4 * rb + AIR_LANES], q[4 * rb + 2 * AIR_LANES], q[4 * rb + 3 * AIR_LANES]);
+                const Q31 r = ins.x == AIR_Q_ADD ? q_add(x, y) : ins.x == AIR_Q_SUB ? q_sub(x, y) : q_mul(x, y);
+                q[4 * dst] = r.a.a; q[4 * dst + AIR_LANES] = r.a.b; q[4 * dst + 2 * AIR_LANES] = r.b.a; q[4 * dst + 3 * AIR_LANES] = r.b.b;
+                break;
+            }
+            case AIR_Q_MULM: {
+                const Q31 x = q_make(q[4 * ra], q[4 * ra + AIR_LANES], q[4 * ra + 2 * AIR_LANES], q[4 * ra + 3 * AIR_LANES]);
+                const Q31 r = q_mulm(x, m[rb]);
+                q[4 * dst] = r.a.a; q[4 * dst + AIR_LANES] = r.a.b; q[4 * dst + 2 * AIR_LANES] = r.b.a; q[4 * dst + 3 * AIR_LANES] = r.b.b;
+                break;
+            }
+            case AIR_C_BASE: {
+                const bf_u32x4 k = coeffs[ci++];
+                const u32 v = m[ra];
+                if (pending == 4) {      // 4 (p - 1)^2 + 2^34 < 2^64
+#pragma unroll
+                    for (int w = 0; w < 4; w++) acc[w] = m_fold(acc[w]);
+                    pending = 0;
+                }
+                acc[0] += (u64)k.x * v; acc[1] += (u64)k.y * v; acc[2] += (u64)k.z * v; acc[3] += (u64)k.w * v;
+                pending++;
+                break;
+            }
+            default: {      // AIR_C_EXT: the validator admits nothing else
+                const bf_u32x4 k = coeffs[ci++];
+                const Q31 x = q_make(q[4 * ra], q[4 * ra + AIR_LANES], q[4 * ra + 2 * AIR_LANES], q[4 * ra + 3 * AIR_LANES]);
+                ext = q_add(ext, q_mul(q_make(k.x, k.y, k.z, k.w), x));
+                break;
+            }
+        }
+    }
+    const u32 dinv = ((g_cu32p)(unsigned long long)ap)[offsetof(AirLaunch, denom_inv) / 4 + (row >> log_size)];
+    const Q31 r = q_mulm(q_add(q_make(m_canon(acc[0]), m_canon(acc[1]), m_canon(acc[2]), m_canon(acc[3])), ext), dinv);
+    g_u32p acc0 = (g_u32p)a->acc[0], acc1 = (g_u32p)a->acc[1], acc2 = (g_u32p)a->acc[2], acc3 = (g_u32p)a->acc[3];
+    acc0[row] = m_add(acc0[row], r.a.a);
+    acc1[row] = m_add(acc1[row], r.a.b);
+    acc2[row] = m_add(acc2[row], r.b.a);
+    acc3[row] = m_add(acc3[row], r.b.b);
+}
+
+}  // namespace bf
+
+using namespace bf;
+
+extern "C" int32_t bfhip_air_eval_domain(bfhip_ctx* ctx, const bfhip_air* air, uint32_t log_size, uint32_t log_expand, const uint32_t* const* cols_h,
+                                         const uint32_t* col_shifts_h, const uint32_t* params_h, uint32_t n_params, const uint32_t* coeffs_h, uint32_t n_coeffs,
+                                         uint32_t* const acc_d[4]) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    const std::string me = "bfhip_air_eval_domain";
+    if (!air || !coeffs_h || !acc_d || (!cols_h && air->n_cols) || (!params_h && n_params)) throw HipError("null argument");
+    if (c.shard.count > 1) throw HipError(me + ": a context in a shard group is not supported (bfhip_ctx_leave_group first)");
+    if (log_expand < 1 || log_expand > 3) throw HipError(me + ": log_expand must be in [1, 3], got " + std::to_string(log_expand));
+    if (log_size < 1 || log_size > 29) throw HipError(me + ": log_size must be at least 1 and log_size + log_expand at most max_log_domain");
+    const u32 el = log_size + log_expand;
+    if (el > c.tw_root_log + 1) throw HipError(me + ": log_size + log_expand = " + std::to_string(el) + " exceeds the context's max_log_domain " + std::to_string(c.tw_root_log + 1));
+    if (n_params != air->n_params) throw HipError(me + ": the program takes " + std::to_string(air->n_params) + " parameters, got " + std::to_string(n_params));
+    if (n_coeffs != air->n_constraints) throw HipError(me + ": the program has " + std::to_string(air->n_constraints) + " constraints, got " + std::to_string(n_coeffs) + " coefficients");
+    for (u32 i = 0; i < 4 * n_params; i++) if (params_h[i] >= P31) throw HipError(me + ": a parameter word is not a canonical M31");
+    for (u32 i = 0; i < 4 * n_coeffs; i++) if (coeffs_h[i] >= P31) throw HipError(me + ": a coefficient word is not a canonical M31");
+    for (int w = 0; w < 4; w++) if (!acc_d[w]) throw HipError(me + ": null accumulator pointer");
+    std::vector<bf_u32x4> cols(air->n_cols ? air->n_cols : 1, bf_u32x4{0, 0, 0, 0});
+    for (u32 k = 0; k < air->n_cols; k++) {
+        const u32 s = col_shifts_h ? col_shifts_h[k] : 0u;
+        if (!cols_h[k]) throw HipError(me + ": null column pointer (column " + std::to_string(k) + ")");
+        if (s == 1 || s > el) throw HipError(me + ": column " + std::to_string(k) + " has shift " + std::to_string(s) + " (0, or 2 .. log_size + log_expand)");
+        if (s && air->col_read_shifted[k]) throw HipError(me + ": column " + std::to_string(k) + " is stored with shift " + std::to_string(s) + " and read at a non-zero offset");
+        const unsigned long long p = (unsigned long long)cols_h[k];
+        cols[k] = bf_u32x4{(u32)p, (u32)(p >> 32), s, 0u};
+    }
+    AirLaunch L{};
+    L.n_instr = air->n_instr; L.n_m = air->n_m; L.log_size = log_size; L.log_expand = log_expand;
+    for (int w = 0; w < 4; w++) L.acc[w] = (u64)acc_d[w];
+    // 1 / coset_vanishing(CanonicCoset(log_size).coset, domain.at(d)) depends on d mod 2^log_expand only; in bit-reversed storage those are the
+    // top bits of the row: entry i = row >> log_size belongs to d = bit_rev(i)
+    for (u32 i = 0; i < (1u << log_expand); i++) L.denom_inv[i] = m_inv(coset_vanishing_m(log_size, canonic_domain_at(el, bit_rev(i, log_expand))));
+    const u32 zero4[4] = {0, 0, 0, 0};
+    c.stage_checkpoint();
+    {
+        StageBatch sb(c);
+        L.code = (u64)c.stage(air->code.data(), air->code.size());
+        L.cols = (u64)c.stage(cols.data(), cols.size());
+        L.params = (u64)c.stage(n_params ? params_h : zero4, n_params ? 4 * (size_t)n_params : 4);
+        L.coeffs = (u64)c.stage(coeffs_h, 4 * (size_t)n_coeffs);
+        const AirLaunch* d_launch = c.stage(&L, 1);
+        sb.end();
+        const u32 n = 1u << el;
+        const size_t lds = sizeof(u32) * AIR_LANES * (air->n_m + 4 * air->n_q);
+        ProfScope ps(c.stream, "k_air_program", 0);
+        hipLaunchKernelGGL(k_air_program, dim3((n + AIR_LANES - 1) / AIR_LANES), dim3(AIR_LANES), lds, c.stream, d_launch);
+    }
+    BF_HIP(hipGetLastError());
+    return 0;
+    API_CATCH
+}
