@@ -509,3 +509,48 @@ impl Drop for AirProgram {
         unsafe { sys::bfhip_air_destroy(self.0) };
     }
 }
+
+// ---- fraction programs (`include/bfhip.h` "Fraction programs"): the logUp interaction trace of ANY AIR ---------------------------------------
+// What a component's `interaction_trace_evaluation` hands to `LogupTraceGenerator::{new_col, write_frac, finalize_col, finalize_last}`, recorded
+// once as bytecode: a constraint program's opcodes without constraints, plus `sys::BFHIP_LOGUP_FRAC` {-, a, b} (add q[a] / q[b] to the open
+// column) and `sys::BFHIP_LOGUP_END_COL`. It runs on the trace domain over columns whose cells are all distinct.
+
+/// `bfhip_logup_shape`.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct LogupShape { pub n_cols: u32, pub n_params: u32, pub n_logup_cols: u32, pub n_fractions: u32, pub n_instr: u32, pub m_regs: u32, pub q_regs: u32 }
+
+/// A validated fraction program (`bfhip_logup`). Host only to create and inspect.
+pub struct LogupProgram(*mut sys::BfhipLogup);
+
+impl LogupProgram {
+    /// `bfhip_logup_create`: a refusal names the instruction index and the rule.
+    pub fn new(code: &[u32], n_cols: u32, n_params: u32) -> Result<Self, String> {
+        let mut p = std::ptr::null_mut();
+        check(unsafe { sys::bfhip_logup_create(code.as_ptr(), code.len(), n_cols, n_params, &mut p) })?;
+        Ok(LogupProgram(p))
+    }
+    pub fn shape(&self) -> Result<LogupShape, String> {
+        let mut o = [0u32; 8];
+        check(unsafe { sys::bfhip_logup_shape(self.0, o.as_mut_ptr()) })?;
+        Ok(LogupShape { n_cols: o[0], n_params: o[1], n_logup_cols: o[2], n_fractions: o[3], n_instr: o[4], m_regs: o[5], q_regs: o[6] })
+    }
+    /// `bfhip_logup_program_generate`: the interaction trace on CanonicCoset(log_size).circle_domain(); returns the claimed sum. `cols`: one device
+    /// column per program column (`shifts`: its storage shift, empty = all 0); `out`: 4 full-size coordinate columns per logUp column. A zero
+    /// denominator is an `Err` that names the fraction and the cell.
+    pub fn generate(&self, ctx: &Context, log_size: u32, cols: &[*const u32], shifts: &[u32], params: &[Felt], out: &[*mut u32]) -> Result<Felt, String> {
+        if !shifts.is_empty() && shifts.len() != cols.len() { return Err("one shift per column".into()); }
+        if out.len() != 4 * self.shape()?.n_logup_cols as usize { return Err("4 coordinate columns per logUp column".into()); }
+        let mut claimed = [0u32; 4];
+        check(unsafe {
+            sys::bfhip_logup_program_generate(ctx.0, self.0, log_size, cols.as_ptr(), if shifts.is_empty() { std::ptr::null() } else { shifts.as_ptr() },
+                                              params.as_ptr() as *const u32, params.len() as u32, out.as_ptr(), claimed.as_mut_ptr())
+        })?;
+        Ok(claimed)
+    }
+}
+
+impl Drop for LogupProgram {
+    fn drop(&mut self) {
+        unsafe { sys::bfhip_logup_destroy(self.0) };
+    }
+}

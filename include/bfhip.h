@@ -663,7 +663,7 @@ int32_t bfhip_brainfuck_composition_at_point(const uint32_t log_sizes_h[13], con
  *   and a second bfhip_pcs_create.
  * Everything else keeps working, which is what the caller's constraint sweep needs: bfhip_malloc / bfhip_free / bfhip_upload / bfhip_download /
  * bfhip_memset_zero, bfhip_interpolate, bfhip_evaluate, bfhip_is_first_coeffs, bfhip_eval_at_point, bfhip_logup_generate, bfhip_eval_constraints,
- * bfhip_air_eval_domain, bfhip_accumulate, the Merkle / fold / grind / gather single operations, resident traces' getters and the profiler.
+ * bfhip_air_eval_domain, bfhip_logup_program_generate, bfhip_accumulate, the Merkle / fold / grind / gather single operations, resident traces' getters and the profiler.
  * Not supported: a context in a shard group (create refuses; joining refuses while a session is open); a pool's sub-context while anything
  * is queued, running or not yet taken on the pool.
  * Launch order: the plain one only (wait, draw, copy, launch). No mailbox order, and the overlap mask (bfhip_ctx_set_overlap) is ignored.
@@ -771,6 +771,46 @@ int32_t bfhip_air_eval_domain(bfhip_ctx* ctx, const bfhip_air* air, uint32_t log
                               const uint32_t* params_h, uint32_t n_params, const uint32_t* coeffs_h, uint32_t n_coeffs, uint32_t* const acc_d[4]);
 int32_t bfhip_air_eval_at_point(const bfhip_air* air, uint32_t log_size, const uint32_t point_h[8], const uint32_t* mask_values_h, uint32_t n_mask,
                                 const uint32_t* params_h, uint32_t n_params, const uint32_t* coeffs_h, uint32_t n_coeffs, uint32_t out_h[4]);
+
+/* ---- Fraction programs: the logUp interaction trace of ANY AIR, on the GPU over the trace domain ---------------------------------------------
+ * bfhip_logup_generate runs one of 13 compiled-in branches (`interaction_trace_evaluation` of memory/table.rs:485-518, processor/table.rs:456-529,
+ * ...: the calls prove makes at mod.rs:596-687) and is built on their 16-fold replicated rows. A fraction program is what such a function hands
+ * to LogupTraceGenerator::{new_col, write_frac, finalize_col, finalize_last}, as data: a constraint program's bytecode (same four-word
+ * instructions, same two register files, same caps: 96 m registers, 24 q registers, 4096 instructions, 256 columns, 64 parameters) without
+ * constraints and with two opcodes that exist only here:
+ *   BFHIP_LOGUP_FRAC     -, a, b   add the fraction q[a] / q[b] to the open logUp column (write_frac)
+ *   BFHIP_LOGUP_END_COL  -         close the open column (finalize_col); the next FRAC opens the next one (new_col)
+ * The value of logUp column k at a cell is the value of column k - 1 at that cell (0 for k = 0) plus the sum of column k's fractions at that
+ * cell. Fractions are field elements: the sum is a value, not an evaluation order (n1/d1 + n2/d2 and (n1 d2 + n2 d1)/(d1 d2) are the same
+ * canonical words). The last column is then replaced by its inclusive prefix sum in coset order (finalize_last: coset index i is circle-domain
+ * index coset_index_to_circle_domain_index(i, log_size), stored bit-reversed — the order the row at offset -1 of a constraint program steps
+ * backwards through), and the claimed sum is the last coset element of that prefix sum: the sum of the last column's per-cell values over
+ * all cells. With bfhip_pcs_* and bfhip_air_* this proves an AIR with lookups that the library has never seen.
+ *
+ * bfhip_logup_create (host only): every rule of bfhip_air_create (opcode, register range, read before write, col and col + 3 within n_cols,
+ *   parameter index, v < p, the instruction / column / parameter caps), and: C_BASE and C_EXT are refused; M_COL and Q_COL at a non-zero offset
+ *   are refused (the generator reads a row's own cells: a "next" value is a column); a FRAC that no END_COL follows, an END_COL with no FRAC
+ *   since the previous one, a program without any column, more than 8 = BFHIP_LOGUP_MAX_COLUMNS columns or 32 = BFHIP_LOGUP_MAX_FRACTIONS
+ *   fractions are refused. Each refusal is -1 with "bfhip_logup_create: instruction <i>: <rule>" (rules about the program as a whole name the
+ *   instruction count). bfhip_air_create keeps refusing opcodes 15 and 16.
+ * bfhip_logup_shape: out = {columns, parameters, logUp columns, fractions, instructions, m registers used, q registers used, 0}.
+ * bfhip_logup_program_generate: column k of cols_h holds 2^log_size cells of CanonicCoset(log_size).circle_domain(), bit-reversed; with
+ *   col_shifts_h[k] = s (0 or >= 2; NULL = all 0) it holds 2^(log_size - s) cells and is read at cell >> s. out_cols_h = 4 * n_logup_columns
+ *   device pointers, every one a full-size coordinate column of 2^log_size cells (no row-granular output). params_h = 4 * n_params canonical
+ *   words; the count must be the program's. 1 <= log_size <= max_log_domain. claimed_sum_h = u32[4]. A context in a shard group is refused.
+ *   Works while a session is open (its scratch is not the arena's). Scratch: one hipMalloc of at most
+ *       24 * 2^log_size + 2^log_size / 128 + 64 bytes,
+ *   freed before the call returns; a failed allocation is -1 with "bfhip_logup_program_generate: cannot allocate <n> bytes of scratch".
+ *   A zero denominator (stwo panics there) is -1 with "bfhip_logup_program_generate: fraction <f> has a zero denominator at cell <c>": <c> the
+ *   lowest such cell (storage index), <f> the lowest such fraction (numbered in program order from 0) at that cell; the outputs are then
+ *   unspecified and the context stays usable. */
+enum { BFHIP_LOGUP_FRAC = 15, BFHIP_LOGUP_END_COL = 16, BFHIP_LOGUP_MAX_COLUMNS = 8, BFHIP_LOGUP_MAX_FRACTIONS = 32 };
+typedef struct bfhip_logup bfhip_logup;
+int32_t bfhip_logup_create(const uint32_t* code, size_t n_words, uint32_t n_cols, uint32_t n_params, bfhip_logup** out);
+int32_t bfhip_logup_destroy(bfhip_logup* lp);
+int32_t bfhip_logup_shape(const bfhip_logup* lp, uint32_t out[8]);
+int32_t bfhip_logup_program_generate(bfhip_ctx* ctx, const bfhip_logup* lp, uint32_t log_size, const uint32_t* const* cols_h, const uint32_t* col_shifts_h,
+                                     const uint32_t* params_h, uint32_t n_params, uint32_t* const* out_cols_h, uint32_t claimed_sum_h[4]);
 
 /* Host-only pieces of the drop-in (usable without a GPU): the Brainfuck compiler (crates/brainfuck_vm/src/compiler.rs:17-37), the VM
  * (crates/brainfuck_vm/src/machine.rs:141-238; trace rows are 7 u32: clk, ip, ci, ni, mp, mv, mvi) and the 13 table builders

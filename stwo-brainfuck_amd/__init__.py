@@ -636,6 +636,24 @@ class Context:
                                            self._u32s([w for q in params for w in q]) if params else None, len(params),
                                            self._u32s([w for q in coeffs for w in q]) if coeffs else None, len(coeffs), self._ptr_array(acc_ptrs)))
 
+    def logup_program_generate(self, program, log_size, col_ptrs, params, out_col_ptrs, col_shifts=None):
+        """bfhip_logup_program_generate: the logUp interaction trace of a LogupProgram on CanonicCoset(log_size).circle_domain(). col_ptrs: one
+        device column per program column (2^(log_size - shift) cells); params: QM31 values (4 words each); out_col_ptrs: 4 full-size
+        coordinate columns per logUp column. Returns the claimed sum (4 u32). A zero denominator raises BfhipError naming fraction and cell."""
+        params = [list(q) for q in params]
+        if any(len(q) != 4 for q in params):
+            raise ValueError("a parameter is 4 words")
+        if len(col_ptrs) != program.shape["n_cols"] or (col_shifts is not None and len(col_shifts) != len(col_ptrs)):
+            raise ValueError("one column pointer (and shift) per program column")
+        if len(out_col_ptrs) != 4 * program.shape["n_logup_cols"]:
+            raise ValueError("4 coordinate columns per logUp column")
+        claimed = (ctypes.c_uint32 * 4)()
+        _check(lib().bfhip_logup_program_generate(self._h, program._h, int(log_size), self._ptr_array(col_ptrs) if col_ptrs else None,
+                                                  None if col_shifts is None or not col_ptrs else self._u32s(col_shifts),
+                                                  self._u32s([w for q in params for w in q]) if params else None, len(params),
+                                                  self._ptr_array(out_col_ptrs), claimed))
+        return list(claimed)
+
     def check_constraints(self, component, log_size, main_row_ptrs, logup_col_ptrs, lookup24, claimed4):
         """bfhip_check_constraints: one component's AIR asserted on its trace domain (stwo's assert_constraints). main_row_ptrs: row-granular
         main columns; logup_col_ptrs: what logup_generate wrote (the last four full size). Returns CheckReport.as_dict(); violations are
@@ -1309,6 +1327,35 @@ class AirProgram:
         return [int(v) for v in out]
 
 
+LOGUP_FRAC, LOGUP_END_COL, LOGUP_MAX_COLUMNS, LOGUP_MAX_FRACTIONS = 15, 16, 8, 32
+
+
+class LogupProgram:
+    """bfhip_logup: a validated fraction program (include/bfhip.h "Fraction programs") — a constraint program's bytecode without constraints,
+    with FRAC (add q[a] / q[b] to the open logUp column) and END_COL. Host only to create; Context.logup_program_generate runs it on the
+    trace domain. A refused program raises BfhipError naming the instruction index and the rule."""
+
+    def __init__(self, code, n_cols, n_params):
+        self.code = [int(w) & 0xFFFFFFFF for w in code]
+        self._h = ctypes.c_void_p()
+        arr = (ctypes.c_uint32 * max(1, len(self.code)))(*self.code)
+        _check(lib().bfhip_logup_create(arr, ctypes.c_size_t(len(self.code)), int(n_cols), int(n_params), ctypes.byref(self._h)))
+        out = (ctypes.c_uint32 * 8)()
+        _check(lib().bfhip_logup_shape(self._h, out))
+        self.shape = {"n_cols": out[0], "n_params": out[1], "n_logup_cols": out[2], "n_fractions": out[3], "n_instr": out[4], "m_regs": out[5], "q_regs": out[6]}
+
+    def close(self):
+        if self._h:
+            lib().bfhip_logup_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class AirExpr:
     """A value of an AirBuilder: kind 'm' (M31, a base-field column expression) or 'q' (QM31). Operators + - * and unary -; a Python int
     stands for const(int). m op q promotes the m side (Q_FROM_M), except a product, which is Q_MULM."""
@@ -1389,6 +1436,16 @@ class AirBuilder:
         expr = self._value(expr)
         self._emit(AIR_C_BASE if expr.kind == "m" else AIR_C_EXT, None, (expr.id,))
 
+    def frac(self, num, den):
+        """BFHIP_LOGUP_FRAC: add num / den to the open logUp column (LogupTraceGenerator::write_frac). A base-field numerator or
+        denominator is lifted (Q_FROM_M). Fraction programs only: see logup_program()."""
+        num, den = self._to_q(self._value(num)), self._to_q(self._value(den))
+        self._emit(LOGUP_FRAC, None, (num.id, den.id))
+
+    def end_column(self):
+        """BFHIP_LOGUP_END_COL: close the open logUp column (finalize_col); the next frac() opens the next one."""
+        self._emit(LOGUP_END_COL, None)
+
     def code(self):
         """The bytecode (a flat list of u32 words). Raises ValueError if the program needs more registers than the caps."""
         import heapq
@@ -1425,6 +1482,8 @@ class AirBuilder:
                 words += [op, dst, imm[0], 0]
             elif op in (AIR_C_BASE, AIR_C_EXT):
                 words += [op, 0, regs[0], 0]
+            elif op == LOGUP_END_COL:
+                words += [op, 0, 0, 0]
             else:
                 words += [op, dst, regs[0], regs[1] if len(regs) > 1 else 0]
         return words
@@ -1434,6 +1493,12 @@ class AirBuilder:
         cols = [imm[0] + (4 if op == AIR_Q_COL else 1) for op, _, _, imm in self._ops if op in (AIR_M_COL, AIR_Q_COL)]
         pars = [imm[0] + 1 for op, _, _, imm in self._ops if op == AIR_Q_PARAM]
         return AirProgram(self.code(), max(cols, default=0) if n_cols is None else n_cols, max(pars, default=0) if n_params is None else n_params)
+
+    def logup_program(self, n_cols=None, n_params=None):
+        """LogupProgram of the bytecode (frac() / end_column() instead of constraint()); n_cols / n_params default as for program()."""
+        cols = [imm[0] + (4 if op == AIR_Q_COL else 1) for op, _, _, imm in self._ops if op in (AIR_M_COL, AIR_Q_COL)]
+        pars = [imm[0] + 1 for op, _, _, imm in self._ops if op == AIR_Q_PARAM]
+        return LogupProgram(self.code(), max(cols, default=0) if n_cols is None else n_cols, max(pars, default=0) if n_params is None else n_params)
 
 
 def _q_mul(x, y):
@@ -1565,3 +1630,53 @@ def brainfuck_air_program(component, logup_mask_order=0):
     names = ["%s.%s" % (r, p) for r in ("memory", "instruction", "processor") for p in ["z"] + ["alpha^%d" % i for i in range(7)]] + ["claimed_sum"]
     columns = ["main%d" % j for j in range(n_main)] + ["logup%d.%d" % (k, w) for k in range(n_logup) for w in range(4)] + ["is_first"]
     return b.program(n_cols=n_main + 4 * n_logup + 1, n_params=BRAINFUCK_AIR_N_PARAMS), names, columns
+
+
+BRAINFUCK_LOGUP_N_PARAMS = 24
+
+
+def brainfuck_logup_program(component):
+    """`interaction_trace_evaluation` of component 0..12 of the Brainfuck AIR as a fraction program — restated from the branches of
+    k_logup_rows (csrc/air.hip; memory/table.rs:485-518, instruction/table.rs:456-490, program/table.rs:233-265, processor/table.rs:456-529,
+    jump/table.rs:436-475, instructions/table.rs:466-505, end_of_execution/table.rs:220-255). Returns (LogupProgram, parameter names).
+    Columns: the n_main main-trace columns. Parameters: the first 24 of brainfuck_air_params. The Processor has three logUp columns of one
+    fraction each (Processor, Instruction, Memory relations), the others one; numerators d - 1, 1 - d or -1."""
+    if not 0 <= component < 13:
+        raise ValueError("component 0..12")
+    b = AirBuilder()
+    n_main = _BF_N_MAIN[component]
+    t = lambda *js: [b.col(j) for j in js]      # only the columns a fraction reads: a column read is never dropped
+    one = b.const(1)
+    REL = {"memory": 0, "instruction": 1, "processor": 2}
+
+    def combine(rel, values):
+        base = 8 * REL[rel]
+        acc = None
+        for i, v in enumerate(values):
+            term = b.param(base + 1 + i) * v
+            acc = term if acc is None else acc + term
+        return acc - b.param(base)
+
+    def column(num, den):
+        b.frac(num, den)
+        b.end_column()
+
+    if component == 0:
+        column(t(3)[0] - one, combine("memory", t(0, 1, 2)))
+    elif component == 1:
+        column(t(3)[0] - one, combine("instruction", t(0, 1, 2)))
+    elif component == 2:
+        column(one - t(3)[0], combine("instruction", t(0, 1, 2)))
+    elif component == 3:
+        num = one - t(7)[0]
+        column(num, combine("processor", t(0, 1, 2, 3, 4, 5, 6)))
+        column(num, combine("instruction", t(1, 2, 3)))
+        column(num, combine("memory", t(0, 4, 5)))
+    elif component in (4, 5):
+        column(t(11)[0] - one, combine("processor", t(0, 1, 2, 3, 4, 5, 6)))
+    elif component == 12:
+        column(b.const(P - 1), combine("processor", t(0, 1, 2, 3, 4, 5, 6)))
+    else:
+        column(t(7)[0] - one, combine("processor", t(0, 1, 2, 3, 4, 5, 6)))
+    names = ["%s.%s" % (r, p) for r in ("memory", "instruction", "processor") for p in ["z"] + ["alpha^%d" % i for i in range(7)]]
+    return b.logup_program(n_cols=n_main, n_params=BRAINFUCK_LOGUP_N_PARAMS), names

@@ -1,0 +1,271 @@
+// The fraction program on the trace domain (include/bfhip.h "Fraction programs": bfhip_logup_program_generate) — what a component's
+// `interaction_trace_evaluation` does with LogupTraceGenerator::{new_col, write_frac, finalize_col, finalize_last} for any AIR, as four gfx950
+// launches that interpret the program instead of one compiled branch per component (air.hip: k_logup_rows). Every cell is distinct: nothing
+// here knows of the 16-fold replication the compiled path is built on.
+//
+// Row stage (k_logup_program): k_air_program's shape. One lane per cell, one wave per workgroup; instruction stream, column descriptors,
+// parameters and output pointers come through scalar loads (address space 4) at wave-uniform addresses, the opcode dispatch is a scalar
+// branch, the two register files live in dynamic LDS laid out [register][lane], no scratch. FRAC folds q[a] / q[b] into the open column's
+// running fraction fn / fd (three products; every denominator is tested for zero where it stands, so a vanishing one is named and not hidden
+// in a product), END_COL adds fn / fd to the running value with the column's one q_inv; END_COL of a column before the last
+// stores the running value to the column's four coordinate columns (lane = cell: 256-byte coalesced stores), END_COL of the last column
+// stores it as one 16-byte word of v[cell], the input of the scan.
+// Scan stage (k_logup_program_scan, k_logup_program_totals, k_logup_program_last): the coset-order inclusive prefix sum of v over N = 2^log_size
+// cells. With d = bit_rev(cell), coset position 2q is d = q and 2q + 1 is d = N - 1 - q: w[q] = v[d = q] + v[d = N - 1 - q] (q < N / 2) is scanned
+// (1024-entry tiles, then the tile totals), and the prefix at 2q + 1 is W[q], at 2q it is W[q] - v[d = N - 1 - q]. Bit reversal commutes with the
+// complement, so in cell indices d = N - 1 - q is cell N - 1 - bit_rev(q): the partner of cell c is always cell N - 1 - c.
+#include "api_guard.h"
+#include "logup_program.h"
+#include "../../include/bfhip.h"
+
+namespace bf {
+
+constexpr u32 LP_LANES = 64, LP_TILE = 1024, LP_CHUNK = 256;
+
+// Staged in HBM. Addresses are kept as integers: read from address space 4 they arrive in SGPRs and are cast to global pointers.
+struct LogupProgLaunch {
+    u64 code;            // bf_u32x4[n_instr]
+    u64 cols;            // bf_u32x4[n_cols]: {pointer low, pointer high, shift, 0}
+    u64 params;          // bf_u32x4[n_params]
+    u64 out[4 * LOGUP_MAX_COLUMNS];
+    u64 v, wloc, totals; // uint4[N], uint4[N / 2], uint4[nb + 1]
+    u64 tail;            // uint4[2]: the claimed sum; {zero-denominator key low, high, -, -}
+    u32 n_instr, n_m, log_size, n_logup_cols, nb, pad;
+};
+
+__device__ __forceinline__ u32 lp_ld_cell(const bf_u32x4 col, u32 idx) {
+    const unsigned long long base = ((unsigned long long)col.y << 32) | col.x;
+    return *(g_cu32p)((const BF_GLOBAL char*)base + ((unsigned long long)idx << 2));
+}
+__device__ __forceinline__ Q31 lp_ld(const uint4* p, u32 i) { const uint4 v = p[i]; return q_make(v.x, v.y, v.z, v.w); }
+__device__ __forceinline__ void lp_st(uint4* p, u32 i, Q31 q) { p[i] = make_uint4(q.a.a, q.a.b, q.b.a, q.b.b); }
+
+__global__ void __launch_bounds__(LP_LANES) k_logup_program(const LogupProgLaunch* __restrict__ ap) {
+    extern __shared__ u32 s_regs[];
+    const BF_CONSTANT LogupProgLaunch* a = (const BF_CONSTANT LogupProgLaunch*)(unsigned long long)ap;
+    const u32 cell = blockIdx.x * LP_LANES + threadIdx.x;
+    if (cell >= (1u << a->log_size)) return;
+    u32* const m = s_regs + threadIdx.x;                          // m[r] = m[r * LP_LANES]
+    u32* const q = s_regs + a->n_m * LP_LANES + threadIdx.x;      // coordinate k of q[r] = q[(4 r + k) * LP_LANES]
+    const BF_CONSTANT bf_u32x4* code = (const BF_CONSTANT bf_u32x4*)a->code;
+    const BF_CONSTANT bf_u32x4* cols = (const BF_CONSTANT bf_u32x4*)a->cols;
+    const BF_CONSTANT bf_u32x4* params = (const BF_CONSTANT bf_u32x4*)a->params;
+    Q31 cur = q_zero();          // LogupTraceGenerator: column k starts from column k - 1 (finalize_col keeps the running sum)
+    u32 col_i = 0, frac_i = 0, open = 0;
+    Q31 fn = q_zero(), fd = q_one();      // the open column's fractions so far as one fraction fn / fd (`open` of them: wave-uniform)
+    const u32 n_instr = a->n_instr, last_col = a->n_logup_cols - 1;
+#pragma unroll 1
+    for (u32 pc = 0; pc < n_instr; pc++) {
+        const bf_u32x4 ins = code[pc];
+        const u32 dst = ins.y * LP_LANES, ra = ins.z * LP_LANES, rb = ins.w * LP_LANES;
+        switch (ins.x) {
+            case AIR_M_COL: { const bf_u32x4 col = cols[ins.z]; m[dst] = lp_ld_cell(col, cell >> col.z); break; }
+            case AIR_M_CONST: m[dst] = ins.z; break;
+            case AIR_M_ADD: m[dst] = m_add(m[ra], m[rb]); break;
+            case AIR_M_SUB: m[dst] = m_sub(m[ra], m[rb]); break;
+            case AIR_M_MUL: m[dst] = m_mul(m[ra], m[rb]); break;
+            case AIR_M_NEG: m[dst] = m_neg(m[ra]); break;
+            case AIR_Q_COL: {
+#pragma unroll
+                for (u32 k = 0; k < 4; k++) {
+                    const bf_u32x4 col = cols[ins.z + k];
+                    q[4 * dst + k * LP_LANES] = lp_ld_cell(col, cell >> col.z);
+                }
+                break;
+            }
+            case AIR_Q_PARAM: {
+                const bf_u32x4 v = params[ins.z];
+                q[4 * dst] = v.x; q[4 * dst + LP_LANES] = v.y; q[4 * dst + 2 * LP_LANES] = v.z; q[4 * dst + 3 * LP_LANES] = v.w;
+                break;
+            }
+            case AIR_Q_FROM_M: q[4 * dst] = m[ra]; q[4 * dst + LP_LANES] = 0; q[4 * dst + 2 * LP_LANES] = 0; q[4 * dst + 3 * LP_LANES] = 0; break;
+            case AIR_Q_ADD: case AIR_Q_SUB: case AIR_Q_MUL: {
+                const Q31 x = q_make(q[4 * ra], q[4 * ra + LP_LANES], q[4 * ra + 2 * LP_LANES], q[4 * ra + 3 * LP_LANES]);
+                const Q31 y = q_make(q[4 * rb], q[4 * rb + LP_LANES], q[4 * rb + 2 * LP_LANES], q[4 * rb + 3 * LP_LANES]);
+                const Q31 r = ins.x == AIR_Q_ADD ? q_add(x, y) : ins.x == AIR_Q_SUB ? q_sub(x, y) : q_mul(x, y);
+                q[4 * dst] = r.a.a; q[4 * dst + LP_LANES] = r.a.b; q[4 * dst + 2 * LP_LANES] = r.b.a; q[4 * dst + 3 * LP_LANES] = r.b.b;
+                break;
+            }
+            case AIR_Q_MULM: {
+                const Q31 x = q_make(q[4 * ra], q[4 * ra + LP_LANES], q[4 * ra + 2 * LP_LANES], q[4 * ra + 3 * LP_LANES]);
+                const Q31 r = q_mulm(x, m[rb]);
+                q[4 * dst] = r.a.a; q[4 * dst + LP_LANES] = r.a.b; q[4 * dst + 2 * LP_LANES] = r.b.a; q[4 * dst + 3 * LP_LANES] = r.b.b;
+                break;
+            }
+            case LOGUP_FRAC: {
+                const Q31 num = q_make(q[4 * ra], q[4 * ra + LP_LANES], q[4 * ra + 2 * LP_LANES], q[4 * ra + 3 * LP_LANES]);
+                const Q31 den = q_make(q[4 * rb], q[4 * rb + LP_LANES], q[4 * rb + 2 * LP_LANES], q[4 * rb + 3 * LP_LANES]);
+                // stwo panics on a zero denominator; q_inv(0) is 0 and would pass for a value. The lowest (cell, fraction) wins the key.
+                if (q_is_zero(den)) atomicMin((unsigned long long*)(a->tail + 16), ((unsigned long long)cell << 8) | frac_i);
+                // fn / fd + num / den = (fn den + num fd) / (fd den): three products per further fraction, one inversion per column
+                if (open) { fn = q_add(q_mul(fn, den), q_mul(num, fd)); fd = q_mul(fd, den); } else { fn = num; fd = den; }
+                open++; frac_i++;
+                break;
+            }
+            default: {      // LOGUP_END_COL: the validator admits nothing else
+                cur = q_add(cur, q_mul(fn, q_inv(fd)));
+                open = 0;
+                if (col_i < last_col) {
+#pragma unroll
+                    for (u32 k = 0; k < 4; k++) {
+                        g_u32p o = (g_u32p)a->out[4 * col_i + k];
+                        o[cell] = k == 0 ? cur.a.a : k == 1 ? cur.a.b : k == 2 ? cur.b.a : cur.b.b;
+                    }
+                } else lp_st((uint4*)a->v, cell, cur);
+                col_i++;
+                break;
+            }
+        }
+    }
+}
+
+// Tile-local inclusive scan of w[q] = v[cell bit_rev(q)] + v[cell N - 1 - bit_rev(q)], q < N / 2: four consecutive entries per thread, the 256
+// thread sums scanned through LDS. The tile's total goes to totals[tile].
+__global__ void __launch_bounds__(256) k_logup_program_scan(const LogupProgLaunch* __restrict__ ap) {
+    __shared__ uint4 s[256];
+    const LogupProgLaunch& a = *ap;
+    const uint4* __restrict__ v = (const uint4*)a.v;
+    uint4* __restrict__ wloc = (uint4*)a.wloc;
+    const u32 log_size = a.log_size, N = 1u << log_size, H = N >> 1;
+    const u32 q0 = blockIdx.x * LP_TILE + 4 * threadIdx.x;
+    Q31 p[4];
+    Q31 run = q_zero();
+#pragma unroll
+    for (u32 j = 0; j < 4; j++) {
+        const u32 qi = q0 + j;
+        if (qi < H) { const u32 c = bit_rev(qi, log_size); run = q_add(run, q_add(lp_ld(v, c), lp_ld(v, N - 1 - c))); }
+        p[j] = run;
+    }
+    lp_st(s, threadIdx.x, run);
+    __syncthreads();
+    for (u32 off = 1; off < 256; off <<= 1) {
+        const Q31 t = threadIdx.x >= off ? q_add(lp_ld(s, threadIdx.x), lp_ld(s, threadIdx.x - off)) : lp_ld(s, threadIdx.x);
+        __syncthreads();
+        lp_st(s, threadIdx.x, t);
+        __syncthreads();
+    }
+    const Q31 before = threadIdx.x ? lp_ld(s, threadIdx.x - 1) : q_zero();
+#pragma unroll
+    for (u32 j = 0; j < 4; j++) if (q0 + j < H) lp_st(wloc, q0 + j, q_add(before, p[j]));
+    if (threadIdx.x == 255) lp_st((uint4*)a.totals, blockIdx.x, lp_ld(s, 255));
+}
+
+// Exclusive scan of the nb tile totals (one workgroup, serial over chunks of 256); totals[nb] receives the grand total W[N / 2 - 1], which is
+// the claimed sum: the last coset element of the prefix sum.
+__global__ void __launch_bounds__(LP_CHUNK) k_logup_program_totals(const LogupProgLaunch* __restrict__ ap) {
+    __shared__ uint4 s[LP_CHUNK];
+    const LogupProgLaunch& a = *ap;
+    uint4* __restrict__ totals = (uint4*)a.totals;
+    const u32 nb = a.nb;
+    Q31 carry = q_zero();
+    for (u32 base = 0; base < nb; base += LP_CHUNK) {
+        const u32 i = base + threadIdx.x;
+        const Q31 v = i < nb ? lp_ld(totals, i) : q_zero();
+        lp_st(s, threadIdx.x, v);
+        __syncthreads();
+        for (u32 off = 1; off < LP_CHUNK; off <<= 1) {
+            const Q31 t = threadIdx.x >= off ? q_add(lp_ld(s, threadIdx.x), lp_ld(s, threadIdx.x - off)) : lp_ld(s, threadIdx.x);
+            __syncthreads();
+            lp_st(s, threadIdx.x, t);
+            __syncthreads();
+        }
+        const Q31 incl = lp_ld(s, threadIdx.x), chunk_total = lp_ld(s, LP_CHUNK - 1);
+        __syncthreads();
+        if (i < nb) lp_st(totals, i, q_add(carry, q_sub(incl, v)));
+        carry = q_add(carry, chunk_total);
+    }
+    if (threadIdx.x == 0) { lp_st(totals, nb, carry); lp_st((uint4*)a.tail, 0, carry); }
+}
+
+// The last logUp column: cell c even is d = bit_rev(c) < N / 2, coset position 2q with q = d: W[q] - v[N - 1 - c]; cell c odd is coset
+// position 2q + 1 with q = N - 1 - d = bit_rev(N - 1 - c): W[q].
+__global__ void __launch_bounds__(256) k_logup_program_last(const LogupProgLaunch* __restrict__ ap) {
+    const LogupProgLaunch& a = *ap;
+    const uint4* __restrict__ v = (const uint4*)a.v;
+    const uint4* __restrict__ wloc = (const uint4*)a.wloc;
+    const uint4* __restrict__ totals = (const uint4*)a.totals;
+    const u32 log_size = a.log_size, N = 1u << log_size;
+    const u32 c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= N) return;
+    const bool even = (c & 1u) == 0;
+    const u32 qi = bit_rev(even ? c : N - 1 - c, log_size);
+    Q31 res = q_add(lp_ld(wloc, qi), lp_ld(totals, qi / LP_TILE));
+    if (even) res = q_sub(res, lp_ld(v, N - 1 - c));
+    const u64* out = a.out + 4 * (a.n_logup_cols - 1);
+    ((u32*)out[0])[c] = res.a.a;
+    ((u32*)out[1])[c] = res.a.b;
+    ((u32*)out[2])[c] = res.b.a;
+    ((u32*)out[3])[c] = res.b.b;
+}
+
+}  // namespace bf
+
+using namespace bf;
+
+extern "C" int32_t bfhip_logup_program_generate(bfhip_ctx* ctx, const bfhip_logup* lp, uint32_t log_size, const uint32_t* const* cols_h, const uint32_t* col_shifts_h,
+                                                const uint32_t* params_h, uint32_t n_params, uint32_t* const* out_cols_h, uint32_t claimed_sum_h[4]) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    const std::string me = "bfhip_logup_program_generate";
+    if (!lp || !out_cols_h || !claimed_sum_h || (!cols_h && lp->n_cols) || (!params_h && n_params)) throw HipError("null argument");
+    if (c.shard.count > 1) throw HipError(me + ": a context in a shard group is not supported (bfhip_ctx_leave_group first)");
+    if (log_size < 1 || log_size > c.tw_root_log + 1 || log_size > 29) throw HipError(me + ": log_size must be in [1, max_log_domain = " + std::to_string(c.tw_root_log + 1) + "], got " + std::to_string(log_size));
+    if (n_params != lp->n_params) throw HipError(me + ": the program takes " + std::to_string(lp->n_params) + " parameters, got " + std::to_string(n_params));
+    for (u32 i = 0; i < 4 * n_params; i++) if (params_h[i] >= P31) throw HipError(me + ": a parameter word is not a canonical M31");
+    std::vector<bf_u32x4> cols(lp->n_cols ? lp->n_cols : 1, bf_u32x4{0, 0, 0, 0});
+    for (u32 k = 0; k < lp->n_cols; k++) {
+        const u32 s = col_shifts_h ? col_shifts_h[k] : 0u;
+        if (!cols_h[k]) throw HipError(me + ": null column pointer (column " + std::to_string(k) + ")");
+        if (s == 1 || s > log_size) throw HipError(me + ": column " + std::to_string(k) + " has shift " + std::to_string(s) + " (0, or 2 .. log_size)");
+        const unsigned long long p = (unsigned long long)cols_h[k];
+        cols[k] = bf_u32x4{(u32)p, (u32)(p >> 32), s, 0u};
+    }
+    LogupProgLaunch L{};
+    for (u32 k = 0; k < 4 * lp->n_logup_cols; k++) {
+        if (!out_cols_h[k]) throw HipError(me + ": null output column pointer (coordinate column " + std::to_string(k) + ")");
+        L.out[k] = (u64)out_cols_h[k];
+    }
+    // scratch, never from the arena (an open session owns it): v[N], wloc[N / 2], totals[nb + 1], tail[2] of 16 bytes each =
+    // 24 N + 16 (nb + 3) bytes with nb = ceil(N / 2048) tiles: at most 24 * 2^log_size + 2^log_size / 128 + 64
+    const size_t N = size_t(1) << log_size, H = N / 2, nb = (H + LP_TILE - 1) / LP_TILE;
+    const size_t bytes = sizeof(uint4) * (N + H + nb + 1 + 2);
+    uint4* scratch = nullptr;
+    if (hipError_t e = hipMalloc((void**)&scratch, bytes); e != hipSuccess) {
+        (void)hipGetLastError();
+        throw HipError(me + ": cannot allocate " + std::to_string(bytes) + " bytes of scratch (" + hipGetErrorString(e) + ")");
+    }
+    uint4 tail[2];
+    try {
+        L.v = (u64)scratch; L.wloc = (u64)(scratch + N); L.totals = (u64)(scratch + N + H); L.tail = (u64)(scratch + N + H + nb + 1);
+        L.n_instr = lp->n_instr; L.n_m = lp->n_m; L.log_size = log_size; L.n_logup_cols = lp->n_logup_cols; L.nb = (u32)nb;
+        const u32 zero4[4] = {0, 0, 0, 0};
+        c.stage_checkpoint();
+        BF_HIP(hipMemsetAsync((void*)L.tail, 0xFF, 2 * sizeof(uint4), c.stream));
+        {
+            StageBatch sb(c);
+            L.code = (u64)c.stage(lp->code.data(), lp->code.size());
+            L.cols = (u64)c.stage(cols.data(), cols.size());
+            L.params = (u64)c.stage(n_params ? params_h : zero4, n_params ? 4 * (size_t)n_params : 4);
+            const LogupProgLaunch* d_launch = c.stage(&L, 1);
+            sb.end();
+            const size_t lds = sizeof(u32) * LP_LANES * (lp->n_m + 4 * lp->n_q);
+            { ProfScope ps(c.stream, "k_logup_program", 0); hipLaunchKernelGGL(k_logup_program, dim3((u32)((N + LP_LANES - 1) / LP_LANES)), dim3(LP_LANES), lds, c.stream, d_launch); }
+            ProfScope ps(c.stream, "k_logup_program_scan", 0);
+            hipLaunchKernelGGL(k_logup_program_scan, dim3((u32)nb), dim3(256), 0, c.stream, d_launch);
+            hipLaunchKernelGGL(k_logup_program_totals, dim3(1), dim3(LP_CHUNK), 0, c.stream, d_launch);
+            hipLaunchKernelGGL(k_logup_program_last, dim3((u32)((N + 255) / 256)), dim3(256), 0, c.stream, d_launch);
+        }
+        BF_HIP(hipGetLastError());
+        c.read_back(tail, (const void*)L.tail, sizeof tail);
+    } catch (...) {
+        (void)hipStreamSynchronize(c.stream);
+        (void)hipFree(scratch);
+        throw;
+    }
+    BF_HIP(hipFree(scratch));
+    const u64 key = ((u64)tail[1].y << 32) | tail[1].x;
+    if (key != ~u64(0)) throw HipError(me + ": fraction " + std::to_string(key & 0xFF) + " has a zero denominator at cell " + std::to_string(key >> 8));
+    claimed_sum_h[0] = tail[0].x; claimed_sum_h[1] = tail[0].y; claimed_sum_h[2] = tail[0].z; claimed_sum_h[3] = tail[0].w;
+    return 0;
+    API_CATCH
+}
