@@ -2,8 +2,9 @@
 header's table alone. Both register files hold QM31 values as uint64 arrays of shape (4, n): n = 1 at a point (a mask value per (column,
 offset)), n = the rows of a domain (an M31 cell v is (v, 0, 0, 0)). The result is sum_j coeffs[j] * C_j WITHOUT the vanishing denominator.
 Also here: the row-offset map of a bit-reversed circle domain from first principles (group indices of the M31 circle), the vanishing
-polynomial of a canonic coset at a point, and a seeded generator of random valid programs that uses every opcode and reuses registers.
-Shared by tests/test_air_program_cpu.py and tests/test_gpu_air_program.py."""
+polynomial of a canonic coset at a point, its inverse at every row of a constraint domain (domain_denominators), and a seeded generator of
+random valid programs that uses every opcode and reuses registers.
+Shared by tests/test_air_program_cpu.py, tests/test_gpu_air_program.py and tests/test_gpu_program_edges.py."""
 import random
 
 import numpy as np
@@ -144,9 +145,48 @@ def coset_vanishing(log_size, point8):
     return [int(v) for v in x[:, 0]]
 
 
-def random_program(seed, n_cols=9, n_params=3, n_ops=60, m_pool=6, q_pool=4, max_off=2):
+CIRCLE_GEN = (2, 1268011823)      # the generator of the M31 circle group (order 2^31)
+
+
+def circle_x(index):
+    """x coordinate of G^index over Python integers"""
+    mul = lambda p, q: ((p[0] * q[0] - p[1] * q[1]) % P, (p[0] * q[1] + p[1] * q[0]) % P)
+    res, cur = (1, 0), CIRCLE_GEN
+    while index:
+        if index & 1:
+            res = mul(res, cur)
+        cur, index = mul(cur, cur), index >> 1
+    return res[0]
+
+
+def domain_group_indices(log_size, log_expand):
+    """Group index of the point of every storage row of CanonicCoset(log_size + log_expand).circle_domain() in bit-reversed order (the
+    indices offset_rows starts from)."""
+    el = log_size + log_expand
+    n, half, order = 1 << el, 1 << (el - 1), 1 << 31
+    I, S = 1 << (30 - el), 1 << (32 - el)
+    d = bit_reverse(np.arange(n), el)
+    return np.where(d < half, I + d * S, -(I + (d - half) * S)) % order
+
+
+def domain_denominators(log_size, log_expand):
+    """1 / coset_vanishing(CanonicCoset(log_size).coset, p) for the point p of every storage row of the constraint domain, as (n,) uint64:
+    the x of G^index doubled log_size - 1 times (x -> 2 x^2 - 1), inverted by Fermat. Exact Python integers, every row on its own: that
+    the value depends on row >> log_size only is the kernel's table, not something the model assumes."""
+    out = []
+    for g in domain_group_indices(log_size, log_expand).tolist():
+        x = circle_x(g)
+        for _ in range(1, log_size):
+            x = (2 * x * x - 1) % P
+        assert x != 0, "a point of the constraint domain lies on the trace domain"
+        out.append(pow(x, P - 2, P))
+    return np.array(out, dtype=np.uint64)
+
+
+def random_program(seed, n_cols=9, n_params=3, n_ops=60, m_pool=6, q_pool=4, max_off=2, max_cons=60):
     """A random valid program over small register pools (so registers are overwritten and reused all the time). Every opcode appears;
-    returns (code words, n_cols, n_params, n_constraints)."""
+    at most max_cons constraints (64 = BFHIP_AIR_MAX_CONSTRAINTS; the default keeps what every earlier seed generated).
+    Returns (code words, n_cols, n_params, n_constraints)."""
     rng = random.Random(seed)
     code, mw, qw, n_cons, used = [], set(), set(), 0, set()
     off = lambda: rng.choice([0, 0, 0] + list(range(-max_off, max_off + 1))) & 0xFFFFFFFF
@@ -173,9 +213,9 @@ def random_program(seed, n_cols=9, n_params=3, n_ops=60, m_pool=6, q_pool=4, max
             code.extend([op, qd, rng.choice(sorted(qw)), rng.choice(sorted(qw))]); qw.add(qd)
         elif op == Q_MULM and qw and mw:
             code.extend([op, qd, rng.choice(sorted(qw)), rng.choice(sorted(mw))]); qw.add(qd)
-        elif op == C_BASE and mw and n_cons < 60:
+        elif op == C_BASE and mw and n_cons < max_cons:
             code.extend([op, rng.getrandbits(32), rng.choice(sorted(mw)), 0]); n_cons += 1
-        elif op == C_EXT and qw and n_cons < 60:
+        elif op == C_EXT and qw and n_cons < max_cons:
             code.extend([op, 0, rng.choice(sorted(qw)), 0]); n_cons += 1
         else:
             return

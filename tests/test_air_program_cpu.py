@@ -9,10 +9,13 @@ import os
 import random
 import re
 import subprocess
+import zlib
 
+import numpy as np
 import pytest
 
 import air_model
+import field_inputs
 import pcs_replay
 from conftest import ROOT
 
@@ -215,6 +218,112 @@ def test_numpy_model_agrees_with_the_point_evaluator_on_random_programs(pkg, see
     at = {m: air_model.q(v) for m, v in zip(mask, mask_values)}
     model = air_model.run(code, lambda col, off: at[(col, off)], params, coeffs)
     assert pcs_replay.q_mul(got, air_model.coset_vanishing(log_size, point)) == [int(w) for w in model[:, 0]]
+
+
+# ---- the model where tests/test_gpu_program_edges.py leans on it ---------------------------------------------------------------------------
+SIZES = [(log_size, log_expand) for log_size in range(1, 6) for log_expand in range(1, 4)]
+
+
+def test_random_program_max_cons_leaves_earlier_seeds_alone_and_reaches_the_cap(pkg):
+    """The default (60) generates what it always did — the programs of seeds 0 .. 11 are pinned by the CRC-32 of their words, taken before
+    the parameter existed — and max_cons = 64 ends on exactly BFHIP_AIR_MAX_CONSTRAINTS constraints, which the validator accepts."""
+    crcs = [3787532931, 2369096354, 1312251463, 2189620099, 3319918802, 4017957922, 3676917133, 2603008569, 2523549129, 882003699, 864611483, 3809035066]
+    for seed in range(12):
+        code = air_model.random_program(seed)[0]
+        assert zlib.crc32(b"".join(w.to_bytes(4, "little") for w in code)) == crcs[seed], seed
+        assert air_model.random_program(seed) == air_model.random_program(seed, max_cons=60)
+    code, n_cols, n_params, n_cons = air_model.random_program(7, n_cols=256, n_params=64, n_ops=3900, m_pool=96, q_pool=24, max_off=16, max_cons=64)
+    assert n_cons == 64 and pkg.AirProgram(code, n_cols, n_params).shape["n_constraints"] == 64
+    assert max(air_model.random_program(s, n_ops=2000)[3] for s in range(3)) == 60
+
+
+@pytest.mark.parametrize("log_size,log_expand", SIZES)
+def test_domain_denominators_invert_the_vanishing_polynomial_at_the_domains_points(log_size, log_expand):
+    """domain_denominators (Python integers on the x of G^index) times coset_vanishing (the model's QM31 arithmetic) at the same point is 1
+    at every row; the group indices are those of a circle domain: the second half holds the conjugates of the first, every index is odd
+    times 2^(30 - el), and no point lies on the trace domain."""
+    el = log_size + log_expand
+    n = 1 << el
+    g = air_model.domain_group_indices(log_size, log_expand)
+    den = air_model.domain_denominators(log_size, log_expand)
+    assert den.shape == (n,) and len(set(g.tolist())) == n
+    assert all(v % (1 << (30 - el)) == 0 and (v >> (30 - el)) & 1 for v in g.tolist())
+    d = air_model.bit_reverse(range(n), el)
+    natural = g[np.argsort(d)]                                      # indices in circle-domain order
+    assert np.array_equal(natural[n // 2:], (-natural[: n // 2]) % (1 << 31))
+    for row in range(n):
+        van = air_model.coset_vanishing(log_size, [air_model.circle_x(int(g[row])), 0, 0, 0, 0, 0, 0, 0])
+        assert van[1:] == [0, 0, 0] and van[0] * int(den[row]) % P == 1, (row, van)
+    # the kernel's table has one entry per row >> log_size: the model, which assumes nothing of the kind, agrees that this is enough
+    assert np.array_equal(den, np.repeat(den[:: 1 << log_size], 1 << log_size)) and len(set(den.tolist())) == 1 << log_expand
+
+
+def test_circle_generator_has_order_two_to_the_31():
+    assert air_model.circle_x(1 << 31) == 1 and air_model.circle_x(1 << 30) == P - 1 and air_model.circle_x(1 << 29) == 0
+    x, y = air_model.CIRCLE_GEN
+    assert (x * x + y * y) % P == 1
+
+
+@pytest.mark.parametrize("log_size,log_expand", SIZES)
+def test_offset_rows_is_the_offset_one_map_composed(log_size, log_expand):
+    """Offsets 1 .. 16 on domains of 4 to 256 rows (on the small ones the offset wraps the half coset several times): a permutation, the
+    offset-1 map applied `off` times, and the map of -off its inverse."""
+    n = 1 << (log_size + log_expand)
+    one, walk = air_model.offset_rows(log_size, log_expand, 1), np.arange(n)
+    for off in range(1, 17):
+        walk = one[walk]
+        fwd, back = air_model.offset_rows(log_size, log_expand, off), air_model.offset_rows(log_size, log_expand, -off)
+        assert sorted(fwd.tolist()) == list(range(n)), off
+        assert np.array_equal(fwd, walk), off
+        assert np.array_equal(back[fwd], np.arange(n)) and np.array_equal(fwd[back], np.arange(n)), off
+    assert np.array_equal(air_model.offset_rows(log_size, log_expand, 1 << log_size), np.arange(n))      # a full turn of the trace coset
+
+
+@pytest.mark.parametrize("cols,consts", field_inputs.CROSS, ids=["%s-%s" % c for c in field_inputs.CROSS])
+def test_model_q_mul_is_exact_at_saturated_values(cols, consts):
+    n = 96
+    x = np.stack(field_inputs.columns(cols, 3, 4, n)).astype(np.uint64)
+    y = field_inputs.const(consts, 5, 4 * n).reshape(n, 4).T.astype(np.uint64)
+    got = air_model.q_mul(x, y)
+    for j in range(n):
+        assert [int(v) for v in got[:, j]] == field_inputs.qm31_mul_int(x[:, j], y[:, j]), (j, x[:, j], y[:, j])
+
+
+def _quads_of(family, seed, n):
+    if family == "zero":
+        return [[0, 0, 0, 0] for _ in range(n)]
+    return field_inputs.const(family, seed, 4 * n).reshape(n, 4).tolist() if n else []
+
+
+SATURATED = ("max", "edge", "heavy", "zero")
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_numpy_model_agrees_with_the_point_evaluator_at_saturated_values(pkg, seed):
+    """Random programs with offsets up to +-16 on mask values, parameters and coefficients from the families max, edge, heavy and all-zero,
+    every crossing of the three: model.run(n = 1) == bfhip_air_eval_at_point times the vanishing polynomial. The host evaluator is C++ and
+    shares no code with the model or with the kernel."""
+    code, n_cols, n_params, n_cons = air_model.random_program(100 + seed, max_off=16)
+    prog = pkg.AirProgram(code, n_cols, n_params)
+    mask = prog.mask()
+    assert max(abs(off) for _, off in mask) > 2
+    log_size = 1 + seed % 5
+    ch = pkg.Channel((0, 0, 0, 0))
+    ch.mix_u64(700 + seed)
+    point = ch.draw_point()
+    van = air_model.coset_vanishing(log_size, point)
+    non_zero = 0
+    for fm in SATURATED:
+        for fp in SATURATED:
+            for fc in SATURATED:
+                mask_values, params, coeffs = _quads_of(fm, seed, len(mask)), _quads_of(fp, seed + 1, n_params), _quads_of(fc, seed + 2, n_cons)
+                got = prog.eval_at_point(log_size, point, mask_values, params, coeffs)
+                at = {m: air_model.q(v) for m, v in zip(mask, mask_values)}
+                model = [int(w) for w in air_model.run(code, lambda col, off: at[(col, off)], params, coeffs)[:, 0]]
+                assert pcs_replay.q_mul(got, van) == model, (fm, fp, fc)
+                non_zero += any(model)
+    print("seed", seed, "non-zero results:", non_zero, "of 64 (16 have all-zero coefficients)")
+    assert non_zero      # not only comparisons of zeros
 
 
 def test_builder_reuses_registers_and_keeps_the_order_of_first_use(pkg):

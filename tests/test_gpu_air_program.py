@@ -174,15 +174,7 @@ def _sweep(ctx, program, log_size, log_expand, lde, coeffs):
         return np.stack([ctx.download(p, n) for p in acc])
 
 
-def _circle_x(index):
-    """x coordinate of G^index, G = (2, 1268011823) the generator of the M31 circle group"""
-    mul = lambda p, q: ((p[0] * q[0] - p[1] * q[1]) % P, (p[0] * q[1] + p[1] * q[0]) % P)
-    res, cur = (1, 0), (2, 1268011823)
-    while index:
-        if index & 1:
-            res = mul(res, cur)
-        cur, index = mul(cur, cur), index >> 1
-    return res[0]
+_circle_x = air_model.circle_x      # x coordinate of G^index, G the generator of the M31 circle group
 
 
 @pytest.mark.parametrize("log_size", [4, 9])
@@ -220,6 +212,7 @@ def test_synthetic_air_on_larger_blowups(_ctx, pkg, _oracle, d, log_expand, log_
         for _ in range(log_size - 1):
             x = (2 * x * x - 1) % P
         assert v * x % P == 1, (i, v, x)
+    assert np.array_equal(den, air_model.domain_denominators(log_size, log_expand))      # the same for every row, from the model
     model = air_model.run(program.code, air_model.domain_reader(lde, log_size, log_expand), [], coeffs, n)
     assert np.array_equal(air_model.q_mul(model, air_model.from_m(den.astype(np.uint64))), acc)
 
