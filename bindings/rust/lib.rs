@@ -493,6 +493,27 @@ impl AirProgram {
                                        params.as_ptr() as *const u32, params.len() as u32, coeffs.as_ptr() as *const u32, coeffs.len() as u32, acc.as_ptr())
         })
     }
+    /// `bfhip_air_check`: stwo's `assert_constraints` on CanonicCoset(log_size) itself — per constraint, how many cells are non-zero and the
+    /// lowest of them; violations are a result, not an error. `cols` / `shifts` / `params` as for `eval_domain`, at 2^(log_size - shift) cells.
+    pub fn check(&self, ctx: &Context, log_size: u32, cols: &[*const u32], shifts: &[u32], params: &[Felt]) -> Result<sys::BfhipAirCheckReport, String> {
+        if !shifts.is_empty() && shifts.len() != cols.len() { return Err("one shift per column".into()); }
+        let mut rep = std::mem::MaybeUninit::<sys::BfhipAirCheckReport>::zeroed();
+        check(unsafe {
+            sys::bfhip_air_check(ctx.0, self.0, log_size, cols.as_ptr(), if shifts.is_empty() { std::ptr::null() } else { shifts.as_ptr() },
+                                 params.as_ptr() as *const u32, params.len() as u32, rep.as_mut_ptr())
+        })?;
+        Ok(unsafe { rep.assume_init() })      // plain integers: all-zero is a value
+    }
+    /// `bfhip_format_air_check`: "air check: ok", or the headline and one line per failing constraint.
+    pub fn format_check(report: &sys::BfhipAirCheckReport) -> Result<String, String> {
+        let mut need = 0usize;
+        let rc = unsafe { sys::bfhip_format_air_check(report, std::ptr::null_mut(), 0, &mut need) };
+        if rc != 0 && rc != -2 { return check(rc).map(|_| String::new()); }
+        let mut buf = vec![0u8; need];
+        check(unsafe { sys::bfhip_format_air_check(report, buf.as_mut_ptr() as *mut std::ffi::c_char, need, std::ptr::null_mut()) })?;
+        buf.pop();
+        String::from_utf8(buf).map_err(|e| e.to_string())
+    }
     /// `bfhip_air_eval_at_point`: stwo's PointEvaluator over the program; `mask_values` in `mask()` order.
     pub fn eval_at_point(&self, log_size: u32, point: &Point, mask_values: &[Felt], params: &[Felt], coeffs: &[Felt]) -> Result<Felt, String> {
         let mut out = [0u32; 4];

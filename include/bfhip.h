@@ -772,6 +772,45 @@ int32_t bfhip_air_eval_domain(bfhip_ctx* ctx, const bfhip_air* air, uint32_t log
 int32_t bfhip_air_eval_at_point(const bfhip_air* air, uint32_t log_size, const uint32_t point_h[8], const uint32_t* mask_values_h, uint32_t n_mask,
                                 const uint32_t* params_h, uint32_t n_params, const uint32_t* coeffs_h, uint32_t n_coeffs, uint32_t out_h[4]);
 
+/* ---- Constraint programs asserted on the trace domain: which constraint of ANY AIR is non-zero at which cell ---------------------------------
+ * stwo's `assert_constraints` for a program, the generic counterpart of bfhip_check_constraints (which runs one of 13 compiled-in AIRs). A wrong
+ * trace cell or a wrongly written constraint otherwise shows only after a whole commit, sweep and open, as a sampled composition value that is
+ * not bfhip_air_eval_at_point's ("OodsNotMatching"), naming neither constraint nor row. bfhip_air_eval_domain cannot stand in: it folds all
+ * constraints into one accumulator under random coefficients and divides by a polynomial that is zero on the trace domain.
+ *
+ * bfhip_air_check: ONE gfx950 interpreter kernel over CanonicCoset(log_size) itself, then one wave at the first bad cell, ONE read-back. No
+ *   coefficients, no vanishing polynomial, no accumulator; constraints are numbered in program order. Column k of cols_h holds 2^log_size
+ *   cells of CanonicCoset(log_size).circle_domain(), bit-reversed; with col_shifts_h[k] = s (0, or 2 <= s <= log_size; NULL = all 0) it holds
+ *   2^(log_size - s) cells and is read at cell >> s. A shifted column that the program reads at a non-zero offset is refused. "The row at
+ *   offset off" is the point plus off * CanonicCoset(log_size).step() on the trace domain itself: a move of off in coset order, the order
+ *   finalize_last's prefix sum runs in (bfhip_logup_program_generate). IsFirst is a column the caller passes: 1 at cell 0. A cell is a storage
+ *   index, as in bfhip_check_report. params_h = 4 * n_params canonical words; the count must be the program's. 1 <= log_size <= max_log_domain.
+ *   A context in a shard group is refused. Works while a session is open (its scratch is not the arena's: bfhip_ctx_memory out[3] is
+ *   unchanged by the call). Returns 0 whether or not the trace is valid — the verdict is in *out, and bfhip_last_error() is not touched by
+ *   violations; -1 only for bad arguments and HIP errors, with "bfhip_air_check: <rule>". Every field is an integer and does not depend on
+ *   the schedule. A trace that is wrong everywhere costs up to 130 atomics per 64 cells; a valid one costs its loads.
+ * bfhip_format_air_check (host only, no GPU): "air check: ok" for a report without violations; otherwise, lines joined by '\n':
+ *   "air check: <n> of <N> cells violate <k> of <K> constraints", then one line per failing constraint in constraint order:
+ *   "constraint <j>: <n> cells, first at cell <i>", with ", value (a, b, c, d)" appended for first_bad_constraint. buf / cap / need / -2 as in
+ *   bfhip_format_preflight.
+ * Layout (natural alignment, declaration order):
+ *   bfhip_air_check_report  1088 bytes: log_size 0, n_constraints 4, n_bad_cells 8, first_bad_cell 16, first_bad_constraint 24, reserved0 28,
+ *                                       first_bad_value 32, bad_per_constraint 48, first_cell_per_constraint 560, reserved 1072 */
+typedef struct bfhip_air_check_report {
+    uint32_t log_size, n_constraints;
+    uint64_t n_bad_cells;                     /* cells where at least one constraint is non-zero */
+    uint64_t first_bad_cell;                  /* lowest such storage index; UINT64_MAX if none */
+    int32_t  first_bad_constraint;            /* lowest constraint that is non-zero there; -1 if none */
+    uint32_t reserved0;
+    uint32_t first_bad_value[4];              /* its value there; a C_BASE constraint as (v, 0, 0, 0) */
+    uint64_t bad_per_constraint[64];          /* cells where constraint j is non-zero (BFHIP_AIR_MAX_CONSTRAINTS) */
+    uint64_t first_cell_per_constraint[64];   /* lowest cell where constraint j is non-zero; UINT64_MAX if none or j >= n_constraints */
+    uint64_t reserved[2];
+} bfhip_air_check_report;
+int32_t bfhip_air_check(bfhip_ctx* ctx, const bfhip_air* air, uint32_t log_size, const uint32_t* const* cols_h, const uint32_t* col_shifts_h,
+                        const uint32_t* params_h, uint32_t n_params, bfhip_air_check_report* out);
+int32_t bfhip_format_air_check(const bfhip_air_check_report* rep, char* buf, size_t cap, size_t* need);
+
 /* ---- Fraction programs: the logUp interaction trace of ANY AIR, on the GPU over the trace domain ---------------------------------------------
  * bfhip_logup_generate runs one of 13 compiled-in branches (`interaction_trace_evaluation` of memory/table.rs:485-518, processor/table.rs:456-529,
  * ...: the calls prove makes at mod.rs:596-687) and is built on their 16-fold replicated rows. A fraction program is what such a function hands

@@ -636,6 +636,22 @@ class Context:
                                            self._u32s([w for q in params for w in q]) if params else None, len(params),
                                            self._u32s([w for q in coeffs for w in q]) if coeffs else None, len(coeffs), self._ptr_array(acc_ptrs)))
 
+    def air_check(self, program, log_size, col_ptrs, params, col_shifts=None):
+        """bfhip_air_check: the constraints of an AirProgram asserted on the trace domain CanonicCoset(log_size) itself (stwo's
+        assert_constraints for any AIR). col_ptrs: one device column per program column (2^(log_size - shift) cells); params: QM31 values (4
+        words each). Returns the AirCheckReport (as_dict() for named fields, format_air_check for the text); violations are a result, not
+        an error."""
+        params = [list(q) for q in params]
+        if any(len(q) != 4 for q in params):
+            raise ValueError("a parameter is 4 words")
+        if len(col_ptrs) != program.shape["n_cols"] or (col_shifts is not None and len(col_shifts) != len(col_ptrs)):
+            raise ValueError("one column pointer (and shift) per program column")
+        rep = AirCheckReport()
+        _check(lib().bfhip_air_check(self._h, program._h, int(log_size), self._ptr_array(col_ptrs) if col_ptrs else None,
+                                     None if col_shifts is None or not col_ptrs else self._u32s(col_shifts),
+                                     self._u32s([w for q in params for w in q]) if params else None, len(params), ctypes.byref(rep)))
+        return rep
+
     def logup_program_generate(self, program, log_size, col_ptrs, params, out_col_ptrs, col_shifts=None):
         """bfhip_logup_program_generate: the logUp interaction trace of a LogupProgram on CanonicCoset(log_size).circle_domain(). col_ptrs: one
         device column per program column (2^(log_size - shift) cells); params: QM31 values (4 words each); out_col_ptrs: 4 full-size
@@ -1325,6 +1341,34 @@ class AirProgram:
         _check(lib().bfhip_air_eval_at_point(self._h, int(log_size), Context._u32s(point8), flat(mask_values), len(mask_values), flat(params), len(params),
                                              flat(coeffs), len(coeffs), out))
         return [int(v) for v in out]
+
+
+class AirCheckReport(ctypes.Structure):
+    """include/bfhip.h `bfhip_air_check_report` (1088 bytes): an AirProgram asserted on its trace domain (Context.air_check)."""
+    _fields_ = [("log_size", ctypes.c_uint32), ("n_constraints", ctypes.c_uint32), ("n_bad_cells", ctypes.c_uint64), ("first_bad_cell", ctypes.c_uint64),
+                ("first_bad_constraint", ctypes.c_int32), ("reserved0", ctypes.c_uint32), ("first_bad_value", ctypes.c_uint32 * 4),
+                ("bad_per_constraint", ctypes.c_uint64 * 64), ("first_cell_per_constraint", ctypes.c_uint64 * 64), ("reserved", ctypes.c_uint64 * 2)]
+
+    def as_dict(self):
+        """Named fields; the per-constraint lists have n_constraints entries. first_bad_cell and first_cell_per_constraint[j] are None where
+        nothing fails (first_bad_constraint is -1 then)."""
+        cell = lambda v: None if v == NO_CELL else int(v)
+        k = min(int(self.n_constraints), 64)
+        return {"log_size": int(self.log_size), "n_constraints": int(self.n_constraints), "ok": self.n_bad_cells == 0, "n_bad_cells": int(self.n_bad_cells),
+                "first_bad_cell": cell(self.first_bad_cell), "first_bad_constraint": int(self.first_bad_constraint),
+                "first_bad_value": [int(v) for v in self.first_bad_value], "bad_per_constraint": [int(v) for v in self.bad_per_constraint[:k]],
+                "first_cell_per_constraint": [cell(v) for v in self.first_cell_per_constraint[:k]]}
+
+
+def format_air_check(report):
+    """bfhip_format_air_check of an AirCheckReport (host only, no GPU): "air check: ok", or the headline and one line per failing constraint."""
+    need = ctypes.c_size_t()
+    rc = lib().bfhip_format_air_check(ctypes.byref(report), None, ctypes.c_size_t(0), ctypes.byref(need))
+    if rc not in (0, -2):
+        raise BfhipError(lib().bfhip_last_error().decode())
+    buf = ctypes.create_string_buffer(need.value)
+    _check(lib().bfhip_format_air_check(ctypes.byref(report), buf, ctypes.c_size_t(need.value), None))
+    return buf.value.decode()
 
 
 LOGUP_FRAC, LOGUP_END_COL, LOGUP_MAX_COLUMNS, LOGUP_MAX_FRACTIONS = 15, 16, 8, 32
