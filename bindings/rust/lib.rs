@@ -575,3 +575,73 @@ impl Drop for LogupProgram {
         unsafe { sys::bfhip_logup_destroy(self.0) };
     }
 }
+
+// ---- relation programs (`include/bfhip.h` "Relation programs"): the lookup tuples of ANY AIR that do not cancel --------------------------------
+// A component's `add_to_relation(relation, multiplicity, values)` calls, recorded once as bytecode: the base-field opcodes of a constraint
+// program, plus `sys::BFHIP_REL_WORD` {-, a} (append m[a] to the pending tuple) and `sys::BFHIP_REL_ENTRY` {relation, a} (the entry, with
+// multiplicity m[a]). stwo's relation tracker for an AIR the library has never seen: run it in front of the session, it needs no lookup
+// elements.
+
+/// `bfhip_relation_program_shape`.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct RelationShape { pub n_cols: u32, pub n_relations: u32, pub n_entries: u32, pub n_instr: u32, pub m_regs: u32 }
+
+/// One table of `RelationProgram::summary`: a program over a component's columns. `cols`: one device column per program column; the program
+/// is evaluated once per 2^row_shift cells; `shifts`: column k holds 2^(log_size - shifts[k]) words (empty = every column holds one word per
+/// evaluated row).
+pub struct RelationProgramTable<'a> { pub program: &'a RelationProgram, pub log_size: u32, pub row_shift: u32, pub cols: &'a [*const u32], pub shifts: &'a [u32] }
+
+/// A validated relation program (`bfhip_relation_program`). Host only to create, inspect and evaluate on one row.
+pub struct RelationProgram(*mut sys::BfhipRelationProgram);
+
+impl RelationProgram {
+    /// `bfhip_relation_program_create`: `relation_words[r]` = the width of relation r (1 to 7). A refusal names the instruction index and the rule.
+    pub fn new(code: &[u32], n_cols: u32, relation_words: &[u32]) -> Result<Self, String> {
+        let mut p = std::ptr::null_mut();
+        let widths: Vec<u32> = if relation_words.is_empty() { vec![0] } else { relation_words.to_vec() };
+        check(unsafe { sys::bfhip_relation_program_create(code.as_ptr(), code.len(), n_cols, widths.as_ptr(), relation_words.len() as u32, &mut p) })?;
+        Ok(RelationProgram(p))
+    }
+    pub fn shape(&self) -> Result<RelationShape, String> {
+        let mut o = [0u32; 8];
+        check(unsafe { sys::bfhip_relation_program_shape(self.0, o.as_mut_ptr()) })?;
+        Ok(RelationShape { n_cols: o[0], n_relations: o[1], n_entries: o[2], n_instr: o[3], m_regs: o[4] })
+    }
+    /// `bfhip_relation_program_eval_row` (host only): the entries of one row in program order, zero multiplicities included, as
+    /// (relation, multiplicity, the tuple zero padded to 7 words).
+    pub fn eval_row(&self, col_values: &[u32]) -> Result<Vec<(u32, u32, [u32; 7])>, String> {
+        let n_entries = self.shape()?.n_entries as usize;
+        if col_values.len() != self.shape()?.n_cols as usize { return Err("one value per program column".into()); }
+        let (mut rel, mut mult, mut tup, mut n) = (vec![0u32; n_entries], vec![0u32; n_entries], vec![0u32; 7 * n_entries], 0u32);
+        check(unsafe { sys::bfhip_relation_program_eval_row(self.0, col_values.as_ptr(), rel.as_mut_ptr(), mult.as_mut_ptr(), tup.as_mut_ptr(), n_entries as u32, &mut n) })?;
+        Ok((0..n as usize).map(|e| { let mut t = [0u32; 7]; t.copy_from_slice(&tup[7 * e..7 * e + 7]); (rel[e], mult[e], t) }).collect())
+    }
+    /// `bfhip_relation_program_summary` over 1..64 tables whose programs share one list of relations: per relation its counts and up to
+    /// `max_entries` tuples whose multiplicities do not cancel, in lexicographic order. An imbalance is a result, not an `Err`. Refused while a
+    /// commitment-scheme session is open on the context.
+    pub fn summary(ctx: &Context, tables: &[RelationProgramTable], max_entries: u32) -> Result<(Vec<sys::BfhipRelationReport>, Vec<sys::BfhipRelationEntry>), String> {
+        let first = tables.first().ok_or("1 to 64 tables")?;
+        let n_rel = first.program.shape()?.n_relations as usize;
+        for t in tables {
+            if t.cols.len() != t.program.shape()?.n_cols as usize || (!t.shifts.is_empty() && t.shifts.len() != t.cols.len()) { return Err("one column pointer (and shift) per program column".into()); }
+        }
+        let raw: Vec<sys::BfhipRelationProgramTable> = tables.iter().map(|t| sys::BfhipRelationProgramTable {
+            program: t.program.0, log_size: t.log_size, row_shift: t.row_shift, cols_h: t.cols.as_ptr(),
+            col_shifts_h: if t.shifts.is_empty() { std::ptr::null() } else { t.shifts.as_ptr() } }).collect();
+        let mut reports = vec![sys::BfhipRelationReport::default(); n_rel];
+        let mut entries = vec![sys::BfhipRelationEntry::default(); n_rel * max_entries as usize];
+        let entries_ptr = if max_entries == 0 { std::ptr::null_mut() } else { entries.as_mut_ptr() };
+        check(unsafe { sys::bfhip_relation_program_summary(ctx.0, raw.as_ptr(), raw.len() as u32, n_rel as u32, reports.as_mut_ptr(), entries_ptr, max_entries) })?;
+        let mut listed = Vec::new();
+        for (r, rep) in reports.iter().enumerate() {
+            listed.extend_from_slice(&entries[r * max_entries as usize..r * max_entries as usize + rep.n_reported as usize]);
+        }
+        Ok((reports, listed))
+    }
+}
+
+impl Drop for RelationProgram {
+    fn drop(&mut self) {
+        unsafe { sys::bfhip_relation_program_destroy(self.0) };
+    }
+}

@@ -658,7 +658,7 @@ int32_t bfhip_brainfuck_composition_at_point(const uint32_t log_sizes_h[13], con
  * from, the arena, or change what the session was created under:
  *   bfhip_prove_trace, bfhip_prove_brainfuck, bfhip_prove_registers (and every pool job or batch that lands on the context),
  *   bfhip_trace_create, bfhip_trace_create_ram, bfhip_trace_create_from_registers (the GPU table builders' scratch),
- *   bfhip_trace_check, bfhip_check_constraints, bfhip_relation_summary, bfhip_trace_relations,
+ *   bfhip_trace_check, bfhip_check_constraints, bfhip_relation_summary, bfhip_trace_relations, bfhip_relation_program_summary,
  *   bfhip_ctx_set_conventions, bfhip_ctx_set_pcs_config, bfhip_ctx_join_local_group, bfhip_ctx_join_rccl_group, bfhip_ctx_destroy,
  *   and a second bfhip_pcs_create.
  * Everything else keeps working, which is what the caller's constraint sweep needs: bfhip_malloc / bfhip_free / bfhip_upload / bfhip_download /
@@ -850,6 +850,72 @@ int32_t bfhip_logup_destroy(bfhip_logup* lp);
 int32_t bfhip_logup_shape(const bfhip_logup* lp, uint32_t out[8]);
 int32_t bfhip_logup_program_generate(bfhip_ctx* ctx, const bfhip_logup* lp, uint32_t log_size, const uint32_t* const* cols_h, const uint32_t* col_shifts_h,
                                      const uint32_t* params_h, uint32_t n_params, uint32_t* const* out_cols_h, uint32_t claimed_sum_h[4]);
+
+/* ---- Relation programs: the lookup tuples of ANY AIR that do not cancel ------------------------------------------------------------------------
+ * bfhip_relation_summary / bfhip_trace_relations know the three Brainfuck relations and the 13 table layouts. An AIR proved through bfhip_pcs_* +
+ * bfhip_air_* + bfhip_logup_* whose lookups do not balance learns only that its claimed sums do not add up to zero; a
+ * fraction program cannot name the tuple to blame, its denominators are already z - sum alpha^i v_i. A relation program is what a component's
+ * `add_to_relation(relation, multiplicity, values)` calls are, as data — stwo's relation tracker, the tool it ships beside `assert_constraints`:
+ * a constraint program's bytecode (same four-word instructions, same m[] register file, same caps: 96 m registers, 4096 instructions, 256
+ * columns), base field only, with two opcodes that exist only here:
+ *   BFHIP_REL_WORD   -, a          append m[a] to the pending tuple
+ *   BFHIP_REL_ENTRY  relation, a   one add_to_relation: the entry (relation `dst`, the pending tuple, multiplicity m[a]); the pending tuple is then empty
+ * A relation program reads a row's own cells, and the multiplicity of an entry is an M31 value, as on the main trace. Admitted: M_COL at offset
+ * 0 (a "next" value is a column, as in fraction programs), M_CONST, M_ADD, M_SUB, M_MUL, M_NEG, REL_WORD, REL_ENTRY. There are no parameters.
+ * Relations are numbered 0 .. n_relations - 1 by the caller; relation r has relation_words_h[r] words, 1 to 7 (what bfhip_relation_entry.tuple
+ * holds: the structs of bfhip_relation_summary are reused unchanged).
+ *
+ * bfhip_relation_program_create (host only): every rule of bfhip_air_create that applies (opcode, register range, read before write, column
+ *   within n_cols, v < p, the instruction and column caps), and: every Q_* opcode, C_BASE, C_EXT, FRAC and END_COL are refused; M_COL at a
+ *   non-zero offset is refused; a relation index not below n_relations, an ENTRY whose pending tuple has not exactly that relation's width, a
+ *   WORD when 7 words are pending, a write to a register that is a word of the pending tuple (the tuple holds registers, not copies, until
+ *   its ENTRY), a WORD that no ENTRY follows, a program without any ENTRY or with more than 32 =
+ *   BFHIP_RELATION_PROGRAM_MAX_ENTRIES, n_relations outside 1 .. 16 = BFHIP_RELATION_PROGRAM_MAX_RELATIONS and a width outside 1 .. 7 =
+ *   BFHIP_RELATION_PROGRAM_MAX_WORDS are refused. Each refusal is -1 with "bfhip_relation_program_create: instruction <i>: <rule>" (rules
+ *   about the program as a whole name the instruction count). bfhip_air_create and bfhip_logup_create keep refusing opcodes 17 and 18.
+ * bfhip_relation_program_shape: out = {columns, relations, entries, instructions, m registers used, 0, 0, 0}.
+ * bfhip_relation_program_eval_row (host only): the entries of ONE row in program order, zero multiplicities included: col_values_h = n_cols
+ *   canonical words; entry e is (relations_out[e], mults_out[e], tuples_out[7 e ..], zero padded). *n = the program's entries; -2
+ *   ("capacity") when cap < *n; all three outputs NULL with cap 0: size query.
+ * bfhip_relation_program_summary: bfhip_relation_summary's semantics, word for word, over 1..64 tables of any programs. Table t is a program
+ *   and its columns: column k holds 2^(log_size - s_k) words (s_k = col_shifts_h[k]; NULL = every s_k = row_shift) of cells of
+ *   CanonicCoset(log_size).circle_domain(), bit-reversed, and the program is evaluated ONCE per 2^row_shift cells: row r of 2^(log_size -
+ *   row_shift) stands for cell r << row_shift and reads column k at (r << row_shift) >> s_k. Row-granular Brainfuck tables are row_shift 4 with
+ *   NULL shifts; full-size columns of a session are row_shift 0. A row's entry with multiplicity 0 is no entry; multiplicity 1 counts as a
+ *   yield, p - 1 as a use, anything else as "other"; net = the canonical M31 sum; a tuple is reported iff net != 0. out[r] = relation r,
+ *   r < n_relations; its reported tuples, in lexicographic order of their words, the first cap_per_relation of them, go to entries_h + r *
+ *   cap_per_relation; first_* = the lowest (table index, row r). entries_h == NULL with cap 0 gives the counts only. Counts are per evaluated
+ *   ROW: with row_shift = s every row stands for 2^s cells, and the logUp sum sees 2^s x net. A relation no program of the list adds to gets a
+ *   report of zeros with its n_words set. Every program of the list must have been created with this n_relations and the same widths:
+ *   otherwise -1, naming the table. Every field is an integer and the same whatever the schedule: entries stand in (table, row, program
+ *   order), no atomics in the extraction. Uses the context's arena (reset as a proof resets it; bfhip_ctx_memory out[3] is put back) and is
+ *   therefore refused while a commitment-scheme session is open: the author's check belongs in front of bfhip_pcs_create, it needs no lookup
+ *   elements. Returns 0 whether or not anything is unbalanced, and bfhip_last_error() is not touched by imbalances; -1 with
+ *   "bfhip_relation_program_summary: <rule>" for null arguments, n_tables outside 1..64, log_size outside [1, max_log_domain], row_shift or a
+ *   column shift above log_size, more than 2^31 (rows x ENTRY instructions of one relation) in total, a context in a shard group, and HIP
+ *   errors.
+ * Not built (each would be half a feature): tuples wider than 7 words (a new entry layout), extension-field multiplicities, column offsets,
+ * use inside an open session, a generic preflight, shard groups.
+ * Layout (natural alignment, declaration order):
+ *   bfhip_relation_program_table  32 bytes: program 0, log_size 8, row_shift 12, cols_h 16, col_shifts_h 24 */
+enum { BFHIP_REL_WORD = 17, BFHIP_REL_ENTRY = 18, BFHIP_RELATION_PROGRAM_MAX_RELATIONS = 16, BFHIP_RELATION_PROGRAM_MAX_WORDS = 7,
+       BFHIP_RELATION_PROGRAM_MAX_ENTRIES = 32 };
+typedef struct bfhip_relation_program bfhip_relation_program;
+int32_t bfhip_relation_program_create(const uint32_t* code, size_t n_words, uint32_t n_cols, const uint32_t* relation_words_h, uint32_t n_relations,
+                                      bfhip_relation_program** out);
+int32_t bfhip_relation_program_destroy(bfhip_relation_program* rp);
+int32_t bfhip_relation_program_shape(const bfhip_relation_program* rp, uint32_t out[8]);
+int32_t bfhip_relation_program_eval_row(const bfhip_relation_program* rp, const uint32_t* col_values_h, uint32_t* relations_out, uint32_t* mults_out,
+                                        uint32_t* tuples_out, uint32_t cap, uint32_t* n);
+typedef struct bfhip_relation_program_table {
+    const bfhip_relation_program* program;
+    uint32_t log_size;                 /* the component's trace: 2^log_size cells */
+    uint32_t row_shift;                /* 0..log_size: ONE evaluation per 2^row_shift cells */
+    const uint32_t* const* cols_h;     /* host array of n_cols device pointers */
+    const uint32_t* col_shifts_h;      /* host array of n_cols shifts; NULL = every s_k = row_shift */
+} bfhip_relation_program_table;
+int32_t bfhip_relation_program_summary(bfhip_ctx* ctx, const bfhip_relation_program_table* tables, uint32_t n_tables, uint32_t n_relations,
+                                       bfhip_relation_report* out, bfhip_relation_entry* entries_h, uint32_t cap_per_relation);
 
 /* Host-only pieces of the drop-in (usable without a GPU): the Brainfuck compiler (crates/brainfuck_vm/src/compiler.rs:17-37), the VM
  * (crates/brainfuck_vm/src/machine.rs:141-238; trace rows are 7 u32: clk, ip, ci, ni, mp, mv, mvi) and the 13 table builders

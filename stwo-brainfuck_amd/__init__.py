@@ -227,9 +227,10 @@ class RelationEntry(ctypes.Structure):
                 ("first_yield_table", ctypes.c_int32), ("first_use_table", ctypes.c_int32), ("first_yield_row", ctypes.c_uint64), ("first_use_row", ctypes.c_uint64),
                 ("reserved", ctypes.c_uint32 * 2)]
 
-    def as_dict(self):
-        """Named fields; tuple cut to n_words; first_yield / first_use = (table index, row) or None."""
-        return {"relation": int(self.relation), "name": RELATION_NAMES[self.relation], "tuple": tuple(int(v) for v in self.tuple[: self.n_words]), "net": int(self.net),
+    def as_dict(self, names=None):
+        """Named fields; tuple cut to n_words; first_yield / first_use = (table index, row) or None. names: the relations' names (None =
+        RELATION_NAMES, the three Brainfuck relations)."""
+        return {"relation": int(self.relation), "name": (RELATION_NAMES if names is None else names)[self.relation], "tuple": tuple(int(v) for v in self.tuple[: self.n_words]), "net": int(self.net),
                 "n_yield": int(self.n_yield), "n_use": int(self.n_use), "n_other": int(self.n_other),
                 "first_yield": None if self.first_yield_table < 0 else (int(self.first_yield_table), int(self.first_yield_row)),
                 "first_use": None if self.first_use_table < 0 else (int(self.first_use_table), int(self.first_use_row))}
@@ -240,14 +241,20 @@ class RelationReport(ctypes.Structure):
     _fields_ = [("relation", ctypes.c_uint32), ("n_words", ctypes.c_uint32), ("n_entries", ctypes.c_uint64), ("n_tuples", ctypes.c_uint64),
                 ("n_unbalanced", ctypes.c_uint64), ("n_reported", ctypes.c_uint64), ("reserved", ctypes.c_uint32 * 2)]
 
-    def as_dict(self):
-        return {"relation": int(self.relation), "name": RELATION_NAMES[self.relation], "n_words": int(self.n_words), "n_entries": int(self.n_entries),
+    def as_dict(self, names=None):
+        return {"relation": int(self.relation), "name": (RELATION_NAMES if names is None else names)[self.relation], "n_words": int(self.n_words), "n_entries": int(self.n_entries),
                 "n_tuples": int(self.n_tuples), "n_unbalanced": int(self.n_unbalanced), "n_reported": int(self.n_reported)}
 
 
 class RelationTable(ctypes.Structure):
     """include/bfhip.h `bfhip_relation_table`."""
     _fields_ = [("component", ctypes.c_int32), ("log_size", ctypes.c_uint32), ("main_rows_h", ctypes.POINTER(ctypes.c_void_p))]
+
+
+class RelationProgramTable(ctypes.Structure):
+    """include/bfhip.h `bfhip_relation_program_table` (32 bytes): one table of Context.relation_program_summary."""
+    _fields_ = [("program", ctypes.c_void_p), ("log_size", ctypes.c_uint32), ("row_shift", ctypes.c_uint32), ("cols_h", ctypes.POINTER(ctypes.c_void_p)),
+                ("col_shifts_h", ctypes.POINTER(ctypes.c_uint32))]
 
 
 def format_relation_entry(entry, table_names=None):
@@ -693,6 +700,36 @@ class Context:
             arr[t] = RelationTable(comp, log_size, None if ptrs is None else ctypes.cast(ptrs, ctypes.POINTER(ctypes.c_void_p)))
         names = ["%s[%d]" % (COMPONENT_NAMES[c] if 0 <= c < 13 else "?", t) for t, (c, _, _) in enumerate(tables)]
         return _relation_result(lambda reps, ents, cap: lib().bfhip_relation_summary(self._h, arr, len(tables), reps, ents, cap), max_entries, names)
+
+    def relation_program_summary(self, tables, max_entries=64, relation_names=None, table_names=None):
+        """bfhip_relation_program_summary: the lookup tuples of ANY AIR that do not cancel — relation_summary for RelationPrograms. tables:
+        (program, log_size, row_shift, col_ptrs) or (program, log_size, row_shift, col_ptrs, col_shifts) each: one device column per program
+        column, the program evaluated once per 2^row_shift cells (row-granular Brainfuck tables: row_shift 4; full-size session columns: 0);
+        col_shifts None = every column holds one word per evaluated row. All programs share one list of relations. Returns a RelationResult
+        (reports and entries for every relation of the programs); relation_names default to "relation <r>", table_names to "table <t>";
+        imbalances are a result, not an error. Refused while a PcsSession is open on the context: run it in front of the session."""
+        if not tables:
+            raise BfhipError("bfhip_relation_program_summary: 1 to 64 tables, got 0")
+        n_rel = tables[0][0].shape["n_relations"]
+        keep, arr = [], (RelationProgramTable * len(tables))()
+        for t, tab in enumerate(tables):
+            program, log_size, row_shift, ptrs = tab[:4]
+            shifts = tab[4] if len(tab) > 4 else None
+            if len(ptrs) != program.shape["n_cols"] or (shifts is not None and len(shifts) != len(ptrs)):
+                raise ValueError("table %d: one column pointer (and shift) per program column" % t)
+            pa = self._ptr_array(ptrs) if ptrs else None
+            sa = None if shifts is None or not ptrs else self._u32s(shifts)
+            keep.append((pa, sa))
+            arr[t] = RelationProgramTable(program._h, int(log_size), int(row_shift), None if pa is None else ctypes.cast(pa, ctypes.POINTER(ctypes.c_void_p)),
+                                          None if sa is None else ctypes.cast(sa, ctypes.POINTER(ctypes.c_uint32)))
+        rel_names = ["relation %d" % r for r in range(n_rel)] if relation_names is None else list(relation_names)
+        if len(rel_names) != n_rel:
+            raise ValueError("one name per relation")
+        reps = (RelationReport * n_rel)()
+        ents = (RelationEntry * (n_rel * max_entries))() if max_entries else None
+        _check(lib().bfhip_relation_program_summary(self._h, arr, len(tables), n_rel, reps, ents, max_entries))
+        return RelationResult([r.as_dict(rel_names) for r in reps], [ents[k * max_entries + i].as_dict(rel_names) for k in range(n_rel) for i in range(reps[k].n_reported)],
+                              ["table %d" % t for t in range(len(tables))] if table_names is None else list(table_names))
 
     def accumulate_quotients(self, log_size, col_ptrs, n_samples, sample_points, sample_values, random_coeff4, out_ptrs, col_shifts=None):
         """QuotientOps::accumulate_quotients for the columns of one LDE size."""
@@ -1400,6 +1437,49 @@ class LogupProgram:
             pass
 
 
+REL_WORD, REL_ENTRY, RELATION_PROGRAM_MAX_RELATIONS, RELATION_PROGRAM_MAX_WORDS, RELATION_PROGRAM_MAX_ENTRIES = 17, 18, 16, 7, 32
+
+
+class RelationProgram:
+    """bfhip_relation_program: a validated relation program (include/bfhip.h "Relation programs") — the base-field opcodes of a constraint
+    program with WORD (append m[a] to the pending tuple) and ENTRY (add_to_relation(relation, multiplicity m[a], the pending tuple)).
+    relation_words[r] = the width of relation r, 1 to 7. Host only to create and for eval_row; Context.relation_program_summary runs it over
+    a component's cells. A refused program raises BfhipError naming the instruction index and the rule."""
+
+    def __init__(self, code, n_cols, relation_words):
+        self.code = [int(w) & 0xFFFFFFFF for w in code]
+        self.relation_words = [int(w) for w in relation_words]
+        self._h = ctypes.c_void_p()
+        arr = (ctypes.c_uint32 * max(1, len(self.code)))(*self.code)
+        widths = (ctypes.c_uint32 * max(1, len(self.relation_words)))(*self.relation_words)
+        _check(lib().bfhip_relation_program_create(arr, ctypes.c_size_t(len(self.code)), int(n_cols), widths, len(self.relation_words), ctypes.byref(self._h)))
+        out = (ctypes.c_uint32 * 8)()
+        _check(lib().bfhip_relation_program_shape(self._h, out))
+        self.shape = {"n_cols": out[0], "n_relations": out[1], "n_entries": out[2], "n_instr": out[3], "m_regs": out[4]}
+
+    def close(self):
+        if self._h:
+            lib().bfhip_relation_program_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def eval_row(self, col_values):
+        """bfhip_relation_program_eval_row (host only): the entries of ONE row, in program order, zero multiplicities included, as
+        [(relation, multiplicity, tuple)] with the tuple cut to the relation's width. col_values: n_cols canonical words."""
+        if len(col_values) != self.shape["n_cols"]:
+            raise ValueError("one value per program column")
+        n = ctypes.c_uint32()
+        cap = self.shape["n_entries"]
+        rels, mults, tups = (ctypes.c_uint32 * cap)(), (ctypes.c_uint32 * cap)(), (ctypes.c_uint32 * (7 * cap))()
+        _check(lib().bfhip_relation_program_eval_row(self._h, Context._u32s(col_values) if len(col_values) else None, rels, mults, tups, cap, ctypes.byref(n)))
+        return [(int(rels[e]), int(mults[e]), tuple(int(v) for v in tups[7 * e: 7 * e + self.relation_words[rels[e]]])) for e in range(n.value)]
+
+
 class AirExpr:
     """A value of an AirBuilder: kind 'm' (M31, a base-field column expression) or 'q' (QM31). Operators + - * and unary -; a Python int
     stands for const(int). m op q promotes the m side (Q_FROM_M), except a product, which is Q_MULM."""
@@ -1490,6 +1570,17 @@ class AirBuilder:
         """BFHIP_LOGUP_END_COL: close the open logUp column (finalize_col); the next frac() opens the next one."""
         self._emit(LOGUP_END_COL, None)
 
+    def relation_entry(self, relation, multiplicity, values):
+        """BFHIP_REL_WORD per value, then BFHIP_REL_ENTRY: one add_to_relation(relation, multiplicity, values). Base-field values only.
+        Relation programs only: see relation_program()."""
+        mult, values = self._value(multiplicity), [self._value(v) for v in values]
+        if mult.kind != "m" or any(v.kind != "m" for v in values):
+            raise ValueError("a relation entry takes base-field values (kind 'm')")
+        for v in values:
+            self._emit(REL_WORD, None, (v.id,))
+        # the words are sources of the ENTRY too: the interpreters read them there, so their registers live until then
+        self._emit(REL_ENTRY, None, (mult.id,) + tuple(v.id for v in values), imm=(int(relation),))
+
     def code(self):
         """The bytecode (a flat list of u32 words). Raises ValueError if the program needs more registers than the caps."""
         import heapq
@@ -1528,6 +1619,10 @@ class AirBuilder:
                 words += [op, 0, regs[0], 0]
             elif op == LOGUP_END_COL:
                 words += [op, 0, 0, 0]
+            elif op == REL_WORD:
+                words += [op, 0, regs[0], 0]
+            elif op == REL_ENTRY:
+                words += [op, imm[0] & 0xFFFFFFFF, regs[0], 0]
             else:
                 words += [op, dst, regs[0], regs[1] if len(regs) > 1 else 0]
         return words
@@ -1543,6 +1638,13 @@ class AirBuilder:
         cols = [imm[0] + (4 if op == AIR_Q_COL else 1) for op, _, _, imm in self._ops if op in (AIR_M_COL, AIR_Q_COL)]
         pars = [imm[0] + 1 for op, _, _, imm in self._ops if op == AIR_Q_PARAM]
         return LogupProgram(self.code(), max(cols, default=0) if n_cols is None else n_cols, max(pars, default=0) if n_params is None else n_params)
+
+
+    def relation_program(self, relation_words, n_cols=None):
+        """RelationProgram of the bytecode (relation_entry() instead of constraint()); relation_words[r] = the width of relation r; n_cols
+        defaults as for program()."""
+        cols = [imm[0] + (4 if op == AIR_Q_COL else 1) for op, _, _, imm in self._ops if op in (AIR_M_COL, AIR_Q_COL)]
+        return RelationProgram(self.code(), max(cols, default=0) if n_cols is None else n_cols, relation_words)
 
 
 def _q_mul(x, y):
@@ -1724,3 +1826,37 @@ def brainfuck_logup_program(component):
         column(t(7)[0] - one, combine("processor", t(0, 1, 2, 3, 4, 5, 6)))
     names = ["%s.%s" % (r, p) for r in ("memory", "instruction", "processor") for p in ["z"] + ["alpha^%d" % i for i in range(7)]]
     return b.logup_program(n_cols=n_main, n_params=BRAINFUCK_LOGUP_N_PARAMS), names
+
+
+BRAINFUCK_RELATION_WORDS = (3, 3, 7)
+
+
+def brainfuck_relation_program(component):
+    """The `add_to_relation` calls of component 0..12 of the Brainfuck AIR as a relation program — restated from the table of
+    include/bfhip.h "the lookup tuples that do not cancel" (components/**/component.rs). Returns (RelationProgram, relation names).
+    Columns: the n_main main-trace columns. Relations: 0 Memory (clk, mp, mv), 1 Instruction (ip, ci, ni), 2 Processor (clk, ip, ci, ni, mp,
+    mv, mvi). Multiplicities d - 1 (a use), 1 - d (a yield) or -1; the Processor adds one entry to each relation."""
+    if not 0 <= component < 13:
+        raise ValueError("component 0..12")
+    b = AirBuilder()
+    n_main = _BF_N_MAIN[component]
+    t = lambda *js: [b.col(j) for j in js]
+    one = b.const(1)
+    if component == 0:
+        b.relation_entry(0, t(3)[0] - one, t(0, 1, 2))
+    elif component == 1:
+        b.relation_entry(1, t(3)[0] - one, t(0, 1, 2))
+    elif component == 2:
+        b.relation_entry(1, one - t(3)[0], t(0, 1, 2))
+    elif component == 3:
+        num = one - t(7)[0]
+        b.relation_entry(0, num, t(0, 4, 5))
+        b.relation_entry(1, num, t(1, 2, 3))
+        b.relation_entry(2, num, t(0, 1, 2, 3, 4, 5, 6))
+    elif component in (4, 5):
+        b.relation_entry(2, t(11)[0] - one, t(0, 1, 2, 3, 4, 5, 6))
+    elif component == 12:
+        b.relation_entry(2, b.const(P - 1), t(0, 1, 2, 3, 4, 5, 6))
+    else:
+        b.relation_entry(2, t(7)[0] - one, t(0, 1, 2, 3, 4, 5, 6))
+    return b.relation_program(BRAINFUCK_RELATION_WORDS, n_cols=n_main), RELATION_NAMES

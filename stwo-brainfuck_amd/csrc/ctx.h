@@ -289,6 +289,13 @@ void shared_preprocessed_invalidate(SharedPreprocessed* sp);
 // given back, nothing is reset (the tables themselves may sit in the arena)
 void relations_in_proof(Ctx& c, const u32* const* const cols[N_COMPONENTS], const u32 log_sizes[N_COMPONENTS], bfhip_relation_report* out,
                         bfhip_relation_entry* entries_h, u32 cap);
+// relations.hip: steps (2) to (5) of a relation summary — sort, segment, net, first yield and first use, report — over n >= 1 entries, shared by
+// the compiled front end (relations.hip) and the relation programs' (relation_program.hip). The entries are SoA arena columns of n words that
+// this function allocates; `emit` enqueues the launches that fill them, on the context's stream, timed under the profiler's name emit_scope
+// (NULL: as part of "relations_sort", where the compiled path has always had them). rep: relation and n_words set by the caller.
+struct RelEntries { u32* w[7]; u32* num; u64* origin; };            // tuple words, multiplicity, (table << 32 | row)
+void relation_aggregate(Ctx& c, u32 relation, u32 n_words, u32 n, u32 cap, bfhip_relation_report& rep, bfhip_relation_entry* entries_h,
+                        const std::function<void(const RelEntries&)>& emit, const char* emit_scope = nullptr);
 
 void mailbox_launch(hipStream_t s, const u32* d_flag, u32 expect, const void* src_pinned_alias, void* dst, size_t bytes, u32* d_err, double timeout_seconds);
 void post_stamp_launch(hipStream_t s, u32* d_stamp, u32 value);

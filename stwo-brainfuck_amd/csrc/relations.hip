@@ -13,6 +13,8 @@
 // other counts are differences of one four-channel inclusive scan at the segment's ends — a segment may span any number of workgroups
 // (an instruction inside a loop repeats its (ip, ci, ni) once per iteration) —, first yield and first use are 64-bit atomicMin;
 // (5) the tuples with net != 0 are compacted in sorted order, up to the caller's cap. Integers only: nothing depends on the schedule.
+// Steps (2) to (5) are relation_aggregate (ctx.h), which the relation programs of any AIR share (relation_program.hip): they bring their own
+// step (1), an interpreter instead of k_rel_flags / k_rel_emit.
 #include "../../include/bfhip.h"
 #include <cstring>
 #include <hip/hip_runtime.h>
@@ -27,7 +29,7 @@ enum : u32 { REL_YIELD = 0, REL_USE = 1, REL_USE_ALWAYS = 2 };      // numerator
 // One table's part in one relation: the columns of the tuple's words, the dummy column, and where its rows lie in the relation's row stream
 struct RelSource { const u32* w[7]; const u32* d; u32 row0, rows, table, kind; };
 struct RelSources { u32 n, n_words, pad_[2]; RelSource src[64]; };
-struct RelEntries { u32* w[7]; u32* num; u64* origin; };            // SoA tuple words, numerator, (table << 32 | row)
+// RelEntries (ctx.h): SoA tuple words, numerator, (table << 32 | row)
 
 static constexpr u32 ST_TILE = 2048;   // 256 lanes x 8, the tile of exclusive_scan_u32
 
@@ -193,7 +195,6 @@ static void relation_run(Ctx& c, u32 relation, const RelSources& S, u32 N, u32 c
     rep = bfhip_relation_report{};
     rep.relation = relation; rep.n_words = S.n_words;
     if (N == 0) return;
-    const u32 n_words = S.n_words;
     // (1)
     const RelSources* d_S = c.stage(&S, 1);
     u32* flags = c.alloc_u32(N); u32* pos = c.alloc_u32(N); u32* tot = c.alloc_u32(N / ST_TILE + 3);
@@ -206,6 +207,14 @@ static void relation_run(Ctx& c, u32 relation, const RelSources& S, u32 N, u32 c
     const u32 n = scan_total(c, d_n);
     rep.n_entries = n;
     if (n == 0) return;
+    relation_aggregate(c, relation, S.n_words, n, cap, rep, entries_h,
+                       [&](const RelEntries& e) { hipLaunchKernelGGL(k_rel_emit, grid256(N), dim3(256), 0, s, d_S, N, flags, pos, e); });
+}
+
+// Steps (2) to (5) over the n >= 1 entries that `emit` writes (ctx.h). Arena memory only; every launch has a non-zero size.
+void relation_aggregate(Ctx& c, u32 relation, u32 n_words, u32 n, u32 cap, bfhip_relation_report& rep, bfhip_relation_entry* entries_h,
+                        const std::function<void(const RelEntries&)>& emit, const char* emit_scope) {
+    hipStream_t s = c.stream;
     RelEntries e{};
     for (u32 k = 0; k < n_words; k++) e.w[k] = c.alloc_u32(n);
     e.num = c.alloc_u32(n);
@@ -219,9 +228,10 @@ static void relation_run(Ctx& c, u32 relation, const RelSources& S, u32 N, u32 c
     u32* heads = c.alloc_u32(n); u32* segx = c.alloc_u32(n); u32* seg_tot = c.alloc_u32(n / ST_TILE + 3);
     const u32* d_n_tuples;
     int cur = 0;
+    if (emit_scope) { ProfScope ps(s, emit_scope, 0); emit(e); }
     {
         ProfScope ps(s, "relations_sort", 0);
-        hipLaunchKernelGGL(k_rel_emit, grid256(N), dim3(256), 0, s, d_S, N, flags, pos, e);
+        if (!emit_scope) emit(e);
         hipLaunchKernelGGL(k_rel_iota, grid256(n), dim3(256), 0, s, perm[0], n);
         // stable LSD passes over (w[k-1], w[k]) pairs from the last word down; word 0 of an odd tuple goes alone (32 key bits)
         for (int k = (int)n_words - 1; k >= 0; k -= 2) {
