@@ -235,7 +235,7 @@ struct Ctx {
     }
     template <class T>
     T* stage(const T* host, size_t n) {
-        size_t bytes = (n * sizeof(T) + 255) & ~size_t(255);
+        size_t bytes = stage_round(n * sizeof(T));
         if (stage_used + bytes > stage_bytes) throw HipError("staging buffer exhausted (call stage_checkpoint() between operations)");
         memcpy(h_stage + stage_used, host, n * sizeof(T));
         if (stage_batch_depth == 0) BF_HIP(hipMemcpyAsync(d_stage + stage_used, h_stage + stage_used, n * sizeof(T), hipMemcpyHostToDevice, stream));
@@ -244,9 +244,11 @@ struct Ctx {
         return r;
     }
     // Called at the start of every high-level operation: recycles the staging ring once it is half full (after a sync, so no
-    // in-flight kernel still reads parameter blocks from it).
-    void stage_checkpoint() {
-        if (stage_batch_depth == 0 && stage_used > stage_bytes / 2) {
+    // in-flight kernel still reads parameter blocks from it). `need`: what the operation is about to stage, every block rounded up as
+    // stage() does, where that can exceed half the ring — the ring is also recycled when it would not fit behind what is in use.
+    static constexpr size_t stage_round(size_t bytes) { return (bytes + 255) & ~size_t(255); }
+    void stage_checkpoint(size_t need = 0) {
+        if (stage_batch_depth == 0 && (stage_used > stage_bytes / 2 || stage_used + need > stage_bytes)) {
             if (mailboxes_pending) {      // a mailbox kernel is waiting for this very thread: waiting for the stream would never return
                 if (stage_used > stage_bytes - (size_t(1) << 20)) throw HipError("staging buffer exhausted while a mailbox is pending");
                 return;

@@ -134,7 +134,19 @@ extern "C" int32_t bfhip_relation_program_summary(bfhip_ctx* ctx, const bfhip_re
     c.sync();
     const Arena::Mark arena_mark = c.arena.mark();
     try {
-        c.stage_checkpoint();
+        // At the caps (64 programs of 4096 instructions) one call stages more than half the ring, so "recycle when half full" is not enough:
+        // count what this call stages — the code of every distinct program, a descriptor block per table, two launch blocks per relation —
+        // and recycle when it would not fit. At most 64 x 64 KiB + 64 x 4 KiB + 16 x 2 x 8 KiB = 4.5 MiB of the ring's 8.
+        size_t need = 0;
+        for (u32 t = 0; t < n_tables; t++) {
+            const bfhip_relation_program& p = *tables[t].program;
+            bool seen = false;
+            for (u32 u = 0; u < t && !seen; u++) seen = tables[u].program == tables[t].program;
+            if (!seen) need += Ctx::stage_round(p.code.size() * sizeof(u32));
+            need += Ctx::stage_round((p.n_cols ? p.n_cols : 1) * sizeof(bf_u32x4));
+        }
+        need += size_t(n_relations) * 2 * Ctx::stage_round(n_tables * sizeof(RelProgLaunch));
+        c.stage_checkpoint(need);
         // every distinct program's code once, every table's column descriptors
         const bf_u32x4* d_code[64] = {};
         const bf_u32x4* d_cols[64] = {};

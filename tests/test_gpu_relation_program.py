@@ -171,10 +171,9 @@ def test_two_entries_per_row_long_segment_and_truncation(ctx, pkg):
     assert {f: last[f] for f in ENTRY_FIELDS} == {"tuple": (P - 1, 0), "net": P - n, "n_yield": 0, "n_use": n, "n_other": 0, "first_yield": None, "first_use": (0, 0)}
 
 
-def test_three_tables_two_relations_shifts_and_an_unused_relation(ctx, pkg):
-    """Three tables of 2^6, 2^9 and 2^4 evaluated rows in one call. Table 1 adds to relations 0 and 2 (and to 0 twice), table 0 and 2 to
-    relation 0 only; nobody adds to relation 1 and 3. Table 0 is read at row_shift 0 with one column of shift 2 and one of shift 6 (a single
-    word); table 2 at row_shift 4 with a full-size column (read at r << 4) beside row-granular ones."""
+def three_table_specs(pkg):
+    """(widths, specs) of test_three_tables_two_relations_shifts_and_an_unused_relation (tests/test_relation_model_np_cpu.py runs the numpy
+    reference on them too)."""
     widths = [1, 3, 7, 2]
     b = pkg.AirBuilder()
     b.relation_entry(0, b.col(1), [b.col(0)])
@@ -189,6 +188,14 @@ def test_three_tables_two_relations_shifts_and_an_unused_relation(ctx, pkg):
     specs = [(t0, 6, 0, [drawn(1, 16, WORDS), np.array([P - 1], dtype=np.uint32)], [2, 6]),
              (t1, 9, 0, [drawn(10 + k, 512, WORDS[: 2 + k % 3]) for k in range(7)] + [drawn(20, 512, MULTS), drawn(21, 512, MULTS)], None),
              (t2, 8, 4, [drawn(30, 256, WORDS), drawn(31, 16, MULTS)], [0, 4])]
+    return widths, specs
+
+
+def test_three_tables_two_relations_shifts_and_an_unused_relation(ctx, pkg):
+    """Three tables of 2^6, 2^9 and 2^4 evaluated rows in one call. Table 1 adds to relations 0 and 2 (and to 0 twice), table 0 and 2 to
+    relation 0 only; nobody adds to relation 1 and 3. Table 0 is read at row_shift 0 with one column of shift 2 and one of shift 6 (a single
+    word); table 2 at row_shift 4 with a full-size column (read at r << 4) beside row-granular ones."""
+    widths, specs = three_table_specs(pkg)
     res, want = run_both(ctx, specs, widths)
     assert [r["n_words"] for r in res.reports] == widths and [r["n_entries"] for r in res.reports][1::2] == [0, 0]
     assert res.reports[0]["n_entries"] > 64 + 512 and res.reports[2]["n_entries"] > 0

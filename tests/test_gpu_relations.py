@@ -144,11 +144,8 @@ def test_long_segment_and_truncation(ctx):
 WORDS = [0, 1, 1 << 16, 1 << 30, P - 2, P - 1]
 
 
-@pytest.mark.parametrize("seed", [1, 2, 3])
-def test_sort_order_and_key_packing(ctx, seed):
-    """Tuples over {0, 1, 2^16, 2^30, p - 2, p - 1}, each differing from its neighbour in ONE word, every word position in turn: a sort pass
-    that drops or swaps a word of its key, or is not stable, orders or merges them differently from the model. Pattern by tuple: yielded 3x
-    and used 3x (balanced: absent), yielded 3x and used 2x (net 1), used only (net p - 1). Uses are split over two plus tables."""
+def sort_order_tables(seed):
+    """The tables of test_sort_order_and_key_packing (tests/test_relation_model_np_cpu.py runs the numpy reference on them too)."""
     r = splitmix_column(1000 * seed, 7 + 60)
     t = [WORDS[int(v) % 6] for v in r[:7]]
     tuples = [tuple(t)]
@@ -165,8 +162,15 @@ def test_sort_order_and_key_packing(ctx, seed):
     uses = [uses[k] for k in order]
     proc = processor_table(yields)
     assert 64 <= proc.shape[1] <= 512
-    tables = [(10, opcode_table(10, uses[: len(uses) // 3])), (3, proc), (10, opcode_table(10, uses[len(uses) // 3:]))]
-    res, model = run_both(ctx, tables)
+    return [(10, opcode_table(10, uses[: len(uses) // 3])), (3, proc), (10, opcode_table(10, uses[len(uses) // 3:]))]
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3])
+def test_sort_order_and_key_packing(ctx, seed):
+    """Tuples over {0, 1, 2^16, 2^30, p - 2, p - 1}, each differing from its neighbour in ONE word, every word position in turn: a sort pass
+    that drops or swaps a word of its key, or is not stable, orders or merges them differently from the model. Pattern by tuple: yielded 3x
+    and used 3x (balanced: absent), yielded 3x and used 2x (net 1), used only (net p - 1). Uses are split over two plus tables."""
+    res, model = run_both(ctx, sort_order_tables(seed))
     nets = [e["net"] for e in res.entries if e["relation"] == 2]
     assert 1 in nets and P - 1 in nets and res.reports[2]["n_tuples"] > res.reports[2]["n_unbalanced"] > 0
     assert res.reports[0]["n_unbalanced"] > 1 and res.reports[1]["n_unbalanced"] > 1        # the 3-word relations see the Processor rows only
