@@ -638,6 +638,28 @@ impl RelationProgram {
         }
         Ok((reports, listed))
     }
+    /// `bfhip_relation_program_multiplicities`: fills `out` — one word per evaluated row of `tables[target_table]`, a device pointer, which
+    /// may be the column the target's multiplicity operand reads — with the net of every other entry of `relation` at the lowest row holding
+    /// each tuple, and returns the counts and up to `max_missing` tuples with a non-zero net that no row of the target holds. The target is
+    /// the `target_entry`-th ENTRY of `relation` in that table's program. Missing tuples are a result, not an `Err`. Refused while a
+    /// commitment-scheme session is open on the context.
+    pub fn multiplicities(ctx: &Context, tables: &[RelationProgramTable], relation: u32, target_table: u32, target_entry: u32, out: *mut u32,
+                          max_missing: u32) -> Result<(sys::BfhipMultiplicityReport, Vec<sys::BfhipRelationEntry>), String> {
+        let first = tables.first().ok_or("1 to 64 tables")?;
+        let n_rel = first.program.shape()?.n_relations;
+        for t in tables {
+            if t.cols.len() != t.program.shape()?.n_cols as usize || (!t.shifts.is_empty() && t.shifts.len() != t.cols.len()) { return Err("one column pointer (and shift) per program column".into()); }
+        }
+        let raw: Vec<sys::BfhipRelationProgramTable> = tables.iter().map(|t| sys::BfhipRelationProgramTable {
+            program: t.program.0, log_size: t.log_size, row_shift: t.row_shift, cols_h: t.cols.as_ptr(),
+            col_shifts_h: if t.shifts.is_empty() { std::ptr::null() } else { t.shifts.as_ptr() } }).collect();
+        let mut report = sys::BfhipMultiplicityReport::default();
+        let mut missing = vec![sys::BfhipRelationEntry::default(); max_missing as usize];
+        let missing_ptr = if max_missing == 0 { std::ptr::null_mut() } else { missing.as_mut_ptr() };
+        check(unsafe { sys::bfhip_relation_program_multiplicities(ctx.0, raw.as_ptr(), raw.len() as u32, n_rel, relation, target_table, target_entry, out, &mut report, missing_ptr, max_missing) })?;
+        missing.truncate(report.n_reported as usize);
+        Ok((report, missing))
+    }
 }
 
 impl Drop for RelationProgram {

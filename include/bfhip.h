@@ -659,6 +659,7 @@ int32_t bfhip_brainfuck_composition_at_point(const uint32_t log_sizes_h[13], con
  *   bfhip_prove_trace, bfhip_prove_brainfuck, bfhip_prove_registers (and every pool job or batch that lands on the context),
  *   bfhip_trace_create, bfhip_trace_create_ram, bfhip_trace_create_from_registers (the GPU table builders' scratch),
  *   bfhip_trace_check, bfhip_check_constraints, bfhip_relation_summary, bfhip_trace_relations, bfhip_relation_program_summary,
+ *   bfhip_relation_program_multiplicities,
  *   bfhip_ctx_set_conventions, bfhip_ctx_set_pcs_config, bfhip_ctx_join_local_group, bfhip_ctx_join_rccl_group, bfhip_ctx_destroy,
  *   and a second bfhip_pcs_create.
  * Everything else keeps working, which is what the caller's constraint sweep needs: bfhip_malloc / bfhip_free / bfhip_upload / bfhip_download /
@@ -916,6 +917,51 @@ typedef struct bfhip_relation_program_table {
 } bfhip_relation_program_table;
 int32_t bfhip_relation_program_summary(bfhip_ctx* ctx, const bfhip_relation_program_table* tables, uint32_t n_tables, uint32_t n_relations,
                                        bfhip_relation_report* out, bfhip_relation_entry* entries_h, uint32_t cap_per_relation);
+
+/* ---- Lookup multiplicities: fill the looked-up table's multiplicity column of ANY AIR on the device -----------------------------------------
+ * The relation tracker reports nets; this entry point writes them. A lookup AIR needs, before anything can be swept, generated or committed,
+ * the multiplicity column of its table: how often every row's tuple is used. bfhip_relation_program_multiplicities counts that from the
+ * relation programs themselves, so the consumers' columns never leave the GPU.
+ *   tables, n_tables, n_relations: exactly what bfhip_relation_program_summary takes — row and column shifts, the validation of the list and
+ *     the limit of 2^31 (rows x ENTRY instructions of one relation) are the same; the target's rows count towards that limit.
+ *   The target — the table side of the lookup — is the target_entry-th ENTRY instruction OF RELATION `relation`, in program order from 0, of
+ *     the program of tables[target_table]. Its tuple is evaluated at every row of that table; its multiplicity operand is evaluated and
+ *     IGNORED: the column it reads may hold anything, and may be out_d itself.
+ *   Every other entry of the relation counts as in the summary (multiplicity 0 is no entry): the other tables', and the other ENTRYs of the
+ *     target table, others of the same relation included.
+ *   out_d: one word per evaluated row of the target table, 2^(log_size - row_shift) words. For each distinct tuple T among the target's rows
+ *     the LOWEST row holding T receives net(T), the canonical M31 sum of the other entries' multiplicities with tuple T; every other row —
+ *     every later duplicate of T included — receives 0. A table side written relation_entry(r, -mult, [t...]) with out_d as its mult column
+ *     is then balanced against everything its rows hold. out_d is written only after every read of the extraction has completed.
+ *   Missing tuples: a tuple with net != 0 among the other entries that NO target row holds cannot be balanced by this table. The first `cap`
+ *     of them, in the lexicographic order of the summary, go to missing_h as bfhip_relation_entry (reused unchanged; net, n_yield, n_use,
+ *     n_other and first_* have their meaning over the other entries). missing_h == NULL with cap 0 gives the counts only. Missing tuples are
+ *     a result, not an error: the call returns 0 and leaves bfhip_last_error() alone.
+ *   Every field of the report and every word of out_d is an integer and the same whatever the schedule: the extraction has no atomics, the
+ *     lowest row is a 64-bit atomicMin, the three tuple counts are integer atomicAdds.
+ *   Uses the context's arena like the summary (bfhip_ctx_memory out[3] is put back on every path) and belongs in front of bfhip_pcs_create.
+ *   Refused, -1 with "bfhip_relation_program_multiplicities: <rule>" and the context still usable: everything the summary refuses; relation
+ *     >= n_relations; target_table >= n_tables; a target program with fewer than target_entry + 1 ENTRYs of that relation (both numbers
+ *     named); NULL out_d or report (or NULL missing_h with cap > 0); an open commitment-scheme session; a context in a shard group.
+ * Not built: extension-field multiplicities, tuples wider than 7 words, column offsets, use inside an open session, shard groups.
+ * Layout (natural alignment, declaration order):
+ *   bfhip_multiplicity_report  80 bytes: relation 0, n_words 4, target_table 8, target_entry 12, n_rows 16, n_row_tuples 24, n_entries 32,
+ *                              n_tuples 40, n_filled 48, n_missing 56, n_reported 64, reserved 72 */
+typedef struct bfhip_multiplicity_report {
+    uint32_t relation, n_words;
+    uint32_t target_table, target_entry;
+    uint64_t n_rows;        /* evaluated rows of the target table, 2^(log_size - row_shift) */
+    uint64_t n_row_tuples;  /* distinct tuples among them (n_rows - n_row_tuples rows are duplicates and get 0) */
+    uint64_t n_entries;     /* entries of the relation from everything BUT the target ENTRY, non-zero multiplicity */
+    uint64_t n_tuples;      /* distinct tuples among those */
+    uint64_t n_filled;      /* target rows that received a non-zero value */
+    uint64_t n_missing;     /* tuples with net != 0 among the other entries that no target row holds, whatever the cap */
+    uint64_t n_reported;    /* min(n_missing, cap) */
+    uint32_t reserved[2];
+} bfhip_multiplicity_report;
+int32_t bfhip_relation_program_multiplicities(bfhip_ctx* ctx, const bfhip_relation_program_table* tables, uint32_t n_tables, uint32_t n_relations,
+                                              uint32_t relation, uint32_t target_table, uint32_t target_entry, uint32_t* out_d,
+                                              bfhip_multiplicity_report* report, bfhip_relation_entry* missing_h, uint32_t cap);
 
 /* Host-only pieces of the drop-in (usable without a GPU): the Brainfuck compiler (crates/brainfuck_vm/src/compiler.rs:17-37), the VM
  * (crates/brainfuck_vm/src/machine.rs:141-238; trace rows are 7 u32: clk, ip, ci, ni, mp, mv, mvi) and the 13 table builders

@@ -287,6 +287,38 @@ class RelationResult:
         return out
 
 
+class MultiplicityReport(ctypes.Structure):
+    """include/bfhip.h `bfhip_multiplicity_report` (80 bytes): the counts of Context.relation_program_multiplicities."""
+    _fields_ = [("relation", ctypes.c_uint32), ("n_words", ctypes.c_uint32), ("target_table", ctypes.c_uint32), ("target_entry", ctypes.c_uint32),
+                ("n_rows", ctypes.c_uint64), ("n_row_tuples", ctypes.c_uint64), ("n_entries", ctypes.c_uint64), ("n_tuples", ctypes.c_uint64),
+                ("n_filled", ctypes.c_uint64), ("n_missing", ctypes.c_uint64), ("n_reported", ctypes.c_uint64), ("reserved", ctypes.c_uint32 * 2)]
+
+    def as_dict(self, names=None):
+        d = {f: int(getattr(self, f)) for f, _ in self._fields_[:-1]}
+        d["name"] = ("relation %d" % self.relation) if names is None else names[self.relation]
+        return d
+
+
+class MultiplicityResult:
+    """Context.relation_program_multiplicities(): report = the counts (a dict), missing = the reported tuples with a non-zero net that no
+    row of the target table holds (dicts shaped like RelationResult.entries, in lexicographic order), ok = there is none."""
+
+    def __init__(self, report, missing, table_names, target_name):
+        self.report, self.missing, self.table_names, self.target_name = report, missing, table_names, target_name
+
+    @property
+    def ok(self):
+        return self.report["n_missing"] == 0
+
+    def lines(self):
+        """One format_relation_entry line per reported missing tuple, each followed by "; no row of <table name> holds it", then one line if
+        the list was cut at max_missing."""
+        out = ["%s; no row of %s holds it" % (format_relation_entry(e, self.table_names), self.target_name) for e in self.missing]
+        if self.report["n_missing"] > self.report["n_reported"]:
+            out.append("%s relation: %d more missing tuples not listed" % (self.report["name"], self.report["n_missing"] - self.report["n_reported"]))
+        return out
+
+
 class PreflightReport(ctypes.Structure):
     """include/bfhip.h `bfhip_preflight_report` (4064 bytes): what the last proof of a context that reached the preflight found."""
     _fields_ = [("ran", ctypes.c_uint32), ("rejected", ctypes.c_uint32), ("n_bad_components", ctypes.c_int32), ("n_entries", ctypes.c_uint32),
@@ -701,16 +733,8 @@ class Context:
         names = ["%s[%d]" % (COMPONENT_NAMES[c] if 0 <= c < 13 else "?", t) for t, (c, _, _) in enumerate(tables)]
         return _relation_result(lambda reps, ents, cap: lib().bfhip_relation_summary(self._h, arr, len(tables), reps, ents, cap), max_entries, names)
 
-    def relation_program_summary(self, tables, max_entries=64, relation_names=None, table_names=None):
-        """bfhip_relation_program_summary: the lookup tuples of ANY AIR that do not cancel — relation_summary for RelationPrograms. tables:
-        (program, log_size, row_shift, col_ptrs) or (program, log_size, row_shift, col_ptrs, col_shifts) each: one device column per program
-        column, the program evaluated once per 2^row_shift cells (row-granular Brainfuck tables: row_shift 4; full-size session columns: 0);
-        col_shifts None = every column holds one word per evaluated row. All programs share one list of relations. Returns a RelationResult
-        (reports and entries for every relation of the programs); relation_names default to "relation <r>", table_names to "table <t>";
-        imbalances are a result, not an error. Refused while a PcsSession is open on the context: run it in front of the session."""
-        if not tables:
-            raise BfhipError("bfhip_relation_program_summary: 1 to 64 tables, got 0")
-        n_rel = tables[0][0].shape["n_relations"]
+    def _relation_program_tables(self, tables):
+        """(RelationProgramTable array, the ctypes arrays it points into) of a list of (program, log_size, row_shift, col_ptrs[, col_shifts])."""
         keep, arr = [], (RelationProgramTable * len(tables))()
         for t, tab in enumerate(tables):
             program, log_size, row_shift, ptrs = tab[:4]
@@ -722,6 +746,19 @@ class Context:
             keep.append((pa, sa))
             arr[t] = RelationProgramTable(program._h, int(log_size), int(row_shift), None if pa is None else ctypes.cast(pa, ctypes.POINTER(ctypes.c_void_p)),
                                           None if sa is None else ctypes.cast(sa, ctypes.POINTER(ctypes.c_uint32)))
+        return arr, keep
+
+    def relation_program_summary(self, tables, max_entries=64, relation_names=None, table_names=None):
+        """bfhip_relation_program_summary: the lookup tuples of ANY AIR that do not cancel — relation_summary for RelationPrograms. tables:
+        (program, log_size, row_shift, col_ptrs) or (program, log_size, row_shift, col_ptrs, col_shifts) each: one device column per program
+        column, the program evaluated once per 2^row_shift cells (row-granular Brainfuck tables: row_shift 4; full-size session columns: 0);
+        col_shifts None = every column holds one word per evaluated row. All programs share one list of relations. Returns a RelationResult
+        (reports and entries for every relation of the programs); relation_names default to "relation <r>", table_names to "table <t>";
+        imbalances are a result, not an error. Refused while a PcsSession is open on the context: run it in front of the session."""
+        if not tables:
+            raise BfhipError("bfhip_relation_program_summary: 1 to 64 tables, got 0")
+        n_rel = tables[0][0].shape["n_relations"]
+        arr, keep = self._relation_program_tables(tables)
         rel_names = ["relation %d" % r for r in range(n_rel)] if relation_names is None else list(relation_names)
         if len(rel_names) != n_rel:
             raise ValueError("one name per relation")
@@ -730,6 +767,27 @@ class Context:
         _check(lib().bfhip_relation_program_summary(self._h, arr, len(tables), n_rel, reps, ents, max_entries))
         return RelationResult([r.as_dict(rel_names) for r in reps], [ents[k * max_entries + i].as_dict(rel_names) for k in range(n_rel) for i in range(reps[k].n_reported)],
                               ["table %d" % t for t in range(len(tables))] if table_names is None else list(table_names))
+
+    def relation_program_multiplicities(self, tables, relation, target_table, target_entry, out_ptr, max_missing=64, relation_names=None, table_names=None):
+        """bfhip_relation_program_multiplicities: fills the multiplicity column of a looked-up table on the device. tables: as for
+        relation_program_summary. The target — the table side of the lookup — is the target_entry-th ENTRY of `relation` (program order, from 0)
+        in the program of tables[target_table]; its multiplicity operand is ignored. out_ptr: one word per evaluated row of that table (it may
+        be the column that operand reads): the lowest row holding a tuple receives the net of every OTHER entry of the relation with that
+        tuple, every other row 0. Returns a MultiplicityResult: the counts, and up to max_missing tuples with a non-zero net that no row of
+        the target holds (a result, not an error). Refused while a PcsSession is open on the context: run it in front of the session."""
+        if not tables:
+            raise BfhipError("bfhip_relation_program_multiplicities: 1 to 64 tables, got 0")
+        n_rel = tables[0][0].shape["n_relations"]
+        arr, keep = self._relation_program_tables(tables)
+        rel_names = ["relation %d" % r for r in range(n_rel)] if relation_names is None else list(relation_names)
+        if len(rel_names) != n_rel:
+            raise ValueError("one name per relation")
+        tab_names = ["table %d" % t for t in range(len(tables))] if table_names is None else list(table_names)
+        rep = MultiplicityReport()
+        miss = (RelationEntry * max_missing)() if max_missing else None
+        _check(lib().bfhip_relation_program_multiplicities(self._h, arr, len(tables), n_rel, int(relation), int(target_table), int(target_entry), ctypes.c_void_p(out_ptr),
+                                                           ctypes.byref(rep), miss, max_missing))
+        return MultiplicityResult(rep.as_dict(rel_names), [miss[i].as_dict(rel_names) for i in range(rep.n_reported)], tab_names, tab_names[rep.target_table])
 
     def accumulate_quotients(self, log_size, col_ptrs, n_samples, sample_points, sample_values, random_coeff4, out_ptrs, col_shifts=None):
         """QuotientOps::accumulate_quotients for the columns of one LDE size."""

@@ -14,6 +14,7 @@
 
 struct bfhip_preflight_report;
 struct bfhip_relation_report;
+struct bfhip_multiplicity_report;
 struct bfhip_relation_entry;
 
 namespace bf {
@@ -298,6 +299,13 @@ void relations_in_proof(Ctx& c, const u32* const* const cols[N_COMPONENTS], cons
 struct RelEntries { u32* w[7]; u32* num; u64* origin; };            // tuple words, multiplicity, (table << 32 | row)
 void relation_aggregate(Ctx& c, u32 relation, u32 n_words, u32 n, u32 cap, bfhip_relation_report& rep, bfhip_relation_entry* entries_h,
                         const std::function<void(const RelEntries&)>& emit, const char* emit_scope = nullptr);
+// relations.hip: the other direction (include/bfhip.h "Lookup multiplicities") over the same steps (2) and (3). Among the n entries those of
+// the looked-up table's rows carry REL_TABLE_SIDE in their origin (table indices are below 64, the bit is free) and count for nothing; per
+// tuple, the net of the others is written to out_d (n_rows words, zeroed first) at the lowest marked row, and the tuples with net != 0 and no
+// marked row are reported like unbalanced ones. rep: relation, n_words, target_*, n_rows set by the caller; this fills the rest.
+constexpr u64 REL_TABLE_SIDE = u64(1) << 63;
+void relation_multiplicities(Ctx& c, u32 relation, u32 n_words, u32 n, u32 n_rows, u32* out_d, u32 cap, bfhip_multiplicity_report& rep,
+                             bfhip_relation_entry* missing_h, const std::function<void(const RelEntries&)>& emit);
 
 void mailbox_launch(hipStream_t s, const u32* d_flag, u32 expect, const void* src_pinned_alias, void* dst, size_t bytes, u32* d_err, double timeout_seconds);
 void post_stamp_launch(hipStream_t s, u32* d_stamp, u32 value);

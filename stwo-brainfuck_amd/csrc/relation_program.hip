@@ -13,6 +13,8 @@
 //   (2) exclusive_scan_u32: pos[row], and the total n;
 //   (3) EMIT = true: the row's entries go to pos[row], pos[row] + 1, ... in program order — words, multiplicity, origin (table << 32 | row).
 // So the entries stand in (table, row, program order) whatever the schedule: no atomics, integers only.
+// bfhip_relation_program_multiplicities (include/bfhip.h "Lookup multiplicities") runs the same three steps for one relation with the looked-up
+// table's launches in TARGET mode and hands the entries to relations.hip's relation_multiplicities instead.
 #include "api_guard.h"
 #include "relation_program.h"
 #include "../../include/bfhip.h"
@@ -31,12 +33,16 @@ struct RelProgLaunch {
     u64 pos;             // u32[rows], the same place in the scanned stream: read by EMIT = true
     u64 w[REL_PROG_MAX_WORDS], num, origin;      // RelEntries
     u32 n_instr, rows, relation, n_words, table, n_m;      // n_m: host side only, the LDS size of the launch
+    u32 target, pad_;    // TARGET launches only: which ENTRY of `relation`, in program order from 0, is the table side
 };
 
 // m[r] of this lane, r taken from byte `k` of the packed pending tuple
 __device__ __forceinline__ u32 rp_pending_reg(u64 pending, u32 k) { return (u32)(pending >> (8u * k)) & 0xffu; }
 
-template <bool EMIT>
+// TARGET (bfhip_relation_program_multiplicities, the looked-up table's launch): the a->target-th ENTRY of the relation is the table side. It
+// gives an entry at EVERY row, whatever its multiplicity operand holds, with REL_TABLE_SIDE in the origin and multiplicity word 0; the
+// ordinal is a wave-uniform counter. Every other ENTRY, and every launch with TARGET = false, is as above.
+template <bool EMIT, bool TARGET>
 __global__ void __launch_bounds__(RP_LANES) k_relation_program(const RelProgLaunch* __restrict__ ap) {
     extern __shared__ u32 s_regs[];
     const BF_CONSTANT RelProgLaunch* a = (const BF_CONSTANT RelProgLaunch*)(unsigned long long)ap;
@@ -50,6 +56,8 @@ __global__ void __launch_bounds__(RP_LANES) k_relation_program(const RelProgLaun
     u32 count = 0;                                                // entries of `relation` with a non-zero multiplicity so far
     u32 at = 0;
     if (EMIT) at = ((g_cu32p)a->pos)[row];
+    u32 ordinal = 0;                                              // TARGET: ENTRYs of `relation` so far
+    const u32 target = TARGET ? a->target : 0u;
 #pragma unroll 1
     for (u32 pc = 0; pc < n_instr; pc++) {
         const bf_u32x4 ins = code[pc];
@@ -70,15 +78,17 @@ __global__ void __launch_bounds__(RP_LANES) k_relation_program(const RelProgLaun
             case REL_WORD: pending = (pending << 8) | ins.z; break;
             default: {      // REL_ENTRY: the validator admits nothing else
                 if (ins.y == relation) {
-                    const u32 mult = m[ra];
-                    if (mult != 0) {
+                    u32 mult = m[ra];
+                    const bool side = TARGET && ordinal++ == target;
+                    if (side) mult = 0;
+                    if (mult != 0 || side) {
                         if (EMIT) {
                             const u32 j = at + count;
 #pragma unroll 1
                             for (u32 k = 0; k < n_words; k++)     // word k was pushed n_words - k WORDs ago
                                 ((g_u32p)a->w[k])[j] = m[rp_pending_reg(pending, n_words - 1 - k) * RP_LANES];
                             ((g_u32p)a->num)[j] = mult;
-                            ((BF_GLOBAL u64*)a->origin)[j] = ((u64)a->table << 32) | row;
+                            ((BF_GLOBAL u64*)a->origin)[j] = (side ? REL_TABLE_SIDE : u64(0)) | ((u64)a->table << 32) | row;
                         }
                         count++;
                     }
@@ -91,16 +101,8 @@ __global__ void __launch_bounds__(RP_LANES) k_relation_program(const RelProgLaun
     if (!EMIT) ((g_u32p)a->counts)[row] = count;
 }
 
-}  // namespace bf
-
-using namespace bf;
-
-extern "C" int32_t bfhip_relation_program_summary(bfhip_ctx* ctx, const bfhip_relation_program_table* tables, uint32_t n_tables, uint32_t n_relations,
-                                                  bfhip_relation_report* out, bfhip_relation_entry* entries_h, uint32_t cap_per_relation) {
-    API_CTX(ctx)
-    Ctx& c = ctx->c;
-    const std::string me = "bfhip_relation_program_summary: ";
-    if (!tables || !out || (!entries_h && cap_per_relation)) throw HipError(me + "null argument");
+// What bfhip_relation_program_summary and bfhip_relation_program_multiplicities refuse about the list of tables, in the caller's name
+static void rp_validate_tables(Ctx& c, const std::string& me, const bfhip_relation_program_table* tables, u32 n_tables, u32 n_relations) {
     if (n_tables < 1 || n_tables > 64) throw HipError(me + "1 to 64 tables, got " + std::to_string(n_tables));
     if (n_relations < 1 || n_relations > REL_PROG_MAX_RELATIONS) throw HipError(me + "1 to 16 relations, got " + std::to_string(n_relations));
     if (c.shard.count > 1) throw HipError(me + "a context in a shard group is not supported (bfhip_ctx_leave_group first)");
@@ -122,52 +124,73 @@ extern "C" int32_t bfhip_relation_program_summary(bfhip_ctx* ctx, const bfhip_re
             if (T.col_shifts_h && T.col_shifts_h[k] > T.log_size) throw HipError(at + "column " + std::to_string(k) + " has shift " + std::to_string(T.col_shifts_h[k]) + " above log_size " + std::to_string(T.log_size));
         }
     }
-    const bfhip_relation_program& first = *tables[0].program;
     for (u32 r = 0; r < n_relations; r++) {
         u64 total = 0;
         for (u32 t = 0; t < n_tables; t++) total += (u64(1) << (tables[t].log_size - tables[t].row_shift)) * tables[t].program->entries_of[r];
         if (total > (u64(1) << 31)) throw HipError(me + "more than 2^31 entries (rows x ENTRY instructions) of relation " + std::to_string(r) + " in total");
     }
+}
+
+// Every distinct program's code once and every table's column descriptors, into the staging ring
+struct RpStaged { const bf_u32x4* code[64] = {}; const bf_u32x4* cols[64] = {}; };
+static void rp_stage_tables(Ctx& c, const bfhip_relation_program_table* tables, u32 n_tables, u32 n_relations, RpStaged& st) {
+    const bf_u32x4** d_code = st.code;
+    const bf_u32x4** d_cols = st.cols;
+    // At the caps (64 programs of 4096 instructions) one call stages more than half the ring, so "recycle when half full" is not enough:
+    // count what this call stages — the code of every distinct program, a descriptor block per table, two launch blocks per relation —
+    // and recycle when it would not fit. At most 64 x 64 KiB + 64 x 4 KiB + 16 x 2 x 8 KiB = 4.5 MiB of the ring's 8.
+    size_t need = 0;
+    for (u32 t = 0; t < n_tables; t++) {
+        const bfhip_relation_program& p = *tables[t].program;
+        bool seen = false;
+        for (u32 u = 0; u < t && !seen; u++) seen = tables[u].program == tables[t].program;
+        if (!seen) need += Ctx::stage_round(p.code.size() * sizeof(u32));
+        need += Ctx::stage_round((p.n_cols ? p.n_cols : 1) * sizeof(bf_u32x4));
+    }
+    need += size_t(n_relations) * 2 * Ctx::stage_round(n_tables * sizeof(RelProgLaunch));
+    c.stage_checkpoint(need);
+    {
+        StageBatch sb(c);
+        for (u32 t = 0; t < n_tables; t++) {
+            const bfhip_relation_program_table& T = tables[t];
+            const bfhip_relation_program& p = *T.program;
+            for (u32 u = 0; u < t && !d_code[t]; u++) if (tables[u].program == T.program) d_code[t] = d_code[u];
+            if (!d_code[t]) d_code[t] = reinterpret_cast<const bf_u32x4*>(c.stage(p.code.data(), p.code.size()));
+            std::vector<bf_u32x4> cols(p.n_cols ? p.n_cols : 1, bf_u32x4{0, 0, 0, 0});
+            for (u32 k = 0; k < p.n_cols; k++) {
+                const u32 sk = T.col_shifts_h ? T.col_shifts_h[k] : T.row_shift;
+                const unsigned long long ptr = (unsigned long long)T.cols_h[k];
+                // (r << row_shift) >> s_k: one of the two shifts is left after cancelling
+                cols[k] = bf_u32x4{(u32)ptr, (u32)(ptr >> 32), sk > T.row_shift ? sk - T.row_shift : 0u, T.row_shift > sk ? T.row_shift - sk : 0u};
+            }
+            d_cols[t] = c.stage(cols.data(), cols.size());
+        }
+        sb.end();
+    }
+}
+
+}  // namespace bf
+
+using namespace bf;
+
+extern "C" int32_t bfhip_relation_program_summary(bfhip_ctx* ctx, const bfhip_relation_program_table* tables, uint32_t n_tables, uint32_t n_relations,
+                                                  bfhip_relation_report* out, bfhip_relation_entry* entries_h, uint32_t cap_per_relation) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    const std::string me = "bfhip_relation_program_summary: ";
+    if (!tables || !out || (!entries_h && cap_per_relation)) throw HipError(me + "null argument");
+    rp_validate_tables(c, me, tables, n_tables, n_relations);
+    const bfhip_relation_program& first = *tables[0].program;
     c.refuse_in_session("bfhip_relation_program_summary");
     hipStream_t s = c.stream;
     // like a proof: nothing of this context is in flight, and its per-proof memory starts empty; the bookkeeping is put back at the end
     c.sync();
     const Arena::Mark arena_mark = c.arena.mark();
     try {
-        // At the caps (64 programs of 4096 instructions) one call stages more than half the ring, so "recycle when half full" is not enough:
-        // count what this call stages — the code of every distinct program, a descriptor block per table, two launch blocks per relation —
-        // and recycle when it would not fit. At most 64 x 64 KiB + 64 x 4 KiB + 16 x 2 x 8 KiB = 4.5 MiB of the ring's 8.
-        size_t need = 0;
-        for (u32 t = 0; t < n_tables; t++) {
-            const bfhip_relation_program& p = *tables[t].program;
-            bool seen = false;
-            for (u32 u = 0; u < t && !seen; u++) seen = tables[u].program == tables[t].program;
-            if (!seen) need += Ctx::stage_round(p.code.size() * sizeof(u32));
-            need += Ctx::stage_round((p.n_cols ? p.n_cols : 1) * sizeof(bf_u32x4));
-        }
-        need += size_t(n_relations) * 2 * Ctx::stage_round(n_tables * sizeof(RelProgLaunch));
-        c.stage_checkpoint(need);
-        // every distinct program's code once, every table's column descriptors
-        const bf_u32x4* d_code[64] = {};
-        const bf_u32x4* d_cols[64] = {};
-        {
-            StageBatch sb(c);
-            for (u32 t = 0; t < n_tables; t++) {
-                const bfhip_relation_program_table& T = tables[t];
-                const bfhip_relation_program& p = *T.program;
-                for (u32 u = 0; u < t && !d_code[t]; u++) if (tables[u].program == T.program) d_code[t] = d_code[u];
-                if (!d_code[t]) d_code[t] = reinterpret_cast<const bf_u32x4*>(c.stage(p.code.data(), p.code.size()));
-                std::vector<bf_u32x4> cols(p.n_cols ? p.n_cols : 1, bf_u32x4{0, 0, 0, 0});
-                for (u32 k = 0; k < p.n_cols; k++) {
-                    const u32 sk = T.col_shifts_h ? T.col_shifts_h[k] : T.row_shift;
-                    const unsigned long long ptr = (unsigned long long)T.cols_h[k];
-                    // (r << row_shift) >> s_k: one of the two shifts is left after cancelling
-                    cols[k] = bf_u32x4{(u32)ptr, (u32)(ptr >> 32), sk > T.row_shift ? sk - T.row_shift : 0u, T.row_shift > sk ? T.row_shift - sk : 0u};
-                }
-                d_cols[t] = c.stage(cols.data(), cols.size());
-            }
-            sb.end();
-        }
+        RpStaged staged;
+        rp_stage_tables(c, tables, n_tables, n_relations, staged);
+        const bf_u32x4* const* d_code = staged.code;
+        const bf_u32x4* const* d_cols = staged.cols;
         for (u32 r = 0; r < n_relations; r++) {
             bfhip_relation_report& rep = out[r];
             rep = bfhip_relation_report{};
@@ -194,7 +217,7 @@ extern "C" int32_t bfhip_relation_program_summary(bfhip_ctx* ctx, const bfhip_re
                 ProfScope ps(s, "relation_program_count", 0);
                 const RelProgLaunch* d_L = c.stage(L, n_part);
                 for (u32 i = 0; i < n_part; i++)
-                    hipLaunchKernelGGL(k_relation_program<false>, dim3((L[i].rows + RP_LANES - 1) / RP_LANES), dim3(RP_LANES), sizeof(u32) * RP_LANES * L[i].n_m, s, d_L + i);
+                    hipLaunchKernelGGL((k_relation_program<false, false>), dim3((L[i].rows + RP_LANES - 1) / RP_LANES), dim3(RP_LANES), sizeof(u32) * RP_LANES * L[i].n_m, s, d_L + i);
                 d_n = exclusive_scan_u32(s, counts, pos, tot, N);
             }
             u32 n = 0;
@@ -209,12 +232,98 @@ extern "C" int32_t bfhip_relation_program_summary(bfhip_ctx* ctx, const bfhip_re
                                    }
                                    const RelProgLaunch* d_L = c.stage(L, n_part);
                                    for (u32 i = 0; i < n_part; i++)
-                                       hipLaunchKernelGGL(k_relation_program<true>, dim3((L[i].rows + RP_LANES - 1) / RP_LANES), dim3(RP_LANES), sizeof(u32) * RP_LANES * L[i].n_m, s, d_L + i);
+                                       hipLaunchKernelGGL((k_relation_program<true, false>), dim3((L[i].rows + RP_LANES - 1) / RP_LANES), dim3(RP_LANES), sizeof(u32) * RP_LANES * L[i].n_m, s, d_L + i);
                                },
                                "relation_program_emit");
         }
         c.sync();
         BF_HIP(hipGetLastError());
+    } catch (...) {
+        (void)hipStreamSynchronize(c.stream);
+        c.arena.rewind(arena_mark);
+        throw;
+    }
+    c.arena.rewind(arena_mark);
+    return 0;
+    API_CATCH
+}
+
+// The other direction (include/bfhip.h "Lookup multiplicities"): the same extraction with the looked-up table's launch in TARGET mode, then
+// relations.hip's relation_multiplicities. One relation, so one pass over the arena.
+extern "C" int32_t bfhip_relation_program_multiplicities(bfhip_ctx* ctx, const bfhip_relation_program_table* tables, uint32_t n_tables, uint32_t n_relations,
+                                                         uint32_t relation, uint32_t target_table, uint32_t target_entry, uint32_t* out_d,
+                                                         bfhip_multiplicity_report* report, bfhip_relation_entry* missing_h, uint32_t cap) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    const std::string me = "bfhip_relation_program_multiplicities: ";
+    if (!tables || !out_d || !report || (!missing_h && cap)) throw HipError(me + "null argument");
+    rp_validate_tables(c, me, tables, n_tables, n_relations);
+    if (relation >= n_relations) throw HipError(me + "relation " + std::to_string(relation) + " out of range (the call names " + std::to_string(n_relations) + " relations)");
+    if (target_table >= n_tables) throw HipError(me + "target table " + std::to_string(target_table) + " out of range (the call names " + std::to_string(n_tables) + " tables)");
+    const u32 target_entries = tables[target_table].program->entries_of[relation];
+    if (target_entry >= target_entries)
+        throw HipError(me + "target entry " + std::to_string(target_entry) + ": the program of table " + std::to_string(target_table) + " has " + std::to_string(target_entries) +
+                       " ENTRY instructions of relation " + std::to_string(relation));
+    c.refuse_in_session("bfhip_relation_program_multiplicities");
+    hipStream_t s = c.stream;
+    const u32 r = relation, n_words = tables[0].program->relation_words[r];
+    const u32 n_rows = 1u << (tables[target_table].log_size - tables[target_table].row_shift);
+    // like a proof: nothing of this context is in flight, and its per-proof memory starts empty; the bookkeeping is put back at the end
+    c.sync();
+    const Arena::Mark arena_mark = c.arena.mark();
+    try {
+        RpStaged staged;
+        rp_stage_tables(c, tables, n_tables, n_relations, staged);
+        bfhip_multiplicity_report rep{};
+        rep.relation = r; rep.n_words = n_words; rep.target_table = target_table; rep.target_entry = target_entry; rep.n_rows = n_rows;
+        u32 N = 0, row0[64] = {};
+        for (u32 t = 0; t < n_tables; t++) if (tables[t].program->entries_of[r]) { row0[t] = N; N += 1u << (tables[t].log_size - tables[t].row_shift); }
+        c.arena.reset();
+        u32* counts = c.alloc_u32(N); u32* pos = c.alloc_u32(N); u32* tot = c.alloc_u32(N / RP_SCAN_TILE + 3);
+        RelProgLaunch L[64];
+        u32 n_part = 0, target_part = 0;
+        for (u32 t = 0; t < n_tables; t++) {
+            const bfhip_relation_program& p = *tables[t].program;
+            if (!p.entries_of[r]) continue;
+            if (t == target_table) target_part = n_part;
+            RelProgLaunch& l = L[n_part++];
+            l = RelProgLaunch{};
+            l.code = (u64)staged.code[t]; l.cols = (u64)staged.cols[t]; l.counts = (u64)(counts + row0[t]); l.pos = (u64)(pos + row0[t]);
+            l.n_instr = p.n_instr; l.rows = 1u << (tables[t].log_size - tables[t].row_shift); l.relation = r; l.n_words = n_words; l.table = t;
+            l.n_m = p.n_m; l.target = target_entry;
+        }
+        auto launch = [&](bool emit) {
+            const RelProgLaunch* d_L = c.stage(L, n_part);
+            for (u32 i = 0; i < n_part; i++) {
+                const dim3 grid((L[i].rows + RP_LANES - 1) / RP_LANES);
+                const size_t lds = sizeof(u32) * RP_LANES * L[i].n_m;
+                if (i == target_part) {
+                    if (emit) hipLaunchKernelGGL((k_relation_program<true, true>), grid, dim3(RP_LANES), lds, s, d_L + i);
+                    else hipLaunchKernelGGL((k_relation_program<false, true>), grid, dim3(RP_LANES), lds, s, d_L + i);
+                } else {
+                    if (emit) hipLaunchKernelGGL((k_relation_program<true, false>), grid, dim3(RP_LANES), lds, s, d_L + i);
+                    else hipLaunchKernelGGL((k_relation_program<false, false>), grid, dim3(RP_LANES), lds, s, d_L + i);
+                }
+            }
+        };
+        const u32* d_n;
+        {
+            ProfScope ps(s, "relation_multiplicities_count", 0);
+            launch(false);
+            d_n = exclusive_scan_u32(s, counts, pos, tot, N);
+        }
+        u32 n = 0;
+        c.read_back(&n, d_n, sizeof n);      // n >= n_rows >= 1: the table side gives an entry at every row
+        relation_multiplicities(c, r, n_words, n, n_rows, out_d, cap, rep, missing_h, [&](const RelEntries& e) {
+            for (u32 i = 0; i < n_part; i++) {
+                for (u32 k = 0; k < n_words; k++) L[i].w[k] = (u64)e.w[k];
+                L[i].num = (u64)e.num; L[i].origin = (u64)e.origin;
+            }
+            launch(true);
+        });
+        c.sync();
+        BF_HIP(hipGetLastError());
+        *report = rep;
     } catch (...) {
         (void)hipStreamSynchronize(c.stream);
         c.arena.rewind(arena_mark);

@@ -14,7 +14,8 @@
 // (an instruction inside a loop repeats its (ip, ci, ni) once per iteration) —, first yield and first use are 64-bit atomicMin;
 // (5) the tuples with net != 0 are compacted in sorted order, up to the caller's cap. Integers only: nothing depends on the schedule.
 // Steps (2) to (5) are relation_aggregate (ctx.h), which the relation programs of any AIR share (relation_program.hip): they bring their own
-// step (1), an interpreter instead of k_rel_flags / k_rel_emit.
+// step (1), an interpreter instead of k_rel_flags / k_rel_emit. relation_multiplicities (ctx.h) shares steps (2) and (3) (relation_sort) and
+// the scan, and writes each tuple's net into the looked-up table's column instead of reporting it.
 #include "../../include/bfhip.h"
 #include <cstring>
 #include <hip/hip_runtime.h>
@@ -111,12 +112,23 @@ __device__ __forceinline__ uint4 st_block_scan(uint4* s, uint4 sum, uint4* total
     __syncthreads();
     return excl;
 }
-__global__ void __launch_bounds__(256) k_rel_stats_local(const u32* __restrict__ num, const u32* __restrict__ perm, uint4* __restrict__ out, uint4* __restrict__ totals, u32 n) {
+// MARKED (relation_multiplicities): an entry whose origin carries REL_TABLE_SIDE contributes nothing to any channel — masked, not given
+// multiplicity 0, which st_of would count as "other"
+template <bool MARKED>
+__global__ void __launch_bounds__(256) k_rel_stats_local(const u32* __restrict__ num, const u64* __restrict__ origin, const u32* __restrict__ perm, uint4* __restrict__ out,
+                                                         uint4* __restrict__ totals, u32 n) {
     __shared__ uint4 s[256];
     const u32 base = blockIdx.x * ST_TILE + threadIdx.x * 8;
     uint4 v[8], sum = make_uint4(0, 0, 0, 0);
 #pragma unroll
-    for (u32 k = 0; k < 8; k++) { v[k] = base + k < n ? st_of(num[perm[base + k]]) : make_uint4(0, 0, 0, 0); sum = st_add(sum, v[k]); }
+    for (u32 k = 0; k < 8; k++) {
+        v[k] = make_uint4(0, 0, 0, 0);
+        if (base + k < n) {
+            const u32 j = perm[base + k];
+            if (!MARKED || !(origin[j] & REL_TABLE_SIDE)) v[k] = st_of(num[j]);
+        }
+        sum = st_add(sum, v[k]);
+    }
     uint4 total, run = st_block_scan(s, sum, &total);
 #pragma unroll
     for (u32 k = 0; k < 8; k++) { run = st_add(run, v[k]); if (base + k < n) out[base + k] = run; }
@@ -139,9 +151,12 @@ __global__ void __launch_bounds__(256) k_rel_stats_add(uint4* __restrict__ out, 
 }
 // First yield and first use of every tuple: the lowest (table, row) among its entries with numerator 1 / p - 1. A lane whose left
 // neighbour in the wave offers a lower origin for the same tuple and kind leaves the atomic to it (a chain of such lanes ends at one that
-// issues): a long segment costs about one atomic per wave, and the minimum is the same.
+// issues): a long segment costs about one atomic per wave, and the minimum is the same. MARKED (relation_multiplicities): an entry whose
+// origin carries REL_TABLE_SIDE is a third kind whatever its multiplicity word, and its minimum goes to first_side — the mark is the top bit
+// of every such origin, so the minimum is still the lowest row.
+template <bool MARKED>
 __global__ void __launch_bounds__(256) k_rel_first(const u32* __restrict__ num, const u64* __restrict__ origin, const u32* __restrict__ perm, const u32* __restrict__ heads,
-                                                   const u32* __restrict__ segx, u32 n, u64* __restrict__ first_yield, u64* __restrict__ first_use) {
+                                                   const u32* __restrict__ segx, u32 n, u64* __restrict__ first_yield, u64* __restrict__ first_use, u64* __restrict__ first_side) {
     const u32 i = blockIdx.x * 256u + threadIdx.x;
     u32 seg = 0xffffffffu, kind = 0;
     u64 org = ~u64(0);
@@ -150,11 +165,12 @@ __global__ void __launch_bounds__(256) k_rel_first(const u32* __restrict__ num, 
         seg = segx[i] + heads[i] - 1;
         kind = v == 1u ? 1u : v == P31 - 1 ? 2u : 0u;
         org = origin[j];
+        if (MARKED && (org & REL_TABLE_SIDE)) kind = 3u;
     }
     const u32 pseg = __shfl_up(seg, 1, 64), pkind = __shfl_up(kind, 1, 64);
     const u64 porg = __shfl_up((unsigned long long)org, 1, 64);
     const bool covered = (threadIdx.x & 63u) != 0 && pseg == seg && pkind == kind && porg < org;
-    if (kind && !covered) atomicMin(reinterpret_cast<unsigned long long*>(kind == 1 ? first_yield + seg : first_use + seg), (unsigned long long)org);
+    if (kind && !covered) atomicMin(reinterpret_cast<unsigned long long*>(kind == 1 ? first_yield + seg : kind == 2 ? first_use + seg : first_side + seg), (unsigned long long)org);
 }
 __device__ __forceinline__ uint4 rel_segment_stats(const uint4* __restrict__ scan, const u32* __restrict__ start, u32 s) {
     const u32 a = start[s], b = start[s + 1];
@@ -211,9 +227,10 @@ static void relation_run(Ctx& c, u32 relation, const RelSources& S, u32 N, u32 c
                        [&](const RelEntries& e) { hipLaunchKernelGGL(k_rel_emit, grid256(N), dim3(256), 0, s, d_S, N, flags, pos, e); });
 }
 
-// Steps (2) to (5) over the n >= 1 entries that `emit` writes (ctx.h). Arena memory only; every launch has a non-zero size.
-void relation_aggregate(Ctx& c, u32 relation, u32 n_words, u32 n, u32 cap, bfhip_relation_report& rep, bfhip_relation_entry* entries_h,
-                        const std::function<void(const RelEntries&)>& emit, const char* emit_scope) {
+// Steps (2) and (3) over the n >= 1 entries that `emit` writes: the entries, their sorted order, the segment heads and their exclusive scan.
+// Shared by relation_aggregate and relation_multiplicities; arena memory only.
+struct RelSorted { RelEntries e; const u32* order; u32* heads; u32* segx; u32 n_tuples; };
+static RelSorted relation_sort(Ctx& c, u32 n_words, u32 n, const std::function<void(const RelEntries&)>& emit, const char* emit_scope, const char* sort_scope) {
     hipStream_t s = c.stream;
     RelEntries e{};
     for (u32 k = 0; k < n_words; k++) e.w[k] = c.alloc_u32(n);
@@ -230,7 +247,7 @@ void relation_aggregate(Ctx& c, u32 relation, u32 n_words, u32 n, u32 cap, bfhip
     int cur = 0;
     if (emit_scope) { ProfScope ps(s, emit_scope, 0); emit(e); }
     {
-        ProfScope ps(s, "relations_sort", 0);
+        ProfScope ps(s, sort_scope, 0);
         if (!emit_scope) emit(e);
         hipLaunchKernelGGL(k_rel_iota, grid256(n), dim3(256), 0, s, perm[0], n);
         // stable LSD passes over (w[k-1], w[k]) pairs from the last word down; word 0 of an odd tuple goes alone (32 key bits)
@@ -243,8 +260,18 @@ void relation_aggregate(Ctx& c, u32 relation, u32 n_words, u32 n, u32 cap, bfhip
         hipLaunchKernelGGL(k_rel_heads, grid256(n), dim3(256), 0, s, e, n_words, (const u32*)perm[cur], n, heads);
         d_n_tuples = exclusive_scan_u32(s, heads, segx, seg_tot, n);
     }
-    const u32* order = perm[cur];
-    const u32 n_tuples = scan_total(c, d_n_tuples);
+    return RelSorted{e, perm[cur], heads, segx, scan_total(c, d_n_tuples)};
+}
+
+// Steps (2) to (5) over the n >= 1 entries that `emit` writes (ctx.h). Arena memory only; every launch has a non-zero size.
+void relation_aggregate(Ctx& c, u32 relation, u32 n_words, u32 n, u32 cap, bfhip_relation_report& rep, bfhip_relation_entry* entries_h,
+                        const std::function<void(const RelEntries&)>& emit, const char* emit_scope) {
+    hipStream_t s = c.stream;
+    const RelSorted sorted = relation_sort(c, n_words, n, emit, emit_scope, "relations_sort");
+    const RelEntries& e = sorted.e;
+    const u32* order = sorted.order;
+    const u32* heads = sorted.heads; const u32* segx = sorted.segx;
+    const u32 n_tuples = sorted.n_tuples;
     rep.n_tuples = n_tuples;
     // (4)
     const u32 nb = (n + ST_TILE - 1) / ST_TILE;
@@ -255,12 +282,13 @@ void relation_aggregate(Ctx& c, u32 relation, u32 n_words, u32 n, u32 cap, bfhip
     const u32* d_n_unb;
     {
         ProfScope ps(s, "relations_reduce", 0);
-        hipLaunchKernelGGL(k_rel_stats_local, dim3(nb), dim3(256), 0, s, (const u32*)e.num, order, scan, scan_tot, n);
+        hipLaunchKernelGGL(k_rel_stats_local<false>, dim3(nb), dim3(256), 0, s, (const u32*)e.num, (const u64*)nullptr, order, scan, scan_tot, n);
         hipLaunchKernelGGL(k_rel_stats_totals, dim3(1), dim3(256), 0, s, scan_tot, nb);
         hipLaunchKernelGGL(k_rel_stats_add, grid256(n), dim3(256), 0, s, scan, (const uint4*)scan_tot, n);
         hipLaunchKernelGGL(k_rel_starts, grid256(n), dim3(256), 0, s, (const u32*)heads, (const u32*)segx, n, start);
         BF_HIP(hipMemsetAsync(first, 0xff, sizeof(u64) * 2 * n_tuples, s));
-        hipLaunchKernelGGL(k_rel_first, grid256(n), dim3(256), 0, s, (const u32*)e.num, (const u64*)e.origin, order, (const u32*)heads, (const u32*)segx, n, first, first + n_tuples);
+        hipLaunchKernelGGL(k_rel_first<false>, grid256(n), dim3(256), 0, s, (const u32*)e.num, (const u64*)e.origin, order, (const u32*)heads, (const u32*)segx, n, first, first + n_tuples,
+                           (u64*)nullptr);
         hipLaunchKernelGGL(k_rel_unbalanced, grid256(n_tuples), dim3(256), 0, s, (const uint4*)scan, (const u32*)start, n_tuples, unb);
         d_n_unb = exclusive_scan_u32(s, unb, upos, unb_tot, n_tuples);
     }
@@ -278,6 +306,82 @@ void relation_aggregate(Ctx& c, u32 relation, u32 n_words, u32 n, u32 cap, bfhip
     }
     BF_HIP(hipGetLastError());
     c.read_back(entries_h, d_out, sizeof(bfhip_relation_entry) * n_rep);
+}
+
+// ---- the other direction: the nets go INTO the looked-up table's multiplicity column (ctx.h: relation_multiplicities) -----------------------
+// One lane per tuple. The scan was taken with the table-side entries masked, so st is the net and the counts of the OTHER entries; side =
+// the lowest table-side origin of the segment (k_rel_first<true>) or ~0. A tuple some row holds: that row's word of out (zeroed before) gets
+// the net. A tuple no row holds with net != 0 is missing. counts = {tuples some row holds, tuples with another entry, rows given a non-zero
+// word}: one integer atomicAdd per wave and counter, of a ballot's population count — the sums do not depend on the order.
+__global__ void __launch_bounds__(256) k_rel_mult_scatter(const uint4* __restrict__ scan, const u32* __restrict__ start, const u64* __restrict__ first_side, u32 n_tuples,
+                                                          u32 n_rows, u32* __restrict__ out, u32* __restrict__ missing, u32* __restrict__ counts) {
+    const u32 s = blockIdx.x * 256u + threadIdx.x;
+    bool held = false, used = false, filled = false;
+    if (s < n_tuples) {
+        const uint4 st = rel_segment_stats(scan, start, s);
+        const u64 side = first_side[s];
+        held = side != ~u64(0);
+        used = (st.y | st.z | st.w) != 0;
+        filled = held && st.x != 0;
+        missing[s] = !held && st.x != 0 ? 1u : 0u;
+        const u32 row = (u32)side;                                // origin = mark | table << 32 | row
+        if (filled && row < n_rows) out[row] = st.x;
+    }
+    const u32 n_held = __popcll(__ballot(held)), n_used = __popcll(__ballot(used)), n_filled = __popcll(__ballot(filled));
+    if ((threadIdx.x & 63u) == 0) {
+        if (n_held) atomicAdd(counts + 0, n_held);
+        if (n_used) atomicAdd(counts + 1, n_used);
+        if (n_filled) atomicAdd(counts + 2, n_filled);
+    }
+}
+
+void relation_multiplicities(Ctx& c, u32 relation, u32 n_words, u32 n, u32 n_rows, u32* out_d, u32 cap, bfhip_multiplicity_report& rep,
+                             bfhip_relation_entry* missing_h, const std::function<void(const RelEntries&)>& emit) {
+    hipStream_t s = c.stream;
+    // (2) + (3): the stable sort keeps (table, row, program order) inside a segment
+    const RelSorted sorted = relation_sort(c, n_words, n, emit, "relation_multiplicities_extract", "relation_multiplicities_sort");
+    const RelEntries& e = sorted.e;
+    const u32* order = sorted.order;
+    const u32 n_tuples = sorted.n_tuples;
+    const u32 nb = (n + ST_TILE - 1) / ST_TILE;
+    uint4* scan = (uint4*)c.arena.alloc(sizeof(uint4) * n); uint4* scan_tot = (uint4*)c.arena.alloc(sizeof(uint4) * nb);
+    u32* start = c.alloc_u32(size_t(n_tuples) + 1);
+    u64* first = (u64*)c.arena.alloc(sizeof(u64) * 3 * n_tuples);      // first yield, first use, lowest table-side row
+    u32* miss = c.alloc_u32(n_tuples); u32* mpos = c.alloc_u32(n_tuples); u32* miss_tot = c.alloc_u32(n_tuples / ST_TILE + 3);
+    u32* counts = c.alloc_u32(4);
+    const u32* d_n_miss;
+    {
+        ProfScope ps(s, "relation_multiplicities_scatter", 0);
+        hipLaunchKernelGGL(k_rel_stats_local<true>, dim3(nb), dim3(256), 0, s, (const u32*)e.num, (const u64*)e.origin, order, scan, scan_tot, n);
+        hipLaunchKernelGGL(k_rel_stats_totals, dim3(1), dim3(256), 0, s, scan_tot, nb);
+        hipLaunchKernelGGL(k_rel_stats_add, grid256(n), dim3(256), 0, s, scan, (const uint4*)scan_tot, n);
+        hipLaunchKernelGGL(k_rel_starts, grid256(n), dim3(256), 0, s, (const u32*)sorted.heads, (const u32*)sorted.segx, n, start);
+        BF_HIP(hipMemsetAsync(first, 0xff, sizeof(u64) * 3 * n_tuples, s));
+        BF_HIP(hipMemsetAsync(counts, 0, sizeof(u32) * 4, s));
+        hipLaunchKernelGGL(k_rel_first<true>, grid256(n), dim3(256), 0, s, (const u32*)e.num, (const u64*)e.origin, order, (const u32*)sorted.heads, (const u32*)sorted.segx, n, first,
+                           first + n_tuples, first + 2 * size_t(n_tuples));
+        // out_d may be a column the extraction read: every launch that reads columns is ahead of these two on the stream
+        BF_HIP(hipMemsetAsync(out_d, 0, sizeof(u32) * size_t(n_rows), s));
+        hipLaunchKernelGGL(k_rel_mult_scatter, grid256(n_tuples), dim3(256), 0, s, (const uint4*)scan, (const u32*)start, (const u64*)(first + 2 * size_t(n_tuples)), n_tuples, n_rows,
+                           out_d, miss, counts);
+        d_n_miss = exclusive_scan_u32(s, miss, mpos, miss_tot, n_tuples);
+    }
+    const u32 n_miss = scan_total(c, d_n_miss);
+    u32 h_counts[4] = {};
+    c.read_back(h_counts, counts, sizeof h_counts);
+    rep.n_row_tuples = h_counts[0]; rep.n_entries = u64(n) - n_rows; rep.n_tuples = h_counts[1]; rep.n_filled = h_counts[2];
+    rep.n_missing = n_miss;
+    const u32 n_rep = n_miss < cap ? n_miss : cap;
+    rep.n_reported = n_rep;
+    if (n_rep == 0) return;
+    bfhip_relation_entry* d_out = (bfhip_relation_entry*)c.arena.alloc(sizeof(bfhip_relation_entry) * n_rep);
+    {
+        ProfScope ps(s, "relation_multiplicities_report", 0);
+        hipLaunchKernelGGL(k_rel_report, grid256(n_tuples), dim3(256), 0, s, e, n_words, relation, order, (const uint4*)scan, (const u32*)start, n_tuples, (const u32*)miss,
+                           (const u32*)mpos, (const u64*)first, (const u64*)(first + n_tuples), n_rep, d_out);
+    }
+    BF_HIP(hipGetLastError());
+    c.read_back(missing_h, d_out, sizeof(bfhip_relation_entry) * n_rep);
 }
 
 struct RelTable { int component; u32 log_size; const u32* const* cols; };
