@@ -161,6 +161,14 @@ int32_t bfhip_evaluate(bfhip_ctx* ctx, uint32_t* const* coeff_cols_h, uint32_t* 
  * log_size in log_min..=log_max): the coefficients of the indicator of cell 0, written in closed form by ONE launch (no transform).
  * dst_cols_h[n - log_min] = device pointer to 2^n words, or NULL to skip that size. 4 <= log_min <= log_max < log_min + 28. */
 int32_t bfhip_is_first_coeffs(bfhip_ctx* ctx, uint32_t log_min, uint32_t log_max, uint32_t* const* dst_cols_h);
+/* The same columns committed (tree_builder.commit -> LDE, mod.rs:500): the evaluations of IsFirst(n) on CanonicCoset(n + log_blowup).circle_domain()
+ * for n = log_min..=log_max, written in closed form by ONE launch — word for word what bfhip_is_first_coeffs followed by bfhip_evaluate leaves, with
+ * neither coefficients nor transforms. dst_cols_h[n - log_min] = device pointer to 2^(n + log_blowup) words, or NULL to skip that size.
+ * 4 <= log_min <= log_max < log_min + 28, log_max + log_blowup within the context's twiddle tree. */
+int32_t bfhip_is_first_lde(bfhip_ctx* ctx, uint32_t log_min, uint32_t log_max, uint32_t log_blowup, uint32_t* const* dst_cols_h);
+/* PolyOps::eval_at_point of IsFirst(log_size) in closed form (no coefficients): what bfhip_eval_at_point returns for the column bfhip_is_first_coeffs
+ * writes. point_h = x then y (u32[8]), out_h = u32[4]. 4 <= log_size <= 31, within the context's twiddle tree. */
+int32_t bfhip_is_first_eval_at_point(bfhip_ctx* ctx, uint32_t log_size, const uint32_t point_h[8], uint32_t out_h[4]);
 
 /* ---- single backend operations (each is what one stwo trait method would call; all reached from mod.rs:732 prover::prove unless noted) ----
  * A secure (QM31) column is passed as 4 coordinate pointers. Values/points passed from the host are u32[4] per QM31. */
@@ -663,7 +671,7 @@ int32_t bfhip_brainfuck_composition_at_point(const uint32_t log_sizes_h[13], con
  *   bfhip_ctx_set_conventions, bfhip_ctx_set_pcs_config, bfhip_ctx_join_local_group, bfhip_ctx_join_rccl_group, bfhip_ctx_destroy,
  *   and a second bfhip_pcs_create.
  * Everything else keeps working, which is what the caller's constraint sweep needs: bfhip_malloc / bfhip_free / bfhip_upload / bfhip_download /
- * bfhip_memset_zero, bfhip_interpolate, bfhip_evaluate, bfhip_is_first_coeffs, bfhip_eval_at_point, bfhip_logup_generate, bfhip_eval_constraints,
+ * bfhip_memset_zero, bfhip_interpolate, bfhip_evaluate, bfhip_is_first_coeffs, bfhip_is_first_lde, bfhip_eval_at_point, bfhip_logup_generate, bfhip_eval_constraints,
  * bfhip_air_eval_domain, bfhip_logup_program_generate, bfhip_accumulate, the Merkle / fold / grind / gather single operations, resident traces' getters and the profiler.
  * Not supported: a context in a shard group (create refuses; joining refuses while a session is open); a pool's sub-context while anything
  * is queued, running or not yet taken on the pool.

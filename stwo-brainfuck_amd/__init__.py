@@ -566,6 +566,18 @@ class Context:
         arr = (ctypes.c_void_p * len(dst_ptrs))(*[p or None for p in dst_ptrs])
         _check(lib().bfhip_is_first_coeffs(self._h, log_min, log_max, arr))
 
+    def is_first_lde(self, log_min, log_max, log_blowup, dst_ptrs):
+        """evaluate(interpolate(gen_is_first(n))) on 2^(n + log_blowup) cells for n = log_min..log_max in closed form; dst_ptrs[n - log_min] may be None."""
+        arr = (ctypes.c_void_p * len(dst_ptrs))(*[p or None for p in dst_ptrs])
+        _check(lib().bfhip_is_first_lde(self._h, log_min, log_max, log_blowup, arr))
+
+    def is_first_eval_at_point(self, log_size, point8):
+        """eval_at_point of IsFirst(log_size) in closed form (no coefficient column)."""
+        pt = (ctypes.c_uint32 * 8)(*[int(v) for v in point8])
+        out = (ctypes.c_uint32 * 4)()
+        _check(lib().bfhip_is_first_eval_at_point(self._h, log_size, pt, out))
+        return list(out)
+
     def eval_at_point(self, coeff_ptr, log_size, point8, replicated=False):
         pt = (ctypes.c_uint32 * 8)(*[int(v) for v in point8])
         out = (ctypes.c_uint32 * 4)()

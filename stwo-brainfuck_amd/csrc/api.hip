@@ -546,6 +546,43 @@ int32_t bfhip_is_first_coeffs(bfhip_ctx* ctx, uint32_t log_min, uint32_t log_max
     return 0;
     API_CATCH
 }
+int32_t bfhip_is_first_lde(bfhip_ctx* ctx, uint32_t log_min, uint32_t log_max, uint32_t log_blowup, uint32_t* const* dst_cols_h) {
+    API_CTX(ctx)
+    if (!dst_cols_h) throw HipError("null argument");
+    if (log_min < 4 || log_max < log_min || log_max - log_min >= 28) throw HipError("is_first_lde: need 4 <= log_min <= log_max < log_min + 28");
+    if (log_blowup > 31 || log_max + log_blowup > ctx->c.tw_root_log + 1 || log_max + log_blowup > 31) throw HipError("log_max + log_blowup exceeds the context's twiddle tree");
+    IsFirstCols a{}; a.log_min = log_min; a.log_max = log_max;
+    for (u32 n = log_min; n <= log_max; n++) a.ptr[n - log_min] = dst_cols_h[n - log_min];
+    is_first_lde(ctx->c.stream, a, log_blowup, ctx->c.d_tw, ctx->c.d_itw, ctx->c.tw_root_log);
+    BF_HIP(hipGetLastError());
+    return 0;
+    API_CATCH
+}
+int32_t bfhip_is_first_eval_at_point(bfhip_ctx* ctx, uint32_t log_size, const uint32_t point_h[8], uint32_t out_h[4]) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    if (!point_h || !out_h) throw HipError("null argument");
+    if (log_size < 4 || log_size > 31 || log_size > c.tw_root_log + 1) throw HipError("is_first_eval_at_point: need 4 <= log_size within the context's twiddle tree");
+    c.stage_checkpoint();
+    uint4 factors[32];
+    Q31 x = q_make(point_h[0], point_h[1], point_h[2], point_h[3]);
+    factors[0] = make_uint4(point_h[4], point_h[5], point_h[6], point_h[7]);
+    for (u32 b = 1; b < 32; b++) { factors[b] = make_uint4(x.a.a, x.a.b, x.b.a, x.b.b); Q31 s = q_mul(x, x); x = q_subm(q_add(s, s), 1); }
+    IsFirstSample job{log_size, 0, 0};
+    const IsFirstSample* dj = c.stage(&job, 1);
+    const uint4* df = c.stage(factors, 32);
+    uint4* dout = nullptr;
+    BF_HIP(hipMalloc((void**)&dout, sizeof(uint4)));
+    is_first_samples(c.stream, dj, 1, df, dout, c.d_itw, c.tw_root_log);
+    uint4 r;
+    hipError_t e = hipMemcpyAsync(&r, dout, sizeof(uint4), hipMemcpyDeviceToHost, c.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    (void)hipFree(dout);
+    BF_HIP(e);
+    out_h[0] = r.x; out_h[1] = r.y; out_h[2] = r.z; out_h[3] = r.w;
+    return 0;
+    API_CATCH
+}
 int32_t bfhip_broadcast16(bfhip_ctx* ctx, const uint32_t* rows_d, uint32_t* dst_d, size_t n_rows) {
     API_CTX(ctx) broadcast16(ctx->c.stream, rows_d, dst_d, (u32)(n_rows * 16)); BF_HIP(hipGetLastError()); return 0; API_CATCH
 }

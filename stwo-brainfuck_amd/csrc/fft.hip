@@ -97,6 +97,101 @@ void is_first_coeffs(hipStream_t stream, const IsFirstCols& a, const u32* itw, u
     hipLaunchKernelGGL(k_is_first_coeffs, dim3((lanes + 255) / 256), dim3(256), 0, stream, a, itw, 1u << tw_root_log);
 }
 
+// The LDE of those columns in closed form as well: evaluate(interpolate(gen_is_first(n))) on the 2^N-cell domain, N = n + log_blowup, for every n in
+// one launch. The tensor product survives the forward butterflies (v0, v1) -> (v0 + v1 T, v0 - v1 T) too: the layers >= n only duplicate, and going
+// down from layer n - 1 the pair of layer i holds (P, P t_i) x (what the layers above made of the cell's block), so layer i multiplies the cell by
+// 1 + t_i T_i(cell >> (i + 1)) or, with bit i of the cell set, 1 - t_i T_i(cell >> (i + 1)):
+//     e(cell) = 2^-n * prod_{i < n} (1 +- t_i T_i(cell >> (i + 1)))
+// T_i(h) = the forward twiddle of pair block h in layer i of the 2^N-cell transform, read exactly as fft_pass_body stages it (layer_table; the circle
+// layer takes [y, -y, -x, x][h & 3] of entry pair h >> 2 of the first line table), t_i as in k_is_first_coeffs. Exact field arithmetic on canonical
+// values: the words are those the general transform writes. One lane owns 16 consecutive cells: the factors of the layers >= 4 are common to them
+// (two products per layer; those of the layers >= 10 are common to the whole wave and computed once for it), the four low layers take 11 products for
+// their 15 distinct factors and 30 to spread them over the cells. No column is read.
+__global__ void __launch_bounds__(256) k_is_first_lde(IsFirstCols a, u32 log_blowup, const u32* __restrict__ tw, const u32* __restrict__ itw, u32 tw_total) {
+    // lanes flattened over the columns in ascending size, lane u = 2^(N-4) + (cell >> 4) of the 2^N-cell column: a wave (64 lanes, 1024 cells) of u >= 64
+    // lies inside one column of >= 2^10 cells (the lanes below 2^(log_min + log_blowup - 4) have no column)
+    const u32 u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u < (1u << (a.log_min + log_blowup - 4)) || u >= (1u << (a.log_max + log_blowup - 3))) return;
+    const u32 N = 35u - __clz(u), n = N - log_blowup;  // column IsFirst(n) on 2^N cells: u in [2^(N-4), 2^(N-3))
+    u32* __restrict__ dst = a.ptr[n - a.log_min];
+    if (!dst) return;                                 // another rank of the shard group owns this column
+    const u32 chi = u - (1u << (N - 4));              // cell >> 4
+    auto t = [&](u32 i) -> u32 { return i == 0 ? itw[tw_total - (1u << (n - 1)) + 1] : itw[tw_total - (1u << (n - i))]; };
+    u32 pre = m_inv_pow2(n), lane_layers = n;         // the layers [4, lane_layers) are this lane's own
+    if (u >= 64u) {
+        // the factors of the layers >= 10 are the same for the wave's 1024 cells: wave-uniform operands, so once per wave (scalar unit) and not per lane
+        const u32 cw = __builtin_amdgcn_readfirstlane(chi >> 6), nw = __builtin_amdgcn_readfirstlane(n), Nw = nw + log_blowup;
+        u32 pw = m_inv_pow2(nw);
+        for (u32 i = 10; i < nw; i++) {
+            const u32 f = m_mul(itw[tw_total - (1u << (nw - i))], tw[tw_total - (1u << (Nw - i)) + (cw >> (i - 9))]);
+            pw = m_mul(pw, (cw >> (i - 10)) & 1 ? m_sub(1u, f) : m_add(1u, f));
+        }
+        pre = pw; lane_layers = min(n, 10u);
+    }
+    for (u32 i = 4; i < lane_layers; i++) {
+        const u32 f = m_mul(t(i), tw[tw_total - (1u << (N - i)) + (chi >> (i - 3))]);
+        pre = m_mul(pre, (chi >> (i - 4)) & 1 ? m_sub(1u, f) : m_add(1u, f));
+    }
+    // layers 1 and 0 share the four entries 4 chi .. 4 chi + 3 of the first line table: T_1 of the cell quads, (x, y) of the two circle-layer chunks
+    const uint4 l0 = *reinterpret_cast<const uint4*>(tw + (tw_total - (1u << (N - 1))) + 4 * (size_t)chi);
+    const u32 l0w[4] = {l0.x, l0.y, l0.z, l0.w};
+    const u32 t0 = t(0), t1 = t(1), t2 = t(2), t3 = t(3);
+    const u32 f3 = m_mul(t3, tw[tw_total - (1u << (N - 3)) + chi]);
+    u32 w3[2] = {m_mul(pre, m_add(1u, f3)), m_mul(pre, m_sub(1u, f3))};
+    u32 v[16];
+#pragma unroll
+    for (u32 b3 = 0; b3 < 2; b3++) {
+        const u32 f2 = m_mul(t2, tw[tw_total - (1u << (N - 2)) + 2 * chi + b3]);
+        const u32 w2[2] = {m_mul(w3[b3], m_add(1u, f2)), m_mul(w3[b3], m_sub(1u, f2))};
+        // circle layer of this half: pairs (y, -y, -x, x) of chunk 2 chi + b3
+        const u32 gx = m_mul(t0, l0w[2 * b3]), gy = m_mul(t0, l0w[2 * b3 + 1]);
+        const u32 py = m_add(1u, gy), ny = m_sub(1u, gy), px = m_add(1u, gx), nx = m_sub(1u, gx);
+        const u32 f0[8] = {py, ny, ny, py, nx, px, px, nx};
+#pragma unroll
+        for (u32 b2 = 0; b2 < 2; b2++) {
+            const u32 f1 = m_mul(t1, l0w[2 * b3 + b2]);
+            const u32 w1[2] = {m_mul(w2[b2], m_add(1u, f1)), m_mul(w2[b2], m_sub(1u, f1))};
+#pragma unroll
+            for (u32 e = 0; e < 4; e++) v[8 * b3 + 4 * b2 + e] = m_mul(w1[e >> 1], f0[4 * b2 + e]);
+        }
+    }
+    g_u32p o = as_global(dst) + 16 * (size_t)chi;
+#pragma unroll
+    for (int q = 0; q < 4; q++) st16(o + 4 * q, make_uint4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]));
+}
+// The same product at a point outside the domain (PolyOps::eval_at_point of these columns): sum_j c_j prod_{bit b of j} F[b] with c_j = 2^-n prod t_b
+// factors into 2^-n prod_{b < n} (1 + t_b F[b]). One wave per (size, point): lane b holds the factor of bit b (n <= 31), five exchange steps multiply them
+// up (exact field arithmetic: the order does not matter). F as eval_at_points takes it (32 QM31 entries per point).
+__global__ void __launch_bounds__(64) k_is_first_samples(const IsFirstSample* __restrict__ jobs, const uint4* __restrict__ factors, uint4* __restrict__ out,
+                                                         const u32* __restrict__ itw, u32 tw_total) {
+    const IsFirstSample job = jobs[blockIdx.x];
+    const u32 n = job.log_n, b = threadIdx.x;
+    Q31 acc = q_one();
+    if (b < n) {
+        const u32 tb = b == 0 ? itw[tw_total - (1u << (n - 1)) + 1] : itw[tw_total - (1u << (n - b))];
+        const uint4 f = factors[(size_t)job.point * 32 + b];
+        acc = q_addm(q_mulm(q_make(f.x, f.y, f.z, f.w), tb), 1u);
+    }
+    for (int s = 1; s < 32; s <<= 1) {      // every lane of the wave takes part (the lanes >= n carry ones)
+        const Q31 o = q_make((u32)__shfl_xor((int)acc.a.a, s), (u32)__shfl_xor((int)acc.a.b, s), (u32)__shfl_xor((int)acc.b.a, s), (u32)__shfl_xor((int)acc.b.b, s));
+        acc = q_mul(acc, o);
+    }
+    if (b == 0) { acc = q_mulm(acc, m_inv_pow2(n)); out[job.out_idx] = make_uint4(acc.a.a, acc.a.b, acc.b.a, acc.b.b); }
+}
+void is_first_samples(hipStream_t stream, const IsFirstSample* d_jobs, u32 n_jobs, const void* d_factors, void* d_out, const u32* itw, u32 tw_root_log) {
+    if (!n_jobs) return;
+    hipLaunchKernelGGL(k_is_first_samples, dim3(n_jobs), dim3(64), 0, stream, d_jobs, (const uint4*)d_factors, (uint4*)d_out, itw, 1u << tw_root_log);
+}
+void is_first_lde(hipStream_t stream, const IsFirstCols& a, u32 log_blowup, const u32* tw, const u32* itw, u32 tw_root_log) {
+    if (a.log_min < 4 || a.log_max < a.log_min || a.log_max - a.log_min >= 28 || a.log_max + log_blowup > tw_root_log + 1 || a.log_max + log_blowup > 31)
+        throw std::runtime_error("is_first_lde: unsupported sizes");
+    const u32 lanes = 1u << (a.log_max + log_blowup - 3);
+    double bytes = 0;
+    for (u32 n = a.log_min; n <= a.log_max; n++) if (a.ptr[n - a.log_min]) bytes += 4.0 * (double)(1ull << (n + log_blowup));
+    ProfScope ps(stream, "k_is_first_lde", bytes, bytes);
+    hipLaunchKernelGGL(k_is_first_lde, dim3((lanes + 255) / 256), dim3(256), 0, stream, a, log_blowup, tw, itw, 1u << tw_root_log);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // One pass = layers [lo, lo+k) of a size-2^log transform, for the columns cols[by * cpb .. +cpb) of one GROUP (columns of one size and
 // storage). A launch covers several groups (PassArgs table in HBM, kernels.h): workgroup b belongs to the group g with

@@ -106,6 +106,13 @@ void fft_run(hipStream_t stream, const FftPlan& plan);
 // launch: ptr[n - log_min] receives 2^n words (nullptr: skipped).
 struct IsFirstCols { u32* ptr[28]; u32 log_min, log_max; };
 void is_first_coeffs(hipStream_t stream, const IsFirstCols& a, const u32* itw, u32 tw_root_log);
+// Their evaluations on the 2^(n + log_blowup)-cell domains, in closed form by one launch: the words evaluate() makes of the coefficients above, without
+// coefficients or transforms. ptr[n - log_min] receives 2^(n + log_blowup) words (nullptr: skipped).
+void is_first_lde(hipStream_t stream, const IsFirstCols& a, u32 log_blowup, const u32* tw, const u32* itw, u32 tw_root_log);
+// IsFirst(n) at out-of-domain points in closed form: 2^-n * prod_{i < n} (1 + t_i F_i), F = the 32-entry factor table of the point (eval_at_points). Job j
+// writes out[out_idx[j]] = IsFirst(log_n[j]) at point[j].
+struct IsFirstSample { u32 log_n, point, out_idx; };
+void is_first_samples(hipStream_t stream, const IsFirstSample* d_jobs, u32 n_jobs, const void* d_factors, void* d_out, const u32* itw, u32 tw_root_log);
 
 // merkle.hip
 // out_shift / prev_shift: replication of this layer / of the child layer (nodes are stored at index node >> shift)

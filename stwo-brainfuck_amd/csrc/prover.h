@@ -42,7 +42,9 @@ struct DCol {
 struct DevMerkle { std::vector<u32*> layers; std::vector<u32> shifts; u32 max_log = 0; Hash32 root; int band_lo = 0, band_hi = -1; std::vector<DCol> cols; };
 // owner[i]: the rank that holds polynomial i (coefficients) and computes its LDE, or OWNER_ALL. prev[i]: previous-row copy of evals[i]
 // (row-sharded last logUp columns only; ptr == nullptr otherwise).
-struct DTree { std::vector<DCol> polys, evals, prev; std::vector<u32> owner; DevMerkle mk; };
+// is_first_closed: the preprocessed tree built without coefficient columns (build_preprocessed: polys[i].ptr == nullptr, evaluations written in closed
+// form) — whoever needs IsFirst(n) elsewhere (an out-of-domain sample, the constraint domain) takes the closed form too (kernels.h: is_first_samples, is_first_lde).
+struct DTree { std::vector<DCol> polys, evals, prev; std::vector<u32> owner; DevMerkle mk; bool is_first_closed = false; };
 struct DSecure {
     u32* c[4]; u32 log_size; u32 lc = 0;     // lc > 0: row-sharded, c[] are virtual bases (see DCol)
     bool mine(u64 cell, u32 rank) const { return lc == 0 || (cell >> (log_size - lc)) == rank; }
@@ -236,7 +238,8 @@ struct HipProver {
     u32* alloc_slice(u32 log, u32 shift = 0);
     std::vector<u32> assign_owners(const std::vector<DCol>& polys, u32 log_blowup) const;
     void commit_tree(DTree& t, Hash32* pinned_root = nullptr, bool with_prev = false);
-    void commit_tree_overlapped(DTree& t, Hash32* pinned_root, const std::vector<DCol>* interp_src = nullptr, int stamp_slot = -1);
+    // evals_ready: t.evals already holds the evaluations (build_preprocessed) — no transforms, only the Merkle tree is planned and run
+    void commit_tree_overlapped(DTree& t, Hash32* pinned_root, const std::vector<DCol>* interp_src = nullptr, int stamp_slot = -1, bool evals_ready = false);
     static void upload_trace(Ctx& c, const std::vector<Registers>& vm_trace, const std::vector<u32>& code, TraceInput& in, bool use_arena = false, bool on_gpu = true);
     // The same from the caller's register rows (n_rows x 7 u32) and program words: device-side ingestion (ingest.hip) + GPU table builders, or
     // with c.tables_on_gpu off the host path above. with_place: a non-canonical register is reported with its (row, register).
@@ -258,7 +261,8 @@ struct HipProver {
     void compute_composition(std::vector<DTree>& trees, const BrainfuckProof& bp, CompositionPlan& cp, Q31 random_coeff, Mailbox* mbx = nullptr);
     // PolyOps::eval_at_point for every (column, mask point).
     // sample_prepare: the job list (addresses, sizes, which point) — known before the out-of-domain point is drawn.
-    struct SamplePlan { std::vector<EvalJob> jobs; u32 partial_off = 0, n_all = 0; };
+    // isf: the samples of a tree with is_first_closed, evaluated in closed form into the same output slots
+    struct SamplePlan { std::vector<EvalJob> jobs; std::vector<IsFirstSample> isf; u32 partial_off = 0, n_all = 0; };
     SamplePlan sample_prepare(const std::vector<DTree>& trees, const std::vector<std::vector<std::vector<u32>>>& mask);
     static void sample_factors(const std::vector<PtQ>& points, uint4* factors);
     struct SampleRun { uint4* h_factors = nullptr; uint4* d_out = nullptr; };

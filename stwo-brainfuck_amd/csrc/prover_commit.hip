@@ -370,9 +370,26 @@ void HipProver::commit_tree(DTree& t, Hash32* pinned_root, bool with_prev) {
 // transformed first and its layers are hashed on the partner stream while the smaller classes are still being transformed.
 // interp_src (optional, one entry per polynomial): evaluations still to be interpolated into t.polys (extend_evals), wave by wave.
 // stamp_slot >= 0: behind the root (in its pinned slot) the proof's number is written into that stamp slot (ctx.h: wait_stamp)
-void HipProver::commit_tree_overlapped(DTree& t, Hash32* pinned_root, const std::vector<DCol>* interp_src, int stamp_slot) {
+void HipProver::commit_tree_overlapped(DTree& t, Hash32* pinned_root, const std::vector<DCol>* interp_src, int stamp_slot, bool evals_ready) {
     const size_t n = t.polys.size();
     t.owner.assign(n, OWNER_ALL);
+    if (evals_ready) {
+        // the columns are on the stream already: nothing to transform and so nothing to hash beside — one stream
+        if (interp_src || t.evals.size() != n) throw HipError("commit_tree_overlapped: ready evaluations do not match the tree");
+        t.prev.assign(n, DCol());
+        c.stage_checkpoint();
+        StageBatch sb(c);
+        MerklePlan mp = merkle_plan(t.evals);
+        sb.end();
+        bool stamped = false;
+        t.mk = merkle_run(mp, pinned_root, false, nullptr, nullptr, stamp_slot, &stamped);
+        if (stamp_slot >= 0 && !stamped) c.post_stamp(stamp_slot);
+        if (!pinned_root) ch.mix_root(t.mk.root);
+#ifdef BFHIP_TEST_HOOKS
+        capture_tree(c, t);
+#endif
+        return;
+    }
     t.evals.resize(n); t.prev.assign(n, DCol());
     u32 max_log = 0;
     for (size_t i = 0; i < n; i++) {
@@ -530,12 +547,33 @@ void HipProver::build_preprocessed(DTree& tree, Hash32* pinned_root) {
         DCol p; p.log_size = log; p.shift = 0; p.ptr = nullptr;
         tree.polys.push_back(p);
     }
+    IsFirstCols ifc{}; ifc.log_min = LOG_N_LANES; ifc.log_max = log_max_rows;
+    if (log_max_rows - LOG_N_LANES >= 28) throw HipError("log_max_rows too large");
+    if (!sharded()) {
+        // One process per proof (and the pool's builder): the LDE columns themselves in closed form, one launch (fft.hip: k_is_first_lde) — no coefficient
+        // columns, no transforms. The samples and the constraint domain of log_blowup != 1 take the closed form as well (DTree::is_first_closed).
+        tree.is_first_closed = true;
+        tree.evals.clear();
+        for (const DCol& p : tree.polys) {
+            DCol e; e.log_size = p.log_size + cfg.log_blowup; e.shift = 0; e.ptr = c.alloc_u32(e.stored());
+            tree.evals.push_back(e);
+            ifc.ptr[p.log_size - LOG_N_LANES] = e.ptr;
+        }
+        is_first_lde(c.stream, ifc, cfg.log_blowup, c.d_tw, c.d_itw, c.tw_root_log);
+#ifdef BFHIP_TEST_HOOKS
+        if (c.capture && c.capture->on) {      // the capture hands out every tree's polynomials: give it the coefficient columns
+            IsFirstCols cf{}; cf.log_min = LOG_N_LANES; cf.log_max = log_max_rows;
+            for (DCol& p : tree.polys) { p.ptr = c.alloc_u32(p.stored()); cf.ptr[p.log_size - LOG_N_LANES] = p.ptr; }
+            is_first_coeffs(c.stream, cf, c.d_itw, c.tw_root_log);
+        }
+#endif
+        commit_tree_overlapped(tree, pinned_root, nullptr, -1, /*evals_ready=*/true);
+        return;
+    }
     // shard group: the big IsFirst columns are column-sharded like the interaction tree's (owner interpolates and extends,
     // every rank receives its row range of the LDE)
     tree.owner = assign_owners(tree.polys, cfg.log_blowup);
     // interpolate(gen_is_first(log)) for every size in closed form, one launch (fft.hip: k_is_first_coeffs)
-    IsFirstCols ifc{}; ifc.log_min = LOG_N_LANES; ifc.log_max = log_max_rows;
-    if (log_max_rows - LOG_N_LANES >= 28) throw HipError("log_max_rows too large");
     for (size_t i = 0; i < tree.polys.size(); i++) {
         if (!transforms_here(tree.owner[i])) continue;
         DCol& p = tree.polys[i];
@@ -543,7 +581,7 @@ void HipProver::build_preprocessed(DTree& tree, Hash32* pinned_root) {
         ifc.ptr[p.log_size - LOG_N_LANES] = p.ptr;
     }
     is_first_coeffs(c.stream, ifc, c.d_itw, c.tw_root_log);
-    if (sharded()) commit_tree(tree, pinned_root); else commit_tree_overlapped(tree, pinned_root);
+    commit_tree(tree, pinned_root);
 }
 // The pool's builder (pool.hip): commits the preprocessed tree on this (otherwise idle) context for every proof of a batch and returns
 // without waiting — sp.ready is recorded behind the tree and the root's store into pinned memory.

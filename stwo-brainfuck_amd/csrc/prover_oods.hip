@@ -14,6 +14,7 @@ HipProver::CompositionPlan HipProver::composition_prepare(std::vector<DTree>& tr
     // coset by one extra batch of forward transforms, into arena memory that only the constraint kernels read.
     const bool own_domain = cfg.log_blowup != 1;
     std::vector<DCol> cd_src, cd_dst;
+    IsFirstCols cd_is_first{}; cd_is_first.log_min = LOG_N_LANES; cd_is_first.log_max = log_max_rows;
     auto on_constraint_domain = [&](const DCol& poly) {
         if (poly.sliced()) throw HipError("composition: a row-sharded polynomial on the constraint domain");
         DCol e; e.log_size = poly.log_size + 1; e.shift = poly.shift; e.ptr = c.alloc_u32(e.stored());
@@ -41,7 +42,12 @@ HipProver::CompositionPlan HipProver::composition_prepare(std::vector<DTree>& tr
         } else {
             const DCol& isf = trees[0].polys[log_max_rows - log];
             if (isf.shift != 0 || isf.log_size != log) throw HipError("composition: unexpected IsFirst polynomial layout");
-            L.is_first = on_constraint_domain(isf).ptr;
+            if (trees[0].is_first_closed) {
+                // no coefficients to transform: IsFirst(log) on CanonicCoset(log + 1) in closed form, one column per size, one launch for all below
+                u32*& e = cd_is_first.ptr[log - LOG_N_LANES];
+                if (!e) e = c.alloc_u32(size_t(1) << eval_log);
+                L.is_first = e;
+            } else L.is_first = on_constraint_domain(isf).ptr;
             for (u32 j = 0; j < n_main_cols(k); j++) L.trace[j] = on_constraint_domain(trees[1].polys[main_off[k] + j]).desc();
             for (u32 j = 0; j < ni; j++) L.inter[j] = on_constraint_domain(trees[2].polys[inter_off[k] + j]).desc();
         }
@@ -54,6 +60,7 @@ HipProver::CompositionPlan HipProver::composition_prepare(std::vector<DTree>& tr
         cp.launches[k] = L;
     }
     if (own_domain) fft_cols(false, cd_src, cd_dst);      // on the stream behind the interaction tree (its polynomials), before the constraints
+    if (own_domain && trees[0].is_first_closed) is_first_lde(c.stream, cd_is_first, 1, c.d_tw, c.d_itw, c.tw_root_log);
     return cp;
 }
 // the challenge-side fields of the 13 launches: coefficient powers and claimed sums
@@ -174,6 +181,7 @@ HipProver::SamplePlan HipProver::sample_prepare(const std::vector<DTree>& trees,
                 const u32 owner = trees[t].owner.empty() ? OWNER_ALL : trees[t].owner[col];
                 if (sharded() && ((owner == OWNER_ALL || replicate()) ? ji % c.shard.count : owner) != c.shard.rank) continue;
                 const DCol& p = trees[t].polys[col];
+                if (trees[t].is_first_closed) { sp.isf.push_back({p.log_size, pt, ji}); continue; }      // IsFirst(n) at the point in closed form: no coefficients
                 EvalJob j{}; j.coeffs = p.ptr; j.log_n = p.log_size - p.shift; j.point = pt; j.factor_shift = p.shift; j.partial_off = sp.partial_off; j.out_idx = ji;
                 sp.partial_off += j.log_n > 12 ? 1u << (j.log_n - 12) : 1u;
                 sp.jobs.push_back(j);
@@ -199,10 +207,11 @@ HipProver::SampleRun HipProver::sample_launch(const SamplePlan& sp, const std::v
     std::vector<uint4> factors(points.size() * 32, make_uint4(0, 0, 0, 0));
     if (!mbx) sample_factors(points, factors.data());
     c.stage_checkpoint();
-    const uint4* d_factors = nullptr; const EvalJob* d_jobs = nullptr;
+    const uint4* d_factors = nullptr; const EvalJob* d_jobs = nullptr; const IsFirstSample* d_isf = nullptr;
     stage_blocks(mbx, [&] {
         d_factors = c.stage(factors.data(), factors.size());     // through the pinned staging ring (no pageable copies)
         d_jobs = sp.jobs.empty() ? nullptr : c.stage(sp.jobs.data(), sp.jobs.size());
+        d_isf = sp.isf.empty() ? nullptr : c.stage(sp.isf.data(), sp.isf.size());
     });
     if (mbx) sr.h_factors = mbx->host(d_factors);
     void* d_partials = c.arena.alloc(size_t(sp.partial_off ? sp.partial_off : 1) * sizeof(uint4));
@@ -211,7 +220,9 @@ HipProver::SampleRun HipProver::sample_launch(const SamplePlan& sp, const std::v
         if (sharded()) BF_HIP(hipMemsetAsync(sr.d_out, 0, sp.n_all * sizeof(uint4), c.stream));
     }
     // pinned: the second stage writes the samples into the bounce buffer itself
-    eval_at_points(c.stream, d_jobs, (u32)sp.jobs.size(), sp.partial_off, d_factors, d_partials, pinned ? (void*)(c.d_small_alias + 4096) : sr.d_out);
+    void* const d_samples = pinned ? (void*)(c.d_small_alias + 4096) : (void*)sr.d_out;
+    eval_at_points(c.stream, d_jobs, (u32)sp.jobs.size(), sp.partial_off, d_factors, d_partials, d_samples);
+    is_first_samples(c.stream, d_isf, (u32)sp.isf.size(), d_factors, d_samples, c.d_itw, c.tw_root_log);
     BF_HIP(hipGetLastError());
     if (sharded()) c.shard.comm->all_reduce_max_u32(c.stream, reinterpret_cast<u32*>(sr.d_out), size_t(sp.n_all) * 4);
     return sr;

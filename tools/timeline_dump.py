@@ -14,7 +14,8 @@ def load(path):
             rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), name, int(r.get("Grid_Size_X", r.get("Grid_Size", 0)) or 0),
                          int(r.get("Workgroup_Size_X", r.get("Workgroup_Size", 0)) or 0), r.get("Queue_Id", "")))
     rows.sort()
-    starts = [i for i, r in enumerate(rows) if r[2].startswith("k_is_first_coeffs") and (i == 0 or not rows[i - 1][2].startswith("k_is_first_coeffs"))]
+    first = ("k_is_first_lde", "k_is_first_coeffs")      # a proof opens with the preprocessed columns (older builds: their coefficients)
+    starts = [i for i, r in enumerate(rows) if r[2].startswith(first) and (i == 0 or not rows[i - 1][2].startswith(first))]
     return rows[starts[-1] if starts else 0:]
 
 

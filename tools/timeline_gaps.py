@@ -39,7 +39,7 @@ def main():
             active[q] = active.get(q, 0) + d
             last = t
         span = w1 - w0
-        starts = sum(1 for i, q in enumerate(inside) if q[3].startswith("k_is_first_coeffs"))
+        starts = sum(1 for i, q in enumerate(inside) if q[3].startswith(("k_is_first_lde", "k_is_first_coeffs")))
         per_q = {}
         for s_, e_, q, _ in inside:
             per_q.setdefault(q, [0, 0]); per_q[q][0] += 1; per_q[q][1] += e_ - s_
@@ -55,8 +55,9 @@ def main():
     # as a gap in front of the kernel that follows it (the few microseconds of its table copy are counted as idle too)
     mailbox = [r for r in rows if r[2].startswith("k_mailbox")]
     rows = [r for r in rows if not r[2].startswith("k_mailbox")]
-    # a proof starts with the k_is_first_coeffs burst of the preprocessed phase: take the last such burst as the start of the last proof
-    starts = [i for i, r in enumerate(rows) if r[2].startswith("k_is_first_coeffs") and (i == 0 or not rows[i - 1][2].startswith("k_is_first_coeffs"))]
+    # a proof starts with the k_is_first_lde launch of the preprocessed phase (older builds and shard groups: k_is_first_coeffs): take the last one as the start of the last proof
+    opening = ("k_is_first_lde", "k_is_first_coeffs")
+    starts = [i for i, r in enumerate(rows) if r[2].startswith(opening) and (i == 0 or not rows[i - 1][2].startswith(opening))]
     first = starts[-1] if starts else 0
     rows = rows[first:]
     t0, t1 = rows[0][0], max(r[1] for r in rows)
