@@ -525,9 +525,58 @@ impl AirProgram {
     }
 }
 
+impl AirProgram {
+    /// `bfhip_air_source`: the HIP source of the kernel `compile` builds (host only; the same program gives the same text).
+    pub fn source(&self) -> Result<String, String> {
+        let mut n = 0usize;
+        check(unsafe { sys::bfhip_air_source(self.0, std::ptr::null_mut(), 0, &mut n) })?;
+        let mut buf = vec![0u8; n];
+        check(unsafe { sys::bfhip_air_source(self.0, buf.as_mut_ptr() as *mut std::ffi::c_char, n, &mut n) })?;
+        String::from_utf8(buf).map_err(|e| e.to_string())
+    }
+    /// `bfhip_air_compile`: this program as its own gfx950 kernel, compiled in-process for the context's device. The kernel keeps its own
+    /// copy of the program and belongs to `ctx`.
+    pub fn compile(&self, ctx: &Context) -> Result<AirKernel, String> {
+        let mut k = std::ptr::null_mut();
+        check(unsafe { sys::bfhip_air_compile(ctx.0, self.0, &mut k) })?;
+        Ok(AirKernel(k))
+    }
+}
+
 impl Drop for AirProgram {
     fn drop(&mut self) {
         unsafe { sys::bfhip_air_destroy(self.0) };
+    }
+}
+
+/// `bfhip_air_kernel_info`.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct AirKernelInfo { pub vgprs: u32, pub sgprs: Option<u32>, pub scratch_bytes: u32, pub lds_bytes: u32, pub code_object_bytes: u32, pub source_bytes: u32, pub compile_us: u32, pub from_cache: bool }
+
+/// A constraint program compiled to its own kernel (`bfhip_air_kernel`): `eval_domain` is `AirProgram::eval_domain` without the interpreter —
+/// the same arguments, checks, messages and result. Drop it before its context; a context destroyed first unloads the kernel.
+pub struct AirKernel(*mut sys::BfhipAirKernel);
+
+impl AirKernel {
+    /// `bfhip_air_kernel_eval_domain`; `ctx` must be the context that compiled the kernel.
+    pub fn eval_domain(&self, ctx: &Context, log_size: u32, log_expand: u32, cols: &[*const u32], shifts: &[u32], params: &[Felt], coeffs: &[Felt], acc: &[*mut u32; 4]) -> Result<(), String> {
+        if !shifts.is_empty() && shifts.len() != cols.len() { return Err("one shift per column".into()); }
+        check(unsafe {
+            sys::bfhip_air_kernel_eval_domain(ctx.0, self.0, log_size, log_expand, cols.as_ptr(), if shifts.is_empty() { std::ptr::null() } else { shifts.as_ptr() },
+                                              params.as_ptr() as *const u32, params.len() as u32, coeffs.as_ptr() as *const u32, coeffs.len() as u32, acc.as_ptr())
+        })
+    }
+    pub fn info(&self) -> Result<AirKernelInfo, String> {
+        let mut o = [0u32; 8];
+        check(unsafe { sys::bfhip_air_kernel_info(self.0, o.as_mut_ptr()) })?;
+        Ok(AirKernelInfo { vgprs: o[0], sgprs: if o[1] == u32::MAX { None } else { Some(o[1]) }, scratch_bytes: o[2], lds_bytes: o[3], code_object_bytes: o[4],
+                           source_bytes: o[5], compile_us: o[6], from_cache: o[7] != 0 })
+    }
+}
+
+impl Drop for AirKernel {
+    fn drop(&mut self) {
+        unsafe { sys::bfhip_air_kernel_destroy(self.0) };
     }
 }
 

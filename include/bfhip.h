@@ -672,7 +672,7 @@ int32_t bfhip_brainfuck_composition_at_point(const uint32_t log_sizes_h[13], con
  *   and a second bfhip_pcs_create.
  * Everything else keeps working, which is what the caller's constraint sweep needs: bfhip_malloc / bfhip_free / bfhip_upload / bfhip_download /
  * bfhip_memset_zero, bfhip_interpolate, bfhip_evaluate, bfhip_is_first_coeffs, bfhip_is_first_lde, bfhip_eval_at_point, bfhip_logup_generate, bfhip_eval_constraints,
- * bfhip_air_eval_domain, bfhip_logup_program_generate, bfhip_accumulate, the Merkle / fold / grind / gather single operations, resident traces' getters and the profiler.
+ * bfhip_air_eval_domain, bfhip_air_kernel_eval_domain (and bfhip_air_compile), bfhip_logup_program_generate, bfhip_accumulate, the Merkle / fold / grind / gather single operations, resident traces' getters and the profiler.
  * Not supported: a context in a shard group (create refuses; joining refuses while a session is open); a pool's sub-context while anything
  * is queued, running or not yet taken on the pool.
  * Launch order: the plain one only (wait, draw, copy, launch). No mailbox order, and the overlap mask (bfhip_ctx_set_overlap) is ignored.
@@ -780,6 +780,37 @@ int32_t bfhip_air_eval_domain(bfhip_ctx* ctx, const bfhip_air* air, uint32_t log
                               const uint32_t* params_h, uint32_t n_params, const uint32_t* coeffs_h, uint32_t n_coeffs, uint32_t* const acc_d[4]);
 int32_t bfhip_air_eval_at_point(const bfhip_air* air, uint32_t log_size, const uint32_t point_h[8], const uint32_t* mask_values_h, uint32_t n_mask,
                                 const uint32_t* params_h, uint32_t n_params, const uint32_t* coeffs_h, uint32_t n_coeffs, uint32_t out_h[4]);
+
+/* ---- Compiled constraint programs: an AIR's own gfx950 kernel, generated and compiled at run time ---------------------------------------------
+ * bfhip_air_eval_domain interprets: per instruction a scalar fetch, a branch and an LDS round trip per operand. A program is straight-line code
+ * whose registers are written before they are read, so it translates in one pass into HIP source with every value a named local, which
+ * libhiprtc (part of ROCm; opened with dlopen at the first compile, never linked) compiles in-process for the device's architecture. The
+ * interpreter stays: it needs no compile time, and it is what a compiled kernel is held to, bit for bit.
+ * bfhip_air_source (host only, no GPU): the generated source, without a terminating NUL; *len = its length. -2 ("capacity") when cap < *len;
+ *   buf NULL with cap 0: size query. The same program gives the same bytes. Compiled with -DBFHIP_AIR_GEN_HOST the text is plain C++ (the
+ *   row function `bfair::air_row(const bfair::Launch*, uint32_t row)` without the kernel wrapper).
+ * bfhip_air_compile: generates, compiles (-O3 -std=c++17, --offload-arch = the device's gcnArchName as reported) and loads the kernel. The
+ *   kernel keeps its own copy of the program: the program may be destroyed. A context keeps one module per distinct source: compiling an
+ *   equal program again while a kernel of it is alive does not run the compiler (bfhip_air_kernel_info out[7] = 1). -1 when libhiprtc or
+ *   one of its symbols is missing (the message names it) and when the compiler fails (the message carries its log, truncated). Nothing is
+ *   written to disk. One kernel serves every log_size, log_expand in 1..3, shift pattern and parameter set.
+ * bfhip_air_kernel_eval_domain: bfhip_air_eval_domain with the kernel in place of the program — the same arguments, the same checks with
+ *   the same messages (they name bfhip_air_eval_domain), the same one copy through the staging ring, no arena use (works while a session
+ *   is open), the same result to the bit. ctx must be the context that compiled the kernel; a context in a shard group is refused.
+ * bfhip_air_kernel_info: out = {VGPRs, SGPRs (0xffffffff if the code object does not say), private-segment (scratch) bytes per lane, static
+ *   LDS bytes, code-object bytes, source bytes, generate + compile + load time in microseconds (of the compile that built the module), 1 if
+ *   the context's cache served this kernel}. Scratch above 0 is reported, not refused.
+ * bfhip_air_kernel_destroy: the module is unloaded when its last kernel goes (after a wait for the context's stream).
+ * bfhip_ctx_destroy with live kernels cleans up: it unloads their modules; the kernel objects stay valid to destroy, and to nothing else
+ *   (eval_domain and info return -1). */
+typedef struct bfhip_air_kernel bfhip_air_kernel;
+int32_t bfhip_air_source(const bfhip_air* air, char* buf, size_t cap, size_t* len);
+int32_t bfhip_air_compile(bfhip_ctx* ctx, const bfhip_air* air, bfhip_air_kernel** out);
+int32_t bfhip_air_kernel_eval_domain(bfhip_ctx* ctx, bfhip_air_kernel* kernel, uint32_t log_size, uint32_t log_expand, const uint32_t* const* cols_h,
+                                     const uint32_t* col_shifts_h, const uint32_t* params_h, uint32_t n_params, const uint32_t* coeffs_h, uint32_t n_coeffs,
+                                     uint32_t* const acc_d[4]);
+int32_t bfhip_air_kernel_info(bfhip_air_kernel* kernel, uint32_t out[8]);
+int32_t bfhip_air_kernel_destroy(bfhip_air_kernel* kernel);
 
 /* ---- Constraint programs asserted on the trace domain: which constraint of ANY AIR is non-zero at which cell ---------------------------------
  * stwo's `assert_constraints` for a program, the generic counterpart of bfhip_check_constraints (which runs one of 13 compiled-in AIRs). A wrong

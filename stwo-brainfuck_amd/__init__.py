@@ -674,7 +674,8 @@ class Context:
     def air_eval_domain(self, program, log_size, log_expand, col_ptrs, params, coeffs, acc_ptrs, col_shifts=None):
         """bfhip_air_eval_domain: the constraints of an AirProgram on CanonicCoset(log_size + log_expand).circle_domain(), each times its
         coefficient, the sum times 1 / vanishing, added into the 4 coordinate columns acc_ptrs. col_ptrs: one device column per program column
-        (2^(log_size + log_expand - shift) cells); params / coeffs: QM31 values (4 words each), one per parameter / constraint."""
+        (2^(log_size + log_expand - shift) cells); params / coeffs: QM31 values (4 words each), one per parameter / constraint.
+        program: an AirProgram (interpreted), or the CompiledAir that this context's air_compile made of one (its own kernel; same result)."""
         params, coeffs = [list(q) for q in params], [list(q) for q in coeffs]
         if any(len(q) != 4 for q in params + coeffs):
             raise ValueError("a parameter or coefficient is 4 words")
@@ -682,10 +683,17 @@ class Context:
             raise ValueError("one column pointer (and shift) per program column")
         if len(acc_ptrs) != 4:
             raise ValueError("the accumulator is 4 coordinate columns")
-        _check(lib().bfhip_air_eval_domain(self._h, program._h, int(log_size), int(log_expand), self._ptr_array(col_ptrs) if col_ptrs else None,
-                                           None if col_shifts is None or not col_ptrs else self._u32s(col_shifts),
-                                           self._u32s([w for q in params for w in q]) if params else None, len(params),
-                                           self._u32s([w for q in coeffs for w in q]) if coeffs else None, len(coeffs), self._ptr_array(acc_ptrs)))
+        # a CompiledAir (Context.air_compile) runs its own kernel behind the same checks: bfhip_air_kernel_eval_domain
+        entry = lib().bfhip_air_kernel_eval_domain if isinstance(program, CompiledAir) else lib().bfhip_air_eval_domain
+        _check(entry(self._h, program._h, int(log_size), int(log_expand), self._ptr_array(col_ptrs) if col_ptrs else None,
+                     None if col_shifts is None or not col_ptrs else self._u32s(col_shifts),
+                     self._u32s([w for q in params for w in q]) if params else None, len(params),
+                     self._u32s([w for q in coeffs for w in q]) if coeffs else None, len(coeffs), self._ptr_array(acc_ptrs)))
+
+    def air_compile(self, program):
+        """bfhip_air_compile: the AirProgram as its own gfx950 kernel, generated (AirProgram.source) and compiled in-process for this
+        context's device. Returns a CompiledAir, which air_eval_domain accepts in place of the program; the program may be closed."""
+        return CompiledAir(self, program)
 
     def air_check(self, program, log_size, col_ptrs, params, col_shifts=None):
         """bfhip_air_check: the constraints of an AirProgram asserted on the trace domain CanonicCoset(log_size) itself (stwo's
@@ -1438,6 +1446,15 @@ class AirProgram:
         _check(lib().bfhip_air_mask(self._h, cols, offs, n.value, ctypes.byref(n)))
         return [(int(cols[i]), int(offs[i])) for i in range(n.value)]
 
+    def source(self):
+        """bfhip_air_source: the HIP source of the kernel Context.air_compile builds from this program (host only; the same program gives
+        the same text). With -DBFHIP_AIR_GEN_HOST it compiles as plain C++."""
+        n = ctypes.c_size_t()
+        _check(lib().bfhip_air_source(self._h, None, ctypes.c_size_t(0), ctypes.byref(n)))
+        buf = ctypes.create_string_buffer(max(1, n.value))
+        _check(lib().bfhip_air_source(self._h, buf, ctypes.c_size_t(n.value), ctypes.byref(n)))
+        return buf.raw[: n.value].decode()
+
     def eval_at_point(self, log_size, point8, mask_values, params, coeffs):
         """bfhip_air_eval_at_point: (sum_j coeffs[j] C_j) / coset_vanishing at a point, from the sampled mask values (QM31 each, mask order)."""
         flat = lambda qs: Context._u32s([w for q in qs for w in q]) if len(qs) else None
@@ -1448,6 +1465,45 @@ class AirProgram:
         _check(lib().bfhip_air_eval_at_point(self._h, int(log_size), Context._u32s(point8), flat(mask_values), len(mask_values), flat(params), len(params),
                                              flat(coeffs), len(coeffs), out))
         return [int(v) for v in out]
+
+
+class CompiledAir:
+    """bfhip_air_kernel: an AirProgram compiled to its own kernel by Context.air_compile. Pass it to Context.air_eval_domain of the context
+    that compiled it. .shape is the program's; info() the kernel's resources. A context that is closed first unloads the kernel: the object can then
+    only be closed."""
+
+    INFO = ("vgprs", "sgprs", "scratch_bytes", "lds_bytes", "code_object_bytes", "source_bytes", "compile_us", "from_cache")
+
+    def __init__(self, ctx, program):
+        self._h = ctypes.c_void_p()
+        self.shape = dict(program.shape)
+        _check(lib().bfhip_air_compile(ctx._h, program._h, ctypes.byref(self._h)))
+
+    def info(self):
+        """bfhip_air_kernel_info as a dict; sgprs is None when the code object does not state it."""
+        out = (ctypes.c_uint32 * 8)()
+        _check(lib().bfhip_air_kernel_info(self._h, out))
+        d = dict(zip(self.INFO, (int(v) for v in out)))
+        d["sgprs"] = None if d["sgprs"] == 0xFFFFFFFF else d["sgprs"]
+        d["from_cache"] = bool(d["from_cache"])
+        return d
+
+    def close(self):
+        if self._h:
+            lib().bfhip_air_kernel_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class AirCheckReport(ctypes.Structure):

@@ -5,6 +5,7 @@
 #pragma once
 #include "m31.h"
 #include <cstdint>
+#include <string>
 #include <vector>
 
 namespace bf {
@@ -19,6 +20,18 @@ enum AirOp : u32 {
 // (96 + 4 x 24) words x 64 lanes x 4 bytes = 48 KiB at the caps, below the 64 KiB a workgroup gets without asking.
 constexpr u32 AIR_MAX_M_REGS = 96, AIR_MAX_Q_REGS = 24, AIR_MAX_INSTRUCTIONS = 4096, AIR_MAX_COLUMNS = 256, AIR_MAX_PARAMS = 64, AIR_MAX_CONSTRAINTS = 64;
 constexpr int AIR_MAX_OFFSET = 16;
+
+// One launch of the domain evaluator, staged in HBM. Addresses are kept as integers: read from address space 4 they arrive in SGPRs and are
+// cast to global pointers. The interpreter (air_program.hip) and the kernels generated from a program (air_codegen.hip, which prints this
+// layout into their source; air_compile.hip) read the same block; a generated kernel has its program compiled in and gets code = 0.
+struct AirLaunch {
+    u64 code;            // bf_u32x4[n_instr]
+    u64 cols;            // bf_u32x4[n_cols]: {pointer low, pointer high, shift, 0}
+    u64 params, coeffs;  // bf_u32x4[n_params], bf_u32x4[n_constraints]
+    u64 acc[4];
+    u32 n_instr, n_m, log_size, log_expand;
+    u32 denom_inv[8];    // 1 / coset_vanishing, indexed by row >> log_size
+};
 
 }  // namespace bf
 
@@ -37,3 +50,17 @@ struct bfhip_air {
         return mask_first[col];
     }
 };
+
+namespace bf {
+struct Ctx;
+// air_program.hip: the argument checks of bfhip_air_eval_domain and its one staged copy (program text only with `with_code`, descriptors,
+// parameters, coefficients, the launch block), shared with bfhip_air_kernel_eval_domain (air_compile.hip). Returns the staged launch block;
+// the caller enqueues its kernel behind it on the context's stream.
+const AirLaunch* air_eval_stage(Ctx& c, const bfhip_air* air, bool with_code, uint32_t log_size, uint32_t log_expand, const uint32_t* const* cols_h,
+                                const uint32_t* col_shifts_h, const uint32_t* params_h, uint32_t n_params, const uint32_t* coeffs_h, uint32_t n_coeffs,
+                                uint32_t* const acc_d[4]);
+}  // namespace bf
+// air_codegen.hip (host only): the HIP source of the kernel that evaluates this program on the constraint domain; the same bytes for the same program
+std::string air_generate_source(const bfhip_air& air);
+constexpr uint32_t AIR_KERNEL_LANES = 256;      // workgroup size of a generated kernel (its __launch_bounds__)
+#define AIR_KERNEL_NAME "bfhip_air_generated"

@@ -18,16 +18,6 @@ namespace bf {
 
 constexpr u32 AIR_LANES = 64;
 
-// Staged in HBM. Addresses are kept as integers: read from address space 4 they arrive in SGPRs and are cast to global pointers.
-struct AirLaunch {
-    u64 code;            // bf_u32x4[n_instr]
-    u64 cols;            // bf_u32x4[n_cols]: {pointer low, pointer high, shift, 0}
-    u64 params, coeffs;  // bf_u32x4[n_params], bf_u32x4[n_constraints]
-    u64 acc[4];
-    u32 n_instr, n_m, log_size, log_expand;
-    u32 denom_inv[8];    // 1 / coset_vanishing, indexed by row >> log_size
-};
-
 // Storage index of the row at trace offset `off` from `row` on the 2^log_expand blowup (prev_lde_row of air.hip is off = -1, log_expand = 1):
 // a trace step is 2^(log_expand - 1) steps of the half coset; in circle-domain order the first half moves with the offset, the conjugate
 // half against it (-P + T = -(P - T)), each cyclically.
@@ -140,11 +130,11 @@ __global__ void __launch_bounds__(AIR_LANES) k_air_program(const AirLaunch* __re
 
 using namespace bf;
 
-extern "C" int32_t bfhip_air_eval_domain(bfhip_ctx* ctx, const bfhip_air* air, uint32_t log_size, uint32_t log_expand, const uint32_t* const* cols_h,
-                                         const uint32_t* col_shifts_h, const uint32_t* params_h, uint32_t n_params, const uint32_t* coeffs_h, uint32_t n_coeffs,
-                                         uint32_t* const acc_d[4]) {
-    API_CTX(ctx)
-    Ctx& c = ctx->c;
+// The checks and the staging of bfhip_air_eval_domain, shared with the compiled kernels' entry point (air_compile.hip): the two answer a bad
+// argument with the same words.
+const AirLaunch* bf::air_eval_stage(Ctx& c, const bfhip_air* air, bool with_code, uint32_t log_size, uint32_t log_expand, const uint32_t* const* cols_h,
+                                    const uint32_t* col_shifts_h, const uint32_t* params_h, uint32_t n_params, const uint32_t* coeffs_h, uint32_t n_coeffs,
+                                    uint32_t* const acc_d[4]) {
     const std::string me = "bfhip_air_eval_domain";
     if (!air || !coeffs_h || !acc_d || (!cols_h && air->n_cols) || (!params_h && n_params)) throw HipError("null argument");
     if (c.shard.count > 1) throw HipError(me + ": a context in a shard group is not supported (bfhip_ctx_leave_group first)");
@@ -176,13 +166,24 @@ extern "C" int32_t bfhip_air_eval_domain(bfhip_ctx* ctx, const bfhip_air* air, u
     c.stage_checkpoint();
     {
         StageBatch sb(c);
-        L.code = (u64)c.stage(air->code.data(), air->code.size());
+        L.code = with_code ? (u64)c.stage(air->code.data(), air->code.size()) : 0;
         L.cols = (u64)c.stage(cols.data(), cols.size());
         L.params = (u64)c.stage(n_params ? params_h : zero4, n_params ? 4 * (size_t)n_params : 4);
         L.coeffs = (u64)c.stage(coeffs_h, 4 * (size_t)n_coeffs);
         const AirLaunch* d_launch = c.stage(&L, 1);
         sb.end();
-        const u32 n = 1u << el;
+        return d_launch;
+    }
+}
+
+extern "C" int32_t bfhip_air_eval_domain(bfhip_ctx* ctx, const bfhip_air* air, uint32_t log_size, uint32_t log_expand, const uint32_t* const* cols_h,
+                                         const uint32_t* col_shifts_h, const uint32_t* params_h, uint32_t n_params, const uint32_t* coeffs_h, uint32_t n_coeffs,
+                                         uint32_t* const acc_d[4]) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    const AirLaunch* d_launch = air_eval_stage(c, air, true, log_size, log_expand, cols_h, col_shifts_h, params_h, n_params, coeffs_h, n_coeffs, acc_d);
+    {
+        const u32 n = 1u << (log_size + log_expand);
         const size_t lds = sizeof(u32) * AIR_LANES * (air->n_m + 4 * air->n_q);
         ProfScope ps(c.stream, "k_air_program", 0);
         hipLaunchKernelGGL(k_air_program, dim3((n + AIR_LANES - 1) / AIR_LANES), dim3(AIR_LANES), lds, c.stream, d_launch);

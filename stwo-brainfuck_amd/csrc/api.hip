@@ -90,6 +90,7 @@ void Ctx::destroy() {
     if (stream) (void)hipStreamSynchronize(stream);
     if (stream2) (void)hipStreamSynchronize(stream2);
     preprocessed_cache_drop(*this);      // the kept preprocessed tree: nothing reads it any more, and its memory goes before the streams do
+    air_kernels_drop(*this);             // the modules of the constraint kernels compiled at run time; kernel objects still alive are orphaned
     for (auto& a : aux) if (a) { (void)hipStreamSynchronize(a); prof_forget(a); (void)hipStreamDestroy(a); a = nullptr; }
     for (auto& e : evp) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     for (auto& e : reap_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }

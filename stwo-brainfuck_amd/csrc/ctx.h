@@ -116,6 +116,9 @@ struct Ctx {
     // The preprocessed tree this context keeps across proofs (bfhip_ctx_reuse_preprocessed; prover.h: PreprocessedCache). Owned: created by
     // preprocessed_cache_of(), released by preprocessed_cache_drop() (destroy() does, behind its stream synchronisations).
     struct PreprocessedCache* pre_cache = nullptr;
+    // The constraint kernels this context compiled at run time (air_compile.hip: bfhip_air_compile): their modules, one per distinct source,
+    // and the kernel objects that use them. Created by the first compile, released by air_kernels_drop() (destroy() does).
+    struct AirKernelCache* air_cache = nullptr;
     uint2* d_tlo = nullptr; uint2* d_thi = nullptr;   // G^a (a < 2^16) and G^(b << 16) (b < 2^15) point tables
     Arena arena;
     // A commitment-scheme session (include/bfhip.h: bfhip_pcs_*; pcs.hip) keeps its polynomials, LDE columns and trees in the arena from
@@ -280,6 +283,7 @@ struct PreprocessedCache;
 PreprocessedCache& preprocessed_cache_of(Ctx& c);   // created on first use
 void preprocessed_cache_drop(Ctx& c);               // frees the kept tree; the caller has waited for the streams that may read it
 void preprocessed_cache_invalidate(Ctx* c);         // called when the context joins or leaves a shard group
+void air_kernels_drop(Ctx& c);                      // air_compile.hip: unloads the compiled constraint kernels' modules; the caller has waited for the streams
 // prover_commit.hip, for pool.hip: the preprocessed tree a pool's builder context commits once for all proofs of a batch (Ctx::shared_pre)
 struct SharedPreprocessed;
 SharedPreprocessed* shared_preprocessed_create(Ctx& builder);

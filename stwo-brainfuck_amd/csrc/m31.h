@@ -3,11 +3,17 @@
 // crates/brainfuck_prover/src/components/mod.rs:13-19 and memory/table.rs:9-18.
 // Storage is a canonical u32 in [0, P); QM31 columns are 4 x u32 SoA (SecureColumnByCoords).
 #pragma once
+// Under hiprtc (csrc/air_codegen.hip embeds this header as text into the kernels it generates) there is no include path: the runtime
+// compiler predefines the fixed-width integer types and the HIP device interface itself.
+#ifndef __HIPCC_RTC__
 #include <cstdint>
 #include <cstddef>
+#endif
 
 #if defined(__HIPCC__)
+#ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
+#endif
 #define BF_HD __host__ __device__ __forceinline__
 #else
 #define BF_HD inline
@@ -15,9 +21,15 @@
 
 namespace bf {
 
+#ifndef __HIPCC_RTC__
 using u8 = uint8_t;
 using u32 = uint32_t;
 using u64 = uint64_t;
+#else      // no <cstdint> there, and the runtime compiler keeps its own fixed-width names in a namespace of its own
+using u8 = unsigned char;
+using u32 = unsigned int;
+using u64 = unsigned long long;
+#endif
 
 constexpr u32 P31 = 0x7fffffffu;
 
