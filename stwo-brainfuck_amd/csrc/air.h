@@ -197,16 +197,19 @@ template <int COMP, class E> BF_HD void air_eval(E& e, const Lookups& el) {
     else air_eoe(e, el);
 }
 
-// Storage index (bit-reversed circle-domain order) of the point at coset offset -1 from cell `cell` on the TRACE domain CanonicCoset(log_size)
-// itself: storage index -> circle-domain index -> coset index, minus 1 mod n, and back (stwo's circle_domain_index_to_coset_index /
-// coset_index_to_circle_domain_index). What `assert_constraints` reads for the {0, -1} mask of a component's last logUp column. Not
-// prev_lde_row of air.hip: that one is the same step on the 2x LDE domain, where it is a cyclic shift inside each half-coset.
-BF_HD u32 prev_trace_cell(u32 cell, u32 log_size) {
+// Storage index (bit-reversed circle-domain order) of the point at coset offset `off` from cell `cell` on the TRACE domain
+// CanonicCoset(log_size) itself: storage index -> circle-domain index -> coset index, plus off mod n, and back (stwo's
+// circle_domain_index_to_coset_index / coset_index_to_circle_domain_index). What `assert_constraints` reads for a mask entry at `off`. Not
+// prev_lde_row of air.hip or air_offset_row of air_program.hip: on a blown-up domain the same step is a cyclic shift inside each half-coset;
+// here the two halves interleave, so an odd offset changes halves.
+BF_HD u32 trace_offset_cell(u32 cell, int off, u32 log_size) {
     const u32 n = 1u << log_size, d = bit_rev(cell, log_size);
     const u32 coset = d < n / 2 ? 2 * d : 2 * (n - 1 - d) + 1;
-    const u32 pc = (coset + n - 1) & (n - 1);
-    return bit_rev((pc & 1u) == 0 ? pc / 2 : n - (pc + 1) / 2, log_size);
+    const u32 oc = (coset + (u32)off) & (n - 1);      // modulo 2^32, of which n is a divisor
+    return bit_rev((oc & 1u) == 0 ? oc / 2 : n - (oc + 1) / 2, log_size);
 }
+// The {0, -1} mask of a component's last logUp column
+BF_HD u32 prev_trace_cell(u32 cell, u32 log_size) { return trace_offset_cell(cell, -1, log_size); }
 
 // logUp row machinery shared by evaluators (stwo LogupAtRow, finalize_logup without batching): every fraction but the last becomes
 // a `(cur - prev_col) * den - num` constraint on a single-offset interaction column; the last one uses the {0,-1} masks and the

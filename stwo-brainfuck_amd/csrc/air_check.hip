@@ -5,21 +5,18 @@
 // that does not contain the trace's points. This pass has no coefficients, no vanishing polynomial and no accumulator: per constraint, which
 // cells of CanonicCoset(log_size) are non-zero.
 //
-// The interpreter is k_air_program's: one lane per cell, one wave per workgroup (at the caps the register file is 48 KiB per wave: four waves
-// would not fit a workgroup's LDS); instruction stream, column descriptors and parameters through scalar loads (address space 4), the opcode
-// dispatch a scalar branch; the two register files in LDS as [register][lane], sized at launch from the registers the program uses. No
-// scratch, no barrier. It is a copy, not a shared body: k_air_program is on a proof's hot path and keeps its code generation to itself.
-// C_BASE / C_EXT set bit j of the lane's 64-bit mask when constraint j is non-zero; nothing leaves early, so the wave stays uniform.
+// The interpreter is the core of program_interp.h, which k_air_program runs too: one lane per cell, one wave per workgroup (at the caps the
+// register file is 48 KiB per wave: four waves would not fit a workgroup's LDS). This file adds what a cell of the trace domain is
+// (AirTraceRow) and what C_BASE / C_EXT do here (AirCheckSink).
 #include "api_guard.h"
-#include "air_program.h"
+#include "program_interp.h"
 #include "../../include/bfhip.h"
 #include <cstddef>
 #include <cstring>
 
 namespace bf {
 
-constexpr u32 AIRC_LANES = 64;
-static_assert(AIR_MAX_CONSTRAINTS <= 64 && AIR_MAX_CONSTRAINTS <= AIRC_LANES, "a lane's mask has one bit per constraint, and lane j reduces constraint j");
+static_assert(AIR_MAX_CONSTRAINTS <= 64 && AIR_MAX_CONSTRAINTS <= PROGRAM_LANES, "a lane's mask has one bit per constraint, and lane j reduces constraint j");
 
 // What the kernels write; bfhip_air_check copies it field by field into bfhip_air_check_report.
 struct AirCheckReportDev {
@@ -37,101 +34,50 @@ struct AirCheckLaunch {
     u32 n_instr, n_m, log_size, n_constraints;
 };
 
-// Storage index of the cell at coset offset `off` from `cell` on the trace domain CanonicCoset(log_size) itself (prev_trace_cell of air.h is
-// off = -1): storage index -> circle-domain index -> coset index, plus off modulo n, and back (stwo's circle_domain_index_to_coset_index /
-// coset_index_to_circle_domain_index). Not air_offset_row of air_program.hip: on a blown-up domain the same step is a cyclic shift inside each
-// half coset; here the two halves interleave, so an odd offset changes halves.
-__device__ __forceinline__ u32 air_trace_offset_cell(u32 cell, int off, u32 log_size) {
-    const u32 n = 1u << log_size, d = bit_rev(cell, log_size);
-    const u32 coset = d < n / 2 ? 2 * d : 2 * (n - 1 - d) + 1;
-    const u32 oc = (coset + (u32)off) & (n - 1);      // modulo 2^32, of which n is a divisor
-    return bit_rev((oc & 1u) == 0 ? oc / 2 : n - (oc + 1) / 2, log_size);
-}
+// A cell of the trace domain CanonicCoset(log_size) itself; a column of shift s holds the cell's own value at cell >> s. The offset map is
+// air.h's trace_offset_cell, not air_offset_row of air_program.hip.
+struct AirTraceRow {
+    static constexpr bool OFFSETS = true;
+    u32 self, log_size;
+    __device__ __forceinline__ u32 at0(const bf_u32x4 col) const { return self >> col.z; }
+    __device__ __forceinline__ u32 at(int off) const { return trace_offset_cell(self, off, log_size); }
+};
 
-__device__ __forceinline__ u32 airc_ld_cell(const bf_u32x4 col, u32 idx) {
-    const unsigned long long base = ((unsigned long long)col.y << 32) | col.x;
-    return *(g_cu32p)((const BF_GLOBAL char*)base + (idx << 2));
-}
-
-// The program at one cell: the mask of its non-zero constraints. RECORD: also the lowest of them and its value (a C_BASE constraint as
-// (v, 0, 0, 0)). `cell` < 2^log_size; every column read is inside its column (a column of shift s is read at cell >> s, and only at offset 0).
+// C_BASE / C_EXT set bit j of the lane's 64-bit mask when constraint j is non-zero; nothing leaves early, so the wave stays uniform.
+// RECORD: also the lowest failing constraint and its value (a C_BASE constraint as (v, 0, 0, 0)).
 template <bool RECORD>
-__device__ __forceinline__ u64 air_check_cell(const BF_CONSTANT AirCheckLaunch* a, u32* s_regs, u32 cell, u32& first, Q31& first_value) {
-    const u32 log_size = a->log_size;
-    u32* const m = s_regs + threadIdx.x;                            // m[r] = m[r * AIRC_LANES]
-    u32* const q = s_regs + a->n_m * AIRC_LANES + threadIdx.x;      // coordinate k of q[r] = q[(4 r + k) * AIRC_LANES]
-    const BF_CONSTANT bf_u32x4* code = (const BF_CONSTANT bf_u32x4*)a->code;
-    const BF_CONSTANT bf_u32x4* cols = (const BF_CONSTANT bf_u32x4*)a->cols;
-    const BF_CONSTANT bf_u32x4* params = (const BF_CONSTANT bf_u32x4*)a->params;
+struct AirCheckSink {
+    static constexpr bool HAS_Q = true;
     u64 mask = 0;
-    u32 ci = 0;
-    const u32 n_instr = a->n_instr;
-#pragma unroll 1
-    for (u32 pc = 0; pc < n_instr; pc++) {
-        const bf_u32x4 ins = code[pc];
-        const u32 dst = ins.y * AIRC_LANES, ra = ins.z * AIRC_LANES, rb = ins.w * AIRC_LANES;
-        switch (ins.x) {
-            case AIR_M_COL: {
-                const bf_u32x4 col = cols[ins.z];
-                const int off = (int)ins.w;
-                m[dst] = airc_ld_cell(col, off ? air_trace_offset_cell(cell, off, log_size) : cell >> col.z);
-                break;
-            }
-            case AIR_M_CONST: m[dst] = ins.z; break;
-            case AIR_M_ADD: m[dst] = m_add(m[ra], m[rb]); break;
-            case AIR_M_SUB: m[dst] = m_sub(m[ra], m[rb]); break;
-            case AIR_M_MUL: m[dst] = m_mul(m[ra], m[rb]); break;
-            case AIR_M_NEG: m[dst] = m_neg(m[ra]); break;
-            case AIR_Q_COL: {
-                const int off = (int)ins.w;
-                const u32 ocell = off ? air_trace_offset_cell(cell, off, log_size) : cell;
-#pragma unroll
-                for (u32 k = 0; k < 4; k++) {
-                    const bf_u32x4 col = cols[ins.z + k];
-                    q[4 * dst + k * AIRC_LANES] = airc_ld_cell(col, off ? ocell : ocell >> col.z);
-                }
-                break;
-            }
-            case AIR_Q_PARAM: {
-                const bf_u32x4 v = params[ins.z];
-                q[4 * dst] = v.x; q[4 * dst + AIRC_LANES] = v.y; q[4 * dst + 2 * AIRC_LANES] = v.z; q[4 * dst + 3 * AIRC_LANES] = v.w;
-                break;
-            }
-            case AIR_Q_FROM_M: q[4 * dst] = m[ra]; q[4 * dst + AIRC_LANES] = 0; q[4 * dst + 2 * AIRC_LANES] = 0; q[4 * dst + 3 * AIRC_LANES] = 0; break;
-            case AIR_Q_ADD: case AIR_Q_SUB: case AIR_Q_MUL: {
-                const Q31 x = q_make(q[4 * ra], q[4 * ra + AIRC_LANES], q[4 * ra + 2 * AIRC_LANES], q[4 * ra + 3 * AIRC_LANES]);
-                const Q31 y = q_make(q[4 * rb], q[4 * rb + AIRC_LANES], q[4 * rb + 2 * AIRC_LANES], q[4 * rb + 3 * AIRC_LANES]);
-                const Q31 r = ins.x == AIR_Q_ADD ? q_add(x, y) : ins.x == AIR_Q_SUB ? q_sub(x, y) : q_mul(x, y);
-                q[4 * dst] = r.a.a; q[4 * dst + AIRC_LANES] = r.a.b; q[4 * dst + 2 * AIRC_LANES] = r.b.a; q[4 * dst + 3 * AIRC_LANES] = r.b.b;
-                break;
-            }
-            case AIR_Q_MULM: {
-                const Q31 x = q_make(q[4 * ra], q[4 * ra + AIRC_LANES], q[4 * ra + 2 * AIRC_LANES], q[4 * ra + 3 * AIRC_LANES]);
-                const Q31 r = q_mulm(x, m[rb]);
-                q[4 * dst] = r.a.a; q[4 * dst + AIRC_LANES] = r.a.b; q[4 * dst + 2 * AIRC_LANES] = r.b.a; q[4 * dst + 3 * AIRC_LANES] = r.b.b;
-                break;
-            }
-            case AIR_C_BASE: {
-                const u32 v = m[ra];
-                if (v != 0) {
-                    if (RECORD && first == 0xffffffffu) { first = ci; first_value = q_from_m(v); }
-                    mask |= (u64)1 << ci;
-                }
-                ci++;
-                break;
-            }
-            default: {      // AIR_C_EXT: the validator admits nothing else
-                const Q31 x = q_make(q[4 * ra], q[4 * ra + AIRC_LANES], q[4 * ra + 2 * AIRC_LANES], q[4 * ra + 3 * AIRC_LANES]);
-                if (!q_is_zero(x)) {
-                    if (RECORD && first == 0xffffffffu) { first = ci; first_value = x; }
-                    mask |= (u64)1 << ci;
-                }
-                ci++;
-                break;
-            }
+    u32 ci = 0, first = 0xffffffffu;
+    Q31 first_value = q_zero();
+    static constexpr u32 OP = AIR_C_BASE;
+    __device__ __forceinline__ void op(const bf_u32x4 ins, const u32* m, const u32*) {
+        const u32 v = m[ins.z * PROGRAM_LANES];
+        if (v != 0) {
+            if (RECORD && first == 0xffffffffu) { first = ci; first_value = q_from_m(v); }
+            mask |= (u64)1 << ci;
         }
+        ci++;
     }
-    return mask;
+    __device__ __forceinline__ void other(const bf_u32x4 ins, const u32*, const u32* q) {      // AIR_C_EXT: the validator admits nothing else
+        const Q31 x = program_q_ld(q, ins.z * PROGRAM_LANES);
+        if (!q_is_zero(x)) {
+            if (RECORD && first == 0xffffffffu) { first = ci; first_value = x; }
+            mask |= (u64)1 << ci;
+        }
+        ci++;
+    }
+};
+
+// The program at one cell. `cell` < 2^log_size; every column read is inside its column (a column of shift s is read at cell >> s, and only at
+// offset 0).
+template <bool RECORD>
+__device__ __forceinline__ AirCheckSink<RECORD> air_check_cell(const BF_CONSTANT AirCheckLaunch* a, u32* s_regs, u32 cell) {
+    AirCheckSink<RECORD> sink;
+    program_run((const BF_CONSTANT bf_u32x4*)a->code, a->n_instr, (const BF_CONSTANT bf_u32x4*)a->cols, (const BF_CONSTANT bf_u32x4*)a->params,
+                s_regs + threadIdx.x, s_regs + a->n_m * PROGRAM_LANES + threadIdx.x, AirTraceRow{cell, a->log_size}, sink);
+    return sink;
 }
 
 // Reduction, after check.hip: the ballot of (mask != 0) decides everything — a wave without a violation issues no atomic, so a valid trace
@@ -139,15 +85,14 @@ __device__ __forceinline__ u64 air_check_cell(const BF_CONSTANT AirCheckLaunch* 
 // lane (lanes are in cell order); lane j keeps constraint j's pair. Then one vector atomicAdd and one vector atomicMin over the lanes whose
 // constraint was touched (consecutive 8-byte slots of the report), and lane 0 adds the wave's bad cells and lowers first_bad_cell: at most
 // 2 * 64 + 2 atomics for a wave in which every constraint fails. Integer atomics only: the report does not depend on the order of arrival.
-__global__ void __launch_bounds__(AIRC_LANES) k_air_check_cells(const AirCheckLaunch* __restrict__ ap) {
+__global__ void __launch_bounds__(PROGRAM_LANES) k_air_check_cells(const AirCheckLaunch* __restrict__ ap) {
     extern __shared__ u32 s_regs[];
     const BF_CONSTANT AirCheckLaunch* a = (const BF_CONSTANT AirCheckLaunch*)(unsigned long long)ap;
     const u32 n = 1u << a->log_size;
-    const u32 base = blockIdx.x * AIRC_LANES, lane = threadIdx.x;
+    const u32 base = blockIdx.x * PROGRAM_LANES, lane = threadIdx.x;
     // a domain below one wave (log_size < 6): the lanes past its end evaluate cell 0 and report nothing, so every lane runs the whole program
     const bool live = base + lane < n;
-    u32 none = 0xffffffffu; Q31 unused = q_zero();
-    u64 mask = air_check_cell<false>(a, s_regs, live ? base + lane : 0u, none, unused);
+    u64 mask = air_check_cell<false>(a, s_regs, live ? base + lane : 0u).mask;
     if (!live) mask = 0;
     const u64 bad = __ballot(mask != 0);
     if (!bad) return;
@@ -170,16 +115,16 @@ __global__ void __launch_bounds__(AIRC_LANES) k_air_check_cells(const AirCheckLa
 
 // One wave re-interprets the program at the first bad cell (known once the cells pass has completed: same stream) and writes the lowest
 // failing constraint and its value; the report keeps -1 and zeros for a trace without violations. Every lane evaluates the same cell.
-__global__ void __launch_bounds__(AIRC_LANES) k_air_check_first(const AirCheckLaunch* __restrict__ ap) {
+__global__ void __launch_bounds__(PROGRAM_LANES) k_air_check_first(const AirCheckLaunch* __restrict__ ap) {
     extern __shared__ u32 s_regs[];
     const BF_CONSTANT AirCheckLaunch* a = (const BF_CONSTANT AirCheckLaunch*)(unsigned long long)ap;
     AirCheckReportDev* rep = (AirCheckReportDev*)a->report;
     const u64 cell = rep->first_bad_cell;
     if (cell >= ((u64)1 << a->log_size)) return;
-    u32 first = 0xffffffffu; Q31 v = q_zero();
-    air_check_cell<true>(a, s_regs, (u32)cell, first, v);
+    const AirCheckSink<true> found = air_check_cell<true>(a, s_regs, (u32)cell);
+    const Q31 v = found.first_value;
     if (threadIdx.x == 0) {
-        rep->first_bad_constraint = first;
+        rep->first_bad_constraint = found.first;
         rep->first_bad_value[0] = v.a.a; rep->first_bad_value[1] = v.a.b; rep->first_bad_value[2] = v.b.a; rep->first_bad_value[3] = v.b.b;
     }
 }
@@ -214,24 +159,13 @@ extern "C" int32_t bfhip_air_check(bfhip_ctx* ctx, const bfhip_air* air, uint32_
     if (!air || !out || (!cols_h && air->n_cols) || (!params_h && n_params)) throw HipError(me + ": null argument");
     if (c.shard.count > 1) throw HipError(me + ": a context in a shard group is not supported (bfhip_ctx_leave_group first)");
     if (log_size < 1 || log_size > c.tw_root_log + 1) throw HipError(me + ": log_size must be in [1, max_log_domain = " + std::to_string(c.tw_root_log + 1) + "], got " + std::to_string(log_size));
-    if (n_params != air->n_params) throw HipError(me + ": the program takes " + std::to_string(air->n_params) + " parameters, got " + std::to_string(n_params));
-    for (u32 i = 0; i < 4 * n_params; i++) if (params_h[i] >= P31) throw HipError(me + ": a parameter word is not a canonical M31");
-    std::vector<bf_u32x4> cols(air->n_cols ? air->n_cols : 1, bf_u32x4{0, 0, 0, 0});
-    for (u32 k = 0; k < air->n_cols; k++) {
-        const u32 s = col_shifts_h ? col_shifts_h[k] : 0u;
-        if (!cols_h[k]) throw HipError(me + ": null column pointer (column " + std::to_string(k) + ")");
-        if (s == 1 || s > log_size) throw HipError(me + ": column " + std::to_string(k) + " has shift " + std::to_string(s) + " (0, or 2 .. log_size)");
-        if (s && air->col_read_shifted[k]) throw HipError(me + ": column " + std::to_string(k) + " is stored with shift " + std::to_string(s) + " and read at a non-zero offset");
-        const unsigned long long p = (unsigned long long)cols_h[k];
-        cols[k] = bf_u32x4{(u32)p, (u32)(p >> 32), s, 0u};
-    }
+    const ProgramInputs in(me, air->n_cols, cols_h, col_shifts_h, log_size, "log_size", air->col_read_shifted.data(), air->n_params, params_h, n_params);
     AirCheckReportDev init{};
     init.first_bad_cell = ~u64(0);
     init.first_bad_constraint = 0xffffffffu;
     for (u32 j = 0; j < AIR_MAX_CONSTRAINTS; j++) init.first_cell_per_constraint[j] = ~u64(0);
     AirCheckLaunch L{};
     L.n_instr = air->n_instr; L.n_m = air->n_m; L.log_size = log_size; L.n_constraints = air->n_constraints;
-    const u32 zero4[4] = {0, 0, 0, 0};
     c.stage_checkpoint();
     AirCheckReportDev* d_report = nullptr;
     {
@@ -239,15 +173,14 @@ extern "C" int32_t bfhip_air_check(bfhip_ctx* ctx, const bfhip_air* air, uint32_
         d_report = c.stage(&init, 1);
         L.report = (u64)d_report;
         L.code = (u64)c.stage(air->code.data(), air->code.size());
-        L.cols = (u64)c.stage(cols.data(), cols.size());
-        L.params = (u64)c.stage(n_params ? params_h : zero4, n_params ? 4 * (size_t)n_params : 4);
+        in.stage(c, L.cols, L.params);
         const AirCheckLaunch* d_launch = c.stage(&L, 1);
         sb.end();
         const u32 n = 1u << log_size;
-        const size_t lds = sizeof(u32) * AIRC_LANES * (air->n_m + 4 * air->n_q);
+        const size_t lds = sizeof(u32) * PROGRAM_LANES * (air->n_m + 4 * air->n_q);
         ProfScope ps(c.stream, "k_air_check", 0);
-        hipLaunchKernelGGL(k_air_check_cells, dim3((n + AIRC_LANES - 1) / AIRC_LANES), dim3(AIRC_LANES), lds, c.stream, d_launch);
-        hipLaunchKernelGGL(k_air_check_first, dim3(1), dim3(AIRC_LANES), lds, c.stream, d_launch);
+        hipLaunchKernelGGL(k_air_check_cells, dim3((n + PROGRAM_LANES - 1) / PROGRAM_LANES), dim3(PROGRAM_LANES), lds, c.stream, d_launch);
+        hipLaunchKernelGGL(k_air_check_first, dim3(1), dim3(PROGRAM_LANES), lds, c.stream, d_launch);
     }
     BF_HIP(hipGetLastError());
     AirCheckReportDev r;

@@ -53,6 +53,20 @@ struct bfhip_air {
 
 namespace bf {
 struct Ctx;
+// air_program.hip: the columns and parameters of one program launch, for every entry point that runs a program on the GPU. The constructor
+// refuses, in the caller's name `me` and before anything is staged: a parameter count other than the program's, a parameter word that is not
+// canonical, a null column pointer, a shift of 1 or above `max_shift` (`max_shift_text` names that bound in the message), and, where the
+// program has offsets (`col_read_shifted` not null), a shifted column that is read at a non-zero offset. cols_h and params_h may be null
+// only where the program has no column / no parameter: the caller's own null-argument check sees to that.
+struct ProgramInputs {
+    std::vector<uint32_t> cols;      // four words per column: {pointer low, pointer high, shift, 0}; one zero descriptor where there is no column
+    const uint32_t* params_h;        // the caller's, four words per parameter
+    uint32_t n_params;
+    ProgramInputs(const std::string& me, uint32_t n_cols, const uint32_t* const* cols_h, const uint32_t* col_shifts_h, uint32_t max_shift, const char* max_shift_text,
+                  const uint8_t* col_read_shifted, uint32_t program_params, const uint32_t* params_h, uint32_t n_params);
+    // inside the caller's StageBatch: the two blocks as the interpreter's bf_u32x4 arrays (one zero parameter where the program has none)
+    void stage(Ctx& c, u64& cols_d, u64& params_d) const;
+};
 // air_program.hip: the argument checks of bfhip_air_eval_domain and its one staged copy (program text only with `with_code`, descriptors,
 // parameters, coefficients, the launch block), shared with bfhip_air_kernel_eval_domain (air_compile.hip). Returns the staged launch block;
 // the caller enqueues its kernel behind it on the context's stream.

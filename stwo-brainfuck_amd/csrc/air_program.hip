@@ -2,21 +2,16 @@
 // `ComponentProver::evaluate_constraint_quotients_on_domain` does for any `FrameworkEval` (reached from prover::prove, mod.rs:732), as ONE
 // gfx950 kernel that interprets the program instead of one compiled kernel per AIR (air.hip: k_constraints<COMP>).
 //
-// One lane per row of CanonicCoset(log_size + log_expand).circle_domain(), one wave per workgroup. The instruction stream, the column
-// descriptors, the parameters and the coefficients are the same for every lane: they live in HBM and are fetched through scalar loads
-// (address space 4, like ConstraintArgs), and the opcode dispatch is a scalar branch. The two register files would be runtime-indexed private
-// arrays, which the compiler puts in scratch; they live in LDS instead, laid out [register][lane] so that the 64 lanes of an access hit 64
-// consecutive banks, and sized at launch from the registers the program uses (a small program keeps its occupancy). No barrier: a lane only
-// ever touches its own slot of each register.
+// One lane per row of CanonicCoset(log_size + log_expand).circle_domain(), one wave per workgroup, on the interpreter core of
+// program_interp.h (scalar loads of the program, scalar dispatch, register files in LDS: see there). This file adds what a row of the blown-up
+// domain is (AirDomainRow) and what C_BASE / C_EXT do (AirDomainSink); the coefficients come through scalar loads like the program.
 #include "api_guard.h"
-#include "air_program.h"
+#include "program_interp.h"
 #include "host/circle.h"
 #include "../../include/bfhip.h"
 #include <cstddef>
 
 namespace bf {
-
-constexpr u32 AIR_LANES = 64;
 
 // Storage index of the row at trace offset `off` from `row` on the 2^log_expand blowup (prev_lde_row of air.hip is off = -1, log_expand = 1):
 // a trace step is 2^(log_expand - 1) steps of the half coset; in circle-domain order the first half moves with the offset, the conjugate
@@ -29,96 +24,52 @@ __device__ __forceinline__ u32 air_offset_row(u32 row, int off, u32 log_size, u3
     return bit_rev(pd, el);
 }
 
-__device__ __forceinline__ u32 air_ld_cell(const bf_u32x4 col, u32 idx) {
-    const unsigned long long base = ((unsigned long long)col.y << 32) | col.x;
-    return *(g_cu32p)((const BF_GLOBAL char*)base + (idx << 2));
-}
+// A row of CanonicCoset(log_size + log_expand).circle_domain(); a column of shift s holds the row's own cell at row >> s
+struct AirDomainRow {
+    static constexpr bool OFFSETS = true;
+    u32 self, log_size, log_expand;
+    __device__ __forceinline__ u32 at0(const bf_u32x4 col) const { return self >> col.z; }
+    __device__ __forceinline__ u32 at(int off) const { return air_offset_row(self, off, log_size, log_expand); }
+};
 
-__global__ void __launch_bounds__(AIR_LANES) k_air_program(const AirLaunch* __restrict__ ap) {
-    extern __shared__ u32 s_regs[];
-    const BF_CONSTANT AirLaunch* a = (const BF_CONSTANT AirLaunch*)(unsigned long long)ap;
-    const u32 log_size = a->log_size, log_expand = a->log_expand;
-    const u32 row = blockIdx.x * AIR_LANES + threadIdx.x;
-    if (row >= (1u << (log_size + log_expand))) return;
-    u32* const m = s_regs + threadIdx.x;                           // m[r] = m[r * AIR_LANES]
-    u32* const q = s_regs + a->n_m * AIR_LANES + threadIdx.x;      // coordinate k of q[r] = q[(4 r + k) * AIR_LANES]
-    const BF_CONSTANT bf_u32x4* code = (const BF_CONSTANT bf_u32x4*)a->code;
-    const BF_CONSTANT bf_u32x4* cols = (const BF_CONSTANT bf_u32x4*)a->cols;
-    const BF_CONSTANT bf_u32x4* params = (const BF_CONSTANT bf_u32x4*)a->params;
-    const BF_CONSTANT bf_u32x4* coeffs = (const BF_CONSTANT bf_u32x4*)a->coeffs;
-    // sum_j coeff_j * c_j as DomainEval::constraint(Fm) of air.hip keeps it: four 64-bit dot products with lazy reduction for the base-field
-    // constraints (four products of canonical values on top of a folded accumulator stay below 2^64), a QM31 sum for the others
+// C_BASE / C_EXT: sum_j coeff_j * c_j as DomainEval::constraint(Fm) of air.hip keeps it: four 64-bit dot products with lazy reduction for
+// the base-field constraints (four products of canonical values on top of a folded accumulator stay below 2^64), a QM31 sum for the others
+struct AirDomainSink {
+    static constexpr bool HAS_Q = true;
+    const BF_CONSTANT bf_u32x4* coeffs;
     u64 acc[4] = {0, 0, 0, 0};
     u32 pending = 0, ci = 0;
     Q31 ext = q_zero();
-    const u32 n_instr = a->n_instr;
-#pragma unroll 1
-    for (u32 pc = 0; pc < n_instr; pc++) {
-        const bf_u32x4 ins = code[pc];
-        const u32 dst = ins.y * AIR_LANES, ra = ins.z * AIR_LANES, rb = ins.w * AIR_LANES;
-        switch (ins.x) {
-            case AIR_M_COL: {
-                const bf_u32x4 col = cols[ins.z];
-                const int off = (int)ins.w;
-                m[dst] = air_ld_cell(col, off ? air_offset_row(row, off, log_size, log_expand) : row >> col.z);
-                break;
-            }
-            case AIR_M_CONST: m[dst] = ins.z; break;
-            case AIR_M_ADD: m[dst] = m_add(m[ra], m[rb]); break;
-            case AIR_M_SUB: m[dst] = m_sub(m[ra], m[rb]); break;
-            case AIR_M_MUL: m[dst] = m_mul(m[ra], m[rb]); break;
-            case AIR_M_NEG: m[dst] = m_neg(m[ra]); break;
-            case AIR_Q_COL: {
-                const int off = (int)ins.w;
-                const u32 orow = off ? air_offset_row(row, off, log_size, log_expand) : row;
+    static constexpr u32 OP = AIR_C_BASE;
+    __device__ __forceinline__ void op(const bf_u32x4 ins, const u32* m, const u32*) {
+        const bf_u32x4 k = coeffs[ci++];
+        const u32 v = m[ins.z * PROGRAM_LANES];
+        if (pending == 4) {      // 4 (p - 1)^2 + 2^34 < 2^64
 #pragma unroll
-                for (u32 k = 0; k < 4; k++) {
-                    const bf_u32x4 col = cols[ins.z + k];
-                    q[4 * dst + k * AIR_LANES] = air_ld_cell(col, off ? orow : orow >> col.z);
-                }
-                break;
-            }
-            case AIR_Q_PARAM: {
-                const bf_u32x4 v = params[ins.z];
-                q[4 * dst] = v.x; q[4 * dst + AIR_LANES] = v.y; q[4 * dst + 2 * AIR_LANES] = v.z; q[4 * dst + 3 * AIR_LANES] = v.w;
-                break;
-            }
-            case AIR_Q_FROM_M: q[4 * dst] = m[ra]; q[4 * dst + AIR_LANES] = 0; q[4 * dst + 2 * AIR_LANES] = 0; q[4 * dst + 3 * AIR_LANES] = 0; break;
-            case AIR_Q_ADD: case AIR_Q_SUB: case AIR_Q_MUL: {
-                const Q31 x = q_make(q[4 * ra], q[4 * ra + AIR_LANES], q[4 * ra + 2 * AIR_LANES], q[4 * ra + 3 * AIR_LANES]);
-                const Q31 y = q_make(q[4 * rb], q[4 * rb + AIR_LANES], q[4 * rb + 2 * AIR_LANES], q[4 * rb + 3 * AIR_LANES]);
-                const Q31 r = ins.x == AIR_Q_ADD ? q_add(x, y) : ins.x == AIR_Q_SUB ? q_sub(x, y) : q_mul(x, y);
-                q[4 * dst] = r.a.a; q[4 * dst + AIR_LANES] = r.a.b; q[4 * dst + 2 * AIR_LANES] = r.b.a; q[4 * dst + 3 * AIR_LANES] = r.b.b;
-                break;
-            }
-            case AIR_Q_MULM: {
-                const Q31 x = q_make(q[4 * ra], q[4 * ra + AIR_LANES], q[4 * ra + 2 * AIR_LANES], q[4 * ra + 3 * AIR_LANES]);
-                const Q31 r = q_mulm(x, m[rb]);
-                q[4 * dst] = r.a.a; q[4 * dst + AIR_LANES] = r.a.b; q[4 * dst + 2 * AIR_LANES] = r.b.a; q[4 * dst + 3 * AIR_LANES] = r.b.b;
-                break;
-            }
-            case AIR_C_BASE: {
-                const bf_u32x4 k = coeffs[ci++];
-                const u32 v = m[ra];
-                if (pending == 4) {      // 4 (p - 1)^2 + 2^34 < 2^64
-#pragma unroll
-                    for (int w = 0; w < 4; w++) acc[w] = m_fold(acc[w]);
-                    pending = 0;
-                }
-                acc[0] += (u64)k.x * v; acc[1] += (u64)k.y * v; acc[2] += (u64)k.z * v; acc[3] += (u64)k.w * v;
-                pending++;
-                break;
-            }
-            default: {      // AIR_C_EXT: the validator admits nothing else
-                const bf_u32x4 k = coeffs[ci++];
-                const Q31 x = q_make(q[4 * ra], q[4 * ra + AIR_LANES], q[4 * ra + 2 * AIR_LANES], q[4 * ra + 3 * AIR_LANES]);
-                ext = q_add(ext, q_mul(q_make(k.x, k.y, k.z, k.w), x));
-                break;
-            }
+            for (int w = 0; w < 4; w++) acc[w] = m_fold(acc[w]);
+            pending = 0;
         }
+        acc[0] += (u64)k.x * v; acc[1] += (u64)k.y * v; acc[2] += (u64)k.z * v; acc[3] += (u64)k.w * v;
+        pending++;
     }
+    __device__ __forceinline__ void other(const bf_u32x4 ins, const u32*, const u32* q) {      // AIR_C_EXT: the validator admits nothing else
+        const bf_u32x4 k = coeffs[ci++];
+        ext = q_add(ext, q_mul(q_make(k.x, k.y, k.z, k.w), program_q_ld(q, ins.z * PROGRAM_LANES)));
+    }
+    __device__ __forceinline__ Q31 sum() const { return q_add(q_make(m_canon(acc[0]), m_canon(acc[1]), m_canon(acc[2]), m_canon(acc[3])), ext); }
+};
+
+__global__ void __launch_bounds__(PROGRAM_LANES) k_air_program(const AirLaunch* __restrict__ ap) {
+    extern __shared__ u32 s_regs[];
+    const BF_CONSTANT AirLaunch* a = (const BF_CONSTANT AirLaunch*)(unsigned long long)ap;
+    const u32 log_size = a->log_size, log_expand = a->log_expand;
+    const u32 row = blockIdx.x * PROGRAM_LANES + threadIdx.x;
+    if (row >= (1u << (log_size + log_expand))) return;
+    AirDomainSink sink{(const BF_CONSTANT bf_u32x4*)a->coeffs};
+    program_run((const BF_CONSTANT bf_u32x4*)a->code, a->n_instr, (const BF_CONSTANT bf_u32x4*)a->cols, (const BF_CONSTANT bf_u32x4*)a->params,
+                s_regs + threadIdx.x, s_regs + a->n_m * PROGRAM_LANES + threadIdx.x, AirDomainRow{row, log_size, log_expand}, sink);
     const u32 dinv = ((g_cu32p)(unsigned long long)ap)[offsetof(AirLaunch, denom_inv) / 4 + (row >> log_size)];
-    const Q31 r = q_mulm(q_add(q_make(m_canon(acc[0]), m_canon(acc[1]), m_canon(acc[2]), m_canon(acc[3])), ext), dinv);
+    const Q31 r = q_mulm(sink.sum(), dinv);
     g_u32p acc0 = (g_u32p)a->acc[0], acc1 = (g_u32p)a->acc[1], acc2 = (g_u32p)a->acc[2], acc3 = (g_u32p)a->acc[3];
     acc0[row] = m_add(acc0[row], r.a.a);
     acc1[row] = m_add(acc1[row], r.a.b);
@@ -129,6 +80,27 @@ __global__ void __launch_bounds__(AIR_LANES) k_air_program(const AirLaunch* __re
 }  // namespace bf
 
 using namespace bf;
+
+bf::ProgramInputs::ProgramInputs(const std::string& me, uint32_t n_cols, const uint32_t* const* cols_h, const uint32_t* col_shifts_h, uint32_t max_shift,
+                                 const char* max_shift_text, const uint8_t* col_read_shifted, uint32_t program_params, const uint32_t* params_h_, uint32_t n_params_)
+    : cols(4 * size_t(n_cols ? n_cols : 1), 0u), params_h(params_h_), n_params(n_params_) {
+    if (n_params != program_params) throw HipError(me + ": the program takes " + std::to_string(program_params) + " parameters, got " + std::to_string(n_params));
+    for (u32 i = 0; i < 4 * n_params; i++) if (params_h[i] >= P31) throw HipError(me + ": a parameter word is not a canonical M31");
+    for (u32 k = 0; k < n_cols; k++) {
+        const u32 s = col_shifts_h ? col_shifts_h[k] : 0u;
+        if (!cols_h[k]) throw HipError(me + ": null column pointer (column " + std::to_string(k) + ")");
+        if (s == 1 || s > max_shift) throw HipError(me + ": column " + std::to_string(k) + " has shift " + std::to_string(s) + " (0, or 2 .. " + max_shift_text + ")");
+        if (s && col_read_shifted && col_read_shifted[k]) throw HipError(me + ": column " + std::to_string(k) + " is stored with shift " + std::to_string(s) + " and read at a non-zero offset");
+        const unsigned long long p = (unsigned long long)cols_h[k];
+        cols[4 * k] = (u32)p; cols[4 * k + 1] = (u32)(p >> 32); cols[4 * k + 2] = s;
+    }
+}
+
+void bf::ProgramInputs::stage(Ctx& c, u64& cols_d, u64& params_d) const {
+    static const u32 zero4[4] = {0, 0, 0, 0};
+    cols_d = (u64)c.stage(cols.data(), cols.size());
+    params_d = (u64)c.stage(n_params ? params_h : zero4, n_params ? 4 * (size_t)n_params : 4);
+}
 
 // The checks and the staging of bfhip_air_eval_domain, shared with the compiled kernels' entry point (air_compile.hip): the two answer a bad
 // argument with the same words.
@@ -142,33 +114,21 @@ const AirLaunch* bf::air_eval_stage(Ctx& c, const bfhip_air* air, bool with_code
     if (log_size < 1 || log_size > 29) throw HipError(me + ": log_size must be at least 1 and log_size + log_expand at most max_log_domain");
     const u32 el = log_size + log_expand;
     if (el > c.tw_root_log + 1) throw HipError(me + ": log_size + log_expand = " + std::to_string(el) + " exceeds the context's max_log_domain " + std::to_string(c.tw_root_log + 1));
-    if (n_params != air->n_params) throw HipError(me + ": the program takes " + std::to_string(air->n_params) + " parameters, got " + std::to_string(n_params));
     if (n_coeffs != air->n_constraints) throw HipError(me + ": the program has " + std::to_string(air->n_constraints) + " constraints, got " + std::to_string(n_coeffs) + " coefficients");
-    for (u32 i = 0; i < 4 * n_params; i++) if (params_h[i] >= P31) throw HipError(me + ": a parameter word is not a canonical M31");
     for (u32 i = 0; i < 4 * n_coeffs; i++) if (coeffs_h[i] >= P31) throw HipError(me + ": a coefficient word is not a canonical M31");
     for (int w = 0; w < 4; w++) if (!acc_d[w]) throw HipError(me + ": null accumulator pointer");
-    std::vector<bf_u32x4> cols(air->n_cols ? air->n_cols : 1, bf_u32x4{0, 0, 0, 0});
-    for (u32 k = 0; k < air->n_cols; k++) {
-        const u32 s = col_shifts_h ? col_shifts_h[k] : 0u;
-        if (!cols_h[k]) throw HipError(me + ": null column pointer (column " + std::to_string(k) + ")");
-        if (s == 1 || s > el) throw HipError(me + ": column " + std::to_string(k) + " has shift " + std::to_string(s) + " (0, or 2 .. log_size + log_expand)");
-        if (s && air->col_read_shifted[k]) throw HipError(me + ": column " + std::to_string(k) + " is stored with shift " + std::to_string(s) + " and read at a non-zero offset");
-        const unsigned long long p = (unsigned long long)cols_h[k];
-        cols[k] = bf_u32x4{(u32)p, (u32)(p >> 32), s, 0u};
-    }
+    const ProgramInputs in(me, air->n_cols, cols_h, col_shifts_h, el, "log_size + log_expand", air->col_read_shifted.data(), air->n_params, params_h, n_params);
     AirLaunch L{};
     L.n_instr = air->n_instr; L.n_m = air->n_m; L.log_size = log_size; L.log_expand = log_expand;
     for (int w = 0; w < 4; w++) L.acc[w] = (u64)acc_d[w];
     // 1 / coset_vanishing(CanonicCoset(log_size).coset, domain.at(d)) depends on d mod 2^log_expand only; in bit-reversed storage those are the
     // top bits of the row: entry i = row >> log_size belongs to d = bit_rev(i)
     for (u32 i = 0; i < (1u << log_expand); i++) L.denom_inv[i] = m_inv(coset_vanishing_m(log_size, canonic_domain_at(el, bit_rev(i, log_expand))));
-    const u32 zero4[4] = {0, 0, 0, 0};
     c.stage_checkpoint();
     {
         StageBatch sb(c);
         L.code = with_code ? (u64)c.stage(air->code.data(), air->code.size()) : 0;
-        L.cols = (u64)c.stage(cols.data(), cols.size());
-        L.params = (u64)c.stage(n_params ? params_h : zero4, n_params ? 4 * (size_t)n_params : 4);
+        in.stage(c, L.cols, L.params);
         L.coeffs = (u64)c.stage(coeffs_h, 4 * (size_t)n_coeffs);
         const AirLaunch* d_launch = c.stage(&L, 1);
         sb.end();
@@ -184,9 +144,9 @@ extern "C" int32_t bfhip_air_eval_domain(bfhip_ctx* ctx, const bfhip_air* air, u
     const AirLaunch* d_launch = air_eval_stage(c, air, true, log_size, log_expand, cols_h, col_shifts_h, params_h, n_params, coeffs_h, n_coeffs, acc_d);
     {
         const u32 n = 1u << (log_size + log_expand);
-        const size_t lds = sizeof(u32) * AIR_LANES * (air->n_m + 4 * air->n_q);
+        const size_t lds = sizeof(u32) * PROGRAM_LANES * (air->n_m + 4 * air->n_q);
         ProfScope ps(c.stream, "k_air_program", 0);
-        hipLaunchKernelGGL(k_air_program, dim3((n + AIR_LANES - 1) / AIR_LANES), dim3(AIR_LANES), lds, c.stream, d_launch);
+        hipLaunchKernelGGL(k_air_program, dim3((n + PROGRAM_LANES - 1) / PROGRAM_LANES), dim3(PROGRAM_LANES), lds, c.stream, d_launch);
     }
     BF_HIP(hipGetLastError());
     return 0;

@@ -5,71 +5,42 @@
 #include "api_guard.h"
 #include "pcs_types.h"
 #include "air_program.h"
+#include "program_validate.h"
 
 using namespace bf;
 
 namespace {
 
-struct Refusal : HipError { using HipError::HipError; };
-[[noreturn]] void refuse(size_t instr, const std::string& rule) { throw Refusal("bfhip_air_create: instruction " + std::to_string(instr) + ": " + rule); }
+const ProgramFamily FAMILY = {"bfhip_air_create", nullptr, nullptr};
 
-const char* op_name(u32 op) {
-    static const char* names[AIR_N_OPS] = {"M_COL", "M_CONST", "M_ADD", "M_SUB", "M_MUL", "M_NEG", "Q_COL", "Q_PARAM", "Q_FROM_M", "Q_ADD", "Q_SUB", "Q_MUL", "Q_MULM",
-                                           "C_BASE", "C_EXT"};
-    return op < AIR_N_OPS ? names[op] : "?";
-}
-
-// One pass over the code: every rule of include/bfhip.h, the register counts, the offsets and the mask.
-void validate(bfhip_air& air) {
+// One pass over the code: the shared rules (program_validate.h), the constraints, the offsets and the mask.
+void validate(bfhip_air& air, ProgramValidator& v) {
     const size_t n = air.n_instr;
-    bool m_written[AIR_MAX_M_REGS] = {}, q_written[AIR_MAX_Q_REGS] = {};
     std::vector<std::vector<int32_t>> offs(air.n_cols);      // per column: its offsets in order of first use
     air.col_read_shifted.assign(air.n_cols, 0);
-    auto m_dst = [&](size_t i, u32 r) { if (r >= AIR_MAX_M_REGS) refuse(i, "m register " + std::to_string(r) + " out of range (BFHIP_AIR_MAX_M_REGS = 96)"); m_written[r] = true; if (r + 1 > air.n_m) air.n_m = r + 1; };
-    auto q_dst = [&](size_t i, u32 r) { if (r >= AIR_MAX_Q_REGS) refuse(i, "q register " + std::to_string(r) + " out of range (BFHIP_AIR_MAX_Q_REGS = 24)"); q_written[r] = true; if (r + 1 > air.n_q) air.n_q = r + 1; };
-    auto m_src = [&](size_t i, u32 r) {
-        if (r >= AIR_MAX_M_REGS) refuse(i, "m register " + std::to_string(r) + " out of range (BFHIP_AIR_MAX_M_REGS = 96)");
-        if (!m_written[r]) refuse(i, "m register " + std::to_string(r) + " is read before it is written");
-    };
-    auto q_src = [&](size_t i, u32 r) {
-        if (r >= AIR_MAX_Q_REGS) refuse(i, "q register " + std::to_string(r) + " out of range (BFHIP_AIR_MAX_Q_REGS = 24)");
-        if (!q_written[r]) refuse(i, "q register " + std::to_string(r) + " is read before it is written");
-    };
-    auto column = [&](size_t i, u32 col, u32 width, u32 off_word) {
-        if (col >= air.n_cols || width > air.n_cols - col) refuse(i, "column " + std::to_string(col) + (width > 1 ? ".." + std::to_string((uint64_t)col + width - 1) : std::string()) + " out of range (the program has " + std::to_string(air.n_cols) + " columns)");
-        const int32_t off = (int32_t)off_word;
-        if (off < -AIR_MAX_OFFSET || off > AIR_MAX_OFFSET) refuse(i, "offset " + std::to_string(off) + " out of range (|offset| <= 16)");
-        if (off < air.min_off) air.min_off = off;
-        if (off > air.max_off) air.max_off = off;
-        for (u32 c = col; c < col + width; c++) {
-            if (off) air.col_read_shifted[c] = 1;
-            bool seen = false;
-            for (int32_t o : offs[c]) seen = seen || o == off;
-            if (!seen) offs[c].push_back(off);
-        }
-    };
     for (size_t i = 0; i < n; i++) {
         const u32 op = air.code[4 * i], dst = air.code[4 * i + 1], a = air.code[4 * i + 2], b = air.code[4 * i + 3];
-        switch (op) {
-            case AIR_M_COL: column(i, a, 1, b); m_dst(i, dst); break;
-            case AIR_M_CONST: if (a >= P31) refuse(i, "constant " + std::to_string(a) + " is not a canonical M31 (v < 2^31 - 1)"); m_dst(i, dst); break;
-            case AIR_M_ADD: case AIR_M_SUB: case AIR_M_MUL: m_src(i, a); m_src(i, b); m_dst(i, dst); break;
-            case AIR_M_NEG: m_src(i, a); m_dst(i, dst); break;
-            case AIR_Q_COL: column(i, a, 4, b); q_dst(i, dst); break;
-            case AIR_Q_PARAM: if (a >= air.n_params) refuse(i, "parameter " + std::to_string(a) + " out of range (the program has " + std::to_string(air.n_params) + " parameters)"); q_dst(i, dst); break;
-            case AIR_Q_FROM_M: m_src(i, a); q_dst(i, dst); break;
-            case AIR_Q_ADD: case AIR_Q_SUB: case AIR_Q_MUL: q_src(i, a); q_src(i, b); q_dst(i, dst); break;
-            case AIR_Q_MULM: q_src(i, a); m_src(i, b); q_dst(i, dst); break;
-            case AIR_C_BASE: m_src(i, a); break;
-            case AIR_C_EXT: q_src(i, a); break;
-            default: refuse(i, "unknown opcode " + std::to_string(op));
+        if (v.shared(i, op, dst, a, b)) {
+            if (op != AIR_M_COL && op != AIR_Q_COL) continue;
+            const int32_t off = (int32_t)b;
+            if (off < air.min_off) air.min_off = off;
+            if (off > air.max_off) air.max_off = off;
+            for (u32 c = a; c < a + (op == AIR_Q_COL ? 4u : 1u); c++) {
+                if (off) air.col_read_shifted[c] = 1;
+                bool seen = false;
+                for (int32_t o : offs[c]) seen = seen || o == off;
+                if (!seen) offs[c].push_back(off);
+            }
+            continue;
         }
-        if (op == AIR_C_BASE || op == AIR_C_EXT) {
-            if (air.n_constraints == AIR_MAX_CONSTRAINTS) refuse(i, std::string(op_name(op)) + ": more than BFHIP_AIR_MAX_CONSTRAINTS (64) constraints");
-            air.n_constraints++;
-        }
+        if (op == AIR_C_BASE) v.m_src(i, a);
+        else if (op == AIR_C_EXT) v.q_src(i, a);
+        else v.refuse(i, "unknown opcode " + std::to_string(op));
+        if (air.n_constraints == AIR_MAX_CONSTRAINTS) v.refuse(i, std::string(op == AIR_C_BASE ? "C_BASE" : "C_EXT") + ": more than BFHIP_AIR_MAX_CONSTRAINTS (64) constraints");
+        air.n_constraints++;
     }
-    if (air.n_constraints == 0) refuse(n, "the program ends without a constraint (at least one C_BASE or C_EXT)");
+    if (air.n_constraints == 0) v.refuse(n, "the program ends without a constraint (at least one C_BASE or C_EXT)");
+    air.n_m = v.n_m; air.n_q = v.n_q;
     air.mask_first.assign(air.n_cols + 1, 0);
     for (u32 c = 0; c < air.n_cols; c++) {
         air.mask_first[c] = (u32)air.mask_cols.size();
@@ -85,15 +56,12 @@ extern "C" {
 int32_t bfhip_air_create(const uint32_t* code, size_t n_words, uint32_t n_cols, uint32_t n_params, bfhip_air** out) {
     API_TRY
     if (!code || !out) throw HipError("null argument");
-    if (n_words == 0 || n_words % 4 != 0) refuse(n_words / 4, "the program is " + std::to_string(n_words) + " words, not a positive multiple of 4");
-    if (n_words / 4 > AIR_MAX_INSTRUCTIONS) refuse(AIR_MAX_INSTRUCTIONS, "more than BFHIP_AIR_MAX_INSTRUCTIONS (4096) instructions");
-    if (n_cols > AIR_MAX_COLUMNS) refuse(0, "more than BFHIP_AIR_MAX_COLUMNS (256) columns");
-    if (n_params > AIR_MAX_PARAMS) refuse(0, "more than BFHIP_AIR_MAX_PARAMS (64) parameters");
+    ProgramValidator v(FAMILY, n_words, n_cols, n_params);
     auto* air = new bfhip_air();
     try {
         air->code.assign(code, code + n_words);
         air->n_instr = (u32)(n_words / 4); air->n_cols = n_cols; air->n_params = n_params;
-        validate(*air);
+        validate(*air, v);
     } catch (...) { delete air; throw; }
     *out = air;
     return 0;

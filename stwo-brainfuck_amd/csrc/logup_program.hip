@@ -3,9 +3,8 @@
 // launches that interpret the program instead of one compiled branch per component (air.hip: k_logup_rows). Every cell is distinct: nothing
 // here knows of the 16-fold replication the compiled path is built on.
 //
-// Row stage (k_logup_program): k_air_program's shape. One lane per cell, one wave per workgroup; instruction stream, column descriptors,
-// parameters and output pointers come through scalar loads (address space 4) at wave-uniform addresses, the opcode dispatch is a scalar
-// branch, the two register files live in dynamic LDS laid out [register][lane], no scratch. FRAC folds q[a] / q[b] into the open column's
+// Row stage (k_logup_program): the interpreter core of program_interp.h, which k_air_program runs too, one lane per cell and one wave per
+// workgroup; the output pointers come through scalar loads (address space 4) like the program. FRAC folds q[a] / q[b] into the open column's
 // running fraction fn / fd (three products; every denominator is tested for zero where it stands, so a vanishing one is named and not hidden
 // in a product), END_COL adds fn / fd to the running value with the column's one q_inv; END_COL of a column before the last
 // stores the running value to the column's four coordinate columns (lane = cell: 256-byte coalesced stores), END_COL of the last column
@@ -16,11 +15,12 @@
 // complement, so in cell indices d = N - 1 - q is cell N - 1 - bit_rev(q): the partner of cell c is always cell N - 1 - c.
 #include "api_guard.h"
 #include "logup_program.h"
+#include "program_interp.h"
 #include "../../include/bfhip.h"
 
 namespace bf {
 
-constexpr u32 LP_LANES = 64, LP_TILE = 1024, LP_CHUNK = 256;
+constexpr u32 LP_TILE = 1024, LP_CHUNK = 256;
 
 // Staged in HBM. Addresses are kept as integers: read from address space 4 they arrive in SGPRs and are cast to global pointers.
 struct LogupProgLaunch {
@@ -33,90 +33,55 @@ struct LogupProgLaunch {
     u32 n_instr, n_m, log_size, n_logup_cols, nb, pad;
 };
 
-__device__ __forceinline__ u32 lp_ld_cell(const bf_u32x4 col, u32 idx) {
-    const unsigned long long base = ((unsigned long long)col.y << 32) | col.x;
-    return *(g_cu32p)((const BF_GLOBAL char*)base + ((unsigned long long)idx << 2));
-}
 __device__ __forceinline__ Q31 lp_ld(const uint4* p, u32 i) { const uint4 v = p[i]; return q_make(v.x, v.y, v.z, v.w); }
 __device__ __forceinline__ void lp_st(uint4* p, u32 i, Q31 q) { p[i] = make_uint4(q.a.a, q.a.b, q.b.a, q.b.b); }
 
-__global__ void __launch_bounds__(LP_LANES) k_logup_program(const LogupProgLaunch* __restrict__ ap) {
-    extern __shared__ u32 s_regs[];
-    const BF_CONSTANT LogupProgLaunch* a = (const BF_CONSTANT LogupProgLaunch*)(unsigned long long)ap;
-    const u32 cell = blockIdx.x * LP_LANES + threadIdx.x;
-    if (cell >= (1u << a->log_size)) return;
-    u32* const m = s_regs + threadIdx.x;                          // m[r] = m[r * LP_LANES]
-    u32* const q = s_regs + a->n_m * LP_LANES + threadIdx.x;      // coordinate k of q[r] = q[(4 r + k) * LP_LANES]
-    const BF_CONSTANT bf_u32x4* code = (const BF_CONSTANT bf_u32x4*)a->code;
-    const BF_CONSTANT bf_u32x4* cols = (const BF_CONSTANT bf_u32x4*)a->cols;
-    const BF_CONSTANT bf_u32x4* params = (const BF_CONSTANT bf_u32x4*)a->params;
+// A cell of the trace domain, read at offset 0 only (bfhip_logup_create refuses offsets): a column of shift s holds it at cell >> s
+struct LogupRow {
+    static constexpr bool OFFSETS = false;
+    u32 self;
+    __device__ __forceinline__ u64 at0(const bf_u32x4 col) const { return self >> col.z; }
+};
+
+// FRAC / END_COL (the file header says what they do)
+struct LogupSink {
+    static constexpr bool HAS_Q = true;
+    const BF_CONSTANT LogupProgLaunch* a;
+    u32 cell, last_col;
     Q31 cur = q_zero();          // LogupTraceGenerator: column k starts from column k - 1 (finalize_col keeps the running sum)
     u32 col_i = 0, frac_i = 0, open = 0;
     Q31 fn = q_zero(), fd = q_one();      // the open column's fractions so far as one fraction fn / fd (`open` of them: wave-uniform)
-    const u32 n_instr = a->n_instr, last_col = a->n_logup_cols - 1;
-#pragma unroll 1
-    for (u32 pc = 0; pc < n_instr; pc++) {
-        const bf_u32x4 ins = code[pc];
-        const u32 dst = ins.y * LP_LANES, ra = ins.z * LP_LANES, rb = ins.w * LP_LANES;
-        switch (ins.x) {
-            case AIR_M_COL: { const bf_u32x4 col = cols[ins.z]; m[dst] = lp_ld_cell(col, cell >> col.z); break; }
-            case AIR_M_CONST: m[dst] = ins.z; break;
-            case AIR_M_ADD: m[dst] = m_add(m[ra], m[rb]); break;
-            case AIR_M_SUB: m[dst] = m_sub(m[ra], m[rb]); break;
-            case AIR_M_MUL: m[dst] = m_mul(m[ra], m[rb]); break;
-            case AIR_M_NEG: m[dst] = m_neg(m[ra]); break;
-            case AIR_Q_COL: {
-#pragma unroll
-                for (u32 k = 0; k < 4; k++) {
-                    const bf_u32x4 col = cols[ins.z + k];
-                    q[4 * dst + k * LP_LANES] = lp_ld_cell(col, cell >> col.z);
-                }
-                break;
-            }
-            case AIR_Q_PARAM: {
-                const bf_u32x4 v = params[ins.z];
-                q[4 * dst] = v.x; q[4 * dst + LP_LANES] = v.y; q[4 * dst + 2 * LP_LANES] = v.z; q[4 * dst + 3 * LP_LANES] = v.w;
-                break;
-            }
-            case AIR_Q_FROM_M: q[4 * dst] = m[ra]; q[4 * dst + LP_LANES] = 0; q[4 * dst + 2 * LP_LANES] = 0; q[4 * dst + 3 * LP_LANES] = 0; break;
-            case AIR_Q_ADD: case AIR_Q_SUB: case AIR_Q_MUL: {
-                const Q31 x = q_make(q[4 * ra], q[4 * ra + LP_LANES], q[4 * ra + 2 * LP_LANES], q[4 * ra + 3 * LP_LANES]);
-                const Q31 y = q_make(q[4 * rb], q[4 * rb + LP_LANES], q[4 * rb + 2 * LP_LANES], q[4 * rb + 3 * LP_LANES]);
-                const Q31 r = ins.x == AIR_Q_ADD ? q_add(x, y) : ins.x == AIR_Q_SUB ? q_sub(x, y) : q_mul(x, y);
-                q[4 * dst] = r.a.a; q[4 * dst + LP_LANES] = r.a.b; q[4 * dst + 2 * LP_LANES] = r.b.a; q[4 * dst + 3 * LP_LANES] = r.b.b;
-                break;
-            }
-            case AIR_Q_MULM: {
-                const Q31 x = q_make(q[4 * ra], q[4 * ra + LP_LANES], q[4 * ra + 2 * LP_LANES], q[4 * ra + 3 * LP_LANES]);
-                const Q31 r = q_mulm(x, m[rb]);
-                q[4 * dst] = r.a.a; q[4 * dst + LP_LANES] = r.a.b; q[4 * dst + 2 * LP_LANES] = r.b.a; q[4 * dst + 3 * LP_LANES] = r.b.b;
-                break;
-            }
-            case LOGUP_FRAC: {
-                const Q31 num = q_make(q[4 * ra], q[4 * ra + LP_LANES], q[4 * ra + 2 * LP_LANES], q[4 * ra + 3 * LP_LANES]);
-                const Q31 den = q_make(q[4 * rb], q[4 * rb + LP_LANES], q[4 * rb + 2 * LP_LANES], q[4 * rb + 3 * LP_LANES]);
-                // stwo panics on a zero denominator; q_inv(0) is 0 and would pass for a value. The lowest (cell, fraction) wins the key.
-                if (q_is_zero(den)) atomicMin((unsigned long long*)(a->tail + 16), ((unsigned long long)cell << 8) | frac_i);
-                // fn / fd + num / den = (fn den + num fd) / (fd den): three products per further fraction, one inversion per column
-                if (open) { fn = q_add(q_mul(fn, den), q_mul(num, fd)); fd = q_mul(fd, den); } else { fn = num; fd = den; }
-                open++; frac_i++;
-                break;
-            }
-            default: {      // LOGUP_END_COL: the validator admits nothing else
-                cur = q_add(cur, q_mul(fn, q_inv(fd)));
-                open = 0;
-                if (col_i < last_col) {
-#pragma unroll
-                    for (u32 k = 0; k < 4; k++) {
-                        g_u32p o = (g_u32p)a->out[4 * col_i + k];
-                        o[cell] = k == 0 ? cur.a.a : k == 1 ? cur.a.b : k == 2 ? cur.b.a : cur.b.b;
-                    }
-                } else lp_st((uint4*)a->v, cell, cur);
-                col_i++;
-                break;
-            }
-        }
+    static constexpr u32 OP = LOGUP_FRAC;
+    __device__ __forceinline__ void op(const bf_u32x4 ins, const u32*, const u32* q) {
+        const Q31 num = program_q_ld(q, ins.z * PROGRAM_LANES), den = program_q_ld(q, ins.w * PROGRAM_LANES);
+        // stwo panics on a zero denominator; q_inv(0) is 0 and would pass for a value. The lowest (cell, fraction) wins the key.
+        if (q_is_zero(den)) atomicMin((unsigned long long*)(a->tail + 16), ((unsigned long long)cell << 8) | frac_i);
+        // fn / fd + num / den = (fn den + num fd) / (fd den): three products per further fraction, one inversion per column
+        if (open) { fn = q_add(q_mul(fn, den), q_mul(num, fd)); fd = q_mul(fd, den); } else { fn = num; fd = den; }
+        open++; frac_i++;
     }
+    __device__ __forceinline__ void other(const bf_u32x4, const u32*, const u32*) {      // LOGUP_END_COL: the validator admits nothing else
+        cur = q_add(cur, q_mul(fn, q_inv(fd)));
+        open = 0;
+        if (col_i < last_col) {
+#pragma unroll
+            for (u32 k = 0; k < 4; k++) {
+                g_u32p o = (g_u32p)a->out[4 * col_i + k];
+                o[cell] = k == 0 ? cur.a.a : k == 1 ? cur.a.b : k == 2 ? cur.b.a : cur.b.b;
+            }
+        } else lp_st((uint4*)a->v, cell, cur);
+        col_i++;
+    }
+};
+
+__global__ void __launch_bounds__(PROGRAM_LANES) k_logup_program(const LogupProgLaunch* __restrict__ ap) {
+    extern __shared__ u32 s_regs[];
+    const BF_CONSTANT LogupProgLaunch* a = (const BF_CONSTANT LogupProgLaunch*)(unsigned long long)ap;
+    const u32 cell = blockIdx.x * PROGRAM_LANES + threadIdx.x;
+    if (cell >= (1u << a->log_size)) return;
+    LogupSink sink{a, cell, a->n_logup_cols - 1};
+    program_run((const BF_CONSTANT bf_u32x4*)a->code, a->n_instr, (const BF_CONSTANT bf_u32x4*)a->cols, (const BF_CONSTANT bf_u32x4*)a->params,
+                s_regs + threadIdx.x, s_regs + a->n_m * PROGRAM_LANES + threadIdx.x, LogupRow{cell}, sink);
 }
 
 // Tile-local inclusive scan of w[q] = v[cell bit_rev(q)] + v[cell N - 1 - bit_rev(q)], q < N / 2: four consecutive entries per thread, the 256
@@ -210,16 +175,7 @@ extern "C" int32_t bfhip_logup_program_generate(bfhip_ctx* ctx, const bfhip_logu
     if (!lp || !out_cols_h || !claimed_sum_h || (!cols_h && lp->n_cols) || (!params_h && n_params)) throw HipError("null argument");
     if (c.shard.count > 1) throw HipError(me + ": a context in a shard group is not supported (bfhip_ctx_leave_group first)");
     if (log_size < 1 || log_size > c.tw_root_log + 1 || log_size > 29) throw HipError(me + ": log_size must be in [1, max_log_domain = " + std::to_string(c.tw_root_log + 1) + "], got " + std::to_string(log_size));
-    if (n_params != lp->n_params) throw HipError(me + ": the program takes " + std::to_string(lp->n_params) + " parameters, got " + std::to_string(n_params));
-    for (u32 i = 0; i < 4 * n_params; i++) if (params_h[i] >= P31) throw HipError(me + ": a parameter word is not a canonical M31");
-    std::vector<bf_u32x4> cols(lp->n_cols ? lp->n_cols : 1, bf_u32x4{0, 0, 0, 0});
-    for (u32 k = 0; k < lp->n_cols; k++) {
-        const u32 s = col_shifts_h ? col_shifts_h[k] : 0u;
-        if (!cols_h[k]) throw HipError(me + ": null column pointer (column " + std::to_string(k) + ")");
-        if (s == 1 || s > log_size) throw HipError(me + ": column " + std::to_string(k) + " has shift " + std::to_string(s) + " (0, or 2 .. log_size)");
-        const unsigned long long p = (unsigned long long)cols_h[k];
-        cols[k] = bf_u32x4{(u32)p, (u32)(p >> 32), s, 0u};
-    }
+    const ProgramInputs in(me, lp->n_cols, cols_h, col_shifts_h, log_size, "log_size", nullptr, lp->n_params, params_h, n_params);
     LogupProgLaunch L{};
     for (u32 k = 0; k < 4 * lp->n_logup_cols; k++) {
         if (!out_cols_h[k]) throw HipError(me + ": null output column pointer (coordinate column " + std::to_string(k) + ")");
@@ -238,18 +194,16 @@ extern "C" int32_t bfhip_logup_program_generate(bfhip_ctx* ctx, const bfhip_logu
     try {
         L.v = (u64)scratch; L.wloc = (u64)(scratch + N); L.totals = (u64)(scratch + N + H); L.tail = (u64)(scratch + N + H + nb + 1);
         L.n_instr = lp->n_instr; L.n_m = lp->n_m; L.log_size = log_size; L.n_logup_cols = lp->n_logup_cols; L.nb = (u32)nb;
-        const u32 zero4[4] = {0, 0, 0, 0};
         c.stage_checkpoint();
         BF_HIP(hipMemsetAsync((void*)L.tail, 0xFF, 2 * sizeof(uint4), c.stream));
         {
             StageBatch sb(c);
             L.code = (u64)c.stage(lp->code.data(), lp->code.size());
-            L.cols = (u64)c.stage(cols.data(), cols.size());
-            L.params = (u64)c.stage(n_params ? params_h : zero4, n_params ? 4 * (size_t)n_params : 4);
+            in.stage(c, L.cols, L.params);
             const LogupProgLaunch* d_launch = c.stage(&L, 1);
             sb.end();
-            const size_t lds = sizeof(u32) * LP_LANES * (lp->n_m + 4 * lp->n_q);
-            { ProfScope ps(c.stream, "k_logup_program", 0); hipLaunchKernelGGL(k_logup_program, dim3((u32)((N + LP_LANES - 1) / LP_LANES)), dim3(LP_LANES), lds, c.stream, d_launch); }
+            const size_t lds = sizeof(u32) * PROGRAM_LANES * (lp->n_m + 4 * lp->n_q);
+            { ProfScope ps(c.stream, "k_logup_program", 0); hipLaunchKernelGGL(k_logup_program, dim3((u32)((N + PROGRAM_LANES - 1) / PROGRAM_LANES)), dim3(PROGRAM_LANES), lds, c.stream, d_launch); }
             ProfScope ps(c.stream, "k_logup_program_scan", 0);
             hipLaunchKernelGGL(k_logup_program_scan, dim3((u32)nb), dim3(256), 0, c.stream, d_launch);
             hipLaunchKernelGGL(k_logup_program_totals, dim3(1), dim3(LP_CHUNK), 0, c.stream, d_launch);

@@ -3,9 +3,8 @@
 // of one compiled branch per Brainfuck table (relations.hip: k_rel_flags, k_rel_emit). The back half — sort, segment, net, first yield and
 // first use, report — is relations.hip's relation_aggregate, unchanged.
 //
-// Interpreter (k_relation_program<EMIT>): k_logup_program's shape. One lane per evaluated row, one wave per workgroup; instruction stream and
-// column descriptors come through scalar loads (address space 4) at wave-uniform addresses, the opcode dispatch is a scalar branch, the
-// register file lives in dynamic LDS laid out [register][lane], no scratch. WORD does not copy a value: the pending tuple is seven register
+// Interpreter (k_relation_program<EMIT>): the core of program_interp.h, which k_air_program and k_logup_program run too, without its q
+// half: one lane per evaluated row, one wave per workgroup, one register file. WORD does not copy a value: the pending tuple is seven register
 // INDICES packed into one wave-uniform 64-bit scalar (8 bits each, newest lowest), taken from the instruction stream. ENTRY of another
 // relation than the launch's only empties it.
 // Per relation r, over the tables whose program has an ENTRY for r, rows concatenated in table order:
@@ -17,11 +16,11 @@
 // table's launches in TARGET mode and hands the entries to relations.hip's relation_multiplicities instead.
 #include "api_guard.h"
 #include "relation_program.h"
+#include "program_interp.h"
 #include "../../include/bfhip.h"
 
 namespace bf {
 
-constexpr u32 RP_LANES = 64;
 static constexpr u32 RP_SCAN_TILE = 2048;   // the tile of exclusive_scan_u32
 
 // Staged in HBM, one per (relation, table). Addresses are kept as integers: read from address space 4 they arrive in SGPRs and are cast to
@@ -36,69 +35,61 @@ struct RelProgLaunch {
     u32 target, pad_;    // TARGET launches only: which ENTRY of `relation`, in program order from 0, is the table side
 };
 
+// An evaluated row r, read at offset 0 only (bfhip_relation_program_create refuses offsets): column k holds it at (r << row_shift) >> s_k,
+// the common part of the two shifts cancelled on the host
+struct RelRow {
+    static constexpr bool OFFSETS = false;
+    u32 self;
+    __device__ __forceinline__ u64 at0(const bf_u32x4 col) const { return (self << col.w) >> col.z; }
+};
+
 // m[r] of this lane, r taken from byte `k` of the packed pending tuple
 __device__ __forceinline__ u32 rp_pending_reg(u64 pending, u32 k) { return (u32)(pending >> (8u * k)) & 0xffu; }
 
-// TARGET (bfhip_relation_program_multiplicities, the looked-up table's launch): the a->target-th ENTRY of the relation is the table side. It
-// gives an entry at EVERY row, whatever its multiplicity operand holds, with REL_TABLE_SIDE in the origin and multiplicity word 0; the
-// ordinal is a wave-uniform counter. Every other ENTRY, and every launch with TARGET = false, is as above.
+// WORD / ENTRY. TARGET (bfhip_relation_program_multiplicities, the looked-up table's launch): the a->target-th ENTRY of the relation is the
+// table side. It gives an entry at EVERY row, whatever its multiplicity operand holds, with REL_TABLE_SIDE in the origin and multiplicity
+// word 0; the ordinal is a wave-uniform counter. Every other ENTRY, and every launch with TARGET = false, is as the file header says.
 template <bool EMIT, bool TARGET>
-__global__ void __launch_bounds__(RP_LANES) k_relation_program(const RelProgLaunch* __restrict__ ap) {
-    extern __shared__ u32 s_regs[];
-    const BF_CONSTANT RelProgLaunch* a = (const BF_CONSTANT RelProgLaunch*)(unsigned long long)ap;
-    const u32 row = blockIdx.x * RP_LANES + threadIdx.x;
-    if (row >= a->rows) return;
-    u32* const m = s_regs + threadIdx.x;                          // m[r] = m[r * RP_LANES]
-    const BF_CONSTANT bf_u32x4* code = (const BF_CONSTANT bf_u32x4*)a->code;
-    const BF_CONSTANT bf_u32x4* cols = (const BF_CONSTANT bf_u32x4*)a->cols;
-    const u32 n_instr = a->n_instr, relation = a->relation, n_words = a->n_words;
+struct RelSink {
+    static constexpr bool HAS_Q = false;
+    const BF_CONSTANT RelProgLaunch* a;
+    u32 row, relation, n_words, target;
+    u32 at;                                                       // EMIT: where the row's entries start
     u64 pending = 0;                                              // wave-uniform: register indices, the newest in the low byte
     u32 count = 0;                                                // entries of `relation` with a non-zero multiplicity so far
-    u32 at = 0;
-    if (EMIT) at = ((g_cu32p)a->pos)[row];
     u32 ordinal = 0;                                              // TARGET: ENTRYs of `relation` so far
-    const u32 target = TARGET ? a->target : 0u;
+    static constexpr u32 OP = REL_WORD;
+    __device__ __forceinline__ void op(const bf_u32x4 ins, const u32*, const u32*) { pending = (pending << 8) | ins.z; }
+    __device__ __forceinline__ void other(const bf_u32x4 ins, const u32* m, const u32*) {      // REL_ENTRY: the validator admits nothing else
+        if (ins.y == relation) {
+            u32 mult = m[ins.z * PROGRAM_LANES];
+            const bool side = TARGET && ordinal++ == target;
+            if (side) mult = 0;
+            if (mult != 0 || side) {
+                if (EMIT) {
+                    const u32 j = at + count;
 #pragma unroll 1
-    for (u32 pc = 0; pc < n_instr; pc++) {
-        const bf_u32x4 ins = code[pc];
-        const u32 dst = ins.y * RP_LANES, ra = ins.z * RP_LANES, rb = ins.w * RP_LANES;
-        switch (ins.x) {
-            case AIR_M_COL: {
-                const bf_u32x4 col = cols[ins.z];
-                const unsigned long long base = ((unsigned long long)col.y << 32) | col.x;
-                const u32 idx = (row << col.w) >> col.z;          // (r << row_shift) >> s_k with the common part of the two shifts cancelled
-                m[dst] = *(g_cu32p)((const BF_GLOBAL char*)base + ((unsigned long long)idx << 2));
-                break;
-            }
-            case AIR_M_CONST: m[dst] = ins.z; break;
-            case AIR_M_ADD: m[dst] = m_add(m[ra], m[rb]); break;
-            case AIR_M_SUB: m[dst] = m_sub(m[ra], m[rb]); break;
-            case AIR_M_MUL: m[dst] = m_mul(m[ra], m[rb]); break;
-            case AIR_M_NEG: m[dst] = m_neg(m[ra]); break;
-            case REL_WORD: pending = (pending << 8) | ins.z; break;
-            default: {      // REL_ENTRY: the validator admits nothing else
-                if (ins.y == relation) {
-                    u32 mult = m[ra];
-                    const bool side = TARGET && ordinal++ == target;
-                    if (side) mult = 0;
-                    if (mult != 0 || side) {
-                        if (EMIT) {
-                            const u32 j = at + count;
-#pragma unroll 1
-                            for (u32 k = 0; k < n_words; k++)     // word k was pushed n_words - k WORDs ago
-                                ((g_u32p)a->w[k])[j] = m[rp_pending_reg(pending, n_words - 1 - k) * RP_LANES];
-                            ((g_u32p)a->num)[j] = mult;
-                            ((BF_GLOBAL u64*)a->origin)[j] = (side ? REL_TABLE_SIDE : u64(0)) | ((u64)a->table << 32) | row;
-                        }
-                        count++;
-                    }
+                    for (u32 k = 0; k < n_words; k++)     // word k was pushed n_words - k WORDs ago
+                        ((g_u32p)a->w[k])[j] = m[rp_pending_reg(pending, n_words - 1 - k) * PROGRAM_LANES];
+                    ((g_u32p)a->num)[j] = mult;
+                    ((BF_GLOBAL u64*)a->origin)[j] = (side ? REL_TABLE_SIDE : u64(0)) | ((u64)a->table << 32) | row;
                 }
-                pending = 0;
-                break;
+                count++;
             }
         }
+        pending = 0;
     }
-    if (!EMIT) ((g_u32p)a->counts)[row] = count;
+};
+
+template <bool EMIT, bool TARGET>
+__global__ void __launch_bounds__(PROGRAM_LANES) k_relation_program(const RelProgLaunch* __restrict__ ap) {
+    extern __shared__ u32 s_regs[];
+    const BF_CONSTANT RelProgLaunch* a = (const BF_CONSTANT RelProgLaunch*)(unsigned long long)ap;
+    const u32 row = blockIdx.x * PROGRAM_LANES + threadIdx.x;
+    if (row >= a->rows) return;
+    RelSink<EMIT, TARGET> sink{a, row, a->relation, a->n_words, TARGET ? a->target : 0u, EMIT ? ((g_cu32p)a->pos)[row] : 0u};
+    program_run((const BF_CONSTANT bf_u32x4*)a->code, a->n_instr, (const BF_CONSTANT bf_u32x4*)a->cols, nullptr, s_regs + threadIdx.x, nullptr, RelRow{row}, sink);
+    if (!EMIT) ((g_u32p)a->counts)[row] = sink.count;
 }
 
 // What bfhip_relation_program_summary and bfhip_relation_program_multiplicities refuse about the list of tables, in the caller's name
@@ -217,7 +208,7 @@ extern "C" int32_t bfhip_relation_program_summary(bfhip_ctx* ctx, const bfhip_re
                 ProfScope ps(s, "relation_program_count", 0);
                 const RelProgLaunch* d_L = c.stage(L, n_part);
                 for (u32 i = 0; i < n_part; i++)
-                    hipLaunchKernelGGL((k_relation_program<false, false>), dim3((L[i].rows + RP_LANES - 1) / RP_LANES), dim3(RP_LANES), sizeof(u32) * RP_LANES * L[i].n_m, s, d_L + i);
+                    hipLaunchKernelGGL((k_relation_program<false, false>), dim3((L[i].rows + PROGRAM_LANES - 1) / PROGRAM_LANES), dim3(PROGRAM_LANES), sizeof(u32) * PROGRAM_LANES * L[i].n_m, s, d_L + i);
                 d_n = exclusive_scan_u32(s, counts, pos, tot, N);
             }
             u32 n = 0;
@@ -232,7 +223,7 @@ extern "C" int32_t bfhip_relation_program_summary(bfhip_ctx* ctx, const bfhip_re
                                    }
                                    const RelProgLaunch* d_L = c.stage(L, n_part);
                                    for (u32 i = 0; i < n_part; i++)
-                                       hipLaunchKernelGGL((k_relation_program<true, false>), dim3((L[i].rows + RP_LANES - 1) / RP_LANES), dim3(RP_LANES), sizeof(u32) * RP_LANES * L[i].n_m, s, d_L + i);
+                                       hipLaunchKernelGGL((k_relation_program<true, false>), dim3((L[i].rows + PROGRAM_LANES - 1) / PROGRAM_LANES), dim3(PROGRAM_LANES), sizeof(u32) * PROGRAM_LANES * L[i].n_m, s, d_L + i);
                                },
                                "relation_program_emit");
         }
@@ -295,14 +286,14 @@ extern "C" int32_t bfhip_relation_program_multiplicities(bfhip_ctx* ctx, const b
         auto launch = [&](bool emit) {
             const RelProgLaunch* d_L = c.stage(L, n_part);
             for (u32 i = 0; i < n_part; i++) {
-                const dim3 grid((L[i].rows + RP_LANES - 1) / RP_LANES);
-                const size_t lds = sizeof(u32) * RP_LANES * L[i].n_m;
+                const dim3 grid((L[i].rows + PROGRAM_LANES - 1) / PROGRAM_LANES);
+                const size_t lds = sizeof(u32) * PROGRAM_LANES * L[i].n_m;
                 if (i == target_part) {
-                    if (emit) hipLaunchKernelGGL((k_relation_program<true, true>), grid, dim3(RP_LANES), lds, s, d_L + i);
-                    else hipLaunchKernelGGL((k_relation_program<false, true>), grid, dim3(RP_LANES), lds, s, d_L + i);
+                    if (emit) hipLaunchKernelGGL((k_relation_program<true, true>), grid, dim3(PROGRAM_LANES), lds, s, d_L + i);
+                    else hipLaunchKernelGGL((k_relation_program<false, true>), grid, dim3(PROGRAM_LANES), lds, s, d_L + i);
                 } else {
-                    if (emit) hipLaunchKernelGGL((k_relation_program<true, false>), grid, dim3(RP_LANES), lds, s, d_L + i);
-                    else hipLaunchKernelGGL((k_relation_program<false, false>), grid, dim3(RP_LANES), lds, s, d_L + i);
+                    if (emit) hipLaunchKernelGGL((k_relation_program<true, false>), grid, dim3(PROGRAM_LANES), lds, s, d_L + i);
+                    else hipLaunchKernelGGL((k_relation_program<false, false>), grid, dim3(PROGRAM_LANES), lds, s, d_L + i);
                 }
             }
         };

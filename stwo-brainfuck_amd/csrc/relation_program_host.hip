@@ -4,64 +4,50 @@
 // in relation_program.hip.
 #include "api_guard.h"
 #include "relation_program.h"
+#include "program_validate.h"
 
 using namespace bf;
 
 namespace {
 
-struct Refusal : HipError { using HipError::HipError; };
-[[noreturn]] void refuse(size_t instr, const std::string& rule) { throw Refusal("bfhip_relation_program_create: instruction " + std::to_string(instr) + ": " + rule); }
+const ProgramFamily FAMILY = {"bfhip_relation_program_create", "a relation program reads a row's own cells (offset 0 only)",
+                              "a relation program is base field only (no q registers, no parameters)"};
 
-// One pass over the code: the rules of bfhip_air_create (in its words) for the base-field opcodes, plus the tuple structure.
-void validate(bfhip_relation_program& rp) {
+// One pass over the code: the shared rules (program_validate.h) for the base-field opcodes, plus the tuple structure.
+void validate(bfhip_relation_program& rp, ProgramValidator& v) {
     const size_t n = rp.n_instr;
-    bool m_written[AIR_MAX_M_REGS] = {};
     u32 pending = 0, pending_regs[REL_PROG_MAX_WORDS] = {};      // the pending tuple: its words are register INDICES until the ENTRY reads them
-    auto m_dst = [&](size_t i, u32 r) {
-        if (r >= AIR_MAX_M_REGS) refuse(i, "m register " + std::to_string(r) + " out of range (BFHIP_AIR_MAX_M_REGS = 96)");
-        for (u32 k = 0; k < pending; k++) if (pending_regs[k] == r) refuse(i, "m register " + std::to_string(r) + " is written while it is a word of the pending tuple");
-        m_written[r] = true; if (r + 1 > rp.n_m) rp.n_m = r + 1;
+    v.on_m_write = [&](size_t i, u32 r) {
+        for (u32 k = 0; k < pending; k++) if (pending_regs[k] == r) v.refuse(i, "m register " + std::to_string(r) + " is written while it is a word of the pending tuple");
     };
-    auto m_src = [&](size_t i, u32 r) {
-        if (r >= AIR_MAX_M_REGS) refuse(i, "m register " + std::to_string(r) + " out of range (BFHIP_AIR_MAX_M_REGS = 96)");
-        if (!m_written[r]) refuse(i, "m register " + std::to_string(r) + " is read before it is written");
-    };
-    static const char* const Q_NAMES[] = {"Q_COL", "Q_PARAM", "Q_FROM_M", "Q_ADD", "Q_SUB", "Q_MUL", "Q_MULM"};
     for (size_t i = 0; i < n; i++) {
         const u32 op = rp.code[4 * i], dst = rp.code[4 * i + 1], a = rp.code[4 * i + 2], b = rp.code[4 * i + 3];
+        if (v.shared(i, op, dst, a, b)) continue;
         switch (op) {
-            case AIR_M_COL:
-                if (a >= rp.n_cols) refuse(i, "column " + std::to_string(a) + " out of range (the program has " + std::to_string(rp.n_cols) + " columns)");
-                if (b) refuse(i, "offset " + std::to_string((int32_t)b) + ": a relation program reads a row's own cells (offset 0 only)");
-                m_dst(i, dst);
-                break;
-            case AIR_M_CONST: if (a >= P31) refuse(i, "constant " + std::to_string(a) + " is not a canonical M31 (v < 2^31 - 1)"); m_dst(i, dst); break;
-            case AIR_M_ADD: case AIR_M_SUB: case AIR_M_MUL: m_src(i, a); m_src(i, b); m_dst(i, dst); break;
-            case AIR_M_NEG: m_src(i, a); m_dst(i, dst); break;
-            case AIR_Q_COL: case AIR_Q_PARAM: case AIR_Q_FROM_M: case AIR_Q_ADD: case AIR_Q_SUB: case AIR_Q_MUL: case AIR_Q_MULM:
-                refuse(i, std::string(Q_NAMES[op - AIR_Q_COL]) + ": a relation program is base field only (no q registers, no parameters)");
-            case AIR_C_BASE: refuse(i, "C_BASE: a relation program has no constraints");
-            case AIR_C_EXT: refuse(i, "C_EXT: a relation program has no constraints");
-            case LOGUP_FRAC: refuse(i, "FRAC: a relation program has no fractions");
-            case LOGUP_END_COL: refuse(i, "END_COL: a relation program has no logUp columns");
+            case AIR_C_BASE: v.refuse(i, "C_BASE: a relation program has no constraints");
+            case AIR_C_EXT: v.refuse(i, "C_EXT: a relation program has no constraints");
+            case LOGUP_FRAC: v.refuse(i, "FRAC: a relation program has no fractions");
+            case LOGUP_END_COL: v.refuse(i, "END_COL: a relation program has no logUp columns");
             case REL_WORD:
-                m_src(i, a);
-                if (pending == REL_PROG_MAX_WORDS) refuse(i, "WORD: more than BFHIP_RELATION_PROGRAM_MAX_WORDS (7) words in a tuple");
+                v.m_src(i, a);
+                if (pending == REL_PROG_MAX_WORDS) v.refuse(i, "WORD: more than BFHIP_RELATION_PROGRAM_MAX_WORDS (7) words in a tuple");
                 pending_regs[pending++] = a;
                 break;
             case REL_ENTRY:
-                if (dst >= rp.n_relations) refuse(i, "ENTRY: relation " + std::to_string(dst) + " out of range (the program has " + std::to_string(rp.n_relations) + " relations)");
-                m_src(i, a);
+                if (dst >= rp.n_relations) v.refuse(i, "ENTRY: relation " + std::to_string(dst) + " out of range (the program has " + std::to_string(rp.n_relations) + " relations)");
+                v.m_src(i, a);
                 if (pending != rp.relation_words[dst])
-                    refuse(i, "ENTRY: the pending tuple has " + std::to_string(pending) + " words, relation " + std::to_string(dst) + " has " + std::to_string(rp.relation_words[dst]));
-                if (rp.n_entries == REL_PROG_MAX_ENTRIES) refuse(i, "ENTRY: more than BFHIP_RELATION_PROGRAM_MAX_ENTRIES (32) entries");
+                    v.refuse(i, "ENTRY: the pending tuple has " + std::to_string(pending) + " words, relation " + std::to_string(dst) + " has " + std::to_string(rp.relation_words[dst]));
+                if (rp.n_entries == REL_PROG_MAX_ENTRIES) v.refuse(i, "ENTRY: more than BFHIP_RELATION_PROGRAM_MAX_ENTRIES (32) entries");
                 rp.n_entries++; rp.entries_of[dst]++; pending = 0;
                 break;
-            default: refuse(i, "unknown opcode " + std::to_string(op));
+            default: v.refuse(i, "unknown opcode " + std::to_string(op));
         }
     }
-    if (pending) refuse(n, "the program ends inside a tuple (a WORD that no ENTRY follows)");
-    if (rp.n_entries == 0) refuse(n, "the program ends without an entry (at least one ENTRY)");
+    if (pending) v.refuse(n, "the program ends inside a tuple (a WORD that no ENTRY follows)");
+    if (rp.n_entries == 0) v.refuse(n, "the program ends without an entry (at least one ENTRY)");
+    v.on_m_write = nullptr;
+    rp.n_m = v.n_m;
 }
 
 }  // namespace
@@ -72,19 +58,17 @@ int32_t bfhip_relation_program_create(const uint32_t* code, size_t n_words, uint
                                       bfhip_relation_program** out) {
     API_TRY
     if (!code || !out || !relation_words_h) throw HipError("null argument");
-    if (n_words == 0 || n_words % 4 != 0) refuse(n_words / 4, "the program is " + std::to_string(n_words) + " words, not a positive multiple of 4");
-    if (n_words / 4 > AIR_MAX_INSTRUCTIONS) refuse(AIR_MAX_INSTRUCTIONS, "more than BFHIP_AIR_MAX_INSTRUCTIONS (4096) instructions");
-    if (n_cols > AIR_MAX_COLUMNS) refuse(0, "more than BFHIP_AIR_MAX_COLUMNS (256) columns");
-    if (n_relations < 1 || n_relations > REL_PROG_MAX_RELATIONS) refuse(0, std::to_string(n_relations) + " relations, not 1 to BFHIP_RELATION_PROGRAM_MAX_RELATIONS (16)");
+    ProgramValidator v(FAMILY, n_words, n_cols, 0);
+    if (n_relations < 1 || n_relations > REL_PROG_MAX_RELATIONS) v.refuse(0, std::to_string(n_relations) + " relations, not 1 to BFHIP_RELATION_PROGRAM_MAX_RELATIONS (16)");
     for (u32 r = 0; r < n_relations; r++)
         if (relation_words_h[r] < 1 || relation_words_h[r] > REL_PROG_MAX_WORDS)
-            refuse(0, "relation " + std::to_string(r) + " has " + std::to_string(relation_words_h[r]) + " words, not 1 to BFHIP_RELATION_PROGRAM_MAX_WORDS (7)");
+            v.refuse(0, "relation " + std::to_string(r) + " has " + std::to_string(relation_words_h[r]) + " words, not 1 to BFHIP_RELATION_PROGRAM_MAX_WORDS (7)");
     auto* rp = new bfhip_relation_program();
     try {
         rp->code.assign(code, code + n_words);
         rp->n_instr = (u32)(n_words / 4); rp->n_cols = n_cols; rp->n_relations = n_relations;
         for (u32 r = 0; r < n_relations; r++) rp->relation_words[r] = relation_words_h[r];
-        validate(*rp);
+        validate(*rp, v);
     } catch (...) { delete rp; throw; }
     *out = rp;
     return 0;
