@@ -1,7 +1,8 @@
 """The reference of bfhip_air_check (include/bfhip.h "Constraint programs asserted on the trace domain") in numpy: the model of
 tests/air_model.py run once per constraint with a one-hot coefficient over the trace domain itself (log_expand = 0, where offset_rows is a
 move in coset order), reduced to the report's fields. tests/test_air_check_cpu.py anchors it to the CPU oracle's AssertEvaluator on the 13
-Brainfuck programs; tests/test_gpu_air_check.py compares the kernel with it."""
+Brainfuck programs; tests/test_gpu_air_check.py compares the kernel with it. one_pass() gives the same report from a single run (pinned to
+report() in tests/test_air_check_cpu.py): what tests/air_check_cases.py and tests/test_gpu_air_check_edges.py use."""
 import numpy as np
 
 import air_model
@@ -29,6 +30,35 @@ def report(code, cols, params, log_size):
         j = int(np.argmax(bad[:, c]))
         out.update(first_bad_cell=c, first_bad_constraint=j, first_bad_value=[int(w) for w in values[j][:, c]])
     return out
+
+
+def one_pass(code, cols, params, log_size):
+    """(the report, bad) from ONE run of the interpreter (air_model.constraint_values hands out every constraint's value as the program
+    reaches it) instead of report()'s run per constraint: what keeps 64 constraints and 2^20 cells cheap. bad: (k, n) bool, bad[j, c] =
+    constraint j is non-zero at cell c — what the tests read the shape of a case from (counts per wave, lowest lanes). Only a constraint's
+    value at its own first bad cell is kept: the first bad cell overall is the lowest of those, and its lowest failing constraint is the
+    lowest j whose own first cell it is. tests/test_air_check_cpu.py pins it to report()."""
+    n = 1 << log_size
+    read = air_model.domain_reader(np.asarray(cols), log_size, 0)
+    bad, firsts = [], []
+    for _, value in air_model.constraint_values(code, read, params, n):
+        b = value.any(axis=0)
+        c = int(np.argmax(b)) if b.any() else None
+        bad.append(b)
+        firsts.append((c, None if c is None else [int(w) for w in value[:, c]]))
+    bad, k = np.stack(bad), len(bad)
+    out = {"log_size": log_size, "n_constraints": k, "n_bad_cells": int(np.count_nonzero(bad.any(axis=0))), "first_bad_cell": None,
+           "first_bad_constraint": -1, "first_bad_value": [0, 0, 0, 0], "bad_per_constraint": [int(b.sum()) for b in bad],
+           "first_cell_per_constraint": [c for c, _ in firsts]}
+    failing = [(c, j) for j, (c, _) in enumerate(firsts) if c is not None]
+    if failing:
+        c, j = min(failing)
+        out.update(first_bad_cell=c, first_bad_constraint=j, first_bad_value=firsts[j][1])
+    return out, bad
+
+
+def report_one_pass(code, cols, params, log_size):
+    return one_pass(code, cols, params, log_size)[0]
 
 
 def same(got, want):

@@ -1,6 +1,7 @@
 """A pure-numpy model of the constraint program (include/bfhip.h "Constraint programs"): the bytecode run over QM31 values, written from the
 header's table alone. Both register files hold QM31 values as uint64 arrays of shape (4, n): n = 1 at a point (a mask value per (column,
-offset)), n = the rows of a domain (an M31 cell v is (v, 0, 0, 0)). The result is sum_j coeffs[j] * C_j WITHOUT the vanishing denominator.
+offset)), n = the rows of a domain (an M31 cell v is (v, 0, 0, 0)). The result is sum_j coeffs[j] * C_j WITHOUT the vanishing denominator
+(run), or every C_j on its own (constraint_values).
 Also here: the row-offset map of a bit-reversed circle domain from first principles (group indices of the M31 circle), the vanishing
 polynomial of a canonic coset at a point, its inverse at every row of a constraint domain (domain_denominators), and a seeded generator of
 random valid programs that uses every opcode and reuses registers.
@@ -54,11 +55,10 @@ def combine_ef(v0, v1, v2, v3):
     return r
 
 
-def run(code, read, params, coeffs, n=1):
-    """code: flat u32 words; read(col, off) -> (4, n) value of that column at that row offset; params / coeffs: lists of 4 words.
-    Returns sum_j coeffs[j] * C_j as (4, n)."""
+def constraint_values(code, read, params, n=1):
+    """The interpreter itself: yields (C_BASE or C_EXT, the constraint's value as (4, n)) for every constraint, in program order, in one pass
+    over the code. code: flat u32 words; read(col, off) -> (4, n) value of that column at that row offset; params: lists of 4 words."""
     m, qr = {}, {}
-    acc, ci = np.zeros((4, n), dtype=np.uint64), 0
     signed = lambda w: w - (1 << 32) if w >= 1 << 31 else w
     for i in range(0, len(code), 4):
         op, dst, a, b = code[i: i + 4]
@@ -89,10 +89,17 @@ def run(code, read, params, coeffs, n=1):
         elif op == Q_MULM:
             qr[dst] = q_mul(qr[a], m[b])
         elif op in (C_BASE, C_EXT):
-            acc = q_add(acc, q_mul(q(coeffs[ci], n), m[a] if op == C_BASE else qr[a]))
-            ci += 1
+            yield op, (m[a] if op == C_BASE else qr[a])
         else:
             raise ValueError("opcode %d" % op)
+
+
+def run(code, read, params, coeffs, n=1):
+    """code, read, params: as for constraint_values; coeffs: lists of 4 words. Returns sum_j coeffs[j] * C_j as (4, n)."""
+    acc, ci = np.zeros((4, n), dtype=np.uint64), 0
+    for _, value in constraint_values(code, read, params, n):
+        acc = q_add(acc, q_mul(q(coeffs[ci], n), value))
+        ci += 1
     assert ci == len(coeffs)
     return acc
 
