@@ -1,0 +1,212 @@
+"""The Brainfuck AIR written with AirBuilder — the worked example of INTEGRATION.md section 2e: the 13 components' constraints, logUp
+fractions and relation entries as programs, and the parameters they take."""
+from ._abi import P
+from .context import LOGUP_MASK_PREV_CUR
+from .programs import AirBuilder
+from .reports import RELATION_NAMES
+
+
+def _q_mul(x, y):
+    """QM31 product of two 4-word values: (a + b u)(c + d u), u^2 = 2 + i, over CM31 = M31[i]."""
+    cm = lambda p, q: ((p[0] * q[0] - p[1] * q[1]) % P, (p[0] * q[1] + p[1] * q[0]) % P)
+    a, b, c, d = (x[0], x[1]), (x[2], x[3]), (y[0], y[1]), (y[2], y[3])
+    bd, ac, ad, bc = cm(b, d), cm(a, c), cm(a, d), cm(b, c)
+    e = cm(bd, (2, 1))
+    return [(ac[0] + e[0]) % P, (ac[1] + e[1]) % P, (ad[0] + bc[0]) % P, (ad[1] + bc[1]) % P]
+
+
+BRAINFUCK_AIR_N_PARAMS = 25
+_BF_N_MAIN = (8, 8, 4, 9, 13, 13, 11, 11, 11, 11, 11, 11, 7)
+_LOOKUP_PARAM_NAMES = ["%s.%s" % (r, p) for r in RELATION_NAMES for p in ["z"] + ["alpha^%d" % i for i in range(7)]]
+
+
+def brainfuck_air_params(lookup24, claimed4):
+    """The 25 parameters of a brainfuck_air_program: for each of the Memory, Instruction and Processor relations z, alpha^0 .. alpha^6
+    (8 values), then the component's claimed sum. lookup24: (z, alpha) of the three relations, as for logup_generate."""
+    out = []
+    for r in range(3):
+        z, alpha = [int(v) for v in lookup24[8 * r: 8 * r + 4]], [int(v) for v in lookup24[8 * r + 4: 8 * r + 8]]
+        out.append(z)
+        cur = [1, 0, 0, 0]
+        for _ in range(7):
+            out.append(cur)
+            cur = _q_mul(cur, alpha)
+    return out + [[int(v) for v in claimed4]]
+
+
+def _combine(b, rel, values):
+    """A relation's combine(values) - z over the parameters of brainfuck_air_params: sum_i alpha^i values[i] - z."""
+    base = 8 * RELATION_NAMES.index(rel)
+    acc = None
+    for i, v in enumerate(values):
+        term = b.param(base + 1 + i) * v
+        acc = term if acc is None else acc + term
+    return acc - b.param(base)
+
+
+def brainfuck_air_program(component, logup_mask_order=0):
+    """The constraints of component 0..12 of the Brainfuck AIR as a program — restated from csrc/air.h (the `FrameworkEval::evaluate` bodies
+    of components/**/component.rs), logUp constraints included; the worked example of INTEGRATION.md section 2e.
+    Returns (AirProgram, parameter names, column names). Columns: the n_main main-trace columns, then 4 coordinate columns per logUp column,
+    then IsFirst — n_main + 4 n_logup + 1. Parameters: brainfuck_air_params. Constraints in bfhip_eval_constraints' order. The last logUp
+    column is read at offsets [0, -1], or [-1, 0] under logup_mask_order = LOGUP_MASK_PREV_CUR."""
+    if not 0 <= component < 13:
+        raise ValueError("component 0..12")
+    b = AirBuilder()
+    n_main, n_logup = _BF_N_MAIN[component], 3 if component == 3 else 1
+    t = [b.col(j) for j in range(n_main)]
+    first_col = n_main + 4 * n_logup
+    is_first, one = b.col(first_col), b.const(1)
+    total = b.param(24)
+    combine = lambda rel, values: _combine(b, rel, values)
+    state = {"col": 0, "prev": None}
+
+    def logup_mid(num, den):
+        cur = b.secure_col(n_main + 4 * state["col"])
+        diff = cur if state["prev"] is None else cur - state["prev"]
+        state["col"], state["prev"] = state["col"] + 1, cur
+        b.constraint(diff * den - b._to_q(num))
+
+    def logup_last(num, den):
+        at = n_main + 4 * state["col"]
+        if logup_mask_order == LOGUP_MASK_PREV_CUR:
+            prev_row, cur = b.secure_col(at, -1), b.secure_col(at)
+        else:
+            cur, prev_row = b.secure_col(at), b.secure_col(at, -1)
+        diff = cur - (prev_row - total * is_first)
+        if state["prev"] is not None:
+            diff = diff - state["prev"]
+        b.constraint(diff * den - b._to_q(num))
+
+    c = b.constraint
+    if component == 0:        # memory/component.rs:62-137
+        clk, mp, mv, d, n_clk, n_mp, n_mv, n_d = t
+        c(is_first * clk); c(is_first * mp); c(is_first * mv); c(is_first * d)
+        c(d * (d - one)); c(n_d * (n_d - one))
+        c((n_mp - mp) * (n_mp - mp - one)); c((n_mp - mp - one) * (n_clk - clk - one)); c((n_mp - mp) * n_mv)
+        c(d * (n_mp - mp)); c(d * (n_mv - mv))
+        logup_last(d - one, combine("memory", (clk, mp, mv)))
+    elif component == 1:      # instruction/component.rs:65-142
+        ip, ci, ni, d, n_ip, n_ci, n_ni, n_d = t
+        c(is_first * ip); c(d * (d - one)); c(n_d * (n_d - one)); c(d * ci); c(d * ni); c(n_d * n_ci); c(n_d * n_ni)
+        c((n_ip - ip) * (n_ip - ip - one)); c((n_ip - ip - one) * (n_ci - ci)); c((n_ip - ip - one) * (n_ni - ni))
+        logup_last(d - one, combine("instruction", (ip, ci, ni)))
+    elif component == 2:      # program/component.rs:60-104
+        ip, ci, ni, d = t
+        c(is_first * ip); c(d * (d - one)); c(d * ci); c(d * ni)
+        logup_last(one - d, combine("instruction", (ip, ci, ni)))
+    elif component == 3:      # processor/component.rs:79-153 — three relation entries: Processor, Instruction, Memory
+        clk, ip, ci, ni, mp, mv, mvi, d, n_clk = t
+        c(is_first * clk); c(is_first * ip); c(is_first * mp); c(is_first * mv)
+        c(mv * (mv * mvi - one)); c(mvi * (mv * mvi - one)); c(n_clk - clk - one)
+        num = one - d
+        den_p, den_i, den_m = combine("processor", (clk, ip, ci, ni, mp, mv, mvi)), combine("instruction", (ip, ci, ni)), combine("memory", (clk, mp, mv))
+        logup_mid(num, den_p); logup_mid(num, den_i); logup_last(num, den_m)
+    elif component in (4, 5):   # jump/jump_if_not_zero_component.rs:61-130, jump/jump_if_zero_component.rs:61-130
+        clk, ip, ci, ni, mp, mv, mvi, n_clk, n_ip, n_mp, n_mv, d, is_mv_zero = t
+        two = b.const(2)
+        c(ci * (ci - b.const(ord("[") if component == 5 else ord("]"))))
+        c(n_clk - clk - one); c(d * (d - one)); c(d * mv); c(d * ci)
+        if component == 5:
+            c((d - one) * (mv * (n_ip - ip - two) + is_mv_zero * (n_ip - (ni + one))))
+        else:
+            c((d - one) * (is_mv_zero * (n_ip - ip - two) + mv * (n_ip - ni)))
+        c(n_mp - mp); c(n_mv - mv)
+        logup_last(d - one, combine("processor", (clk, ip, ci, ni, mp, mv, mvi)))
+    elif component == 12:     # end_of_execution/component.rs:61-90
+        clk, ip, ci, ni, mp, mv, mvi = t
+        c(ci)
+        logup_last(b.const(P - 1), combine("processor", (clk, ip, ci, ni, mp, mv, mvi)))
+    else:                     # processor/instructions/{input,left,minus,output,plus,right}_component.rs:62-122
+        clk, ip, ci, ni, mp, mv, mvi, d, n_ip, n_mp, n_mv = t
+        opcode = {6: ",", 7: "<", 8: "-", 9: ".", 10: "+", 11: ">"}[component]
+        c(ci * (ci - b.const(ord(opcode)))); c(d * (d - one)); c(d * mv); c(d * ci); c((one - d) * (n_ip - ip - one))
+        if opcode == "+":
+            c(n_mp - mp); c((one - d) * (n_mv - mv - one))
+        elif opcode == "-":
+            c(n_mp - mp); c((one - d) * (n_mv - mv + one))
+        elif opcode == "<":
+            c((one - d) * (n_mp - mp + one))
+        elif opcode == ">":
+            c((one - d) * (n_mp - mp - one))
+        elif opcode == ",":
+            c(n_mp - mp)
+        else:
+            c(n_mp - mp); c(n_mv - mv)
+        logup_last(d - one, combine("processor", (clk, ip, ci, ni, mp, mv, mvi)))
+    columns = ["main%d" % j for j in range(n_main)] + ["logup%d.%d" % (k, w) for k in range(n_logup) for w in range(4)] + ["is_first"]
+    return b.program(n_cols=n_main + 4 * n_logup + 1, n_params=BRAINFUCK_AIR_N_PARAMS), _LOOKUP_PARAM_NAMES + ["claimed_sum"], columns
+
+
+BRAINFUCK_LOGUP_N_PARAMS = 24
+
+
+def brainfuck_logup_program(component):
+    """`interaction_trace_evaluation` of component 0..12 of the Brainfuck AIR as a fraction program — restated from the branches of
+    k_logup_rows (csrc/air.hip; memory/table.rs:485-518, instruction/table.rs:456-490, program/table.rs:233-265, processor/table.rs:456-529,
+    jump/table.rs:436-475, instructions/table.rs:466-505, end_of_execution/table.rs:220-255). Returns (LogupProgram, parameter names).
+    Columns: the n_main main-trace columns. Parameters: the first 24 of brainfuck_air_params. The Processor has three logUp columns of one
+    fraction each (Processor, Instruction, Memory relations), the others one; numerators d - 1, 1 - d or -1."""
+    if not 0 <= component < 13:
+        raise ValueError("component 0..12")
+    b = AirBuilder()
+    n_main = _BF_N_MAIN[component]
+    t = lambda *js: [b.col(j) for j in js]      # only the columns a fraction reads: a column read is never dropped
+    one = b.const(1)
+
+    def column(num, rel, values):
+        b.frac(num, _combine(b, rel, values))
+        b.end_column()
+
+    if component == 0:
+        column(t(3)[0] - one, "memory", t(0, 1, 2))
+    elif component == 1:
+        column(t(3)[0] - one, "instruction", t(0, 1, 2))
+    elif component == 2:
+        column(one - t(3)[0], "instruction", t(0, 1, 2))
+    elif component == 3:
+        num = one - t(7)[0]
+        column(num, "processor", t(0, 1, 2, 3, 4, 5, 6))
+        column(num, "instruction", t(1, 2, 3))
+        column(num, "memory", t(0, 4, 5))
+    elif component in (4, 5):
+        column(t(11)[0] - one, "processor", t(0, 1, 2, 3, 4, 5, 6))
+    elif component == 12:
+        column(b.const(P - 1), "processor", t(0, 1, 2, 3, 4, 5, 6))
+    else:
+        column(t(7)[0] - one, "processor", t(0, 1, 2, 3, 4, 5, 6))
+    return b.logup_program(n_cols=n_main, n_params=BRAINFUCK_LOGUP_N_PARAMS), list(_LOOKUP_PARAM_NAMES)
+
+
+BRAINFUCK_RELATION_WORDS = (3, 3, 7)
+
+
+def brainfuck_relation_program(component):
+    """The `add_to_relation` calls of component 0..12 of the Brainfuck AIR as a relation program — restated from the table of
+    include/bfhip.h "the lookup tuples that do not cancel" (components/**/component.rs). Returns (RelationProgram, relation names).
+    Columns: the n_main main-trace columns. Relations: 0 Memory (clk, mp, mv), 1 Instruction (ip, ci, ni), 2 Processor (clk, ip, ci, ni, mp,
+    mv, mvi). Multiplicities d - 1 (a use), 1 - d (a yield) or -1; the Processor adds one entry to each relation."""
+    if not 0 <= component < 13:
+        raise ValueError("component 0..12")
+    b = AirBuilder()
+    n_main = _BF_N_MAIN[component]
+    t = lambda *js: [b.col(j) for j in js]
+    one = b.const(1)
+    if component == 0:
+        b.relation_entry(0, t(3)[0] - one, t(0, 1, 2))
+    elif component == 1:
+        b.relation_entry(1, t(3)[0] - one, t(0, 1, 2))
+    elif component == 2:
+        b.relation_entry(1, one - t(3)[0], t(0, 1, 2))
+    elif component == 3:
+        num = one - t(7)[0]
+        b.relation_entry(0, num, t(0, 4, 5))
+        b.relation_entry(1, num, t(1, 2, 3))
+        b.relation_entry(2, num, t(0, 1, 2, 3, 4, 5, 6))
+    elif component in (4, 5):
+        b.relation_entry(2, t(11)[0] - one, t(0, 1, 2, 3, 4, 5, 6))
+    elif component == 12:
+        b.relation_entry(2, b.const(P - 1), t(0, 1, 2, 3, 4, 5, 6))
+    else:
+        b.relation_entry(2, t(7)[0] - one, t(0, 1, 2, 3, 4, 5, 6))
+    return b.relation_program(BRAINFUCK_RELATION_WORDS, n_cols=n_main), RELATION_NAMES

@@ -1,0 +1,297 @@
+"""Any AIR given as programs (include/bfhip.h "Constraint programs", "Fraction programs", "Relation programs"): the validated handles
+AirProgram, CompiledAir, LogupProgram and RelationProgram, and AirBuilder, which writes their bytecode from expressions."""
+import ctypes
+
+import numpy as np
+
+from ._abi import Owned, P, _check, _qm31s, _u32s, abi
+from ._abi_gen import (BFHIP_AIR_C_BASE as AIR_C_BASE, BFHIP_AIR_C_EXT as AIR_C_EXT, BFHIP_AIR_M_ADD as AIR_M_ADD, BFHIP_AIR_M_COL as AIR_M_COL,
+                       BFHIP_AIR_M_CONST as AIR_M_CONST, BFHIP_AIR_M_MUL as AIR_M_MUL, BFHIP_AIR_M_NEG as AIR_M_NEG, BFHIP_AIR_M_SUB as AIR_M_SUB,
+                       BFHIP_AIR_MAX_COLUMNS as AIR_MAX_COLUMNS, BFHIP_AIR_MAX_CONSTRAINTS as AIR_MAX_CONSTRAINTS, BFHIP_AIR_MAX_INSTRUCTIONS as AIR_MAX_INSTRUCTIONS,
+                       BFHIP_AIR_MAX_M_REGS as AIR_MAX_M_REGS, BFHIP_AIR_MAX_OFFSET as AIR_MAX_OFFSET, BFHIP_AIR_MAX_PARAMS as AIR_MAX_PARAMS,
+                       BFHIP_AIR_MAX_Q_REGS as AIR_MAX_Q_REGS, BFHIP_AIR_Q_ADD as AIR_Q_ADD, BFHIP_AIR_Q_COL as AIR_Q_COL, BFHIP_AIR_Q_FROM_M as AIR_Q_FROM_M,
+                       BFHIP_AIR_Q_MUL as AIR_Q_MUL, BFHIP_AIR_Q_MULM as AIR_Q_MULM, BFHIP_AIR_Q_PARAM as AIR_Q_PARAM, BFHIP_AIR_Q_SUB as AIR_Q_SUB,
+                       BFHIP_LOGUP_END_COL as LOGUP_END_COL, BFHIP_LOGUP_FRAC as LOGUP_FRAC, BFHIP_LOGUP_MAX_COLUMNS as LOGUP_MAX_COLUMNS,
+                       BFHIP_LOGUP_MAX_FRACTIONS as LOGUP_MAX_FRACTIONS, BFHIP_REL_ENTRY as REL_ENTRY, BFHIP_REL_WORD as REL_WORD,
+                       BFHIP_RELATION_PROGRAM_MAX_ENTRIES as RELATION_PROGRAM_MAX_ENTRIES, BFHIP_RELATION_PROGRAM_MAX_RELATIONS as RELATION_PROGRAM_MAX_RELATIONS,
+                       BFHIP_RELATION_PROGRAM_MAX_WORDS as RELATION_PROGRAM_MAX_WORDS)
+
+AIR_OPS = ("M_COL", "M_CONST", "M_ADD", "M_SUB", "M_MUL", "M_NEG", "Q_COL", "Q_PARAM", "Q_FROM_M", "Q_ADD", "Q_SUB", "Q_MUL", "Q_MULM", "C_BASE", "C_EXT")
+
+
+class _Program(Owned):
+    """A validated program of the library: .code = the bytecode, four u32 words {op, dst, a, b} per instruction (what bindings pass;
+    AirBuilder writes it from expressions). A refused program raises BfhipError naming the instruction index and the rule."""
+
+    def _create(self, code, create, shape_entry):
+        """create(words, n_words, handle*) validates the bytecode; returns the 8 words of the program's shape entry."""
+        self.code = [int(w) & 0xFFFFFFFF for w in code]
+        self._h = ctypes.c_void_p()
+        _check(create((ctypes.c_uint32 * max(1, len(self.code)))(*self.code), len(self.code), ctypes.byref(self._h)))
+        out = (ctypes.c_uint32 * 8)()
+        _check(shape_entry(self._h, out))
+        return out
+
+
+class AirProgram(_Program):
+    """bfhip_air: a validated constraint program. code = the bytecode, four u32 words {op, dst, a, b} per instruction (what bindings pass;
+    AirBuilder writes it from expressions). Host only: creating, shape, mask and eval_at_point need no GPU; Context.air_eval_domain runs it
+    on the constraint domain. A refused program raises BfhipError naming the instruction index and the rule."""
+    _destroy = "bfhip_air_destroy"
+
+    def __init__(self, code, n_cols, n_params):
+        out = self._create(code, lambda words, n, h: abi().bfhip_air_create(words, n, int(n_cols), int(n_params), h), abi().bfhip_air_shape)
+        signed = lambda v: v - (1 << 32) if v >= 1 << 31 else v
+        self.shape = {"n_cols": out[0], "n_params": out[1], "n_constraints": out[2], "n_instr": out[3], "m_regs": out[4], "q_regs": out[5],
+                      "min_offset": signed(out[6]), "max_offset": signed(out[7])}
+
+    def mask(self):
+        """bfhip_air_mask: [(column, offset)] — by column, within a column by first use. The order of a column's samples for
+        PcsSession.prove_values and of eval_at_point's mask values."""
+        n = ctypes.c_uint32()
+        _check(abi().bfhip_air_mask(self._h, None, None, 0, ctypes.byref(n)))
+        cols, offs = (ctypes.c_uint32 * max(1, n.value))(), (ctypes.c_int32 * max(1, n.value))()
+        _check(abi().bfhip_air_mask(self._h, cols, offs, n.value, ctypes.byref(n)))
+        return [(int(cols[i]), int(offs[i])) for i in range(n.value)]
+
+    def source(self):
+        """bfhip_air_source: the HIP source of the kernel Context.air_compile builds from this program (host only; the same program gives
+        the same text). With -DBFHIP_AIR_GEN_HOST it compiles as plain C++."""
+        n = ctypes.c_size_t()
+        _check(abi().bfhip_air_source(self._h, None, 0, ctypes.byref(n)))
+        buf = ctypes.create_string_buffer(max(1, n.value))
+        _check(abi().bfhip_air_source(self._h, buf, n.value, ctypes.byref(n)))
+        return buf.raw[: n.value].decode()
+
+    def eval_at_point(self, log_size, point8, mask_values, params, coeffs):
+        """bfhip_air_eval_at_point: (sum_j coeffs[j] C_j) / coset_vanishing at a point, from the sampled mask values (QM31 each, mask order)."""
+        flat = [_qm31s(qs, "a QM31 value") for qs in (mask_values, params, coeffs)]
+        out = (ctypes.c_uint32 * 4)()
+        _check(abi().bfhip_air_eval_at_point(self._h, int(log_size), _u32s(point8), *flat[0], *flat[1], *flat[2], out))
+        return [int(v) for v in out]
+
+
+class CompiledAir(Owned):
+    """bfhip_air_kernel: an AirProgram compiled to its own kernel by Context.air_compile. Pass it to Context.air_eval_domain of the context
+    that compiled it. .shape is the program's; info() the kernel's resources. A context that is closed first unloads the kernel: the object can then
+    only be closed."""
+    _destroy = "bfhip_air_kernel_destroy"
+    INFO = ("vgprs", "sgprs", "scratch_bytes", "lds_bytes", "code_object_bytes", "source_bytes", "compile_us", "from_cache")
+
+    def __init__(self, ctx, program):
+        self._h = ctypes.c_void_p()
+        self.shape = dict(program.shape)
+        _check(abi().bfhip_air_compile(ctx._h, program._h, ctypes.byref(self._h)))
+
+    def info(self):
+        """bfhip_air_kernel_info as a dict; sgprs is None when the code object does not state it."""
+        out = (ctypes.c_uint32 * 8)()
+        _check(abi().bfhip_air_kernel_info(self._h, out))
+        d = dict(zip(self.INFO, (int(v) for v in out)))
+        d["sgprs"] = None if d["sgprs"] == 0xFFFFFFFF else d["sgprs"]
+        d["from_cache"] = bool(d["from_cache"])
+        return d
+
+
+class LogupProgram(_Program):
+    """bfhip_logup: a validated fraction program (include/bfhip.h "Fraction programs") — a constraint program's bytecode without constraints,
+    with FRAC (add q[a] / q[b] to the open logUp column) and END_COL. Host only to create; Context.logup_program_generate runs it on the
+    trace domain. A refused program raises BfhipError naming the instruction index and the rule."""
+    _destroy = "bfhip_logup_destroy"
+
+    def __init__(self, code, n_cols, n_params):
+        out = self._create(code, lambda words, n, h: abi().bfhip_logup_create(words, n, int(n_cols), int(n_params), h), abi().bfhip_logup_shape)
+        self.shape = {"n_cols": out[0], "n_params": out[1], "n_logup_cols": out[2], "n_fractions": out[3], "n_instr": out[4], "m_regs": out[5], "q_regs": out[6]}
+
+
+class RelationProgram(_Program):
+    """bfhip_relation_program: a validated relation program (include/bfhip.h "Relation programs") — the base-field opcodes of a constraint
+    program with WORD (append m[a] to the pending tuple) and ENTRY (add_to_relation(relation, multiplicity m[a], the pending tuple)).
+    relation_words[r] = the width of relation r, 1 to 7. Host only to create and for eval_row; Context.relation_program_summary runs it over
+    a component's cells. A refused program raises BfhipError naming the instruction index and the rule."""
+    _destroy = "bfhip_relation_program_destroy"
+
+    def __init__(self, code, n_cols, relation_words):
+        self.relation_words = [int(w) for w in relation_words]
+        widths = (ctypes.c_uint32 * max(1, len(self.relation_words)))(*self.relation_words)
+        out = self._create(code, lambda words, n, h: abi().bfhip_relation_program_create(words, n, int(n_cols), widths, len(self.relation_words), h),
+                           abi().bfhip_relation_program_shape)
+        self.shape = {"n_cols": out[0], "n_relations": out[1], "n_entries": out[2], "n_instr": out[3], "m_regs": out[4]}
+
+    def eval_row(self, col_values):
+        """bfhip_relation_program_eval_row (host only): the entries of ONE row, in program order, zero multiplicities included, as
+        [(relation, multiplicity, tuple)] with the tuple cut to the relation's width. col_values: n_cols canonical words."""
+        if len(col_values) != self.shape["n_cols"]:
+            raise ValueError("one value per program column")
+        n = ctypes.c_uint32()
+        cap = self.shape["n_entries"]
+        rels, mults, tups = (ctypes.c_uint32 * cap)(), (ctypes.c_uint32 * cap)(), (ctypes.c_uint32 * (7 * cap))()
+        _check(abi().bfhip_relation_program_eval_row(self._h, _u32s(col_values) if len(col_values) else None, rels, mults, tups, cap, ctypes.byref(n)))
+        return [(int(rels[e]), int(mults[e]), tuple(int(v) for v in tups[7 * e: 7 * e + self.relation_words[rels[e]]])) for e in range(n.value)]
+
+
+class AirExpr:
+    """A value of an AirBuilder: kind 'm' (M31, a base-field column expression) or 'q' (QM31). Operators + - * and unary -; a Python int
+    stands for const(int). m op q promotes the m side (Q_FROM_M), except a product, which is Q_MULM."""
+    __slots__ = ("builder", "id", "kind")
+
+    def __init__(self, builder, vid, kind):
+        self.builder, self.id, self.kind = builder, vid, kind
+
+    def __add__(self, other): return self.builder._binary("add", self, other)
+    def __radd__(self, other): return self.builder._binary("add", other, self)
+    def __sub__(self, other): return self.builder._binary("sub", self, other)
+    def __rsub__(self, other): return self.builder._binary("sub", other, self)
+    def __mul__(self, other): return self.builder._binary("mul", self, other)
+    def __rmul__(self, other): return self.builder._binary("mul", other, self)
+    def __neg__(self): return self.builder._negate(self)
+
+
+class AirBuilder:
+    """Writes a constraint program from expressions — what a user writes; the bytecode is what bindings pass.
+        b = AirBuilder(); a, x = b.col(0), b.col(1); b.constraint(a * a - x); prog = b.program()
+    col(i, off) / secure_col(i, off) (coordinates in columns i..i+3) / param(i) / const(v) give values; every value is computed once, in
+    the order it was created (so the order of first use of a column's offsets — the mask order — is the order of the col() calls that are
+    used); other values no constraint depends on are dropped, but a column read stays (like stwo's next_trace_mask, it is part of the mask
+    whether or not a constraint uses it); a register is reused after its value's last use."""
+
+    def __init__(self):
+        self._ops = []        # [op, kind of the result or None, sources (value ids), immediates]
+        self._memo = {}
+
+    def _emit(self, op, kind, srcs=(), imm=(), key=None):
+        if key is not None and key in self._memo:
+            return self._memo[key]
+        self._ops.append((op, kind, tuple(srcs), tuple(imm)))
+        e = AirExpr(self, len(self._ops) - 1, kind) if kind else None
+        if key is not None:
+            self._memo[key] = e
+        return e
+
+    def col(self, i, off=0):
+        return self._emit(AIR_M_COL, "m", imm=(int(i), int(off)), key=("col", int(i), int(off)))
+
+    def secure_col(self, i, off=0):
+        return self._emit(AIR_Q_COL, "q", imm=(int(i), int(off)), key=("qcol", int(i), int(off)))
+
+    def param(self, i):
+        return self._emit(AIR_Q_PARAM, "q", imm=(int(i),), key=("param", int(i)))
+
+    def const(self, v):
+        return self._emit(AIR_M_CONST, "m", imm=(int(v) % P,), key=("const", int(v) % P))
+
+    def _value(self, x):
+        if isinstance(x, AirExpr):
+            if x.builder is not self:
+                raise ValueError("a value of another AirBuilder")
+            return x
+        if isinstance(x, (int, np.integer)):
+            return self.const(int(x))
+        raise TypeError("an AirBuilder value or an int, got %r" % (x,))
+
+    def _to_q(self, x):
+        return x if x.kind == "q" else self._emit(AIR_Q_FROM_M, "q", (x.id,), key=("from_m", x.id))
+
+    def _binary(self, what, x, y):
+        x, y = self._value(x), self._value(y)
+        if x.kind == "m" and y.kind == "m":
+            return self._emit({"add": AIR_M_ADD, "sub": AIR_M_SUB, "mul": AIR_M_MUL}[what], "m", (x.id, y.id))
+        if what == "mul" and x.kind != y.kind:
+            qv, mv = (x, y) if x.kind == "q" else (y, x)
+            return self._emit(AIR_Q_MULM, "q", (qv.id, mv.id))
+        return self._emit({"add": AIR_Q_ADD, "sub": AIR_Q_SUB, "mul": AIR_Q_MUL}[what], "q", (self._to_q(x).id, self._to_q(y).id))
+
+    def _negate(self, x):
+        if x.kind == "m":
+            return self._emit(AIR_M_NEG, "m", (x.id,))
+        return self._emit(AIR_Q_MULM, "q", (x.id, self.const(P - 1).id))
+
+    def constraint(self, expr):
+        expr = self._value(expr)
+        self._emit(AIR_C_BASE if expr.kind == "m" else AIR_C_EXT, None, (expr.id,))
+
+    def frac(self, num, den):
+        """BFHIP_LOGUP_FRAC: add num / den to the open logUp column (LogupTraceGenerator::write_frac). A base-field numerator or
+        denominator is lifted (Q_FROM_M). Fraction programs only: see logup_program()."""
+        num, den = self._to_q(self._value(num)), self._to_q(self._value(den))
+        self._emit(LOGUP_FRAC, None, (num.id, den.id))
+
+    def end_column(self):
+        """BFHIP_LOGUP_END_COL: close the open logUp column (finalize_col); the next frac() opens the next one."""
+        self._emit(LOGUP_END_COL, None)
+
+    def relation_entry(self, relation, multiplicity, values):
+        """BFHIP_REL_WORD per value, then BFHIP_REL_ENTRY: one add_to_relation(relation, multiplicity, values). Base-field values only.
+        Relation programs only: see relation_program()."""
+        mult, values = self._value(multiplicity), [self._value(v) for v in values]
+        if mult.kind != "m" or any(v.kind != "m" for v in values):
+            raise ValueError("a relation entry takes base-field values (kind 'm')")
+        for v in values:
+            self._emit(REL_WORD, None, (v.id,))
+        # the words are sources of the ENTRY too: the interpreters read them there, so their registers live until then
+        self._emit(REL_ENTRY, None, (mult.id,) + tuple(v.id for v in values), imm=(int(relation),))
+
+    def code(self):
+        """The bytecode (a flat list of u32 words). Raises ValueError if the program needs more registers than the caps."""
+        import heapq
+        ops = self._ops
+        live = [kind is None or op in (AIR_M_COL, AIR_Q_COL) for op, kind, _, _ in ops]
+        for i in range(len(ops) - 1, -1, -1):
+            if live[i]:
+                for s in ops[i][2]:
+                    live[s] = True
+        last_use = {}
+        for i, (_, _, srcs, _) in enumerate(ops):
+            if live[i]:
+                for s in srcs:
+                    last_use[s] = i
+        free = {"m": list(range(AIR_MAX_M_REGS + 1)), "q": list(range(AIR_MAX_Q_REGS + 1))}
+        reg, words = {}, []
+        for i, (op, kind, srcs, imm) in enumerate(ops):
+            if not live[i]:
+                continue
+            regs = [reg[s] for s in srcs]
+            for s in set(srcs):
+                if last_use[s] == i:
+                    heapq.heappush(free[ops[s][1]], reg[s])
+            dst = 0
+            if kind:
+                dst = reg[i] = heapq.heappop(free[kind])
+                if dst >= (AIR_MAX_M_REGS if kind == "m" else AIR_MAX_Q_REGS):
+                    raise ValueError("the program needs more than %d %s registers" % ((AIR_MAX_M_REGS, "m") if kind == "m" else (AIR_MAX_Q_REGS, "q")))
+                if i not in last_use:         # a column read no constraint uses: it stays for the mask, its register is free at once
+                    heapq.heappush(free[kind], dst)
+            if op in (AIR_M_COL, AIR_Q_COL):
+                words += [op, dst, imm[0], imm[1] & 0xFFFFFFFF]
+            elif op in (AIR_M_CONST, AIR_Q_PARAM):
+                words += [op, dst, imm[0], 0]
+            elif op in (AIR_C_BASE, AIR_C_EXT):
+                words += [op, 0, regs[0], 0]
+            elif op == LOGUP_END_COL:
+                words += [op, 0, 0, 0]
+            elif op == REL_WORD:
+                words += [op, 0, regs[0], 0]
+            elif op == REL_ENTRY:
+                words += [op, imm[0] & 0xFFFFFFFF, regs[0], 0]
+            else:
+                words += [op, dst, regs[0], regs[1] if len(regs) > 1 else 0]
+        return words
+
+    def _counts(self, n_cols, n_params=None):
+        """(n_cols, n_params) of a program: where None, one more than the highest column / parameter any col() / param() named."""
+        cols = [imm[0] + (4 if op == AIR_Q_COL else 1) for op, _, _, imm in self._ops if op in (AIR_M_COL, AIR_Q_COL)]
+        pars = [imm[0] + 1 for op, _, _, imm in self._ops if op == AIR_Q_PARAM]
+        return max(cols, default=0) if n_cols is None else n_cols, max(pars, default=0) if n_params is None else n_params
+
+    def program(self, n_cols=None, n_params=None):
+        """AirProgram of the bytecode; n_cols / n_params default to one more than the highest column / parameter any col() / param() named."""
+        return AirProgram(self.code(), *self._counts(n_cols, n_params))
+
+    def logup_program(self, n_cols=None, n_params=None):
+        """LogupProgram of the bytecode (frac() / end_column() instead of constraint()); n_cols / n_params default as for program()."""
+        return LogupProgram(self.code(), *self._counts(n_cols, n_params))
+
+    def relation_program(self, relation_words, n_cols=None):
+        """RelationProgram of the bytecode (relation_entry() instead of constraint()); relation_words[r] = the width of relation r; n_cols
+        defaults as for program()."""
+        return RelationProgram(self.code(), self._counts(n_cols)[0], relation_words)

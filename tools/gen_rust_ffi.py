@@ -1,145 +1,94 @@
 #!/usr/bin/env python3
-"""Generates bindings/rust/bfhip_sys.rs — the `extern "C"` block a Rust `HipBackend` crate links against — from include/bfhip.h, so
-that the Rust-side binding of INTEGRATION.md can never drift from the C ABI. No Rust toolchain exists in the build image: the file is
-source only; tests/test_abi_and_replicas.py checks that it declares every symbol the header and the library export."""
+"""Generates bindings/rust/bfhip_sys.rs — the `extern "C"` block a Rust `HipBackend` crate links against — from include/bfhip.h
+(tools/bfhip_header.py reads it), so that the Rust-side binding of INTEGRATION.md can never drift from the C ABI: functions, opaque
+handles, `#[repr(C)]` structs and constants are all derived. No Rust toolchain exists in the build image: the file is source only
+(SURVEY.md §8 (f)4); tests/test_abi_and_replicas.py checks that it declares every symbol the header and the library export."""
 import os
 import re
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import bfhip_header
 
-TYPES = {
-    "void": "c_void", "char": "c_char", "int32_t": "i32", "uint32_t": "u32", "uint64_t": "u64", "uint8_t": "u8", "size_t": "usize", "double": "f64",
-    "bfhip_ctx": "BfhipCtx", "bfhip_trace": "BfhipTrace", "bfhip_local_group": "BfhipLocalGroup", "bfhip_pool": "BfhipPool",
-    "bfhip_conventions": "BfhipConventions", "bfhip_pcs_config": "BfhipPcsConfig", "bfhip_check_report": "BfhipCheckReport",
-    "bfhip_relation_entry": "BfhipRelationEntry", "bfhip_relation_report": "BfhipRelationReport", "bfhip_relation_table": "BfhipRelationTable",
-    "bfhip_pool_result": "BfhipPoolResult", "bfhip_preflight_report": "BfhipPreflightReport",
-    "bfhip_channel": "BfhipChannel", "bfhip_pcs": "BfhipPcs", "bfhip_pcs_verifier": "BfhipPcsVerifier", "bfhip_air": "BfhipAir",
-    "bfhip_logup": "BfhipLogup", "bfhip_air_check_report": "BfhipAirCheckReport",
-    "bfhip_relation_program": "BfhipRelationProgram", "bfhip_relation_program_table": "BfhipRelationProgramTable",
-    "bfhip_multiplicity_report": "BfhipMultiplicityReport", "bfhip_air_kernel": "BfhipAirKernel",
+SCALARS = {"void": "c_void", "char": "c_char", "int32_t": "i32", "uint32_t": "u32", "uint64_t": "u64", "uint8_t": "u8", "size_t": "usize", "double": "f64"}
+# what the header cannot say: the doc comment of a type, and a derive list that differs from the computed one
+DOCS = {
+    "bfhip_conventions": "`bfhip_conventions`: byte-level stwo conventions, all zero = defaults (include/bfhip.h).",
+    "bfhip_pcs_config": "`bfhip_pcs_config`: stwo's PcsConfig (include/bfhip.h). All zero is NOT the default: PcsConfig::default() is\n"
+                        "{ pow_bits: 5, log_blowup_factor: 1, log_last_layer_degree_bound: 0, n_queries: 3, reserved: [0; 4] }, or pass a null pointer.",
+    "bfhip_check_report": "`bfhip_check_report`: one component's AIR asserted on its trace domain (include/bfhip.h). first_bad_cell = u64::MAX and\n"
+                          "first_bad_constraint = -1 without violations; table row = first_bad_cell >> 4.",
+    "bfhip_relation_entry": "`bfhip_relation_entry`: one unbalanced tuple of a lookup relation (include/bfhip.h). first_*_table = -1 and first_*_row = u64::MAX if none.",
+    "bfhip_relation_report": "`bfhip_relation_report`: the counts of one relation (0 Memory, 1 Instruction, 2 Processor).",
+    "bfhip_relation_table": "`bfhip_relation_table`: one caller-supplied table; main_rows_h = host array of device pointers to its row-granular main columns.",
+    "bfhip_preflight_report": "`bfhip_preflight_report`: what a proof's preflight found (include/bfhip.h), 4064 bytes. relation r's entries at entries[4 r ..], n_reported of them.",
+    "bfhip_pool_result": "`bfhip_pool_result`: one finished job of a pool's queue (include/bfhip.h), 88 bytes. proof_json and error are malloc'd: bfhip_free_host.",
+    "bfhip_channel": "Commitment-scheme session (include/bfhip.h): the channel, the prover session of a context and the host-only verifier session.",
+    "bfhip_air": "A validated constraint program (include/bfhip.h \"Constraint programs\"): opcodes BFHIP_AIR_*, four u32 words {op, dst, a, b} per instruction.",
+    "bfhip_air_kernel": "A constraint program compiled to its own kernel at run time (include/bfhip.h \"Compiled constraint programs\"); belongs to the context that compiled it.",
+    "bfhip_air_check_report": "`bfhip_air_check_report`: a constraint program asserted on its trace domain (include/bfhip.h), 1088 bytes. first_bad_cell and\n"
+                              "first_cell_per_constraint[j] = u64::MAX and first_bad_constraint = -1 where nothing fails. (No Default: arrays of 64.)",
+    "bfhip_logup": "A validated fraction program (include/bfhip.h \"Fraction programs\"): a constraint program's opcodes without C_BASE / C_EXT, plus BFHIP_LOGUP_FRAC and BFHIP_LOGUP_END_COL.",
+    "bfhip_relation_program": "A validated relation program (include/bfhip.h \"Relation programs\"): the base-field opcodes of a constraint program, plus BFHIP_REL_WORD and BFHIP_REL_ENTRY.",
+    "bfhip_relation_program_table": "`bfhip_relation_program_table`: one table of bfhip_relation_program_summary, 32 bytes. cols_h = host array of device pointers; col_shifts_h may be null.",
+    "bfhip_multiplicity_report": "`bfhip_multiplicity_report`: the counts of bfhip_relation_program_multiplicities (include/bfhip.h \"Lookup multiplicities\"), 80 bytes.",
 }
+DERIVES = {"bfhip_pcs_config": "Clone, Copy, Debug, PartialEq, Eq"}      # no Default: all zero is not PcsConfig::default()
+# constants the Rust side states itself: the convention switches are fields of BfhipConventions it fills by value, the PcsConfig bounds are
+# checked by the library
+NOT_IN_RUST = ("BFHIP_MERKLE_", "BFHIP_MIX_U64_", "BFHIP_LOGUP_MASK_", "BFHIP_CHANNEL_", "BFHIP_MAX_")
+SIGNED = {"BFHIP_AIR_MAX_OFFSET"}                                         # compared with i32 row offsets
+
+
+def rust_name(c):
+    return SCALARS.get(c) or "".join(w.capitalize() for w in c.split("_"))
 
 
 def rust_type(c):
-    """C parameter type (without the name) -> Rust type."""
-    c = c.strip()
-    arr = re.search(r"\[(\d*)\]$", c)          # T name[4] decays to a pointer
-    if arr:
-        c = c[: arr.start()].strip() + "*"
-    m = re.match(r"^(const\s+)?(\w+)\s*((?:\*\s*(?:const\s*)?)*)$", c)
-    if not m:
-        raise ValueError(c)
-    const, base, stars = m.group(1), m.group(2), m.group(3)
-    t = TYPES[base]
-    levels = re.findall(r"\*\s*(const)?", stars)
+    """C type as tools/bfhip_header.py normalises it (`const uint32_t*const*`) -> Rust type."""
+    const, base, stars = re.match(r"^(const\s+)?(\w+)((?:\*(?:const)?)*)$", c).groups()
+    levels = re.findall(r"\*(const)?", stars)
     # innermost pointee constness comes from the leading `const`; outer levels from `* const`
-    out = t
-    for k, lvl in enumerate(levels):
+    out = rust_name(base)
+    for k in range(len(levels)):
         is_const = bool(const) if k == 0 else (levels[k - 1] == "const")
         out = ("*const " if is_const else "*mut ") + out
     return out
 
 
-def parse(header):
-    text = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    protos = re.findall(r"^(const char\*|int32_t|void)\s+(bfhip_\w+)\s*\((.*?)\)\s*;", text, flags=re.S | re.M)
-    out = []
-    for ret, name, params in protos:
-        params = " ".join(params.split())
-        args = []
-        if params and params != "void":
-            for p in params.split(","):
-                p = p.strip()
-                m = re.match(r"^(.*?)(\w+)(\[\d*\])?$", p)
-                ctype, pname, arr = m.group(1), m.group(2), m.group(3) or ""
-                if pname == "type":
-                    pname = "type_"
-                args.append((pname, rust_type(ctype + arr)))
-        rret = {"const char*": "*const c_char", "int32_t": "i32", "void": None}[ret]
-        out.append((name, args, rret))
-    return out
+def derives(fields):
+    """What the layout allows: a pointer, a double or a nested struct leaves Clone, Copy, Debug; std has no Default for arrays above 32."""
+    if any("*" in f.ctype or f.ctype == "double" or f.ctype not in SCALARS for f in fields):
+        return "Clone, Copy, Debug"
+    return "Clone, Copy, " + ("" if any((f.array or 0) > 32 for f in fields) else "Default, ") + "Debug, PartialEq, Eq"
 
 
 def main():
-    header = open(os.path.join(ROOT, "include", "bfhip.h")).read()
-    fns = parse(header)
+    hdr = bfhip_header.parse()
     lines = [
         "// GENERATED by tools/gen_rust_ffi.py from include/bfhip.h — do not edit. Raw FFI of libbfhip.so for a Rust `HipBackend`",
         "// (crates/brainfuck_prover would depend on this as a `-sys` module; see INTEGRATION.md for the trait mapping).",
         "#![allow(non_camel_case_types, dead_code)]",
         "use std::ffi::{c_char, c_void};",
         "",
-        "#[repr(C)] pub struct BfhipCtx { _private: [u8; 0] }",
-        "#[repr(C)] pub struct BfhipTrace { _private: [u8; 0] }",
-        "/// `bfhip_conventions`: byte-level stwo conventions, all zero = defaults (include/bfhip.h).",
-        "#[repr(C)] #[derive(Clone, Copy, Default, Debug, PartialEq, Eq)] pub struct BfhipConventions { pub merkle_node_hash: u32, pub mix_u64: u32, pub logup_mask_order: u32, pub merkle_channel: u32, pub reserved: [u32; 4] }",
-        "/// `bfhip_pcs_config`: stwo's PcsConfig (include/bfhip.h). All zero is NOT the default: PcsConfig::default() is",
-        "/// { pow_bits: 5, log_blowup_factor: 1, log_last_layer_degree_bound: 0, n_queries: 3, reserved: [0; 4] }, or pass a null pointer.",
-        "#[repr(C)] #[derive(Clone, Copy, Debug, PartialEq, Eq)] pub struct BfhipPcsConfig { pub pow_bits: u32, pub log_blowup_factor: u32, pub log_last_layer_degree_bound: u32, pub n_queries: u32, pub reserved: [u32; 4] }",
-        "/// `bfhip_check_report`: one component's AIR asserted on its trace domain (include/bfhip.h). first_bad_cell = u64::MAX and",
-        "/// first_bad_constraint = -1 without violations; table row = first_bad_cell >> 4.",
-        "#[repr(C)] #[derive(Clone, Copy, Default, Debug, PartialEq, Eq)] pub struct BfhipCheckReport { pub component: u32, pub log_size: u32, pub n_bad_cells: u64, pub first_bad_cell: u64, pub first_bad_constraint: i32, pub first_bad_value: [u32; 4], pub bad_per_constraint: [u64; 16], pub claimed_sum: [u32; 4], pub reserved: [u32; 3] }",
-        "/// `bfhip_relation_entry`: one unbalanced tuple of a lookup relation (include/bfhip.h). first_*_table = -1 and first_*_row = u64::MAX if none.",
-        "#[repr(C)] #[derive(Clone, Copy, Default, Debug, PartialEq, Eq)] pub struct BfhipRelationEntry { pub relation: u32, pub n_words: u32, pub tuple: [u32; 7], pub net: u32, pub n_yield: u64, pub n_use: u64, pub n_other: u64, pub first_yield_table: i32, pub first_use_table: i32, pub first_yield_row: u64, pub first_use_row: u64, pub reserved: [u32; 2] }",
-        "/// `bfhip_relation_report`: the counts of one relation (0 Memory, 1 Instruction, 2 Processor).",
-        "#[repr(C)] #[derive(Clone, Copy, Default, Debug, PartialEq, Eq)] pub struct BfhipRelationReport { pub relation: u32, pub n_words: u32, pub n_entries: u64, pub n_tuples: u64, pub n_unbalanced: u64, pub n_reported: u64, pub reserved: [u32; 2] }",
-        "/// `bfhip_relation_table`: one caller-supplied table; main_rows_h = host array of device pointers to its row-granular main columns.",
-        "#[repr(C)] #[derive(Clone, Copy, Debug)] pub struct BfhipRelationTable { pub component: i32, pub log_size: u32, pub main_rows_h: *const *const u32 }",
-        "#[repr(C)] pub struct BfhipLocalGroup { _private: [u8; 0] }",
-        "#[repr(C)] pub struct BfhipPool { _private: [u8; 0] }",
-        "/// Commitment-scheme session (include/bfhip.h): the channel, the prover session of a context and the host-only verifier session.",
-        "#[repr(C)] pub struct BfhipChannel { _private: [u8; 0] }",
-        "#[repr(C)] pub struct BfhipPcs { _private: [u8; 0] }",
-        "#[repr(C)] pub struct BfhipPcsVerifier { _private: [u8; 0] }",
-        "/// A validated constraint program (include/bfhip.h \"Constraint programs\"): opcodes BFHIP_AIR_*, four u32 words {op, dst, a, b} per instruction.",
-        "#[repr(C)] pub struct BfhipAir { _private: [u8; 0] }",
-        "/// A constraint program compiled to its own kernel at run time (include/bfhip.h \"Compiled constraint programs\"); belongs to the context that compiled it.",
-        "#[repr(C)] pub struct BfhipAirKernel { _private: [u8; 0] }",
-        "/// `bfhip_air_check_report`: a constraint program asserted on its trace domain (include/bfhip.h), 1088 bytes. first_bad_cell and",
-        "/// first_cell_per_constraint[j] = u64::MAX and first_bad_constraint = -1 where nothing fails. (No Default: arrays of 64.)",
-        "#[repr(C)] #[derive(Clone, Copy, Debug, PartialEq, Eq)] pub struct BfhipAirCheckReport { pub log_size: u32, pub n_constraints: u32, pub n_bad_cells: u64, pub first_bad_cell: u64, pub first_bad_constraint: i32, pub reserved0: u32, pub first_bad_value: [u32; 4], pub bad_per_constraint: [u64; 64], pub first_cell_per_constraint: [u64; 64], pub reserved: [u64; 2] }",
-        "/// A validated fraction program (include/bfhip.h \"Fraction programs\"): a constraint program's opcodes without C_BASE / C_EXT, plus BFHIP_LOGUP_FRAC and BFHIP_LOGUP_END_COL.",
-        "#[repr(C)] pub struct BfhipLogup { _private: [u8; 0] }",
-        "/// A validated relation program (include/bfhip.h \"Relation programs\"): the base-field opcodes of a constraint program, plus BFHIP_REL_WORD and BFHIP_REL_ENTRY.",
-        "#[repr(C)] pub struct BfhipRelationProgram { _private: [u8; 0] }",
-        "/// `bfhip_relation_program_table`: one table of bfhip_relation_program_summary, 32 bytes. cols_h = host array of device pointers; col_shifts_h may be null.",
-        "#[repr(C)] #[derive(Clone, Copy, Debug)] pub struct BfhipRelationProgramTable { pub program: *const BfhipRelationProgram, pub log_size: u32, pub row_shift: u32, pub cols_h: *const *const u32, pub col_shifts_h: *const u32 }",
-        "/// `bfhip_multiplicity_report`: the counts of bfhip_relation_program_multiplicities (include/bfhip.h \"Lookup multiplicities\"), 80 bytes.",
-        "#[repr(C)] #[derive(Clone, Copy, Default, Debug, PartialEq, Eq)] pub struct BfhipMultiplicityReport { pub relation: u32, pub n_words: u32, pub target_table: u32, pub target_entry: u32, pub n_rows: u64, pub n_row_tuples: u64, pub n_entries: u64, pub n_tuples: u64, pub n_filled: u64, pub n_missing: u64, pub n_reported: u64, pub reserved: [u32; 2] }",
-        "/// `bfhip_pool_result`: one finished job of a pool's queue (include/bfhip.h), 88 bytes. proof_json and error are malloc'd: bfhip_free_host.",
-        "#[repr(C)] #[derive(Clone, Copy, Debug)] pub struct BfhipPoolResult { pub ticket: u64, pub user_tag: u64, pub status: i32, pub worker: u32, pub flags: u32, pub log_max_rows: u32, pub proof_json: *mut c_char, pub proof_len: usize, pub error: *mut c_char, pub seconds_queued: f64, pub seconds_proving: f64, pub reserved: [u64; 2] }",
-        "/// `bfhip_preflight_report`: what a proof's preflight found (include/bfhip.h), 4064 bytes. relation r's entries at entries[4 r ..], n_reported of them.",
-        "#[repr(C)] #[derive(Clone, Copy, Debug)] pub struct BfhipPreflightReport { pub ran: u32, pub rejected: u32, pub n_bad_components: i32, pub n_entries: u32, pub logup_total: [u32; 4], pub components: [BfhipCheckReport; 13], pub relations: [BfhipRelationReport; 3], pub entries: [BfhipRelationEntry; 12], pub seconds: f64, pub reserved: [u64; 3] }",
-        "pub const BFHIP_TRACE_REJECTED: i32 = -3;",
-        "pub const BFHIP_JOB_CANCELLED: i32 = -2;",
-        "pub const BFHIP_POOL_MAX_OUTSTANDING: u32 = 4096;",
-        "pub const BFHIP_PCS_MAX_SAMPLES_PER_COLUMN: u32 = 2;",
-        "pub const BFHIP_PCS_MAX_POINTS: u32 = 64;",
-        "pub const BFHIP_PCS_MAX_COLUMNS: u32 = 4096;",
-        "pub const BFHIP_PCS_MAX_TREES: u32 = 64;",
-        "pub const BFHIP_AIR_M_COL: u32 = 0; pub const BFHIP_AIR_M_CONST: u32 = 1; pub const BFHIP_AIR_M_ADD: u32 = 2; pub const BFHIP_AIR_M_SUB: u32 = 3;",
-        "pub const BFHIP_AIR_M_MUL: u32 = 4; pub const BFHIP_AIR_M_NEG: u32 = 5; pub const BFHIP_AIR_Q_COL: u32 = 6; pub const BFHIP_AIR_Q_PARAM: u32 = 7;",
-        "pub const BFHIP_AIR_Q_FROM_M: u32 = 8; pub const BFHIP_AIR_Q_ADD: u32 = 9; pub const BFHIP_AIR_Q_SUB: u32 = 10; pub const BFHIP_AIR_Q_MUL: u32 = 11;",
-        "pub const BFHIP_AIR_Q_MULM: u32 = 12; pub const BFHIP_AIR_C_BASE: u32 = 13; pub const BFHIP_AIR_C_EXT: u32 = 14;",
-        "pub const BFHIP_AIR_MAX_M_REGS: u32 = 96; pub const BFHIP_AIR_MAX_Q_REGS: u32 = 24; pub const BFHIP_AIR_MAX_INSTRUCTIONS: u32 = 4096;",
-        "pub const BFHIP_AIR_MAX_COLUMNS: u32 = 256; pub const BFHIP_AIR_MAX_PARAMS: u32 = 64; pub const BFHIP_AIR_MAX_CONSTRAINTS: u32 = 64;",
-        "pub const BFHIP_AIR_MAX_OFFSET: i32 = 16;",
-        "pub const BFHIP_LOGUP_FRAC: u32 = 15; pub const BFHIP_LOGUP_END_COL: u32 = 16; pub const BFHIP_LOGUP_MAX_COLUMNS: u32 = 8; pub const BFHIP_LOGUP_MAX_FRACTIONS: u32 = 32;",
-        "pub const BFHIP_REL_WORD: u32 = 17; pub const BFHIP_REL_ENTRY: u32 = 18; pub const BFHIP_RELATION_PROGRAM_MAX_RELATIONS: u32 = 16;",
-        "pub const BFHIP_RELATION_PROGRAM_MAX_WORDS: u32 = 7; pub const BFHIP_RELATION_PROGRAM_MAX_ENTRIES: u32 = 32;",
-        "",
-        "#[link(name = \"bfhip\")]",
-        "extern \"C\" {",
     ]
-    for name, args, ret in fns:
-        a = ", ".join(f"{n}: {t}" for n, t in args)
-        lines.append(f"    pub fn {name}({a})" + (f" -> {ret};" if ret else ";"))
+    for name, fields in hdr.typedefs:
+        lines += ["/// " + d for d in DOCS.get(name, "").split("\n") if d]
+        if fields is None:
+            lines.append("#[repr(C)] pub struct %s { _private: [u8; 0] }" % rust_name(name))
+            continue
+        body = ", ".join("pub %s: %s" % (f.name, "[%s; %d]" % (rust_type(f.ctype), f.array) if f.array else rust_type(f.ctype)) for f in fields)
+        lines.append("#[repr(C)] #[derive(%s)] pub struct %s { %s }" % (DERIVES.get(name) or derives(fields), rust_name(name), body))
+    lines += ["pub const %s: %s = %d;" % (n, "i32" if v < 0 or n in SIGNED else "u32", v) for n, v in hdr.constants if not n.startswith(NOT_IN_RUST)]
+    lines += ["", "#[link(name = \"bfhip\")]", "extern \"C\" {"]
+    for fn in hdr.functions:
+        a = ", ".join("%s: %s" % ("type_" if p.name == "type" else p.name, rust_type(p.ctype)) for p in fn.params)
+        ret = {"const char*": " -> *const c_char", "int32_t": " -> i32", "void": ""}[fn.ret]
+        lines.append("    pub fn %s(%s)%s;" % (fn.name, a, ret))
     lines += ["}", ""]
-    out = os.path.join(ROOT, "bindings", "rust", "bfhip_sys.rs")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
+    out = os.path.join(bfhip_header.ROOT, "bindings", "rust", "bfhip_sys.rs")
     open(out, "w").write("\n".join(lines))
-    print(f"wrote {out}: {len(fns)} functions")
+    print(f"wrote {out}: {len(hdr.functions)} functions, {len(hdr.typedefs)} types")
 
 
 if __name__ == "__main__":
