@@ -580,6 +580,50 @@ impl Drop for AirKernel {
     }
 }
 
+// ---- composition (`include/bfhip.h` "Composition"): ALL components of an AIR to the composition polynomial ----------------------------------
+/// How one component of `air_compose` runs: interpreted, or as the kernel its context compiled.
+pub enum AirRunner<'a> { Program(&'a AirProgram), Kernel(&'a AirKernel) }
+
+/// One component of `air_compose`: `cols` / `shifts` / `params` as for `AirProgram::eval_domain`, on CanonicCoset(log_size + log_expand).circle_domain().
+pub struct AirComponent<'a> { pub runner: AirRunner<'a>, pub log_size: u32, pub log_expand: u32, pub cols: &'a [*const u32], pub shifts: &'a [u32], pub params: &'a [Felt] }
+
+/// One component of `air_compose_at_point`: `mask_values` in `program.mask()` order.
+pub struct AirPointComponent<'a> { pub program: &'a AirProgram, pub log_size: u32, pub mask_values: &'a [Felt], pub params: &'a [Felt] }
+
+/// `bfhip_air_compose_coeffs`: constraint g of all T = sum(n_constraints) gets random_coeff^(T - 1 - g); slice it per component for `eval_domain`.
+pub fn air_compose_coeffs(n_constraints: &[u32], random_coeff: &Felt) -> Result<Vec<Felt>, String> {
+    let total: usize = n_constraints.iter().filter(|&&c| c <= sys::BFHIP_AIR_MAX_CONSTRAINTS).map(|&c| c as usize).sum();
+    let mut out = vec![[0u32; 4]; total.max(1)];
+    check(unsafe { sys::bfhip_air_compose_coeffs(n_constraints.as_ptr(), n_constraints.len() as u32, random_coeff.as_ptr(), out.as_mut_ptr() as *mut u32) })?;
+    out.truncate(total);
+    Ok(out)
+}
+
+/// `bfhip_air_compose`: `ComponentProvers::compute_composition_polynomial` — the 4 coefficient columns of 2^dst_log words into `dst`
+/// (overwritten), ready for `PcsProver::commit` (form 1). `dst_log` = the largest log_size + log_expand of the list. Interpreted components
+/// run in one launch, compiled ones in one launch each behind it; works while a session is open.
+pub fn air_compose(ctx: &Context, comps: &[AirComponent], random_coeff: &Felt, dst_log: u32, dst: &[*mut u32; 4]) -> Result<(), String> {
+    let mut raw = Vec::with_capacity(comps.len());
+    for c in comps {
+        if !c.shifts.is_empty() && c.shifts.len() != c.cols.len() { return Err("one shift per column".into()); }
+        let (program, kernel) = match c.runner { AirRunner::Program(p) => (p.0 as *const sys::BfhipAir, std::ptr::null_mut()), AirRunner::Kernel(k) => (std::ptr::null(), k.0) };
+        raw.push(sys::BfhipAirComponent { program, kernel, log_size: c.log_size, log_expand: c.log_expand, cols_h: c.cols.as_ptr(),
+                                          col_shifts_h: if c.shifts.is_empty() { std::ptr::null() } else { c.shifts.as_ptr() },
+                                          params_h: c.params.as_ptr() as *const u32, n_params: c.params.len() as u32, reserved: 0 });
+    }
+    check(unsafe { sys::bfhip_air_compose(ctx.0, raw.as_ptr(), raw.len() as u32, random_coeff.as_ptr(), dst_log, dst.as_ptr()) })
+}
+
+/// `bfhip_air_compose_at_point` (host only): `Components::eval_composition_polynomial_at_point` from the sampled mask values.
+pub fn air_compose_at_point(comps: &[AirPointComponent], point: &Point, random_coeff: &Felt) -> Result<Felt, String> {
+    let raw: Vec<sys::BfhipAirPointComponent> = comps.iter().map(|c| sys::BfhipAirPointComponent {
+        program: c.program.0 as *const sys::BfhipAir, log_size: c.log_size, n_mask: c.mask_values.len() as u32, mask_values_h: c.mask_values.as_ptr() as *const u32,
+        params_h: c.params.as_ptr() as *const u32, n_params: c.params.len() as u32, reserved: 0 }).collect();
+    let mut out = [0u32; 4];
+    check(unsafe { sys::bfhip_air_compose_at_point(raw.as_ptr(), raw.len() as u32, point.as_ptr(), random_coeff.as_ptr(), out.as_mut_ptr()) })?;
+    Ok(out)
+}
+
 // ---- fraction programs (`include/bfhip.h` "Fraction programs"): the logUp interaction trace of ANY AIR ---------------------------------------
 // What a component's `interaction_trace_evaluation` hands to `LogupTraceGenerator::{new_col, write_frac, finalize_col, finalize_last}`, recorded
 // once as bytecode: a constraint program's opcodes without constraints, plus `sys::BFHIP_LOGUP_FRAC` {-, a, b} (add q[a] / q[b] to the open

@@ -242,7 +242,7 @@ int32_t bfhip_logup_generate(bfhip_ctx* ctx, int32_t component, uint32_t log_siz
  * is_first_d: the preprocessed IsFirst LDE (2^(log_size+1) cells). main_lde_h / inter_lde_h: device pointers to the n_main and
  * 4 * n_logup LDE columns; *_shifts_h (may be NULL = 0) give the replication shift of each (cell i is read at index i >> shift).
  * coeffs_h = u32[4 * n_constraints]: the coefficient of constraint j in evaluation order (the caller reverses the accumulator's
- * power slice the way `accum.columns()` does). claimed_sum_h = the component's logUp total. */
+ * power slice the way `accum.columns()` does; bfhip_air_compose_coeffs writes exactly these, for all components). claimed_sum_h = the component's logUp total. */
 int32_t bfhip_eval_constraints(bfhip_ctx* ctx, int32_t component, uint32_t log_size, const uint32_t* is_first_d, const uint32_t* const* main_lde_h,
                                const uint32_t* main_shifts_h, const uint32_t* const* inter_lde_h, const uint32_t* inter_shifts_h, const uint32_t lookup_h[24],
                                const uint32_t claimed_sum_h[4], const uint32_t* coeffs_h, uint32_t* const acc_d[4]);
@@ -811,6 +811,62 @@ int32_t bfhip_air_kernel_eval_domain(bfhip_ctx* ctx, bfhip_air_kernel* kernel, u
                                      uint32_t* const acc_d[4]);
 int32_t bfhip_air_kernel_info(bfhip_air_kernel* kernel, uint32_t out[8]);
 int32_t bfhip_air_kernel_destroy(bfhip_air_kernel* kernel);
+
+/* ---- Composition: ALL components of an AIR to the composition polynomial's four coefficient columns, in one call ----------------------------
+ * `ComponentProvers::compute_composition_polynomial` (reached from prover::prove) for an AIR given as programs: what a caller of
+ * bfhip_air_eval_domain otherwise does by hand — coefficient slices, one sweep and one accumulator pass per component, one interpolation per
+ * size, the additions of DomainEvaluationAccumulator::finalize — and its mirror at a point for the verifier. No channel, no session, no
+ * protocol: the caller draws random_coeff and commits the result (bfhip_pcs_commit, form 1).
+ *
+ * Coefficients. T = the sum of the components' constraint counts. The constraint with global index g (components in list order, constraints
+ *   in program order) gets random_coeff^(T - 1 - g): what `accum.columns()` hands the components on the domain and what
+ *   PointEvaluationAccumulator's Horner sum gives at a point. bfhip_air_compose_coeffs (host only) writes these T values of 4 words in global
+ *   order, so that a caller who sweeps component by component uses the same numbers; a count outside 1..64 constraints is refused.
+ * Buckets. Component k is evaluated on the domain of el_k = log_size_k + log_expand_k. Components of equal el share an accumulator, whatever
+ *   their log_size. For every row of a bucket the accumulator holds the sum, over the bucket's components in list order, of
+ *       (sum_j coeff_j C_j(row)) * 1 / coset_vanishing(CanonicCoset(log_size_k).coset, point(row)):
+ *   for a single component bfhip_air_eval_domain's value from a zero accumulator, bit for bit.
+ * Finalize. Each bucket is interpolated on its own domain and the smaller buckets' coefficients are added onto the prefix of the largest
+ *   one: evaluating a polynomial on a larger domain is zero extension of its coefficients, and interpolation is linear. dst_d receives the 4
+ *   coefficient columns of 2^dst_log words, overwritten, not accumulated. dst_log must equal max_k el_k; another value is refused and the
+ *   message names the expected one.
+ * bfhip_air_compose: the interpreted components (kernel == NULL) run in one gfx950 kernel in which a wave owns 64 rows of a bucket, walks the
+ *   bucket's components and writes the row's sum once, with no read and no zero fill (one launch for all buckets below 2^16 rows, one per
+ *   larger bucket: DESIGN.md section 9n); a component given as its compiled kernel (this
+ *   context's bfhip_air_compile; program may then be NULL) runs after that, one launch each, and adds into its bucket. Then one batched
+ *   inverse transform over all buckets and the additions. Works while a commitment-scheme session is open and takes nothing from the arena:
+ *   with more than one bucket it makes one hipMalloc of at most 16 * 2^dst_log bytes for the smaller buckets' accumulators (the largest
+ *   accumulates in dst_d), freed before return (the call then waits for the stream); with one bucket it allocates nothing and does not
+ *   wait. A context in a shard group is refused.
+ *   Refusals: -1 with "bfhip_air_compose: component <k>: <rule>", or "bfhip_air_compose: <rule>" for a rule about the list; nothing has
+ *   been enqueued and the context stays usable. n outside 1..64, null pointers, reserved != 0, neither program nor kernel, a kernel of
+ *   another context, every rule of bfhip_air_eval_domain about one component (log_expand, log_size, max_log_domain, shifts, a shifted
+ *   column read at an offset, the parameter count, canonical words), a non-canonical random_coeff, dst_log != max_k el_k, and a list
+ *   whose staged blocks do not fit the context's staging ring (the message names the bytes).
+ * bfhip_air_compose_at_point (host only, plain C++): `Components::eval_composition_polynomial_at_point` — for every component
+ *   bfhip_air_eval_at_point under its slice of the coefficients, summed. Refusals as above, in its own name.
+ * Layouts (natural alignment, LP64):
+ *   bfhip_air_component        56 bytes: program 0, kernel 8, log_size 16, log_expand 20, cols_h 24, col_shifts_h 32, params_h 40, n_params 48,
+ *                              reserved 52
+ *   bfhip_air_point_component  40 bytes: program 0, log_size 8, n_mask 12, mask_values_h 16, params_h 24, n_params 32, reserved 36 */
+enum { BFHIP_AIR_COMPOSE_MAX_COMPONENTS = 64 };
+typedef struct bfhip_air_component {
+    const bfhip_air*  program;      /* interpreted when kernel == NULL */
+    bfhip_air_kernel* kernel;       /* optional: the component's compiled kernel (this context's); program may then be NULL */
+    uint32_t log_size, log_expand;  /* as for bfhip_air_eval_domain */
+    const uint32_t* const* cols_h;  /* columns on CanonicCoset(log_size + log_expand).circle_domain(), bit-reversed */
+    const uint32_t* col_shifts_h;   /* NULL = all 0; same rules as bfhip_air_eval_domain */
+    const uint32_t* params_h; uint32_t n_params, reserved;   /* reserved must be 0 */
+} bfhip_air_component;
+int32_t bfhip_air_compose_coeffs(const uint32_t* n_constraints_h, uint32_t n, const uint32_t random_coeff_h[4], uint32_t* coeffs_out /* 4 * T words */);
+int32_t bfhip_air_compose(bfhip_ctx* ctx, const bfhip_air_component* comps, uint32_t n, const uint32_t random_coeff_h[4],
+                          uint32_t dst_log, uint32_t* const dst_d[4]);
+typedef struct bfhip_air_point_component {
+    const bfhip_air* program; uint32_t log_size, n_mask;
+    const uint32_t* mask_values_h; const uint32_t* params_h; uint32_t n_params, reserved;
+} bfhip_air_point_component;
+int32_t bfhip_air_compose_at_point(const bfhip_air_point_component* comps, uint32_t n, const uint32_t point_h[8],
+                                   const uint32_t random_coeff_h[4], uint32_t out_h[4]);
 
 /* ---- Constraint programs asserted on the trace domain: which constraint of ANY AIR is non-zero at which cell ---------------------------------
  * stwo's `assert_constraints` for a program, the generic counterpart of bfhip_check_constraints (which runs one of 13 compiled-in AIRs). A wrong

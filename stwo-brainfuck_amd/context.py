@@ -9,7 +9,7 @@ from ._abi import BfhipError, Owned, _check, _ptr_array, _qm31s, _u32s, abi, str
 from ._abi_gen import (BFHIP_CHANNEL_BLAKE2S as CHANNEL_BLAKE2S, BFHIP_CHANNEL_POSEIDON252 as CHANNEL_POSEIDON252, BFHIP_LOGUP_MASK_CUR_PREV as LOGUP_MASK_CUR_PREV,
                        BFHIP_LOGUP_MASK_PREV_CUR as LOGUP_MASK_PREV_CUR, BFHIP_MERKLE_RFC7693 as MERKLE_RFC7693, BFHIP_MERKLE_STWO_COMPRESS as MERKLE_STWO_COMPRESS,
                        BFHIP_MIX_U64_COMPRESS as MIX_U64_COMPRESS, BFHIP_MIX_U64_HASH as MIX_U64_HASH)
-from .programs import CompiledAir
+from .programs import AirComponent, CompiledAir
 from .reports import (COMPONENT_NAMES, AirCheckReport, CheckReport, MultiplicityReport, MultiplicityResult, PreflightReport, RelationEntry, RelationProgramTable,
                       RelationTable, _relation_result)
 
@@ -401,6 +401,28 @@ class Context(Owned):
         # a CompiledAir (Context.air_compile) runs its own kernel behind the same checks: bfhip_air_kernel_eval_domain
         entry = abi().bfhip_air_kernel_eval_domain if isinstance(program, CompiledAir) else abi().bfhip_air_eval_domain
         _check(entry(self._h, program._h, int(log_size), int(log_expand), cols, shifts, *pars, *coes, _ptr_array(acc_ptrs)))
+
+    def air_compose(self, components, random_coeff, dst_ptrs, dst_log):
+        """bfhip_air_compose: the composition polynomial of ALL components of an AIR — its 4 coefficient columns of 2^dst_log words written
+        to dst_ptrs (overwritten), ready for PcsSession.commit(form 1). A component is (program_or_CompiledAir, log_size, log_expand,
+        col_ptrs, params[, col_shifts]) with the columns on CanonicCoset(log_size + log_expand).circle_domain(); constraint g of all T gets
+        random_coeff^(T - 1 - g) (air_compose_coeffs). dst_log = the largest log_size + log_expand of the list. AirPrograms run in one
+        launch, CompiledAirs in one launch each behind it."""
+        if len(dst_ptrs) != 4:
+            raise ValueError("the destination is 4 coordinate columns")
+        r = [int(w) for w in random_coeff]
+        if len(r) != 4:
+            raise ValueError("random_coeff is 4 words")
+        comps, keep = (AirComponent * max(1, len(components)))(), []
+        for k, comp in enumerate(components):
+            program, log_size, log_expand, col_ptrs, params = comp[:5]
+            cols, shifts = _program_columns(program, col_ptrs, comp[5] if len(comp) > 5 else None, "component %d: " % k)
+            pars, n_params = _qm31s(params, "a parameter")
+            keep += [cols, shifts, pars, program]
+            compiled = isinstance(program, CompiledAir)
+            comps[k] = AirComponent(None if compiled else program._h.value, program._h.value if compiled else None, int(log_size), int(log_expand),
+                                    None if cols is None else ctypes.cast(cols, ctypes.POINTER(ctypes.c_void_p)), shifts, pars, n_params, 0)
+        _check(abi().bfhip_air_compose(self._h, comps, len(components), _u32s(r), int(dst_log), _ptr_array(dst_ptrs)))
 
     def air_compile(self, program):
         """bfhip_air_compile: the AirProgram as its own gfx950 kernel, generated (AirProgram.source) and compiled in-process for this

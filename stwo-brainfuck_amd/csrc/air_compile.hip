@@ -157,6 +157,17 @@ void bf::air_kernels_drop(Ctx& c) {
     c.air_cache = nullptr;
 }
 
+const bfhip_air& bf::air_kernel_program(bfhip_ctx* ctx, bfhip_air_kernel* kernel, const std::string& me) {
+    if (kernel->ctx != ctx || !kernel->mod) throw HipError(me + ": the kernel was compiled by another context (a module belongs to the context that loaded it)");
+    return kernel->prog;
+}
+
+void bf::air_kernel_launch(Ctx& c, bfhip_air_kernel* kernel, const AirLaunch* d_launch, uint32_t n_rows) {
+    void* args[] = {(void*)&d_launch};
+    ProfScope ps(c.stream, AIR_KERNEL_NAME, 0);
+    BF_HIP(hipModuleLaunchKernel(kernel->mod->fn, (n_rows + AIR_KERNEL_LANES - 1) / AIR_KERNEL_LANES, 1, 1, AIR_KERNEL_LANES, 1, 1, 0, c.stream, args, nullptr));
+}
+
 extern "C" {
 
 int32_t bfhip_air_compile(bfhip_ctx* ctx, const bfhip_air* air, bfhip_air_kernel** out) {
@@ -204,15 +215,10 @@ int32_t bfhip_air_kernel_eval_domain(bfhip_ctx* ctx, bfhip_air_kernel* kernel, u
                                      uint32_t* const acc_d[4]) {
     API_CTX(ctx)
     if (!kernel) throw HipError("null argument");
-    if (kernel->ctx != ctx || !kernel->mod) throw HipError("bfhip_air_kernel_eval_domain: the kernel was compiled by another context (a module belongs to the context that loaded it)");
+    const bfhip_air& prog = air_kernel_program(ctx, kernel, "bfhip_air_kernel_eval_domain");
     Ctx& c = ctx->c;
-    const AirLaunch* d_launch = air_eval_stage(c, &kernel->prog, false, log_size, log_expand, cols_h, col_shifts_h, params_h, n_params, coeffs_h, n_coeffs, acc_d);
-    {
-        const u32 n = 1u << (log_size + log_expand);
-        void* args[] = {(void*)&d_launch};
-        ProfScope ps(c.stream, AIR_KERNEL_NAME, 0);
-        BF_HIP(hipModuleLaunchKernel(kernel->mod->fn, (n + AIR_KERNEL_LANES - 1) / AIR_KERNEL_LANES, 1, 1, AIR_KERNEL_LANES, 1, 1, 0, c.stream, args, nullptr));
-    }
+    const AirLaunch* d_launch = air_eval_stage(c, &prog, false, log_size, log_expand, cols_h, col_shifts_h, params_h, n_params, coeffs_h, n_coeffs, acc_d);
+    air_kernel_launch(c, kernel, d_launch, 1u << (log_size + log_expand));
     return 0;
     API_CATCH
 }

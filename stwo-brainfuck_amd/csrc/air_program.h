@@ -74,6 +74,25 @@ const AirLaunch* air_eval_stage(Ctx& c, const bfhip_air* air, bool with_code, ui
                                 const uint32_t* col_shifts_h, const uint32_t* params_h, uint32_t n_params, const uint32_t* coeffs_h, uint32_t n_coeffs,
                                 uint32_t* const acc_d[4]);
 }  // namespace bf
+// air_program.hip: the two pieces of air_eval_stage that bfhip_air_compose (air_compose.hip) applies to every component of its list: the
+// rules about log_size and log_expand (each refusal opens with `me`), and the 2^log_expand inverse denominators of AirLaunch::denom_inv
+namespace bf {
+void air_domain_checks(const Ctx& c, const std::string& me, uint32_t log_size, uint32_t log_expand);
+void air_denominators(uint32_t log_size, uint32_t log_expand, uint32_t denom_inv[8]);
+}  // namespace bf
+struct bfhip_ctx;
+struct bfhip_air_kernel;
+namespace bf {
+// air_program_host.hip (host only): what the composition entries share (include/bfhip.h "Composition"). air_compose_count refuses a list of
+// 0 or more than 64 components; air_compose_coeffs writes r^(T - 1 - g) for every constraint g of the list, 4 words each, after refusing a
+// count outside 1..64 constraints and a non-canonical r. Each refusal opens with `me`.
+void air_compose_count(const std::string& me, uint32_t n);
+void air_compose_coeffs(const std::string& me, const uint32_t* n_constraints_h, uint32_t n, const uint32_t random_coeff_h[4], uint32_t* coeffs_out);
+// air_compile.hip: the program a compiled kernel was made of; refuses, in the caller's name `me`, a kernel that `ctx` did not compile
+const bfhip_air& air_kernel_program(bfhip_ctx* ctx, bfhip_air_kernel* kernel, const std::string& me);
+// air_compile.hip: the kernel's launch over n_rows rows behind a staged AirLaunch (code = 0), on the context's stream
+void air_kernel_launch(Ctx& c, bfhip_air_kernel* kernel, const AirLaunch* d_launch, uint32_t n_rows);
+}  // namespace bf
 // air_codegen.hip (host only): the HIP source of the kernel that evaluates this program on the constraint domain; the same bytes for the same program
 std::string air_generate_source(const bfhip_air& air);
 constexpr uint32_t AIR_KERNEL_LANES = 256;      // workgroup size of a generated kernel (its __launch_bounds__)

@@ -4,60 +4,15 @@
 //
 // One lane per row of CanonicCoset(log_size + log_expand).circle_domain(), one wave per workgroup, on the interpreter core of
 // program_interp.h (scalar loads of the program, scalar dispatch, register files in LDS: see there). This file adds what a row of the blown-up
-// domain is (AirDomainRow) and what C_BASE / C_EXT do (AirDomainSink); the coefficients come through scalar loads like the program.
+// domain is (AirDomainRow) and what C_BASE / C_EXT do (AirDomainSink), both in air_domain.h; the coefficients come through scalar loads like
+// the program.
 #include "api_guard.h"
-#include "program_interp.h"
+#include "air_domain.h"
 #include "host/circle.h"
 #include "../../include/bfhip.h"
 #include <cstddef>
 
 namespace bf {
-
-// Storage index of the row at trace offset `off` from `row` on the 2^log_expand blowup (prev_lde_row of air.hip is off = -1, log_expand = 1):
-// a trace step is 2^(log_expand - 1) steps of the half coset; in circle-domain order the first half moves with the offset, the conjugate
-// half against it (-P + T = -(P - T)), each cyclically.
-__device__ __forceinline__ u32 air_offset_row(u32 row, int off, u32 log_size, u32 log_expand) {
-    const u32 el = log_size + log_expand, half = 1u << (el - 1);
-    const u32 d = bit_rev(row, el);
-    const u32 step = (u32)off * (1u << (log_expand - 1));      // modulo 2^32, of which half is a divisor
-    const u32 pd = d < half ? ((d + step) & (half - 1)) : (((d - half - step) & (half - 1)) + half);
-    return bit_rev(pd, el);
-}
-
-// A row of CanonicCoset(log_size + log_expand).circle_domain(); a column of shift s holds the row's own cell at row >> s
-struct AirDomainRow {
-    static constexpr bool OFFSETS = true;
-    u32 self, log_size, log_expand;
-    __device__ __forceinline__ u32 at0(const bf_u32x4 col) const { return self >> col.z; }
-    __device__ __forceinline__ u32 at(int off) const { return air_offset_row(self, off, log_size, log_expand); }
-};
-
-// C_BASE / C_EXT: sum_j coeff_j * c_j as DomainEval::constraint(Fm) of air.hip keeps it: four 64-bit dot products with lazy reduction for
-// the base-field constraints (four products of canonical values on top of a folded accumulator stay below 2^64), a QM31 sum for the others
-struct AirDomainSink {
-    static constexpr bool HAS_Q = true;
-    const BF_CONSTANT bf_u32x4* coeffs;
-    u64 acc[4] = {0, 0, 0, 0};
-    u32 pending = 0, ci = 0;
-    Q31 ext = q_zero();
-    static constexpr u32 OP = AIR_C_BASE;
-    __device__ __forceinline__ void op(const bf_u32x4 ins, const u32* m, const u32*) {
-        const bf_u32x4 k = coeffs[ci++];
-        const u32 v = m[ins.z * PROGRAM_LANES];
-        if (pending == 4) {      // 4 (p - 1)^2 + 2^34 < 2^64
-#pragma unroll
-            for (int w = 0; w < 4; w++) acc[w] = m_fold(acc[w]);
-            pending = 0;
-        }
-        acc[0] += (u64)k.x * v; acc[1] += (u64)k.y * v; acc[2] += (u64)k.z * v; acc[3] += (u64)k.w * v;
-        pending++;
-    }
-    __device__ __forceinline__ void other(const bf_u32x4 ins, const u32*, const u32* q) {      // AIR_C_EXT: the validator admits nothing else
-        const bf_u32x4 k = coeffs[ci++];
-        ext = q_add(ext, q_mul(q_make(k.x, k.y, k.z, k.w), program_q_ld(q, ins.z * PROGRAM_LANES)));
-    }
-    __device__ __forceinline__ Q31 sum() const { return q_add(q_make(m_canon(acc[0]), m_canon(acc[1]), m_canon(acc[2]), m_canon(acc[3])), ext); }
-};
 
 __global__ void __launch_bounds__(PROGRAM_LANES) k_air_program(const AirLaunch* __restrict__ ap) {
     extern __shared__ u32 s_regs[];
@@ -102,6 +57,21 @@ void bf::ProgramInputs::stage(Ctx& c, u64& cols_d, u64& params_d) const {
     params_d = (u64)c.stage(n_params ? params_h : zero4, n_params ? 4 * (size_t)n_params : 4);
 }
 
+// The rules about one component's domain, in the caller's name `me` (bfhip_air_eval_domain; bfhip_air_compose names the component too)
+void bf::air_domain_checks(const Ctx& c, const std::string& me, uint32_t log_size, uint32_t log_expand) {
+    if (log_expand < 1 || log_expand > 3) throw HipError(me + ": log_expand must be in [1, 3], got " + std::to_string(log_expand));
+    if (log_size < 1 || log_size > 29) throw HipError(me + ": log_size must be at least 1 and log_size + log_expand at most max_log_domain");
+    const u32 el = log_size + log_expand;
+    if (el > c.tw_root_log + 1) throw HipError(me + ": log_size + log_expand = " + std::to_string(el) + " exceeds the context's max_log_domain " + std::to_string(c.tw_root_log + 1));
+}
+
+// 1 / coset_vanishing(CanonicCoset(log_size).coset, domain.at(d)) depends on d mod 2^log_expand only; in bit-reversed storage those are the
+// top bits of the row: entry i = row >> log_size belongs to d = bit_rev(i)
+void bf::air_denominators(uint32_t log_size, uint32_t log_expand, uint32_t denom_inv[8]) {
+    const u32 el = log_size + log_expand;
+    for (u32 i = 0; i < (1u << log_expand); i++) denom_inv[i] = m_inv(coset_vanishing_m(log_size, canonic_domain_at(el, bit_rev(i, log_expand))));
+}
+
 // The checks and the staging of bfhip_air_eval_domain, shared with the compiled kernels' entry point (air_compile.hip): the two answer a bad
 // argument with the same words.
 const AirLaunch* bf::air_eval_stage(Ctx& c, const bfhip_air* air, bool with_code, uint32_t log_size, uint32_t log_expand, const uint32_t* const* cols_h,
@@ -110,10 +80,8 @@ const AirLaunch* bf::air_eval_stage(Ctx& c, const bfhip_air* air, bool with_code
     const std::string me = "bfhip_air_eval_domain";
     if (!air || !coeffs_h || !acc_d || (!cols_h && air->n_cols) || (!params_h && n_params)) throw HipError("null argument");
     if (c.shard.count > 1) throw HipError(me + ": a context in a shard group is not supported (bfhip_ctx_leave_group first)");
-    if (log_expand < 1 || log_expand > 3) throw HipError(me + ": log_expand must be in [1, 3], got " + std::to_string(log_expand));
-    if (log_size < 1 || log_size > 29) throw HipError(me + ": log_size must be at least 1 and log_size + log_expand at most max_log_domain");
+    air_domain_checks(c, me, log_size, log_expand);
     const u32 el = log_size + log_expand;
-    if (el > c.tw_root_log + 1) throw HipError(me + ": log_size + log_expand = " + std::to_string(el) + " exceeds the context's max_log_domain " + std::to_string(c.tw_root_log + 1));
     if (n_coeffs != air->n_constraints) throw HipError(me + ": the program has " + std::to_string(air->n_constraints) + " constraints, got " + std::to_string(n_coeffs) + " coefficients");
     for (u32 i = 0; i < 4 * n_coeffs; i++) if (coeffs_h[i] >= P31) throw HipError(me + ": a coefficient word is not a canonical M31");
     for (int w = 0; w < 4; w++) if (!acc_d[w]) throw HipError(me + ": null accumulator pointer");
@@ -121,9 +89,7 @@ const AirLaunch* bf::air_eval_stage(Ctx& c, const bfhip_air* air, bool with_code
     AirLaunch L{};
     L.n_instr = air->n_instr; L.n_m = air->n_m; L.log_size = log_size; L.log_expand = log_expand;
     for (int w = 0; w < 4; w++) L.acc[w] = (u64)acc_d[w];
-    // 1 / coset_vanishing(CanonicCoset(log_size).coset, domain.at(d)) depends on d mod 2^log_expand only; in bit-reversed storage those are the
-    // top bits of the row: entry i = row >> log_size belongs to d = bit_rev(i)
-    for (u32 i = 0; i < (1u << log_expand); i++) L.denom_inv[i] = m_inv(coset_vanishing_m(log_size, canonic_domain_at(el, bit_rev(i, log_expand))));
+    air_denominators(log_size, log_expand, L.denom_inv);
     c.stage_checkpoint();
     {
         StageBatch sb(c);

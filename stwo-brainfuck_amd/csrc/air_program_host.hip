@@ -6,6 +6,7 @@
 #include "pcs_types.h"
 #include "air_program.h"
 #include "program_validate.h"
+#include "../../include/bfhip.h"
 
 using namespace bf;
 
@@ -51,53 +52,30 @@ void validate(bfhip_air& air, ProgramValidator& v) {
 
 }  // namespace
 
-extern "C" {
-
-int32_t bfhip_air_create(const uint32_t* code, size_t n_words, uint32_t n_cols, uint32_t n_params, bfhip_air** out) {
-    API_TRY
-    if (!code || !out) throw HipError("null argument");
-    ProgramValidator v(FAMILY, n_words, n_cols, n_params);
-    auto* air = new bfhip_air();
-    try {
-        air->code.assign(code, code + n_words);
-        air->n_instr = (u32)(n_words / 4); air->n_cols = n_cols; air->n_params = n_params;
-        validate(*air, v);
-    } catch (...) { delete air; throw; }
-    *out = air;
-    return 0;
-    API_CATCH
+// The list rules and the coefficients that bfhip_air_compose (air_compose.hip) shares with the host-only entries below; `me` names the caller
+void bf::air_compose_count(const std::string& me, uint32_t n) {
+    if (n < 1 || n > BFHIP_AIR_COMPOSE_MAX_COMPONENTS) throw HipError(me + ": 1 to BFHIP_AIR_COMPOSE_MAX_COMPONENTS (64) components, got " + std::to_string(n));
 }
-int32_t bfhip_air_destroy(bfhip_air* air) { API_TRY delete air; return 0; API_CATCH }
-
-int32_t bfhip_air_shape(const bfhip_air* air, uint32_t out[8]) {
-    API_TRY
-    if (!air || !out) throw HipError("null argument");
-    const u32 v[8] = {air->n_cols, air->n_params, air->n_constraints, air->n_instr, air->n_m, air->n_q, (u32)air->min_off, (u32)air->max_off};
-    memcpy(out, v, sizeof v);
-    return 0;
-    API_CATCH
+void bf::air_compose_coeffs(const std::string& me, const uint32_t* n_constraints_h, uint32_t n, const uint32_t random_coeff_h[4], uint32_t* coeffs_out) {
+    air_compose_count(me, n);
+    size_t total = 0;
+    for (u32 k = 0; k < n; k++) {
+        if (n_constraints_h[k] < 1 || n_constraints_h[k] > AIR_MAX_CONSTRAINTS)
+            throw HipError(me + ": component " + std::to_string(k) + ": a component has 1 to BFHIP_AIR_MAX_CONSTRAINTS (64) constraints, got " + std::to_string(n_constraints_h[k]));
+        total += n_constraints_h[k];
+    }
+    const Q31 r = canonical_q31(random_coeff_h, (me + ": random_coeff").c_str());
+    Q31 cur = q_one();
+    for (size_t g = total; g-- > 0;) { q31_words(cur, coeffs_out + 4 * g); cur = q_mul(cur, r); }      // constraint g gets r^(T - 1 - g)
 }
 
-int32_t bfhip_air_mask(const bfhip_air* air, uint32_t* cols_out, int32_t* offs_out, uint32_t cap, uint32_t* n) {
-    API_TRY
-    if (!air || !n) throw HipError("null argument");
-    *n = (u32)air->mask_cols.size();
-    if (!cols_out && !offs_out && cap == 0) return 0;      // size query
-    if (cap < *n) { bfhip_set_error("bfhip_air_mask: capacity"); return -2; }
-    if (!cols_out || !offs_out) throw HipError("null argument");
-    for (u32 i = 0; i < *n; i++) { cols_out[i] = air->mask_cols[i]; offs_out[i] = air->mask_offs[i]; }
-    return 0;
-    API_CATCH
-}
+namespace {
 
 // stwo's PointEvaluator over the program: both register files hold QM31 values, a mask entry is the column's sampled value at
 // point + off * CanonicCoset(log_size).step(), a Q_COL combines its four coordinates' samples (SecureField::from_partial_evals, what
 // `combine_ef` does at a point), and the weighted sum is divided by coset_vanishing(CanonicCoset(log_size).coset, point).
-int32_t bfhip_air_eval_at_point(const bfhip_air* air, uint32_t log_size, const uint32_t point_h[8], const uint32_t* mask_values_h, uint32_t n_mask,
-                                const uint32_t* params_h, uint32_t n_params, const uint32_t* coeffs_h, uint32_t n_coeffs, uint32_t out_h[4]) {
-    API_TRY
-    const char* me = "bfhip_air_eval_at_point";
-    if (!air || !point_h || !coeffs_h || !out_h || (!mask_values_h && n_mask) || (!params_h && n_params)) throw HipError("null argument");
+Q31 eval_at_point(const char* me, const bfhip_air* air, uint32_t log_size, const uint32_t point_h[8], const uint32_t* mask_values_h, uint32_t n_mask,
+                  const uint32_t* params_h, uint32_t n_params, const uint32_t* coeffs_h, uint32_t n_coeffs) {
     if (log_size < 1 || log_size > 30) throw HipError(std::string(me) + ": log_size must be in [1, 30]");
     if (n_mask != air->mask_cols.size()) throw HipError(std::string(me) + ": the program's mask has " + std::to_string(air->mask_cols.size()) + " entries, got " + std::to_string(n_mask) + " values");
     if (n_params != air->n_params) throw HipError(std::string(me) + ": the program takes " + std::to_string(air->n_params) + " parameters, got " + std::to_string(n_params));
@@ -139,7 +117,94 @@ int32_t bfhip_air_eval_at_point(const bfhip_air* air, uint32_t log_size, const u
             default: acc = q_add(acc, q_mul(coeffs[ci++], q[a])); break;      // AIR_C_EXT: the validator admits nothing else
         }
     }
-    q31_words(q_mul(acc, q_inv(denom)), out_h);
+    return q_mul(acc, q_inv(denom));
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t bfhip_air_create(const uint32_t* code, size_t n_words, uint32_t n_cols, uint32_t n_params, bfhip_air** out) {
+    API_TRY
+    if (!code || !out) throw HipError("null argument");
+    ProgramValidator v(FAMILY, n_words, n_cols, n_params);
+    auto* air = new bfhip_air();
+    try {
+        air->code.assign(code, code + n_words);
+        air->n_instr = (u32)(n_words / 4); air->n_cols = n_cols; air->n_params = n_params;
+        validate(*air, v);
+    } catch (...) { delete air; throw; }
+    *out = air;
+    return 0;
+    API_CATCH
+}
+int32_t bfhip_air_destroy(bfhip_air* air) { API_TRY delete air; return 0; API_CATCH }
+
+int32_t bfhip_air_shape(const bfhip_air* air, uint32_t out[8]) {
+    API_TRY
+    if (!air || !out) throw HipError("null argument");
+    const u32 v[8] = {air->n_cols, air->n_params, air->n_constraints, air->n_instr, air->n_m, air->n_q, (u32)air->min_off, (u32)air->max_off};
+    memcpy(out, v, sizeof v);
+    return 0;
+    API_CATCH
+}
+
+int32_t bfhip_air_mask(const bfhip_air* air, uint32_t* cols_out, int32_t* offs_out, uint32_t cap, uint32_t* n) {
+    API_TRY
+    if (!air || !n) throw HipError("null argument");
+    *n = (u32)air->mask_cols.size();
+    if (!cols_out && !offs_out && cap == 0) return 0;      // size query
+    if (cap < *n) { bfhip_set_error("bfhip_air_mask: capacity"); return -2; }
+    if (!cols_out || !offs_out) throw HipError("null argument");
+    for (u32 i = 0; i < *n; i++) { cols_out[i] = air->mask_cols[i]; offs_out[i] = air->mask_offs[i]; }
+    return 0;
+    API_CATCH
+}
+
+int32_t bfhip_air_eval_at_point(const bfhip_air* air, uint32_t log_size, const uint32_t point_h[8], const uint32_t* mask_values_h, uint32_t n_mask,
+                                const uint32_t* params_h, uint32_t n_params, const uint32_t* coeffs_h, uint32_t n_coeffs, uint32_t out_h[4]) {
+    API_TRY
+    if (!air || !point_h || !coeffs_h || !out_h || (!mask_values_h && n_mask) || (!params_h && n_params)) throw HipError("null argument");
+    q31_words(eval_at_point("bfhip_air_eval_at_point", air, log_size, point_h, mask_values_h, n_mask, params_h, n_params, coeffs_h, n_coeffs), out_h);
+    return 0;
+    API_CATCH
+}
+
+// The coefficient of every constraint of an AIR (include/bfhip.h "Composition"): global index g gets r^(T - 1 - g)
+int32_t bfhip_air_compose_coeffs(const uint32_t* n_constraints_h, uint32_t n, const uint32_t random_coeff_h[4], uint32_t* coeffs_out) {
+    API_TRY
+    if (!n_constraints_h || !random_coeff_h || !coeffs_out) throw HipError("null argument");
+    air_compose_coeffs("bfhip_air_compose_coeffs", n_constraints_h, n, random_coeff_h, coeffs_out);
+    return 0;
+    API_CATCH
+}
+
+// Components::eval_composition_polynomial_at_point: every component's bfhip_air_eval_at_point under its slice of the coefficients, summed
+int32_t bfhip_air_compose_at_point(const bfhip_air_point_component* comps, uint32_t n, const uint32_t point_h[8], const uint32_t random_coeff_h[4],
+                                   uint32_t out_h[4]) {
+    API_TRY
+    const std::string me = "bfhip_air_compose_at_point";
+    if (!comps || !point_h || !random_coeff_h || !out_h) throw HipError("null argument");
+    air_compose_count(me, n);
+    std::vector<u32> counts(n);
+    for (u32 k = 0; k < n; k++) {
+        const std::string mk = me + ": component " + std::to_string(k);
+        const bfhip_air_point_component& p = comps[k];
+        if (!p.program || (!p.mask_values_h && p.n_mask) || (!p.params_h && p.n_params)) throw HipError(mk + ": null argument");
+        if (p.reserved != 0) throw HipError(mk + ": reserved must be 0");
+        counts[k] = p.program->n_constraints;
+    }
+    std::vector<u32> coeffs(4 * (size_t)AIR_MAX_CONSTRAINTS * n);
+    air_compose_coeffs(me, counts.data(), n, random_coeff_h, coeffs.data());
+    Q31 sum = q_zero();
+    size_t first = 0;
+    for (u32 k = 0; k < n; k++) {
+        const bfhip_air_point_component& p = comps[k];
+        const std::string mk = me + ": component " + std::to_string(k);
+        sum = q_add(sum, eval_at_point(mk.c_str(), p.program, p.log_size, point_h, p.mask_values_h, p.n_mask, p.params_h, p.n_params, coeffs.data() + 4 * first, counts[k]));
+        first += counts[k];
+    }
+    q31_words(sum, out_h);
     return 0;
     API_CATCH
 }

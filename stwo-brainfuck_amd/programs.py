@@ -4,7 +4,7 @@ import ctypes
 
 import numpy as np
 
-from ._abi import Owned, P, _check, _qm31s, _u32s, abi
+from ._abi import Owned, P, _check, _qm31s, _u32s, abi, struct_fields
 from ._abi_gen import (BFHIP_AIR_C_BASE as AIR_C_BASE, BFHIP_AIR_C_EXT as AIR_C_EXT, BFHIP_AIR_M_ADD as AIR_M_ADD, BFHIP_AIR_M_COL as AIR_M_COL,
                        BFHIP_AIR_M_CONST as AIR_M_CONST, BFHIP_AIR_M_MUL as AIR_M_MUL, BFHIP_AIR_M_NEG as AIR_M_NEG, BFHIP_AIR_M_SUB as AIR_M_SUB,
                        BFHIP_AIR_MAX_COLUMNS as AIR_MAX_COLUMNS, BFHIP_AIR_MAX_CONSTRAINTS as AIR_MAX_CONSTRAINTS, BFHIP_AIR_MAX_INSTRUCTIONS as AIR_MAX_INSTRUCTIONS,
@@ -91,6 +91,47 @@ class CompiledAir(Owned):
         d["sgprs"] = None if d["sgprs"] == 0xFFFFFFFF else d["sgprs"]
         d["from_cache"] = bool(d["from_cache"])
         return d
+
+
+class AirComponent(ctypes.Structure):
+    """include/bfhip.h `bfhip_air_component`: one component of Context.air_compose's list."""
+    _fields_ = struct_fields("bfhip_air_component")
+
+
+class AirPointComponent(ctypes.Structure):
+    """include/bfhip.h `bfhip_air_point_component`: one component of air_compose_at_point's list."""
+    _fields_ = struct_fields("bfhip_air_point_component")
+
+
+def air_compose_coeffs(n_constraints, random_coeff):
+    """bfhip_air_compose_coeffs (host only): the coefficient of every constraint of an AIR whose components have n_constraints[k]
+    constraints, as lists of 4 words in global order — constraint g of T gets random_coeff^(T - 1 - g). What Context.air_compose and
+    air_compose_at_point use; slice it by component for air_eval_domain / eval_at_point."""
+    counts = [int(c) for c in n_constraints]
+    out = (ctypes.c_uint32 * max(4, 4 * sum(c for c in counts if 0 < c <= AIR_MAX_CONSTRAINTS)))()
+    _check(abi().bfhip_air_compose_coeffs(_u32s(counts or [0]), len(counts), _u32s(_qm31(random_coeff, "random_coeff")), out))
+    return [[int(out[4 * g + w]) for w in range(4)] for g in range(sum(counts))]
+
+
+def air_compose_at_point(components, point8, random_coeff):
+    """bfhip_air_compose_at_point (host only): the composition polynomial of all components at a point, from the sampled mask values —
+    every component's eval_at_point under its slice of air_compose_coeffs, summed. components: (AirProgram, log_size, mask_values,
+    params) each, mask values and params as QM31 values of 4 words."""
+    comps, keep = (AirPointComponent * max(1, len(components)))(), []
+    for k, (program, log_size, mask_values, params) in enumerate(components):
+        (mask, n_mask), (pars, n_params) = _qm31s(mask_values, "a mask value"), _qm31s(params, "a parameter")
+        keep += [mask, pars, program]
+        comps[k] = AirPointComponent(program._h.value, int(log_size), n_mask, mask, pars, n_params, 0)
+    out = (ctypes.c_uint32 * 4)()
+    _check(abi().bfhip_air_compose_at_point(comps, len(components), _u32s(point8), _u32s(_qm31(random_coeff, "random_coeff")), out))
+    return [int(v) for v in out]
+
+
+def _qm31(value, what):
+    value = [int(w) for w in value]
+    if len(value) != 4:
+        raise ValueError(what + " is 4 words")
+    return value
 
 
 class LogupProgram(_Program):
