@@ -624,6 +624,28 @@ pub fn air_compose_at_point(comps: &[AirPointComponent], point: &Point, random_c
     Ok(out)
 }
 
+/// One component of `logup_program_generate_batch`: `cols` / `shifts` / `params` / `out` as for `LogupProgram::generate`.
+pub struct LogupComponent<'a> { pub program: &'a LogupProgram, pub log_size: u32, pub cols: &'a [*const u32], pub shifts: &'a [u32], pub params: &'a [Felt], pub out: &'a [*mut u32] }
+
+/// `bfhip_logup_program_generate_batch`: the interaction trace of ALL components in one call (one allocation, the row stage in one launch for
+/// the components below 2^16 cells and one per larger one, three scan launches, one read-back). Returns every component's claimed sum, word
+/// for word `LogupProgram::generate`'s, and their sum. No output column may overlap another column of the list; works while a session is
+/// open. A zero denominator is an `Err` that names the lowest such component, the fraction and the cell.
+pub fn logup_program_generate_batch(ctx: &Context, comps: &[LogupComponent]) -> Result<(Vec<Felt>, Felt), String> {
+    let mut raw = Vec::with_capacity(comps.len());
+    for c in comps {
+        if !c.shifts.is_empty() && c.shifts.len() != c.cols.len() { return Err("one shift per column".into()); }
+        if c.out.len() != 4 * c.program.shape()?.n_logup_cols as usize { return Err("4 coordinate columns per logUp column".into()); }
+        raw.push(sys::BfhipLogupComponent { program: c.program.0 as *const sys::BfhipLogup, log_size: c.log_size, n_params: c.params.len() as u32, cols_h: c.cols.as_ptr(),
+                                            col_shifts_h: if c.shifts.is_empty() { std::ptr::null() } else { c.shifts.as_ptr() },
+                                            params_h: c.params.as_ptr() as *const u32, out_cols_h: c.out.as_ptr(), reserved: 0 });
+    }
+    let (mut claimed, mut total) = (vec![[0u32; 4]; comps.len().max(1)], [0u32; 4]);
+    check(unsafe { sys::bfhip_logup_program_generate_batch(ctx.0, raw.as_ptr(), raw.len() as u32, claimed.as_mut_ptr() as *mut u32, total.as_mut_ptr()) })?;
+    claimed.truncate(comps.len());
+    Ok((claimed, total))
+}
+
 // ---- fraction programs (`include/bfhip.h` "Fraction programs"): the logUp interaction trace of ANY AIR ---------------------------------------
 // What a component's `interaction_trace_evaluation` hands to `LogupTraceGenerator::{new_col, write_frac, finalize_col, finalize_last}`, recorded
 // once as bytecode: a constraint program's opcodes without constraints, plus `sys::BFHIP_LOGUP_FRAC` {-, a, b} (add q[a] / q[b] to the open

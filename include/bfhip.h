@@ -947,6 +947,51 @@ int32_t bfhip_logup_shape(const bfhip_logup* lp, uint32_t out[8]);
 int32_t bfhip_logup_program_generate(bfhip_ctx* ctx, const bfhip_logup* lp, uint32_t log_size, const uint32_t* const* cols_h, const uint32_t* col_shifts_h,
                                      const uint32_t* params_h, uint32_t n_params, uint32_t* const* out_cols_h, uint32_t claimed_sum_h[4]);
 
+/* ---- Fraction programs, batched: the logUp interaction trace of ALL components of an AIR, in one call ---------------------------------------
+ * The calls prove makes to every component's `interaction_trace_evaluation` (mod.rs:596-687) for an AIR given as fraction programs: what a
+ * caller of bfhip_logup_program_generate otherwise does component by component, each call with its own allocation, staging, four launches,
+ * blocking read-back and free. No channel, no session, no protocol: the caller mixes the claimed sums and commits the columns.
+ *
+ * Semantics. For every component k the output columns and claimed_sums_h[4 k .. 4 k + 3] are exactly what bfhip_logup_program_generate
+ *   produces for that component alone, word for word (the field arithmetic is exact). total_h, when not NULL, receives the sum of the n
+ *   claimed sums: what `lookup_sum_valid` tests against zero.
+ * Launches. Row stage: one gfx950 kernel in which a wave owns 64 consecutive cells of one component, which it finds in a table; one
+ *   launch for all components, except that a component of 2^16 cells and more gets a launch of its own when the register files of the
+ *   list's largest program would lower its occupancy. Scan stage: three launches for the whole list (tiles, tile
+ *   totals, last column).
+ * Cost. One hipMalloc, of at most the sum over the list of bfhip_logup_program_generate's stated bound
+ *       24 * 2^log_size + 2^log_size / 128 + 64 bytes,
+ *   one read-back of 32 * n bytes, one hipFree. Nothing is taken from the arena: the call works while a commitment-scheme session is open
+ *   and bfhip_ctx_memory out[3] does not move. Programs, descriptors, parameters and the lookup tables of the launches go through the
+ *   context's staging ring; a program that appears several times in the list is staged once. A failed allocation is -1 with
+ *   "bfhip_logup_program_generate_batch: cannot allocate <n> bytes of scratch".
+ * Zero denominators. Each component keeps its own record. The call is -1 with
+ *   "bfhip_logup_program_generate_batch: component <k>: fraction <f> has a zero denominator at cell <c>", <k> the lowest component index that
+ *   has one, <f> and <c> as for bfhip_logup_program_generate. The outputs (claimed_sums_h and total_h too) are then unspecified, nothing
+ *   faults and the context stays usable.
+ * Refusals: -1 with "bfhip_logup_program_generate_batch: component <k>: <rule>", or "bfhip_logup_program_generate_batch: <rule>" for a rule
+ *   about the list; nothing has been enqueued and the context stays usable. n outside 1..64, null pointers (comps, claimed_sums_h; a
+ *   component's program, out_cols_h, cols_h where the program has columns, params_h where n_params != 0), reserved != 0, every rule of
+ *   bfhip_logup_program_generate about one component in the same words (log_size range, shifts, the parameter count, canonical words, a null
+ *   column or output column pointer), a context in a shard group, a list of more than 2^31 cells in all (the message names the count), a
+ *   list whose staged blocks do not fit the context's staging ring (the message names the bytes), and an output column whose byte range — 4 * 2^log_size bytes; an input column of shift s has
+ *   4 * 2^(log_size - s) — shares a byte with an input column or with another output column anywhere in the list: the components run side
+ *   by side. The message names the two components. Input columns may be shared.
+ * Layout (natural alignment, LP64):
+ *   bfhip_logup_component  56 bytes: program 0, log_size 8, n_params 12, cols_h 16, col_shifts_h 24, params_h 32, out_cols_h 40, reserved 48 */
+enum { BFHIP_LOGUP_BATCH_MAX_COMPONENTS = 64 };
+typedef struct bfhip_logup_component {
+    const bfhip_logup* program;
+    uint32_t log_size, n_params;    /* as for bfhip_logup_program_generate */
+    const uint32_t* const* cols_h;  /* columns on CanonicCoset(log_size).circle_domain(), bit-reversed */
+    const uint32_t* col_shifts_h;   /* NULL = all 0; same rules as bfhip_logup_program_generate */
+    const uint32_t* params_h;
+    uint32_t* const* out_cols_h;    /* 4 * n_logup_columns device pointers, every one a full-size coordinate column */
+    uint64_t reserved;              /* must be 0 */
+} bfhip_logup_component;
+int32_t bfhip_logup_program_generate_batch(bfhip_ctx* ctx, const bfhip_logup_component* comps, uint32_t n, uint32_t* claimed_sums_h /* 4 * n words */,
+                                           uint32_t total_h[4] /* may be NULL */);
+
 /* ---- Relation programs: the lookup tuples of ANY AIR that do not cancel ------------------------------------------------------------------------
  * bfhip_relation_summary / bfhip_trace_relations know the three Brainfuck relations and the 13 table layouts. An AIR proved through bfhip_pcs_* +
  * bfhip_air_* + bfhip_logup_* whose lookups do not balance learns only that its claimed sums do not add up to zero; a

@@ -9,7 +9,7 @@ from ._abi import BfhipError, Owned, _check, _ptr_array, _qm31s, _u32s, abi, str
 from ._abi_gen import (BFHIP_CHANNEL_BLAKE2S as CHANNEL_BLAKE2S, BFHIP_CHANNEL_POSEIDON252 as CHANNEL_POSEIDON252, BFHIP_LOGUP_MASK_CUR_PREV as LOGUP_MASK_CUR_PREV,
                        BFHIP_LOGUP_MASK_PREV_CUR as LOGUP_MASK_PREV_CUR, BFHIP_MERKLE_RFC7693 as MERKLE_RFC7693, BFHIP_MERKLE_STWO_COMPRESS as MERKLE_STWO_COMPRESS,
                        BFHIP_MIX_U64_COMPRESS as MIX_U64_COMPRESS, BFHIP_MIX_U64_HASH as MIX_U64_HASH)
-from .programs import AirComponent, CompiledAir
+from .programs import AirComponent, CompiledAir, LogupComponent
 from .reports import (COMPONENT_NAMES, AirCheckReport, CheckReport, MultiplicityReport, MultiplicityResult, PreflightReport, RelationEntry, RelationProgramTable,
                       RelationTable, _relation_result)
 
@@ -451,6 +451,27 @@ class Context(Owned):
         claimed = (ctypes.c_uint32 * 4)()
         _check(abi().bfhip_logup_program_generate(self._h, program._h, int(log_size), cols, shifts, *pars, _ptr_array(out_col_ptrs), claimed))
         return list(claimed)
+
+    def logup_program_generate_batch(self, components):
+        """bfhip_logup_program_generate_batch: the logUp interaction trace of ALL components of an AIR in one call — one allocation, one
+        row-stage launch for the components below 2^16 cells and one per larger one, three scan launches, one read-back. A component is
+        (LogupProgram, log_size, col_ptrs, params, out_col_ptrs[, col_shifts]), each as for logup_program_generate; no output column may
+        overlap another column of the list. Returns (claimed_sums, total): one claimed sum (4 u32) per component, word for word
+        logup_program_generate's, and their QM31 sum. A zero denominator raises BfhipError naming the lowest such component, fraction, cell."""
+        comps, keep = (LogupComponent * max(1, len(components)))(), []
+        for k, comp in enumerate(components):
+            program, log_size, col_ptrs, params, out_col_ptrs = comp[:5]
+            cols, shifts = _program_columns(program, col_ptrs, comp[5] if len(comp) > 5 else None, "component %d: " % k)
+            pars, n_params = _qm31s(params, "a parameter")
+            if len(out_col_ptrs) != 4 * program.shape["n_logup_cols"]:
+                raise ValueError("component %d: 4 coordinate columns per logUp column" % k)
+            outs = _ptr_array(out_col_ptrs)
+            keep += [cols, shifts, pars, outs, program]
+            comps[k] = LogupComponent(program._h.value, int(log_size), n_params, None if cols is None else ctypes.cast(cols, ctypes.POINTER(ctypes.c_void_p)),
+                                      shifts, pars, ctypes.cast(outs, ctypes.POINTER(ctypes.c_void_p)), 0)
+        claimed, total = (ctypes.c_uint32 * (4 * max(1, len(components))))(), (ctypes.c_uint32 * 4)()
+        _check(abi().bfhip_logup_program_generate_batch(self._h, comps, len(components), claimed, total))
+        return [[int(claimed[4 * k + w]) for w in range(4)] for k in range(len(components))], list(total)
 
     def check_constraints(self, component, log_size, main_row_ptrs, logup_col_ptrs, lookup24, claimed4):
         """bfhip_check_constraints: one component's AIR asserted on its trace domain (stwo's assert_constraints). main_row_ptrs: row-granular

@@ -11,7 +11,8 @@ from ._abi_gen import (BFHIP_AIR_C_BASE as AIR_C_BASE, BFHIP_AIR_C_EXT as AIR_C_
                        BFHIP_AIR_MAX_M_REGS as AIR_MAX_M_REGS, BFHIP_AIR_MAX_OFFSET as AIR_MAX_OFFSET, BFHIP_AIR_MAX_PARAMS as AIR_MAX_PARAMS,
                        BFHIP_AIR_MAX_Q_REGS as AIR_MAX_Q_REGS, BFHIP_AIR_Q_ADD as AIR_Q_ADD, BFHIP_AIR_Q_COL as AIR_Q_COL, BFHIP_AIR_Q_FROM_M as AIR_Q_FROM_M,
                        BFHIP_AIR_Q_MUL as AIR_Q_MUL, BFHIP_AIR_Q_MULM as AIR_Q_MULM, BFHIP_AIR_Q_PARAM as AIR_Q_PARAM, BFHIP_AIR_Q_SUB as AIR_Q_SUB,
-                       BFHIP_LOGUP_END_COL as LOGUP_END_COL, BFHIP_LOGUP_FRAC as LOGUP_FRAC, BFHIP_LOGUP_MAX_COLUMNS as LOGUP_MAX_COLUMNS,
+                       BFHIP_LOGUP_BATCH_MAX_COMPONENTS as LOGUP_BATCH_MAX_COMPONENTS, BFHIP_LOGUP_END_COL as LOGUP_END_COL, BFHIP_LOGUP_FRAC as LOGUP_FRAC,
+                       BFHIP_LOGUP_MAX_COLUMNS as LOGUP_MAX_COLUMNS,
                        BFHIP_LOGUP_MAX_FRACTIONS as LOGUP_MAX_FRACTIONS, BFHIP_REL_ENTRY as REL_ENTRY, BFHIP_REL_WORD as REL_WORD,
                        BFHIP_RELATION_PROGRAM_MAX_ENTRIES as RELATION_PROGRAM_MAX_ENTRIES, BFHIP_RELATION_PROGRAM_MAX_RELATIONS as RELATION_PROGRAM_MAX_RELATIONS,
                        BFHIP_RELATION_PROGRAM_MAX_WORDS as RELATION_PROGRAM_MAX_WORDS)
@@ -143,6 +144,11 @@ class LogupProgram(_Program):
     def __init__(self, code, n_cols, n_params):
         out = self._create(code, lambda words, n, h: abi().bfhip_logup_create(words, n, int(n_cols), int(n_params), h), abi().bfhip_logup_shape)
         self.shape = {"n_cols": out[0], "n_params": out[1], "n_logup_cols": out[2], "n_fractions": out[3], "n_instr": out[4], "m_regs": out[5], "q_regs": out[6]}
+
+
+class LogupComponent(ctypes.Structure):
+    """include/bfhip.h `bfhip_logup_component`: one component of Context.logup_program_generate_batch's list."""
+    _fields_ = struct_fields("bfhip_logup_component")
 
 
 class RelationProgram(_Program):
