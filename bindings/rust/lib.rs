@@ -646,6 +646,95 @@ pub fn logup_program_generate_batch(ctx: &Context, comps: &[LogupComponent]) -> 
     Ok((claimed, total))
 }
 
+// ---- the protocol driver (`include/bfhip.h` "Proving an AIR given as programs") ----------------------------------------------------------------
+// `prover::prove` / `verify` for an AIR given as a statement: trees, relations, components with their column bindings and parameter rules.
+// `air_prove` orders the session, the mixes and draws, the batched interaction trace, `air_compose`, the mask and `prove_values`;
+// `air_verify` replays it on the host. The statement holds no device pointers and is shared by both.
+
+/// A caller tree of an `AirStatement`: trace-domain log sizes, form (0 = evaluations, 1 = coefficients) and the words mixed in front of its commit.
+pub struct AirStatementTree { pub log_sizes: Vec<u32>, pub form: u32, pub mix_u64: Vec<u64> }
+
+/// `columns[c]` = (tree, column) for column c of `program`; tree `sys::BFHIP_AIR_TREE_INTERACTION` = the component's own j-th interaction
+/// coordinate column. `fraction_columns` likewise for `fractions`. `params`: one rule per parameter of `program` (`AirStatement::z` ...).
+pub struct AirStatementComponent<'a> {
+    pub program: &'a AirProgram, pub fractions: Option<&'a LogupProgram>, pub log_size: u32, pub log_expand: u32,
+    pub columns: Vec<(u32, u32)>, pub fraction_columns: Vec<(u32, u32)>, pub params: Vec<sys::BfhipAirParamRule>,
+}
+
+/// `bfhip_air_statement`, owned: build it with `tree` and `component`, pass it to `air_prove` and `air_verify`.
+pub struct AirStatement<'a> { pub n_relations: u32, pub trees: Vec<AirStatementTree>, pub components: Vec<AirStatementComponent<'a>> }
+
+// what a `sys::BfhipAirStatement` points into, alive for one call
+struct RawStatement { _cols: Vec<[Vec<u32>; 4]>, _trees: Vec<sys::BfhipAirStatementTree>, _comps: Vec<sys::BfhipAirStatementComponent>, st: sys::BfhipAirStatement }
+
+impl<'a> AirStatement<'a> {
+    pub fn new(n_relations: u32) -> Self { AirStatement { n_relations, trees: Vec::new(), components: Vec::new() } }
+    pub fn const_param(value: Felt) -> sys::BfhipAirParamRule { sys::BfhipAirParamRule { kind: sys::BFHIP_AIR_PARAM_CONST, relation: 0, power: 0, reserved: 0, value } }
+    pub fn z(relation: u32) -> sys::BfhipAirParamRule { sys::BfhipAirParamRule { kind: sys::BFHIP_AIR_PARAM_LOOKUP_Z, relation, power: 0, reserved: 0, value: [0; 4] } }
+    pub fn alpha_pow(relation: u32, power: u32) -> sys::BfhipAirParamRule { sys::BfhipAirParamRule { kind: sys::BFHIP_AIR_PARAM_LOOKUP_ALPHA_POW, relation, power, reserved: 0, value: [0; 4] } }
+    pub fn claimed_sum() -> sys::BfhipAirParamRule { sys::BfhipAirParamRule { kind: sys::BFHIP_AIR_PARAM_CLAIMED_SUM, relation: 0, power: 0, reserved: 0, value: [0; 4] } }
+    /// A caller tree; returns its index.
+    pub fn tree(&mut self, log_sizes: &[u32], form: u32, mix_u64: &[u64]) -> u32 {
+        self.trees.push(AirStatementTree { log_sizes: log_sizes.to_vec(), form, mix_u64: mix_u64.to_vec() });
+        self.trees.len() as u32 - 1
+    }
+    /// A component; returns its index.
+    pub fn component(&mut self, component: AirStatementComponent<'a>) -> u32 {
+        self.components.push(component);
+        self.components.len() as u32 - 1
+    }
+    fn raw(&self) -> RawStatement {
+        let cols: Vec<[Vec<u32>; 4]> = self.components.iter().map(|c| [c.columns.iter().map(|p| p.0).collect(), c.columns.iter().map(|p| p.1).collect(),
+                                                                       c.fraction_columns.iter().map(|p| p.0).collect(), c.fraction_columns.iter().map(|p| p.1).collect()]).collect();
+        let trees: Vec<sys::BfhipAirStatementTree> = self.trees.iter().map(|t| sys::BfhipAirStatementTree {
+            n_cols: t.log_sizes.len() as u32, form: t.form, log_sizes_h: t.log_sizes.as_ptr(), mix_u64_h: t.mix_u64.as_ptr(), n_mix: t.mix_u64.len() as u32, reserved: 0 }).collect();
+        let comps: Vec<sys::BfhipAirStatementComponent> = self.components.iter().zip(cols.iter()).map(|(c, a)| sys::BfhipAirStatementComponent {
+            program: c.program.0 as *const sys::BfhipAir, fractions: c.fractions.map_or(std::ptr::null(), |f| f.0 as *const sys::BfhipLogup), log_size: c.log_size,
+            log_expand: c.log_expand, col_trees_h: a[0].as_ptr(), col_columns_h: a[1].as_ptr(), frac_trees_h: a[2].as_ptr(), frac_columns_h: a[3].as_ptr(),
+            params_h: c.params.as_ptr(), n_params: c.params.len() as u32, reserved: 0 }).collect();
+        let st = sys::BfhipAirStatement { trees: trees.as_ptr(), components: comps.as_ptr(), n_trees: trees.len() as u32, n_relations: self.n_relations,
+                                          n_components: comps.len() as u32, reserved: 0 };
+        RawStatement { _cols: cols, _trees: trees, _comps: comps, st }      // moving a Vec does not move its heap block: the pointers hold
+    }
+}
+
+/// `bfhip_air_prove`: the whole proof of the statement's AIR. `tree_cols[t][c]` = device column c of caller tree t (full size); `kernels`:
+/// empty, or per component `None` / the `AirKernel` this context compiled of its program; `check`: `BFHIP_AIR_PROVE_CHECK`. Returns the bytes
+/// `{"claimed_sums": [...], "proof": <CommitmentSchemeProof>}` that `air_verify` takes. No session is left open, whatever the outcome.
+pub fn air_prove(ctx: &Context, statement: &AirStatement, tree_cols: &[&[*const u32]], kernels: &[Option<&AirKernel>], channel: &mut Channel, check_trace: bool) -> Result<Vec<u8>, String> {
+    if tree_cols.len() != statement.trees.len() || tree_cols.iter().zip(statement.trees.iter()).any(|(c, t)| c.len() != t.log_sizes.len()) {
+        return Err("one device column per column of every caller tree".into());
+    }
+    if !kernels.is_empty() && kernels.len() != statement.components.len() { return Err("one kernel (or None) per component".into()); }
+    let raw = statement.raw();
+    let trees: Vec<*const *const u32> = tree_cols.iter().map(|c| c.as_ptr()).collect();
+    let ks: Vec<*mut sys::BfhipAirKernel> = kernels.iter().map(|k| k.map_or(std::ptr::null_mut(), |k| k.0)).collect();
+    let (mut js, mut len): (*mut c_char, usize) = (std::ptr::null_mut(), 0);
+    check(unsafe {
+        sys::bfhip_air_prove(ctx.0, &raw.st, trees.as_ptr(), if ks.is_empty() { std::ptr::null() } else { ks.as_ptr() }, channel.0,
+                             if check_trace { sys::BFHIP_AIR_PROVE_CHECK } else { 0 }, &mut js, &mut len)
+    })?;
+    let out = unsafe { std::slice::from_raw_parts(js as *const u8, len) }.to_vec();
+    unsafe { sys::bfhip_free_host(js as *mut c_void) };
+    Ok(out)
+}
+
+/// `bfhip_air_verify` (host only): `Ok(Ok(()))` accepted, `Ok(Err(name))` rejected with the `VerificationError` name, `Err` = a statement the
+/// validator refuses or bad arguments. `channel`: a fresh channel carrying what the prover's carried before `air_prove`.
+pub fn air_verify(statement: &AirStatement, conv: Option<&sys::BfhipConventions>, config: Option<&sys::BfhipPcsConfig>, channel: &mut Channel, proof_json: &[u8]) -> Result<Result<(), String>, String> {
+    let raw = statement.raw();
+    let mut err = [0 as c_char; 512];
+    let rc = unsafe {
+        sys::bfhip_air_verify(&raw.st, conv.map_or(std::ptr::null(), |c| c as *const _), config.map_or(std::ptr::null(), |c| c as *const _), channel.0,
+                              proof_json.as_ptr() as *const c_char, proof_json.len(), err.as_mut_ptr(), err.len())
+    };
+    match rc {
+        0 => Ok(Ok(())),
+        1 => Ok(Err(unsafe { CStr::from_ptr(err.as_ptr()) }.to_string_lossy().into_owned())),
+        _ => Err(last_error()),
+    }
+}
+
 // ---- fraction programs (`include/bfhip.h` "Fraction programs"): the logUp interaction trace of ANY AIR ---------------------------------------
 // What a component's `interaction_trace_evaluation` hands to `LogupTraceGenerator::{new_col, write_frac, finalize_col, finalize_last}`, recorded
 // once as bytecode: a constraint program's opcodes without constraints, plus `sys::BFHIP_LOGUP_FRAC` {-, a, b} (add q[a] / q[b] to the open

@@ -669,6 +669,7 @@ int32_t bfhip_brainfuck_composition_at_point(const uint32_t log_sizes_h[13], con
  *   bfhip_trace_check, bfhip_check_constraints, bfhip_relation_summary, bfhip_trace_relations, bfhip_relation_program_summary,
  *   bfhip_relation_program_multiplicities,
  *   bfhip_ctx_set_conventions, bfhip_ctx_set_pcs_config, bfhip_ctx_join_local_group, bfhip_ctx_join_rccl_group, bfhip_ctx_destroy,
+ *   bfhip_air_prove (it opens a session of its own),
  *   and a second bfhip_pcs_create.
  * Everything else keeps working, which is what the caller's constraint sweep needs: bfhip_malloc / bfhip_free / bfhip_upload / bfhip_download /
  * bfhip_memset_zero, bfhip_interpolate, bfhip_evaluate, bfhip_is_first_coeffs, bfhip_is_first_lde, bfhip_eval_at_point, bfhip_logup_generate, bfhip_eval_constraints,
@@ -991,6 +992,127 @@ typedef struct bfhip_logup_component {
 } bfhip_logup_component;
 int32_t bfhip_logup_program_generate_batch(bfhip_ctx* ctx, const bfhip_logup_component* comps, uint32_t n, uint32_t* claimed_sums_h /* 4 * n words */,
                                            uint32_t total_h[4] /* may be NULL */);
+
+/* ---- Proving an AIR given as programs: the protocol driver and its verifier ----------------------------------------------------------------
+ * `prover::prove` / `verify` for an AIR that is not the Brainfuck snapshot: the order of mixes and draws, the interaction tree's column order,
+ * the coefficient draw, the constraint domain when log_blowup_factor != log_expand, the mask points, the per-column sample description, the
+ * out-of-domain sanity check and the same replay on the verifier's side — what a caller of bfhip_pcs_* + bfhip_air_compose +
+ * bfhip_logup_program_generate_batch otherwise writes by hand. No kernel of its own: the device work of a proof is
+ * the session's launches, bfhip_air_compose's (or the compiled kernels') and the batch's, and bfhip_evaluate's where a constraint domain is
+ * not the session's LDE.
+ *
+ * The statement: the AIR as data, shared by prover and verifier. It holds no device pointers.
+ *   Caller trees, in commit order: n_cols columns with trace-domain log_sizes_h, form (0 = evaluations, 1 = coefficients: bfhip_pcs_commit's),
+ *     and n_mix words mix_u64_h that are mixed with bfhip_channel_mix_u64 immediately before that tree's commit (a claim: the Brainfuck
+ *     protocol mixes its 13 log sizes in front of tree 1).
+ *   n_relations: the number of lookup-element draws; draw r is one draw_felts(2) = (z_r, alpha_r).
+ *   Components, in list order: the constraint program, log_size, log_expand in 1..3, an optional fraction program (NULL = none), and
+ *     col_trees_h[c] / col_columns_h[c] for every column c of the constraint program: a caller tree and a column of it, or
+ *       BFHIP_AIR_TREE_INTERACTION and j = the j-th of this component's own 4 * n_logup_columns interaction coordinate columns (logUp
+ *       columns in program order, four coordinates each); only a component with a fraction program may use it;
+ *     frac_trees_h[c] / frac_columns_h[c] for every column c of the fraction program: a caller tree of form 0 and a column of it;
+ *     params_h: one rule per parameter of the constraint program —
+ *       BFHIP_AIR_PARAM_CONST             value[4]
+ *       BFHIP_AIR_PARAM_LOOKUP_Z          z of relation `relation`
+ *       BFHIP_AIR_PARAM_LOOKUP_ALPHA_POW  alpha^power of relation `relation`, power <= 63 = BFHIP_AIR_STATEMENT_MAX_POWER
+ *       BFHIP_AIR_PARAM_CLAIMED_SUM       this component's own claimed sum (needs a fraction program)
+ *     The fraction program's parameters are the first n_params(fractions) rules of the same table; none of them may be CLAIMED_SUM.
+ *
+ * bfhip_air_prove. tree_cols_h[t][c] = device column c of caller tree t, 2^log_size words, full size, as for bfhip_pcs_commit.
+ *   kernels (may be NULL): kernels[k], where not NULL, is component k's bfhip_air_kernel of this context, compiled from the statement's
+ *   program; it is handed to bfhip_air_compose in place of the program. ch is the caller's channel and may already carry mixes.
+ *   The protocol, in this order (normative):
+ *    1. bfhip_pcs_create. A context with an open session, or one in a shard group, is refused.
+ *    2. per caller tree: mix_u64 of its words, then bfhip_pcs_commit.
+ *    3. draw_felts(2) = (z_r, alpha_r) for r = 0 .. n_relations - 1.
+ *    4. if any component has a fraction program: ONE bfhip_logup_program_generate_batch over those components in list order, into columns
+ *       of the driver; mix_felts([claimed_k]) per such component in list order; bfhip_pcs_commit of the interaction tree in form 0
+ *       (components in list order, logUp columns in program order, four coordinates each). Otherwise there is no interaction tree.
+ *    5. random_coeff = draw_felt().
+ *    6. ONE bfhip_air_compose over all components. Component k reads its columns on CanonicCoset(log_size + log_expand).circle_domain():
+ *       where log_expand == log_blowup_factor the session's own LDE columns (bfhip_pcs_tree_columns), otherwise the tree's coefficient
+ *       columns evaluated on that domain (bfhip_evaluate) into scratch — an LDE of another blowup is no superset of it. Only the columns
+ *       some component reads are evaluated, once per (column, log_expand).
+ *    7. bfhip_pcs_commit of the four composition columns in form 1, log size max_k(log_size_k + log_expand_k).
+ *    8. oods = draw_point(). Point 0 is oods; then one point per distinct (log_size, offset != 0) in order of first use — components in
+ *       list order, within a component bfhip_air_mask's order — bfhip_circle_point_offset(oods, log_size, offset). A column's samples
+ *       are the points of all components that read it, in first-use order, each once; a column no component reads gets none; the
+ *       composition columns get [0].
+ *    9. bfhip_pcs_prove_values.
+ *   10. The sanity check of prover::prove: the sampled composition value (from_partial_evals of the four coordinates) must equal
+ *       bfhip_air_compose_at_point over the sampled mask values; otherwise -1 with "bfhip_air_prove: ConstraintsNotSatisfied".
+ *   11. *proof_json = {"claimed_sums":[...],"proof":<CommitmentSchemeProof>}: one SecureField per component with a fraction program, in
+ *       the serde form of interaction_claim.*.claimed_sum; the "proof" member is byte for byte what bfhip_pcs_prove_values returned.
+ *       malloc'd, release with bfhip_free_host.
+ *   flags: BFHIP_AIR_PROVE_CHECK — after step 4's batch, bfhip_air_check on every component over the trace-domain columns (every tree a
+ *     component binds must then be form 0); a violation is -1 with "bfhip_air_prove: component <k>: " and the first failing line of
+ *     bfhip_format_air_check.
+ *   Validation: everything the statement alone decides is checked by one host function before anything is enqueued and before the session
+ *     opens; bfhip_air_verify runs the same function. -1 with "bfhip_air_prove: component <k>: <rule>", "bfhip_air_prove: tree <t>: <rule>"
+ *     or "bfhip_air_prove: <rule>"; the context stays usable. Caps: trees <= 8, relations <= 16, components <= 64; null pointers and
+ *     reserved fields; column and tree indices in range; a bound column's log_size equal to the component's; 4 <= log_size <=
+ *     max_log_domain - max(log_blowup_factor, log_expand); as many rules as the constraint program has parameters, at least as many as
+ *     the fraction program has; relation and power indices in range; CLAIMED_SUM without, or among the parameters of, a fraction program;
+ *     a fraction column bound to a form-1 tree; BFHIP_AIR_TREE_INTERACTION without a fraction program; a column that would be opened at
+ *     more than BFHIP_PCS_MAX_SAMPLES_PER_COLUMN points (the message names it); more than BFHIP_PCS_MAX_POINTS points. A failure of a
+ *     call the driver makes comes back as "bfhip_air_prove: " + that call's message (in the batch's, a component index counts the
+ *     components with a fraction program).
+ *   Memory: the driver's own buffers (interaction columns, composition columns, constraint-domain scratch) are ONE hipMalloc, not the
+ *     session's arena, freed before return on every path after a wait for the context's streams; the session is destroyed on every
+ *     path: bfhip_ctx_memory out[3] is what it was before the call. A failed allocation is -1 with "bfhip_air_prove: cannot allocate <n> bytes
+ *     ...", before the session opens. After a failure behind that point the channel has advanced: replay with a fresh one.
+ * bfhip_air_verify (host only, plain C++): replays steps 2 to 8 with the roots of proof.commitments (bfhip_pcs_verifier_commit, trace-domain
+ *   log sizes), tests the claimed sums' total ("InvalidLookup: Invalid LogUp sum", where the Brainfuck verifier tests it: after the draws of
+ *   step 3), compares bfhip_air_compose_at_point over proof.sampled_values with the sampled composition value ("OodsNotMatching") and calls
+ *   bfhip_pcs_verifier_verify_values, whose rejection names pass through. A proof that does not parse, or a wrong number of commitments,
+ *   sampled columns, samples or claimed sums is "InvalidStructure". conv / pcs (NULL = defaults): what the proof was made under.
+ *   0 = accepted, 1 = rejected (the name in err), -1 = bad arguments (the validator's refusals, in bfhip_air_verify's name).
+ * Layouts (natural alignment, LP64):
+ *   bfhip_air_statement_tree       32 bytes: n_cols 0, form 4, log_sizes_h 8, mix_u64_h 16, n_mix 24, reserved 28
+ *   bfhip_air_param_rule           32 bytes: kind 0, relation 4, power 8, reserved 12, value 16
+ *   bfhip_air_statement_component  72 bytes: program 0, fractions 8, log_size 16, log_expand 20, col_trees_h 24, col_columns_h 32,
+ *                                  frac_trees_h 40, frac_columns_h 48, params_h 56, n_params 64, reserved 68
+ *   bfhip_air_statement            32 bytes: trees 0, components 8, n_trees 16, n_relations 20, n_components 24, reserved 28 */
+enum { BFHIP_AIR_TREE_INTERACTION = 255, BFHIP_AIR_PROVE_CHECK = 1, BFHIP_AIR_STATEMENT_MAX_TREES = 8, BFHIP_AIR_STATEMENT_MAX_RELATIONS = 16,
+       BFHIP_AIR_STATEMENT_MAX_POWER = 63 };
+enum { BFHIP_AIR_PARAM_CONST = 0, BFHIP_AIR_PARAM_LOOKUP_Z = 1, BFHIP_AIR_PARAM_LOOKUP_ALPHA_POW = 2, BFHIP_AIR_PARAM_CLAIMED_SUM = 3 };
+typedef struct bfhip_air_statement_tree {
+    uint32_t n_cols, form;            /* form: 0 = evaluations, 1 = coefficients */
+    const uint32_t* log_sizes_h;      /* n_cols trace-domain log sizes */
+    const uint64_t* mix_u64_h;        /* n_mix words mixed in front of this tree's commit; may be NULL when n_mix = 0 */
+    uint32_t n_mix, reserved;         /* reserved must be 0 */
+} bfhip_air_statement_tree;
+typedef struct bfhip_air_param_rule {
+    uint32_t kind, relation, power, reserved;   /* BFHIP_AIR_PARAM_*; reserved must be 0 */
+    uint32_t value[4];                          /* BFHIP_AIR_PARAM_CONST */
+} bfhip_air_param_rule;
+typedef struct bfhip_air_statement_component {
+    const bfhip_air* program;
+    const bfhip_logup* fractions;     /* NULL = the component has no lookups */
+    uint32_t log_size, log_expand;
+    const uint32_t* col_trees_h;      /* per column of program: a caller tree, or BFHIP_AIR_TREE_INTERACTION */
+    const uint32_t* col_columns_h;    /* its column in that tree / among the component's own interaction columns */
+    const uint32_t* frac_trees_h;     /* per column of fractions: a caller tree of form 0 */
+    const uint32_t* frac_columns_h;
+    const bfhip_air_param_rule* params_h;
+    uint32_t n_params, reserved;      /* reserved must be 0 */
+} bfhip_air_statement_component;
+typedef struct bfhip_air_statement {
+    const bfhip_air_statement_tree* trees;
+    const bfhip_air_statement_component* components;
+    uint32_t n_trees, n_relations, n_components, reserved;   /* reserved must be 0 */
+} bfhip_air_statement;
+int32_t bfhip_air_prove(bfhip_ctx* ctx, const bfhip_air_statement* statement, const uint32_t* const* const* tree_cols_h, bfhip_air_kernel* const* kernels,
+                        bfhip_channel* ch, uint32_t flags, char** proof_json, size_t* proof_len);
+int32_t bfhip_air_verify(const bfhip_air_statement* statement, const bfhip_conventions* conv, const bfhip_pcs_config* pcs, bfhip_channel* ch,
+                         const char* proof_json, size_t proof_len, char* err, size_t err_cap);
+/* The sample description both of them derive from the statement (host only): the validator, then counts = {trees (caller trees, the
+ * interaction tree if any, the composition tree), points, columns of all trees, point indices of all columns}. With every array NULL that is
+ * all (a size query); otherwise every array is written: tree_n_cols[trees], the points as (point_log_sizes, point_offsets)[points] — point 0,
+ * the drawn point itself, as (0, 0) — and n_samples[columns] / point_idx[indices] as bfhip_pcs_prove_values takes them. pcs = the PcsConfig
+ * the rules are checked under (NULL = defaults), with max_log_domain 30. Refusals are the validator's, in this function's name. */
+int32_t bfhip_air_statement_samples(const bfhip_air_statement* statement, const bfhip_pcs_config* pcs, uint32_t counts[4], uint32_t* tree_n_cols,
+                                    uint32_t* point_log_sizes, int32_t* point_offsets, uint32_t* n_samples, uint32_t* point_idx);
 
 /* ---- Relation programs: the lookup tuples of ANY AIR that do not cancel ------------------------------------------------------------------------
  * bfhip_relation_summary / bfhip_trace_relations know the three Brainfuck relations and the 13 table layouts. An AIR proved through bfhip_pcs_* +

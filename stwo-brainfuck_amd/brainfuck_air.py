@@ -2,7 +2,7 @@
 fractions and relation entries as programs, and the parameters they take."""
 from ._abi import P
 from .context import LOGUP_MASK_PREV_CUR
-from .programs import AirBuilder
+from .programs import AirBuilder, AirStatement
 from .reports import RELATION_NAMES
 
 
@@ -176,6 +176,29 @@ def brainfuck_logup_program(component):
     else:
         column(t(7)[0] - one, "processor", t(0, 1, 2, 3, 4, 5, 6))
     return b.logup_program(n_cols=n_main, n_params=BRAINFUCK_LOGUP_N_PARAMS), list(_LOOKUP_PARAM_NAMES)
+
+
+def brainfuck_air_statement(log_sizes, log_max_rows, logup_mask_order=0):
+    """The Brainfuck protocol of mod.rs:471-735 as an AirStatement over the 13 program triples — the worked example of Context.air_prove /
+    air_verify. Tree 0: the IsFirst columns of log sizes log_max_rows .. 4 as coefficients (is_first_coeffs); tree 1: the main trace,
+    components in claim order, as trace-domain evaluations, with the 13 log sizes mixed in front of it (claim.mix_into). Three relations
+    (Memory, Instruction, Processor). Component k: brainfuck_air_program(k, logup_mask_order) at log_expand 1 over its main columns, its own
+    interaction columns and IsFirst of its size, brainfuck_logup_program(k) over the main columns, and brainfuck_air_params as rules."""
+    log_sizes = [int(l) for l in log_sizes]
+    if len(log_sizes) != 13:
+        raise ValueError("13 log sizes")
+    st = AirStatement(n_relations=3)
+    t0 = st.tree(list(range(log_max_rows, 3, -1)), form=1)
+    t1 = st.tree([log_sizes[k] for k in range(13) for _ in range(_BF_N_MAIN[k])], form=0, mix_u64=log_sizes)
+    rules = [r for rel in range(3) for r in [AirStatement.z(rel)] + [AirStatement.alpha_pow(rel, i) for i in range(7)]] + [AirStatement.claimed_sum()]
+    first = 0
+    for k in range(13):
+        n_main, n_logup = _BF_N_MAIN[k], 3 if k == 3 else 1
+        main = [(t1, first + j) for j in range(n_main)]
+        columns = main + [(AirStatement.INTERACTION, j) for j in range(4 * n_logup)] + [(t0, log_max_rows - log_sizes[k])]
+        st.component(brainfuck_air_program(k, logup_mask_order)[0], log_sizes[k], 1, columns, rules, fractions=brainfuck_logup_program(k)[0], fraction_columns=main)
+        first += n_main
+    return st
 
 
 BRAINFUCK_RELATION_WORDS = (3, 3, 7)

@@ -5,11 +5,11 @@ import weakref
 
 import numpy as np
 
-from ._abi import BfhipError, Owned, _check, _ptr_array, _qm31s, _u32s, abi, struct_fields
+from ._abi import BfhipError, Owned, _check, _ptr_array, _qm31s, _take_host_string, _u32s, abi, struct_fields
 from ._abi_gen import (BFHIP_CHANNEL_BLAKE2S as CHANNEL_BLAKE2S, BFHIP_CHANNEL_POSEIDON252 as CHANNEL_POSEIDON252, BFHIP_LOGUP_MASK_CUR_PREV as LOGUP_MASK_CUR_PREV,
                        BFHIP_LOGUP_MASK_PREV_CUR as LOGUP_MASK_PREV_CUR, BFHIP_MERKLE_RFC7693 as MERKLE_RFC7693, BFHIP_MERKLE_STWO_COMPRESS as MERKLE_STWO_COMPRESS,
                        BFHIP_MIX_U64_COMPRESS as MIX_U64_COMPRESS, BFHIP_MIX_U64_HASH as MIX_U64_HASH)
-from .programs import AirComponent, CompiledAir, LogupComponent
+from .programs import AIR_PROVE_CHECK, AirComponent, CompiledAir, LogupComponent
 from .reports import (COMPONENT_NAMES, AirCheckReport, CheckReport, MultiplicityReport, MultiplicityResult, PreflightReport, RelationEntry, RelationProgramTable,
                       RelationTable, _relation_result)
 
@@ -423,6 +423,24 @@ class Context(Owned):
             comps[k] = AirComponent(None if compiled else program._h.value, program._h.value if compiled else None, int(log_size), int(log_expand),
                                     None if cols is None else ctypes.cast(cols, ctypes.POINTER(ctypes.c_void_p)), shifts, pars, n_params, 0)
         _check(abi().bfhip_air_compose(self._h, comps, len(components), _u32s(r), int(dst_log), _ptr_array(dst_ptrs)))
+
+    def air_prove(self, statement, tree_cols, channel, kernels=None, check=False):
+        """bfhip_air_prove: the whole proof of an AIR given as an AirStatement — the session, the mixes and draws, the batched interaction
+        trace, air_compose, the mask, prove_values and the sanity check, in the order include/bfhip.h states. tree_cols[t][c]: device
+        column c of caller tree t (full size). kernels: per component None or the CompiledAir of its program. check: air_check on every
+        component behind the interaction trace; a violation raises BfhipError naming component, constraint and cell. Returns the bytes
+        {"claimed_sums": [...], "proof": <CommitmentSchemeProof>} that air_verify takes."""
+        st = statement._c()
+        if len(tree_cols) != len(statement.trees) or any(len(cols) != len(tree[0]) for cols, tree in zip(tree_cols, statement.trees)):
+            raise ValueError("one device column per column of every caller tree")
+        if kernels is not None and len(kernels) != len(statement.components):
+            raise ValueError("one kernel (or None) per component")
+        per_tree = [_ptr_array(cols) for cols in tree_cols]
+        trees = (ctypes.c_void_p * max(1, len(per_tree)))(*[ctypes.cast(a, ctypes.c_void_p) for a in per_tree])
+        ks = None if kernels is None else (ctypes.c_void_p * len(kernels))(*[None if k is None else k._h for k in kernels])
+        js, n = ctypes.c_void_p(), ctypes.c_size_t()
+        _check(abi().bfhip_air_prove(self._h, ctypes.byref(st), trees, ks, channel._h, AIR_PROVE_CHECK if check else 0, ctypes.byref(js), ctypes.byref(n)))
+        return _take_host_string(js, n.value)
 
     def air_compile(self, program):
         """bfhip_air_compile: the AirProgram as its own gfx950 kernel, generated (AirProgram.source) and compiled in-process for this

@@ -4,12 +4,14 @@ import ctypes
 
 import numpy as np
 
-from ._abi import Owned, P, _check, _qm31s, _u32s, abi, struct_fields
+from ._abi import Owned, P, _check, _last_error, _qm31s, _u32s, abi, struct_fields
 from ._abi_gen import (BFHIP_AIR_C_BASE as AIR_C_BASE, BFHIP_AIR_C_EXT as AIR_C_EXT, BFHIP_AIR_M_ADD as AIR_M_ADD, BFHIP_AIR_M_COL as AIR_M_COL,
                        BFHIP_AIR_M_CONST as AIR_M_CONST, BFHIP_AIR_M_MUL as AIR_M_MUL, BFHIP_AIR_M_NEG as AIR_M_NEG, BFHIP_AIR_M_SUB as AIR_M_SUB,
                        BFHIP_AIR_MAX_COLUMNS as AIR_MAX_COLUMNS, BFHIP_AIR_MAX_CONSTRAINTS as AIR_MAX_CONSTRAINTS, BFHIP_AIR_MAX_INSTRUCTIONS as AIR_MAX_INSTRUCTIONS,
                        BFHIP_AIR_MAX_M_REGS as AIR_MAX_M_REGS, BFHIP_AIR_MAX_OFFSET as AIR_MAX_OFFSET, BFHIP_AIR_MAX_PARAMS as AIR_MAX_PARAMS,
-                       BFHIP_AIR_MAX_Q_REGS as AIR_MAX_Q_REGS, BFHIP_AIR_Q_ADD as AIR_Q_ADD, BFHIP_AIR_Q_COL as AIR_Q_COL, BFHIP_AIR_Q_FROM_M as AIR_Q_FROM_M,
+                       BFHIP_AIR_MAX_Q_REGS as AIR_MAX_Q_REGS, BFHIP_AIR_PARAM_CLAIMED_SUM as AIR_PARAM_CLAIMED_SUM, BFHIP_AIR_PARAM_CONST as AIR_PARAM_CONST,
+                       BFHIP_AIR_PARAM_LOOKUP_ALPHA_POW as AIR_PARAM_LOOKUP_ALPHA_POW, BFHIP_AIR_PARAM_LOOKUP_Z as AIR_PARAM_LOOKUP_Z,
+                       BFHIP_AIR_PROVE_CHECK as AIR_PROVE_CHECK, BFHIP_AIR_TREE_INTERACTION as AIR_TREE_INTERACTION, BFHIP_AIR_Q_ADD as AIR_Q_ADD, BFHIP_AIR_Q_COL as AIR_Q_COL, BFHIP_AIR_Q_FROM_M as AIR_Q_FROM_M,
                        BFHIP_AIR_Q_MUL as AIR_Q_MUL, BFHIP_AIR_Q_MULM as AIR_Q_MULM, BFHIP_AIR_Q_PARAM as AIR_Q_PARAM, BFHIP_AIR_Q_SUB as AIR_Q_SUB,
                        BFHIP_LOGUP_BATCH_MAX_COMPONENTS as LOGUP_BATCH_MAX_COMPONENTS, BFHIP_LOGUP_END_COL as LOGUP_END_COL, BFHIP_LOGUP_FRAC as LOGUP_FRAC,
                        BFHIP_LOGUP_MAX_COLUMNS as LOGUP_MAX_COLUMNS,
@@ -149,6 +151,135 @@ class LogupProgram(_Program):
 class LogupComponent(ctypes.Structure):
     """include/bfhip.h `bfhip_logup_component`: one component of Context.logup_program_generate_batch's list."""
     _fields_ = struct_fields("bfhip_logup_component")
+
+
+class _StatementTree(ctypes.Structure):
+    _fields_ = struct_fields("bfhip_air_statement_tree")
+
+
+class _ParamRule(ctypes.Structure):
+    _fields_ = struct_fields("bfhip_air_param_rule")
+
+
+class _StatementComponent(ctypes.Structure):
+    _fields_ = struct_fields("bfhip_air_statement_component")
+
+
+class _Statement(ctypes.Structure):
+    _fields_ = struct_fields("bfhip_air_statement")
+
+
+class AirStatement:
+    """bfhip_air_statement: an AIR as data, what Context.air_prove and air_verify share (include/bfhip.h "Proving an AIR given as
+    programs"). It holds no device pointers.
+        st = AirStatement(n_relations=1)
+        t0 = st.tree([log_size] * 4)                                   # caller trees in commit order; form=1: coefficients; mix_u64: a claim
+        st.component(prog, log_size, 1, [(t0, 0), (t0, 1), (t0, 2), (t0, 3)] + [(AirStatement.INTERACTION, j) for j in range(8)],
+                     [AirStatement.z(0), AirStatement.alpha_pow(0, 1), AirStatement.claimed_sum()],
+                     fractions=fractions, fraction_columns=[(t0, 0), (t0, 1), (t0, 2)])
+    A component's columns are (tree, column) pairs, one per column of its constraint program; (INTERACTION, j) is the j-th of its own 4 *
+    n_logup_cols interaction coordinate columns. Its parameter rules are const(q) / z(r) / alpha_pow(r, i) / claimed_sum(), one per
+    parameter of the constraint program; the fraction program takes the first of them. Nothing is checked here: the library's validator
+    refuses a wrong statement by name when it is used."""
+    INTERACTION = AIR_TREE_INTERACTION
+
+    @staticmethod
+    def const(q):
+        return (AIR_PARAM_CONST, 0, 0, _qm31(q, "a constant parameter"))
+
+    @staticmethod
+    def z(relation):
+        return (AIR_PARAM_LOOKUP_Z, int(relation), 0, [0, 0, 0, 0])
+
+    @staticmethod
+    def alpha_pow(relation, power):
+        return (AIR_PARAM_LOOKUP_ALPHA_POW, int(relation), int(power), [0, 0, 0, 0])
+
+    @staticmethod
+    def claimed_sum():
+        return (AIR_PARAM_CLAIMED_SUM, 0, 0, [0, 0, 0, 0])
+
+    def __init__(self, n_relations=0):
+        self.n_relations = int(n_relations)
+        self.trees = []          # (log_sizes, form, mix_u64)
+        self.components = []     # (program, log_size, log_expand, columns, params, fractions, fraction_columns)
+        self._built = None
+
+    def tree(self, log_sizes, form=0, mix_u64=()):
+        """A caller tree; returns its index. mix_u64: the words mixed into the channel immediately before its commit."""
+        self.trees.append(([int(l) for l in log_sizes], int(form), [int(v) for v in mix_u64]))
+        self._built = None
+        return len(self.trees) - 1
+
+    def component(self, program, log_size, log_expand, columns, params, fractions=None, fraction_columns=()):
+        """A component; returns its index."""
+        self.components.append((program, int(log_size), int(log_expand), [(int(t), int(c)) for t, c in columns], [tuple(r) for r in params], fractions,
+                                [(int(t), int(c)) for t, c in fraction_columns]))
+        self._built = None
+        return len(self.components) - 1
+
+    @property
+    def fraction_components(self):
+        """The indices of the components with a fraction program: the order of a proof's claimed_sums."""
+        return [k for k, comp in enumerate(self.components) if comp[5] is not None]
+
+    def _c(self):
+        """(the bfhip_air_statement, everything it points to)"""
+        if self._built is None:
+            keep = []
+            trees = (_StatementTree * max(1, len(self.trees)))()
+            for t, (logs, form, mix) in enumerate(self.trees):
+                la, ma = _u32s(logs or [0]), (ctypes.c_uint64 * max(1, len(mix)))(*mix)
+                keep += [la, ma]
+                trees[t] = _StatementTree(len(logs), form, la, ma, len(mix), 0)
+            comps = (_StatementComponent * max(1, len(self.components)))()
+            for k, (program, log_size, log_expand, columns, params, fractions, frac_columns) in enumerate(self.components):
+                rules = (_ParamRule * max(1, len(params)))()
+                for i, (kind, relation, power, value) in enumerate(params):
+                    rules[i] = _ParamRule(kind, relation, power, 0, (ctypes.c_uint32 * 4)(*value))
+                arrays = [_u32s([t for t, _ in columns] or [0]), _u32s([c for _, c in columns] or [0]),
+                          _u32s([t for t, _ in frac_columns] or [0]), _u32s([c for _, c in frac_columns] or [0])]
+                keep += arrays + [rules, program, fractions]
+                comps[k] = _StatementComponent(program._h.value, None if fractions is None else fractions._h.value, log_size, log_expand, *arrays,
+                                               ctypes.cast(rules, ctypes.c_void_p), len(params), 0)
+            st = _Statement(ctypes.cast(trees, ctypes.c_void_p), ctypes.cast(comps, ctypes.c_void_p), len(self.trees), self.n_relations, len(self.components), 0)
+            self._built = (st, keep + [trees, comps])
+        return self._built[0]
+
+    def samples(self, pcs_config=None):
+        """bfhip_air_statement_samples (host only): (points, samples) as the prover and the verifier derive them — points = [(log_size,
+        offset)], point 0 = (0, 0) the drawn point itself, the others circle_point_offset(oods, log_size, offset); samples[tree][column] =
+        point indices over the caller trees, the interaction tree (if any) and the composition tree. Runs the validator."""
+        from .context import _pcs_ref
+        counts = (ctypes.c_uint32 * 4)()
+        _check(abi().bfhip_air_statement_samples(ctypes.byref(self._c()), _pcs_ref(pcs_config), counts, None, None, None, None, None))
+        n_trees, n_points, n_cols, n_idx = (int(v) for v in counts)
+        per_tree, logs, offs = (ctypes.c_uint32 * n_trees)(), (ctypes.c_uint32 * n_points)(), (ctypes.c_int32 * n_points)()
+        ns, idx = (ctypes.c_uint32 * max(1, n_cols))(), (ctypes.c_uint32 * max(1, n_idx))()
+        _check(abi().bfhip_air_statement_samples(ctypes.byref(self._c()), _pcs_ref(pcs_config), counts, per_tree, logs, offs, ns, idx))
+        samples, col, at = [], 0, 0
+        for t in range(n_trees):
+            tree = []
+            for _ in range(per_tree[t]):
+                tree.append([int(idx[at + i]) for i in range(ns[col])])
+                at += ns[col]
+                col += 1
+            samples.append(tree)
+        return [(int(logs[i]), int(offs[i])) for i in range(n_points)], samples
+
+
+def air_verify(statement, proof, channel, conventions=None, pcs_config=None):
+    """bfhip_air_verify (host only): (ok, reason) for the bytes Context.air_prove returned — the channel replay, the claimed sums' total,
+    the composition check at the drawn point and verify_values. channel: a fresh Channel carrying what the prover's carried before the
+    call. conventions / pcs_config: what the proof was made under (None = the mirror's defaults / the default PcsConfig). A statement the
+    validator refuses raises BfhipError."""
+    from .context import _conv_ref, _pcs_ref
+    proof = bytes(proof)
+    err = ctypes.create_string_buffer(512)
+    rc = abi().bfhip_air_verify(ctypes.byref(statement._c()), _conv_ref(conventions), _pcs_ref(pcs_config), channel._h, proof, len(proof), err, 512)
+    if rc < 0:
+        raise _last_error()
+    return rc == 0, err.value.decode()
 
 
 class RelationProgram(_Program):

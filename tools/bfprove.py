@@ -5,10 +5,10 @@ tracker for it:
 
   bfprove.py prove  (--file prog.bf | --code '++>,<[>+.<-]') [--input-file in.bin] [--ram-size N] [--output proof.json]
                     [--log-max-rows 24] [--conventions a,b,c,d | --poseidon252] [--all-sets DIR] [PCS options]
-                    [--preflight] [--set-register ROW:NAME=VALUE ...] [--set-word INDEX=VALUE ...]
+                    [--preflight] [--set-register ROW:NAME=VALUE ...] [--set-word INDEX=VALUE ...] [--generic]
   bfprove.py prove  --queue N --programs a.bf b.bf ... --output-dir DIR [--input-file in.bin] [--ram-size N] [--log-max-rows 24]
                     [--conventions a,b,c,d | --poseidon252] [PCS options] [--preflight] [--set-register ...]
-  bfprove.py verify proof.json [--log-max-rows 24] [--conventions a,b,c,d | --poseidon252 | --try-all] [PCS options]
+  bfprove.py verify proof.json [--log-max-rows 24] [--conventions a,b,c,d | --poseidon252 | --try-all] [PCS options] [--generic]
   bfprove.py check  (--file prog.bf | --code '++>,<[>+.<-]') [--input-file in.bin] [--ram-size N] [--set-register ROW:NAME=VALUE ...]
   bfprove.py relations (--file prog.bf | --code ...) [--input-file in.bin] [--ram-size N] [--set-register ROW:NAME=VALUE ...]
                     [--set-word INDEX=VALUE ...] [--max-entries 64]
@@ -35,6 +35,12 @@ print — "TraceRejected: 1 of 13 components violate their constraints ..." on s
 "ConstraintsNotSatisfied". In --queue mode a rejected program is reported with those lines and does not stop the others. --set-register /
 --set-word hand the prover the executed machine with one register / program word altered (in --queue mode: of every program).
 
+prove --generic proves the same trace through bfhip_air_prove: the 13 components as constraint and fraction programs under
+brainfuck_air_statement, the main trace handed over as full-size device columns, IsFirst as coefficients. The file it writes is the same
+BrainfuckProof (claim and interaction claim put around the driver's claimed sums and proof member) — byte for byte the file of the
+built-in path, which plain `verify` accepts. verify --generic checks a BrainfuckProof file through bfhip_air_verify under the statement
+that its claim describes. Neither works with --all-sets, --queue or --preflight.
+
 PCS options (stwo's PcsConfig; the defaults are PcsConfig::default()): --pow-bits 5 --log-blowup-factor 1 --n-queries 3. The proof file does
 not record them: verify with the values the proof was made with. prove prints the config and its security bits (pow + blowup x queries).
 
@@ -57,6 +63,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from conftest import load_package
+import pcs_replay
 
 NAMES = ("merkle_node_hash", "mix_u64", "logup_mask_order", "merkle_channel")
 VALUES = (("stwo-compress", "rfc7693"), ("compress", "hash"), ("[0,-1]", "[-1,0]"), ("blake2s", "poseidon252"))
@@ -120,9 +127,11 @@ def main():
     p.add_argument("--programs", nargs="+", default=[], metavar="FILE"); p.add_argument("--output-dir", metavar="DIR")
     p.add_argument("--preflight", action="store_true", help="reject a trace that cannot be proved before proving it, naming row and tuple")
     p.add_argument("--set-register", action="append", default=[], metavar="ROW:NAME=VALUE"); p.add_argument("--set-word", action="append", default=[], metavar="INDEX=VALUE")
+    p.add_argument("--generic", action="store_true", help="prove through bfhip_air_prove with the 13 components as programs")
     v = sub.add_parser("verify")
     v.add_argument("proof"); v.add_argument("--log-max-rows", type=int, default=24); v.add_argument("--poseidon252", action="store_true")
     v.add_argument("--conventions"); v.add_argument("--try-all", action="store_true")
+    v.add_argument("--generic", action="store_true", help="verify through bfhip_air_verify under brainfuck_air_statement")
     k = sub.add_parser("check")
     k.add_argument("--file"); k.add_argument("--code"); k.add_argument("--input-file"); k.add_argument("--ram-size", type=int, default=0)
     k.add_argument("--set-register", action="append", default=[], metavar="ROW:NAME=VALUE")
@@ -240,7 +249,69 @@ def prove_queue(pkg, a, ap):
     return 1 if failed else 0
 
 
+def generic_columns(pkg, ctx, tr, log_max_rows):
+    """The caller trees of brainfuck_air_statement for a resident trace, as device columns: ([IsFirst coefficients of log sizes log_max_rows
+    .. 4], [the main trace, components in claim order, every column full size]) and every pointer to free."""
+    pre = [ctx.malloc(4 << n) for n in range(4, log_max_rows + 1)]
+    ctx.is_first_coeffs(4, log_max_rows, pre)
+    main, scratch = [], []
+    for k in range(13):
+        n = 1 << tr.log_sizes[k]
+        for j in range(pkg._BF_N_MAIN[k]):
+            rows = tr.column(k, j)
+            src = ctx.upload(rows)
+            if len(rows) == n:
+                main.append(src)
+                continue
+            assert 16 * len(rows) == n, "a resident trace holds row-granular columns"
+            scratch.append(src)
+            main.append(ctx.malloc(4 * n))
+            ctx.broadcast16(src, main[-1], len(rows))
+    ctx.sync()
+    for p in scratch:
+        ctx.free(p)
+    return [pre[::-1], main], pre + main
+
+
+def generic_prove(pkg, ctx, tr, log_max_rows, conv, kernels=None, columns=None):
+    """(the BrainfuckProof bytes, air_prove's own result) of a resident trace through bfhip_air_prove"""
+    st = pkg.brainfuck_air_statement(tr.log_sizes, log_max_rows, conv[2])
+    cols, ptrs = columns or generic_columns(pkg, ctx, tr, log_max_rows)
+    try:
+        with pkg.Channel(conv) as ch:
+            raw = ctx.air_prove(st, cols, ch, kernels=kernels)
+    finally:
+        if columns is None:
+            for p in ptrs:
+                ctx.free(p)
+    head, at = b'{"claimed_sums":[', raw.index(b'],"proof":')
+    sums = raw[len(head): at].replace(b"]],[[", b"]]\n[[").split(b"\n")
+    assert raw.startswith(head) and len(sums) == 13
+    claim = b",".join(b'"%s":{"log_size":%d,"_marker":null}' % (n.encode(), l) for n, l in zip(pcs_replay.NAMES, tr.log_sizes))
+    inter = b",".join(b'"%s":{"claimed_sum":%s}' % (n.encode(), c) for n, c in zip(pcs_replay.NAMES, sums))
+    return b'{"claim":{' + claim + b'},"interaction_claim":{' + inter + b'},"proof":' + raw[at + len(b'],"proof":'):], raw
+
+
+def generic_verify(pkg, proof, log_max_rows, conv, pcs):
+    """(ok, reason) of a BrainfuckProof file through bfhip_air_verify under the statement that its claim describes"""
+    import json
+    try:
+        full = json.loads(proof)
+        log_sizes = [full["claim"][n]["log_size"] for n in pcs_replay.NAMES]
+        sums = [full["interaction_claim"][n]["claimed_sum"] for n in pcs_replay.NAMES]
+        member = pcs_replay.proof_member(proof)
+    except (ValueError, KeyError, TypeError) as e:
+        return False, "InvalidStructure: %s" % e
+    if any(not isinstance(l, int) or l < 4 or l > log_max_rows for l in log_sizes):
+        return False, "InvalidStructure: log_size"
+    st = pkg.brainfuck_air_statement(log_sizes, log_max_rows, conv[2])
+    with pkg.Channel(conv) as ch:
+        return pkg.air_verify(st, b'{"claimed_sums":' + pcs_replay.compact(sums) + b',"proof":' + member + b"}", ch, conv, pcs)
+
+
 def run(pkg, a, ap):
+    if a.cmd == "prove" and a.generic and (a.queue or a.all_sets or a.preflight):
+        ap.error("--generic does not go with --queue, --all-sets or --preflight")
     if a.cmd == "prove" and a.queue:
         return prove_queue(pkg, a, ap)
     if a.cmd == "check":
@@ -271,7 +342,7 @@ def run(pkg, a, ap):
             ctx.set_conventions(*conv)
             t_start = time.time()
             try:
-                proof, _ = tr.prove(a.log_max_rows)
+                proof = generic_prove(pkg, ctx, tr, a.log_max_rows, conv)[0] if a.generic else tr.prove(a.log_max_rows)[0]
             except pkg.TraceRejected as e:          # --preflight: the lines check / relations would print
                 print(e)
                 tr.close(); ctx.close()
@@ -299,7 +370,10 @@ def run(pkg, a, ap):
                 print("  %d,%d,%d,%d  %s" % (conv + (why,)))
         return 0 if accepted else 1
     conv = parse_conventions(a)
-    ok, why = pkg.verify_brainfuck(proof, a.log_max_rows, conventions=conv, pcs_config=parse_pcs(pkg, a))
+    if a.generic:
+        ok, why = generic_verify(pkg, proof, a.log_max_rows, conv, parse_pcs(pkg, a))
+    else:
+        ok, why = pkg.verify_brainfuck(proof, a.log_max_rows, conventions=conv, pcs_config=parse_pcs(pkg, a))
     print("Proof verified" if ok else f"Verification failed: {why}")
     return 0 if ok else 1
 
