@@ -87,14 +87,6 @@ struct Bucket {
     std::vector<u32> interpreted, compiled;      // indices into the caller's list, in list order
 };
 
-// The smaller buckets' accumulators: no launch that uses them is in flight when they are freed
-struct CallScratch {
-    Ctx& c;
-    u32* p = nullptr;
-    explicit CallScratch(Ctx& c_) : c(c_) {}
-    ~CallScratch() { if (p) { (void)hipStreamSynchronize(c.stream); (void)hipFree(p); } }
-};
-
 }  // namespace
 
 extern "C" int32_t bfhip_air_compose(bfhip_ctx* ctx, const bfhip_air_component* comps, uint32_t n, const uint32_t random_coeff_h[4], uint32_t dst_log,
@@ -165,10 +157,12 @@ extern "C" int32_t bfhip_air_compose(bfhip_ctx* ctx, const bfhip_air_component* 
     }
     if (need > c.stage_bytes) throw HipError(me + ": the list stages " + std::to_string(need) + " bytes, the context's staging ring holds " + std::to_string(c.stage_bytes));
 
-    CallScratch scratch(c);
-    if (scratch_words) BF_HIP(hipMalloc((void**)&scratch.p, scratch_words * sizeof(u32)));
+    // the smaller buckets' accumulators: no launch that uses them is in flight when the guard frees them
+    DeviceScratch scratch(c);
+    u32* small_acc = nullptr;
+    if (scratch_words) scratch.alloc(&small_acc, scratch_words * sizeof(u32));
     {
-        u32* at = scratch.p;
+        u32* at = small_acc;
         for (size_t b = 0; b < buckets.size(); b++)
             for (int w = 0; w < 4; w++) {
                 if (b == 0) buckets[b].acc[w] = dst_d[w];
@@ -282,7 +276,7 @@ extern "C" int32_t bfhip_air_compose(bfhip_ctx* ctx, const bfhip_air_component* 
         accumulate_sizes(c.stream, as);
     }
     BF_HIP(hipGetLastError());
-    if (scratch.p) c.sync();      // the scratch is freed on return
+    if (small_acc) c.sync();      // the scratch is freed on return
     return 0;
     API_CATCH
 }

@@ -13,17 +13,11 @@ using namespace bf;
 
 namespace {
 
-// The session and the driver's buffer, released on every path: the session first (bfhip_pcs_destroy waits for every stream of the context),
-// then the buffer, which no launch reads any more
-struct Owned {
-    Ctx& c;
+// The session, closed on every path. Declared behind the driver's buffer (a DeviceScratch), so closed before the buffer goes:
+// bfhip_pcs_destroy waits for every stream of the context, and then no launch reads the buffer any more
+struct Session {
     bfhip_pcs* pcs = nullptr;
-    u32* buf = nullptr;
-    explicit Owned(Ctx& c_) : c(c_) {}
-    ~Owned() {
-        if (pcs) (void)bfhip_pcs_destroy(pcs);
-        if (buf) { (void)hipStreamSynchronize(c.stream); (void)hipFree(buf); }
-    }
+    ~Session() { if (pcs) (void)bfhip_pcs_destroy(pcs); }
 };
 
 }  // namespace
@@ -86,15 +80,14 @@ extern "C" int32_t bfhip_air_prove(bfhip_ctx* ctx, const bfhip_air_statement* st
         }
     }
 
-    Owned own(c);
-    if (hipMalloc((void**)&own.buf, words * sizeof(u32)) != hipSuccess) {
-        (void)hipGetLastError();
-        own.buf = nullptr;
+    DeviceScratch scratch(c);
+    u32* buf = nullptr;
+    if (scratch.try_alloc(&buf, words * sizeof(u32)) != hipSuccess)
         throw HipError(me + ": cannot allocate " + std::to_string(words * sizeof(u32)) + " bytes for the interaction, composition and constraint-domain columns");
-    }
-    for (auto& s : scratch_at) expanded[s.first] = own.buf + s.second;
+    Session own;
+    for (auto& s : scratch_at) expanded[s.first] = buf + s.second;
     u32* comp_cols[4];
-    for (int w = 0; w < 4; w++) comp_cols[w] = own.buf + comp_at + (size_t(w) << plan.composition_log);
+    for (int w = 0; w < 4; w++) comp_cols[w] = buf + comp_at + (size_t(w) << plan.composition_log);
 
     // ---- 1, 2: the session; the caller's trees ---------------------------------------------------------------------------------------------
     ok(bfhip_pcs_create(ctx, &own.pcs));
@@ -113,7 +106,7 @@ extern "C" int32_t bfhip_air_prove(bfhip_ctx* ctx, const bfhip_air_statement* st
     std::vector<u32> claimed(4 * (size_t)n, 0);
     std::vector<u32*> inter_cols;
     if (plan.has_interaction) {
-        for (size_t at : inter_at) inter_cols.push_back(own.buf + at);
+        for (size_t at : inter_at) inter_cols.push_back(buf + at);
         const size_t nf = plan.frac_comps.size();
         std::vector<bfhip_logup_component> lc(nf);
         std::vector<std::vector<const u32*>> in(nf);

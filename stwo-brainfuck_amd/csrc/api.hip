@@ -118,6 +118,15 @@ void Ctx::destroy() {
 
 // pcs_config_from (ctx.h): pcs_host.hip, with the other host-only checks of the commitment scheme's settings
 
+// The two timing events of a clock probe (Ctx::ev holds a proof's phase times and is not borrowed)
+namespace {
+struct ProbeEvents {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    void create() { BF_HIP(hipEventCreate(&e0)); BF_HIP(hipEventCreate(&e1)); }
+    ~ProbeEvents() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+};
+}  // namespace
+
 extern "C" {
 
 const char* bfhip_last_error(void) { return g_err.c_str(); }
@@ -147,28 +156,26 @@ int32_t bfhip_clock_probe(bfhip_ctx* ctx, double seconds, double out[6]) {
     c.sync();
     const u32 blocks = 256 * 8, iters = 2048;          // 8 workgroups of 4 waves per CU; ~2.5 ms per launch
     uint4* d_stamps = nullptr; u32* d_sink = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    std::vector<uint4> st(blocks);
+    std::vector<uint4> st(blocks);      // declared before the guard: the copy into it has completed when it goes
     u64 launches = 0; float ms = 0.f;
-    try {
-        BF_HIP(hipMalloc((void**)&d_stamps, blocks * sizeof(uint4)));
-        BF_HIP(hipMalloc((void**)&d_sink, (size_t)blocks * 256 * sizeof(u32)));
-        BF_HIP(hipEventCreate(&e0)); BF_HIP(hipEventCreate(&e1));
-        const auto t0 = std::chrono::steady_clock::now();
-        // back-to-back launches (a few in the queue at any time) until `seconds` have passed; the LAST launch's stamps are read
-        while (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < seconds) {
-            for (int k = 0; k < 8; k++) { clock_probe_launch(c.stream, d_stamps, d_sink, blocks, iters); launches++; }
-            BF_HIP(hipGetLastError());
-            c.sync();
-        }
-        BF_HIP(hipEventRecord(e0, c.stream));
-        for (int k = 0; k < 8; k++) clock_probe_launch(c.stream, d_stamps, d_sink, blocks, iters);
-        BF_HIP(hipEventRecord(e1, c.stream));
-        BF_HIP(hipMemcpyAsync(st.data(), d_stamps, blocks * sizeof(uint4), hipMemcpyDeviceToHost, c.stream));
+    DeviceScratch scratch(c);
+    scratch.alloc(&d_stamps, blocks * sizeof(uint4));
+    scratch.alloc(&d_sink, (size_t)blocks * 256 * sizeof(u32));
+    ProbeEvents ev;
+    ev.create();
+    const auto t0 = std::chrono::steady_clock::now();
+    // back-to-back launches (a few in the queue at any time) until `seconds` have passed; the LAST launch's stamps are read
+    while (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < seconds) {
+        for (int k = 0; k < 8; k++) { clock_probe_launch(c.stream, d_stamps, d_sink, blocks, iters); launches++; }
+        BF_HIP(hipGetLastError());
         c.sync();
-        BF_HIP(hipEventElapsedTime(&ms, e0, e1));
-    } catch (...) { (void)hipFree(d_stamps); (void)hipFree(d_sink); if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); throw; }
-    (void)hipFree(d_stamps); (void)hipFree(d_sink); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    }
+    BF_HIP(hipEventRecord(ev.e0, c.stream));
+    for (int k = 0; k < 8; k++) clock_probe_launch(c.stream, d_stamps, d_sink, blocks, iters);
+    BF_HIP(hipEventRecord(ev.e1, c.stream));
+    BF_HIP(hipMemcpyAsync(st.data(), d_stamps, blocks * sizeof(uint4), hipMemcpyDeviceToHost, c.stream));
+    c.sync();
+    BF_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
     std::vector<double> ghz;
     for (auto& s4 : st) {
         const double cyc = (double)(((u64)s4.y << 32) | s4.x), ticks = (double)(((u64)s4.w << 32) | s4.z);
@@ -197,42 +204,41 @@ int32_t bfhip_clock_probe_mix(bfhip_ctx* ctx, double seconds, uint32_t log_nodes
     const u32 log = log_nodes;                            // an inner layer of 2^log nodes without columns: one compression per node, 96 B of traffic per node
     const size_t prev_words = (size_t(2) << log) * 8, out_words = (size_t(1) << log) * 8;
     u32 *d_prev = nullptr, *d_out = nullptr; uint4* d_stamp = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    u32* stop = reinterpret_cast<u32*>(c.h_small + 3456);     // a pinned word between the flag and stamp slots (unused by proofs)
     uint4 st[2] = {};
     u64 launches = 0; float ms = 0.f;
-    try {
-        BF_HIP(hipMalloc((void**)&d_prev, prev_words * sizeof(u32)));
-        BF_HIP(hipMalloc((void**)&d_out, out_words * sizeof(u32)));
-        BF_HIP(hipMalloc((void**)&d_stamp, 2 * sizeof(uint4)));
-        BF_HIP(hipEventCreate(&e0)); BF_HIP(hipEventCreate(&e1));
-        fill_mix(c.stream, d_prev, prev_words);
-        for (int k = 0; k < 8; k++) merkle_layer(c.stream, d_out, d_prev, nullptr, 0, log, 0.0, 0, 0, 0);      // warm
+    DeviceScratch scratch(c);
+    scratch.alloc(&d_prev, prev_words * sizeof(u32));
+    scratch.alloc(&d_out, out_words * sizeof(u32));
+    scratch.alloc(&d_stamp, 2 * sizeof(uint4));
+    ProbeEvents ev;
+    ev.create();
+    // The sampler on the side stream runs until the host stores the stop flag. Declared behind the scratch, so destroyed before it: on every
+    // path the sampler has been told to stop and has ended before the buffer it writes is freed.
+    struct Sampler {
+        Ctx& c; u32* stop;
+        void end() { __atomic_store_n(stop, 1u, __ATOMIC_RELEASE); }
+        ~Sampler() { end(); (void)hipStreamSynchronize(c.stream2); }
+    } sampler{c, reinterpret_cast<u32*>(c.h_small + 3456)};     // a pinned word between the flag and stamp slots (unused by proofs)
+    fill_mix(c.stream, d_prev, prev_words);
+    for (int k = 0; k < 8; k++) merkle_layer(c.stream, d_out, d_prev, nullptr, 0, log, 0.0, 0, 0, 0);      // warm
+    BF_HIP(hipGetLastError());
+    c.sync();
+    __atomic_store_n(sampler.stop, 0u, __ATOMIC_RELEASE);
+    // the sampler first (it is resident before the wide launches arrive), bounded by 4 x the window whatever happens
+    clock_sampler_launch(c.stream2, d_stamp, c.small_alias(sampler.stop), (unsigned long long)(seconds * 4.0 * 1e8));
+    BF_HIP(hipEventRecord(ev.e0, c.stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    while (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < seconds) {
+        for (int k = 0; k < (log >= 24 ? 4 : 32); k++) { merkle_layer(c.stream, d_out, d_prev, nullptr, 0, log, 0.0, 0, 0, 0); launches++; }
         BF_HIP(hipGetLastError());
         c.sync();
-        __atomic_store_n(stop, 0u, __ATOMIC_RELEASE);
-        // the sampler first (it is resident before the wide launches arrive), bounded by 4 x the window whatever happens
-        clock_sampler_launch(c.stream2, d_stamp, c.small_alias(stop), (unsigned long long)(seconds * 4.0 * 1e8));
-        BF_HIP(hipEventRecord(e0, c.stream));
-        const auto t0 = std::chrono::steady_clock::now();
-        while (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < seconds) {
-            for (int k = 0; k < (log >= 24 ? 4 : 32); k++) { merkle_layer(c.stream, d_out, d_prev, nullptr, 0, log, 0.0, 0, 0, 0); launches++; }
-            BF_HIP(hipGetLastError());
-            c.sync();
-        }
-        BF_HIP(hipEventRecord(e1, c.stream));
-        c.sync();
-        __atomic_store_n(stop, 1u, __ATOMIC_RELEASE);
-        BF_HIP(hipStreamSynchronize(c.stream2));
-        BF_HIP(hipMemcpy(st, d_stamp, sizeof st, hipMemcpyDeviceToHost));
-        BF_HIP(hipEventElapsedTime(&ms, e0, e1));
-    } catch (...) {
-        __atomic_store_n(stop, 1u, __ATOMIC_RELEASE);
-        (void)hipStreamSynchronize(c.stream2);
-        (void)hipFree(d_prev); (void)hipFree(d_out); (void)hipFree(d_stamp); if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1);
-        throw;
     }
-    (void)hipFree(d_prev); (void)hipFree(d_out); (void)hipFree(d_stamp); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    BF_HIP(hipEventRecord(ev.e1, c.stream));
+    c.sync();
+    sampler.end();
+    BF_HIP(hipStreamSynchronize(c.stream2));
+    BF_HIP(hipMemcpy(st, d_stamp, sizeof st, hipMemcpyDeviceToHost));
+    BF_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
     const double cyc = (double)(((u64)st[0].y << 32) | st[0].x), ticks = (double)(((u64)st[0].w << 32) | st[0].z);
     const double comp = (double)launches * (double)(size_t(1) << log);
     out[0] = ticks > 0 ? cyc / ticks * 0.1 : 0.0;                    // GHz under the real kernel's mix
@@ -360,20 +366,17 @@ int32_t bfhip_rccl_selftest(bfhip_ctx* ctx) {
     std::unique_ptr<Comm> comm = rccl_comm_join(id, 0, 1);
     const u32 n = 1024;
     u32 *a = nullptr, *b = nullptr;
-    BF_HIP(hipMalloc((void**)&a, n * sizeof(u32)));
-    hipError_t e = hipMalloc((void**)&b, n * sizeof(u32));
-    if (e != hipSuccess) { (void)hipFree(a); BF_HIP(e); }
-    std::vector<u32> h(n), out(n);
+    std::vector<u32> h(n), out(n);      // declared before the guard: the copies from and into them have completed when it goes
     for (u32 i = 0; i < n; i++) h[i] = i * 2654435761u;
-    try {
-        BF_HIP(hipMemcpyAsync(a, h.data(), n * sizeof(u32), hipMemcpyHostToDevice, c.stream));
-        comm->all_gather(c.stream, a, n * sizeof(u32));
-        comm->all_reduce_max_u32(c.stream, a, n);
-        comm->exchange(c.stream, {Xfer{0, a, n * sizeof(u32)}}, {Xfer{0, b, n * sizeof(u32)}});
-        BF_HIP(hipMemcpyAsync(out.data(), b, n * sizeof(u32), hipMemcpyDeviceToHost, c.stream));
-        c.sync();
-    } catch (...) { (void)hipFree(a); (void)hipFree(b); throw; }
-    (void)hipFree(a); (void)hipFree(b);
+    DeviceScratch scratch(c);
+    scratch.alloc(&a, n * sizeof(u32));
+    scratch.alloc(&b, n * sizeof(u32));
+    BF_HIP(hipMemcpyAsync(a, h.data(), n * sizeof(u32), hipMemcpyHostToDevice, c.stream));
+    comm->all_gather(c.stream, a, n * sizeof(u32));
+    comm->all_reduce_max_u32(c.stream, a, n);
+    comm->exchange(c.stream, {Xfer{0, a, n * sizeof(u32)}}, {Xfer{0, b, n * sizeof(u32)}});
+    BF_HIP(hipMemcpyAsync(out.data(), b, n * sizeof(u32), hipMemcpyDeviceToHost, c.stream));
+    c.sync();
     if (out != h) throw HipError("RCCL self-test: data mismatch");
     return 0;
     API_CATCH
@@ -489,6 +492,20 @@ int32_t bfhip_twiddles(bfhip_ctx* ctx, const uint32_t** tw_d, const uint32_t** i
     API_CTX(ctx) if (!tw_d || !itw_d || !root_log) throw HipError("null argument"); *tw_d = ctx->c.d_tw; *itw_d = ctx->c.d_itw; *root_log = ctx->c.tw_root_log; return 0; API_CATCH
 }
 
+// What bfhip_interpolate and bfhip_evaluate share behind their argument checks: the job's column lists staged, one plan, its launches
+static void fft_columns(Ctx& c, bool inverse, FftJob job, uint32_t* const* src_cols_h, uint32_t* const* dst_cols_h) {
+    c.stage_checkpoint();
+    StageBatch sb(c);
+    job.d_src = (const u32* const*)c.stage(src_cols_h, job.ncols);
+    job.d_dst = (u32* const*)c.stage(dst_cols_h, job.ncols);
+    FftPlan plan;
+    fft_plan(plan, inverse, &job, 1, c.d_tw, c.d_itw, c.tw_root_log);
+    plan.d_groups = c.stage(plan.groups.data(), plan.groups.size());
+    sb.end();
+    fft_run(c.stream, plan);
+    BF_HIP(hipGetLastError());
+}
+
 int32_t bfhip_interpolate(bfhip_ctx* ctx, uint32_t* const* src_cols_h, uint32_t* const* dst_cols_h, uint32_t n_cols, uint32_t log_size, int32_t replicated) {
     API_CTX(ctx)
     Ctx& c = ctx->c;
@@ -496,17 +513,7 @@ int32_t bfhip_interpolate(bfhip_ctx* ctx, uint32_t* const* src_cols_h, uint32_t*
     if (!replicated && log_size < 3) throw HipError("circle transforms need log_size >= 3");
     if (log_size > c.tw_root_log + 1) throw HipError("log_size exceeds the context's twiddle tree");
     u32 log = replicated ? log_size - 4 : log_size;
-    c.stage_checkpoint();
-    StageBatch sb(c);
-    auto* s = c.stage(src_cols_h, n_cols);
-    auto* d = c.stage(dst_cols_h, n_cols);
-    const FftJob job{(const u32* const*)s, (u32* const*)d, n_cols, log, log, !replicated};
-    FftPlan plan;
-    fft_plan(plan, true, &job, 1, c.d_tw, c.d_itw, c.tw_root_log);
-    plan.d_groups = c.stage(plan.groups.data(), plan.groups.size());
-    sb.end();
-    fft_run(c.stream, plan);
-    BF_HIP(hipGetLastError());
+    fft_columns(c, true, FftJob{nullptr, nullptr, n_cols, log, log, !replicated}, src_cols_h, dst_cols_h);
     return 0;
     API_CATCH
 }
@@ -519,17 +526,7 @@ int32_t bfhip_evaluate(bfhip_ctx* ctx, uint32_t* const* coeff_cols_h, uint32_t* 
     if (!replicated && log_eval < 3) throw HipError("circle transforms need log_eval >= 3");
     if (log_eval > c.tw_root_log + 1) throw HipError("log_eval exceeds the context's twiddle tree");
     u32 sh = replicated ? 4 : 0;
-    c.stage_checkpoint();
-    StageBatch sb(c);
-    auto* s = c.stage(coeff_cols_h, n_cols);
-    auto* d = c.stage(dst_cols_h, n_cols);
-    const FftJob job{(const u32* const*)s, (u32* const*)d, n_cols, log_eval - sh, log_size - sh, !replicated};
-    FftPlan plan;
-    fft_plan(plan, false, &job, 1, c.d_tw, c.d_itw, c.tw_root_log);
-    plan.d_groups = c.stage(plan.groups.data(), plan.groups.size());
-    sb.end();
-    fft_run(c.stream, plan);
-    BF_HIP(hipGetLastError());
+    fft_columns(c, false, FftJob{nullptr, nullptr, n_cols, log_eval - sh, log_size - sh, !replicated}, coeff_cols_h, dst_cols_h);
     return 0;
     API_CATCH
 }
@@ -559,27 +556,30 @@ int32_t bfhip_is_first_lde(bfhip_ctx* ctx, uint32_t log_min, uint32_t log_max, u
     return 0;
     API_CATCH
 }
+// The 32 factors of a fold-by-halves evaluation at point_h = (x, y), staged: y, then x and its images under the doubling map x -> 2 x^2 - 1
+static const uint4* stage_point_factors(Ctx& c, const uint32_t point_h[8]) {
+    uint4 factors[32];
+    Q31 x = q_make(point_h[0], point_h[1], point_h[2], point_h[3]);
+    factors[0] = make_uint4(point_h[4], point_h[5], point_h[6], point_h[7]);
+    for (u32 b = 1; b < 32; b++) { factors[b] = make_uint4(x.a.a, x.a.b, x.b.a, x.b.b); Q31 s = q_mul(x, x); x = q_subm(q_add(s, s), 1); }
+    return c.stage(factors, 32);
+}
 int32_t bfhip_is_first_eval_at_point(bfhip_ctx* ctx, uint32_t log_size, const uint32_t point_h[8], uint32_t out_h[4]) {
     API_CTX(ctx)
     Ctx& c = ctx->c;
     if (!point_h || !out_h) throw HipError("null argument");
     if (log_size < 4 || log_size > 31 || log_size > c.tw_root_log + 1) throw HipError("is_first_eval_at_point: need 4 <= log_size within the context's twiddle tree");
     c.stage_checkpoint();
-    uint4 factors[32];
-    Q31 x = q_make(point_h[0], point_h[1], point_h[2], point_h[3]);
-    factors[0] = make_uint4(point_h[4], point_h[5], point_h[6], point_h[7]);
-    for (u32 b = 1; b < 32; b++) { factors[b] = make_uint4(x.a.a, x.a.b, x.b.a, x.b.b); Q31 s = q_mul(x, x); x = q_subm(q_add(s, s), 1); }
     IsFirstSample job{log_size, 0, 0};
     const IsFirstSample* dj = c.stage(&job, 1);
-    const uint4* df = c.stage(factors, 32);
+    const uint4* df = stage_point_factors(c, point_h);
+    uint4 r;      // declared before the guard: the copy into it has completed when it goes
+    DeviceScratch scratch(c);
     uint4* dout = nullptr;
-    BF_HIP(hipMalloc((void**)&dout, sizeof(uint4)));
+    scratch.alloc(&dout, sizeof(uint4));
     is_first_samples(c.stream, dj, 1, df, dout, c.d_itw, c.tw_root_log);
-    uint4 r;
-    hipError_t e = hipMemcpyAsync(&r, dout, sizeof(uint4), hipMemcpyDeviceToHost, c.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
-    (void)hipFree(dout);
-    BF_HIP(e);
+    BF_HIP(hipMemcpyAsync(&r, dout, sizeof(uint4), hipMemcpyDeviceToHost, c.stream));
+    BF_HIP(hipStreamSynchronize(c.stream));
     out_h[0] = r.x; out_h[1] = r.y; out_h[2] = r.z; out_h[3] = r.w;
     return 0;
     API_CATCH
@@ -604,34 +604,34 @@ int32_t bfhip_eval_at_point(bfhip_ctx* ctx, const uint32_t* coeffs_d, uint32_t l
     Ctx& c = ctx->c;
     if (replicated && log_size < 4) throw HipError("replicated columns need log_size >= 4");
     c.stage_checkpoint();
-    uint4 factors[32];
-    Q31 x = q_make(point_h[0], point_h[1], point_h[2], point_h[3]);
-    factors[0] = make_uint4(point_h[4], point_h[5], point_h[6], point_h[7]);
-    for (u32 b = 1; b < 32; b++) { factors[b] = make_uint4(x.a.a, x.a.b, x.b.a, x.b.b); Q31 s = q_mul(x, x); x = q_subm(q_add(s, s), 1); }
     EvalJob job{coeffs_d, replicated ? log_size - 4 : log_size, 0, replicated ? 4u : 0u, 0};
     const EvalJob* dj = c.stage(&job, 1);
-    const uint4* df = c.stage(factors, 32);
+    const uint4* df = stage_point_factors(c, point_h);
     u32 nchunks = job.log_n > 12 ? 1u << (job.log_n - 12) : 1u;
-    uint4* partials = nullptr; uint4* dout = nullptr;
-    BF_HIP(hipMalloc((void**)&partials, sizeof(uint4) * (nchunks + 1)));
-    dout = partials + nchunks;
+    uint4 r;      // declared before the guard: the copy into it has completed when it goes
+    DeviceScratch scratch(c);
+    uint4* partials = nullptr;
+    scratch.alloc(&partials, sizeof(uint4) * (nchunks + 1));
+    uint4* dout = partials + nchunks;
     eval_at_points(c.stream, dj, 1, nchunks, df, partials, dout);
-    uint4 r;
-    hipError_t e = hipMemcpyAsync(&r, dout, sizeof(uint4), hipMemcpyDeviceToHost, c.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
-    (void)hipFree(partials);
-    BF_HIP(e);
+    BF_HIP(hipMemcpyAsync(&r, dout, sizeof(uint4), hipMemcpyDeviceToHost, c.stream));
+    BF_HIP(hipStreamSynchronize(c.stream));
     out_h[0] = r.x; out_h[1] = r.y; out_h[2] = r.z; out_h[3] = r.w;
     return 0;
     API_CATCH
+}
+// Column descriptors of (pointer, shift) lists; no shifts = every column at full size
+static std::vector<ColDesc> col_descs(const uint32_t* const* cols_h, const uint32_t* col_shifts_h, uint32_t n_cols) {
+    std::vector<ColDesc> d(n_cols);
+    for (u32 k = 0; k < n_cols; k++) d[k] = ColDesc{cols_h[k], col_shifts_h ? col_shifts_h[k] : 0u, 0};
+    return d;
 }
 int32_t bfhip_merkle_commit_layer(bfhip_ctx* ctx, uint32_t log_size, const void* prev_layer_d, const uint32_t* const* cols_h, const uint32_t* col_shifts_h,
                                   uint32_t n_cols, void* out_hashes_d) {
     API_CTX(ctx)
     Ctx& c = ctx->c;
     c.stage_checkpoint();
-    std::vector<ColDesc> d(n_cols);
-    for (u32 k = 0; k < n_cols; k++) d[k] = ColDesc{cols_h[k], col_shifts_h ? col_shifts_h[k] : 0u, 0};
+    const std::vector<ColDesc> d = col_descs(cols_h, col_shifts_h, n_cols);
     const ColDesc* dd = n_cols ? c.stage(d.data(), n_cols) : nullptr;
     merkle_layer(c.stream, out_hashes_d, prev_layer_d, dd, n_cols, log_size, 0.0, 0, 0, c.conv.merkle_node_hash);
     BF_HIP(hipGetLastError());
@@ -643,8 +643,7 @@ int32_t bfhip_merkle_commit_layer_poseidon252(bfhip_ctx* ctx, uint32_t log_size,
     API_CTX(ctx)
     Ctx& c = ctx->c;
     c.stage_checkpoint();
-    std::vector<ColDesc> d(n_cols);
-    for (u32 k = 0; k < n_cols; k++) d[k] = ColDesc{cols_h[k], col_shifts_h ? col_shifts_h[k] : 0u, 0};
+    const std::vector<ColDesc> d = col_descs(cols_h, col_shifts_h, n_cols);
     const ColDesc* dd = n_cols ? c.stage(d.data(), n_cols) : nullptr;
     merkle_layer_poseidon(c.stream, out_hashes_d, prev_layer_d, dd, n_cols, log_size);
     BF_HIP(hipGetLastError());
@@ -750,14 +749,14 @@ int32_t bfhip_gather(bfhip_ctx* ctx, const uint32_t* col_d, const uint64_t* idx_
     Ctx& c = ctx->c;
     std::vector<GatherReq> req(n);
     for (size_t i = 0; i < n; i++) req[i] = GatherReq{col_d, idx_h[i], (u32)i, 1u};
+    DeviceScratch scratch(c);      // behind req: the copy from it has completed when the guard goes
     GatherReq* dreq = nullptr; u32* dout = nullptr;
-    BF_HIP(hipMalloc((void**)&dreq, sizeof(GatherReq) * (n + 1)));
-    hipError_t e = hipMalloc((void**)&dout, sizeof(u32) * (n + 1));
-    if (e == hipSuccess) e = hipMemcpyAsync(dreq, req.data(), sizeof(GatherReq) * n, hipMemcpyHostToDevice, c.stream);
-    if (e == hipSuccess) { gather_u32(c.stream, dreq, (u32)n, dout); e = hipMemcpyAsync(out_h, dout, sizeof(u32) * n, hipMemcpyDeviceToHost, c.stream); }
-    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
-    (void)hipFree(dreq); (void)hipFree(dout);
-    BF_HIP(e);
+    scratch.alloc(&dreq, sizeof(GatherReq) * (n + 1));
+    scratch.alloc(&dout, sizeof(u32) * (n + 1));
+    BF_HIP(hipMemcpyAsync(dreq, req.data(), sizeof(GatherReq) * n, hipMemcpyHostToDevice, c.stream));
+    gather_u32(c.stream, dreq, (u32)n, dout);
+    BF_HIP(hipMemcpyAsync(out_h, dout, sizeof(u32) * n, hipMemcpyDeviceToHost, c.stream));
+    BF_HIP(hipStreamSynchronize(c.stream));
     return 0;
     API_CATCH
 }
@@ -796,8 +795,10 @@ int32_t bfhip_logup_generate(bfhip_ctx* ctx, int32_t component, uint32_t log_siz
     for (int w = 0; w < 4; w++) L.out_last[w] = out_cols_h[4 * (nl - 1) + w];
     // scratch: vrow[M], wloc[M], totals[M / 1024 + 2], claimed[1]
     size_t n_tot = M / 1024 + 2;
+    uint4 r;      // declared before the guard: the copy into it has completed when it goes
+    DeviceScratch owner(c);
     uint4* scratch = nullptr;
-    BF_HIP(hipMalloc((void**)&scratch, sizeof(uint4) * (2 * M + n_tot + 1)));
+    owner.alloc(&scratch, sizeof(uint4) * (2 * M + n_tot + 1));
     L.vrow = scratch; L.wloc = scratch + M; L.totals = scratch + 2 * M; L.claimed = scratch + 2 * M + n_tot;
     L.el = lookups_from_h(lookup_h); L.log_rows = log_rows; L.comp = component;
     {
@@ -806,12 +807,9 @@ int32_t bfhip_logup_generate(bfhip_ctx* ctx, int32_t component, uint32_t log_siz
         c.stage_checkpoint();
         logup_batch_run(c.stream, c.stage(&lb, 1), lb);
     }
-    uint4 r;
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(&r, L.claimed, sizeof(uint4), hipMemcpyDeviceToHost, c.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
-    (void)hipFree(scratch);
-    BF_HIP(e);
+    BF_HIP(hipGetLastError());
+    BF_HIP(hipMemcpyAsync(&r, L.claimed, sizeof(uint4), hipMemcpyDeviceToHost, c.stream));
+    BF_HIP(hipStreamSynchronize(c.stream));
     claimed_sum_h[0] = r.x; claimed_sum_h[1] = r.y; claimed_sum_h[2] = r.z; claimed_sum_h[3] = r.w;
     return 0;
     API_CATCH
@@ -957,11 +955,10 @@ int32_t bfhip_accumulate_quotients(bfhip_ctx* ctx, uint32_t log_size, const uint
     API_CTX(ctx)
     Ctx& c = ctx->c;
     if (log_size < 3 || log_size > c.tw_root_log + 1) throw HipError("accumulate_quotients: log_size outside the twiddle tree");
-    std::vector<ColDesc> descs(n_cols);
+    const std::vector<ColDesc> descs = col_descs(cols_h, col_shifts_h, n_cols);
     std::vector<std::vector<ColumnSample>> samples(n_cols);
     size_t si = 0;
     for (u32 k = 0; k < n_cols; k++) {
-        descs[k] = ColDesc{cols_h[k], col_shifts_h ? col_shifts_h[k] : 0u, 0};
         if (descs[k].shift == 1) throw HipError("accumulate_quotients: column shift must be 0 or >= 2");
         for (u32 s = 0; s < n_samples_h[k]; s++, si++) {
             const uint32_t* p = sample_points_h + 8 * si;

@@ -1,7 +1,8 @@
 // The error boundary of the C ABI (include/bfhip.h): every extern "C" function that returns int32_t opens with API_TRY, API_CTX(ctx) or
 // API_POOL(pool) and closes with API_CATCH — the ONLY place where an exception becomes bfhip_set_error(...) and the return value -1, whatever
 // was thrown (nothing may unwind through extern "C"); a bf::TraceRejected (a proof's preflight) becomes BFHIP_TRACE_REJECTED. Codes other than -1 (-2 = "capacity", 1 = proof rejected) are returned by the entry
-// points themselves. Clean-up that has to run on failure is an inner `catch (...) { clean up; throw; }` in front of this boundary.
+// points themselves. Device memory of one call is owned by a scope guard (ctx.h: DeviceScratch, ArenaBorrow); other clean-up that has to run
+// on failure is an inner `catch (...) { clean up; throw; }` in front of this boundary.
 #pragma once
 #include "ctx.h"
 

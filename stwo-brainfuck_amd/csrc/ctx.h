@@ -367,6 +367,44 @@ struct StageBatch {
     ~StageBatch() { if (open) { if (--c.stage_batch_depth < 0) c.stage_batch_depth = 0; } }
 };
 
+// Device memory that lives for one call, from hipMalloc (the arena may belong to an open session). Going out of scope waits for the context's
+// stream — a launch of a call that failed half way may still use the memory — and frees. A guard declared before another owner is destroyed
+// after it: a call that also uses a second stream, or a session, declares the guard first and lets the other owner quiesce its own work.
+struct DeviceScratch {
+    Ctx& c; std::vector<void*> owned;
+    explicit DeviceScratch(Ctx& c_) : c(c_) {}
+    DeviceScratch(const DeviceScratch&) = delete; DeviceScratch& operator=(const DeviceScratch&) = delete;
+    // a failure leaves *p null and the thread's last error clear (as BF_HIP does): the caller words its own message
+    template <class T> hipError_t try_alloc(T** p, size_t bytes) {
+        *p = nullptr;
+        owned.reserve(owned.size() + 1);
+        hipError_t e = hipMalloc((void**)p, bytes);
+        if (e != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return e; }
+        owned.push_back(*p);
+        return e;
+    }
+    template <class T> void alloc(T** p, size_t bytes) { BF_HIP(try_alloc(p, bytes)); }
+    ~DeviceScratch() {
+        if (owned.empty()) return;
+        (void)hipStreamSynchronize(c.stream);
+        for (void* p : owned) (void)hipFree(p);
+    }
+};
+
+// Arena memory that lives for one call: what is allocated after construction is given back when the scope ends, behind a wait for the
+// context's stream (on the failure path kernels may still use it). The caller has waited for the stream before either of these:
+// rewind_now() gives the space back in the middle of the scope, for a call that goes on to reuse it (relations.hip); end() gives it back
+// for good, and the destructor has nothing left to do (as StageBatch::end) — the wait of its own is 20 us on an idle stream, which a
+// relation summary and a proof's preflight would pay on every good call.
+struct ArenaBorrow {
+    Ctx& c; const Arena::Mark mark; bool open = true;
+    explicit ArenaBorrow(Ctx& c_) : c(c_), mark(c_.arena.mark()) {}
+    ArenaBorrow(const ArenaBorrow&) = delete; ArenaBorrow& operator=(const ArenaBorrow&) = delete;
+    void rewind_now() { c.arena.rewind(mark); }
+    void end() { rewind_now(); open = false; }
+    ~ArenaBorrow() { if (open) { (void)hipStreamSynchronize(c.stream); rewind_now(); } }
+};
+
 }  // namespace bf
 
 struct bfhip_ctx { bf::Ctx c; };

@@ -130,53 +130,45 @@ extern "C" int32_t bfhip_logup_program_generate_batch(bfhip_ctx* ctx, const bfhi
 
     // scratch, never from the arena (an open session owns it): every component's v, wloc and totals as the single call has them, then the
     // 2 n tail words: exactly the sum of the single calls' allocations, each of which is within its stated bound
-    char* scratch = nullptr;
-    if (hipError_t e = hipMalloc((void**)&scratch, plan.bytes); e != hipSuccess) {
-        (void)hipGetLastError();
-        throw HipError(me + ": cannot allocate " + std::to_string(plan.bytes) + " bytes of scratch (" + hipGetErrorString(e) + ")");
-    }
     std::vector<uint4> tails(2 * (size_t)n);
-    try {
-        c.stage_checkpoint(need);
-        BF_HIP(hipMemsetAsync(scratch + plan.tails, 0xFF, 32 * (size_t)n, c.stream));
-        {
-            StageBatch sb(c);
-            std::map<const bfhip_logup*, u64> code_d;      // equal programs are staged once
-            std::vector<LogupProgLaunch> L(n);
-            for (u32 k = 0; k < n; k++) {
-                const bfhip_logup* lp = comps[k].program;
-                auto it = code_d.find(lp);
-                if (it == code_d.end()) it = code_d.emplace(lp, (u64)c.stage(lp->code.data(), lp->code.size())).first;
-                L[k].code = it->second;
-                inputs[k].stage(c, L[k].cols, L[k].params);
-                for (u32 j = 0; j < 4 * lp->n_logup_cols; j++) L[k].out[j] = (u64)comps[k].out_cols_h[j];
-                const LogupBatchScratch& s = plan.scratch[k];
-                L[k].v = (u64)(scratch + s.v); L[k].wloc = (u64)(scratch + s.wloc); L[k].totals = (u64)(scratch + s.totals);
-                L[k].tail = (u64)(scratch + plan.tails + 32 * (size_t)k);
-                L[k].n_instr = lp->n_instr; L[k].n_m = lp->n_m; L[k].log_size = log_sizes[k]; L[k].n_logup_cols = lp->n_logup_cols; L[k].nb = s.nb;
-            }
-            const LogupProgLaunch* d_launch = c.stage(L.data(), L.size());
-            const LogupBatchSeg* d_segs = c.stage(plan.segs.data(), plan.segs.size());
-            const u32* d_tile0 = c.stage(plan.tile0.data(), plan.tile0.size());
-            const u32* d_block0 = c.stage(plan.block0.data(), plan.block0.size());
-            sb.end();
-            for (const LogupBatchGroup& g : plan.groups) {
-                ProfScope ps(c.stream, "k_logup_program_batch", 0);
-                hipLaunchKernelGGL(k_logup_program_batch, dim3(g.blocks), dim3(PROGRAM_LANES), g.lds, c.stream, d_launch, d_segs + g.first, (u32)g.count);
-            }
-            ProfScope ps(c.stream, "k_logup_batch_scan", 0);
-            hipLaunchKernelGGL(k_logup_batch_scan, dim3(plan.tile0[n]), dim3(256), 0, c.stream, d_launch, d_tile0, n);
-            hipLaunchKernelGGL(k_logup_batch_totals, dim3(n), dim3(LP_CHUNK), 0, c.stream, d_launch);
-            hipLaunchKernelGGL(k_logup_batch_last, dim3(plan.block0[n]), dim3(256), 0, c.stream, d_launch, d_block0, n);
+    DeviceScratch owner(c);
+    char* scratch = nullptr;
+    if (hipError_t e = owner.try_alloc(&scratch, plan.bytes); e != hipSuccess)
+        throw HipError(me + ": cannot allocate " + std::to_string(plan.bytes) + " bytes of scratch (" + hipGetErrorString(e) + ")");
+    c.stage_checkpoint(need);
+    BF_HIP(hipMemsetAsync(scratch + plan.tails, 0xFF, 32 * (size_t)n, c.stream));
+    {
+        StageBatch sb(c);
+        std::map<const bfhip_logup*, u64> code_d;      // equal programs are staged once
+        std::vector<LogupProgLaunch> L(n);
+        for (u32 k = 0; k < n; k++) {
+            const bfhip_logup* lp = comps[k].program;
+            auto it = code_d.find(lp);
+            if (it == code_d.end()) it = code_d.emplace(lp, (u64)c.stage(lp->code.data(), lp->code.size())).first;
+            L[k].code = it->second;
+            inputs[k].stage(c, L[k].cols, L[k].params);
+            for (u32 j = 0; j < 4 * lp->n_logup_cols; j++) L[k].out[j] = (u64)comps[k].out_cols_h[j];
+            const LogupBatchScratch& s = plan.scratch[k];
+            L[k].v = (u64)(scratch + s.v); L[k].wloc = (u64)(scratch + s.wloc); L[k].totals = (u64)(scratch + s.totals);
+            L[k].tail = (u64)(scratch + plan.tails + 32 * (size_t)k);
+            L[k].n_instr = lp->n_instr; L[k].n_m = lp->n_m; L[k].log_size = log_sizes[k]; L[k].n_logup_cols = lp->n_logup_cols; L[k].nb = s.nb;
         }
-        BF_HIP(hipGetLastError());
-        c.read_back(tails.data(), scratch + plan.tails, 32 * (size_t)n);
-    } catch (...) {
-        (void)hipStreamSynchronize(c.stream);
-        (void)hipFree(scratch);
-        throw;
+        const LogupProgLaunch* d_launch = c.stage(L.data(), L.size());
+        const LogupBatchSeg* d_segs = c.stage(plan.segs.data(), plan.segs.size());
+        const u32* d_tile0 = c.stage(plan.tile0.data(), plan.tile0.size());
+        const u32* d_block0 = c.stage(plan.block0.data(), plan.block0.size());
+        sb.end();
+        for (const LogupBatchGroup& g : plan.groups) {
+            ProfScope ps(c.stream, "k_logup_program_batch", 0);
+            hipLaunchKernelGGL(k_logup_program_batch, dim3(g.blocks), dim3(PROGRAM_LANES), g.lds, c.stream, d_launch, d_segs + g.first, (u32)g.count);
+        }
+        ProfScope ps(c.stream, "k_logup_batch_scan", 0);
+        hipLaunchKernelGGL(k_logup_batch_scan, dim3(plan.tile0[n]), dim3(256), 0, c.stream, d_launch, d_tile0, n);
+        hipLaunchKernelGGL(k_logup_batch_totals, dim3(n), dim3(LP_CHUNK), 0, c.stream, d_launch);
+        hipLaunchKernelGGL(k_logup_batch_last, dim3(plan.block0[n]), dim3(256), 0, c.stream, d_launch, d_block0, n);
     }
-    BF_HIP(hipFree(scratch));
+    BF_HIP(hipGetLastError());
+    c.read_back(tails.data(), scratch + plan.tails, 32 * (size_t)n);
     u32 total[4] = {0, 0, 0, 0};
     for (u32 k = 0; k < n; k++) {
         const u64 key = ((u64)tails[2 * k + 1].y << 32) | tails[2 * k + 1].x;

@@ -58,38 +58,30 @@ extern "C" int32_t bfhip_logup_program_generate(bfhip_ctx* ctx, const bfhip_logu
     // 24 N + 16 (nb + 3) bytes with nb = ceil(N / 2048) tiles: at most 24 * 2^log_size + 2^log_size / 128 + 64
     const size_t N = size_t(1) << log_size, H = N / 2, nb = (H + LP_TILE - 1) / LP_TILE;
     const size_t bytes = sizeof(uint4) * (N + H + nb + 1 + 2);
-    uint4* scratch = nullptr;
-    if (hipError_t e = hipMalloc((void**)&scratch, bytes); e != hipSuccess) {
-        (void)hipGetLastError();
-        throw HipError(me + ": cannot allocate " + std::to_string(bytes) + " bytes of scratch (" + hipGetErrorString(e) + ")");
-    }
     uint4 tail[2];
-    try {
-        L.v = (u64)scratch; L.wloc = (u64)(scratch + N); L.totals = (u64)(scratch + N + H); L.tail = (u64)(scratch + N + H + nb + 1);
-        L.n_instr = lp->n_instr; L.n_m = lp->n_m; L.log_size = log_size; L.n_logup_cols = lp->n_logup_cols; L.nb = (u32)nb;
-        c.stage_checkpoint();
-        BF_HIP(hipMemsetAsync((void*)L.tail, 0xFF, 2 * sizeof(uint4), c.stream));
-        {
-            StageBatch sb(c);
-            L.code = (u64)c.stage(lp->code.data(), lp->code.size());
-            in.stage(c, L.cols, L.params);
-            const LogupProgLaunch* d_launch = c.stage(&L, 1);
-            sb.end();
-            const size_t lds = sizeof(u32) * PROGRAM_LANES * (lp->n_m + 4 * lp->n_q);
-            { ProfScope ps(c.stream, "k_logup_program", 0); hipLaunchKernelGGL(k_logup_program, dim3((u32)((N + PROGRAM_LANES - 1) / PROGRAM_LANES)), dim3(PROGRAM_LANES), lds, c.stream, d_launch); }
-            ProfScope ps(c.stream, "k_logup_program_scan", 0);
-            hipLaunchKernelGGL(k_logup_program_scan, dim3((u32)nb), dim3(256), 0, c.stream, d_launch);
-            hipLaunchKernelGGL(k_logup_program_totals, dim3(1), dim3(LP_CHUNK), 0, c.stream, d_launch);
-            hipLaunchKernelGGL(k_logup_program_last, dim3((u32)((N + 255) / 256)), dim3(256), 0, c.stream, d_launch);
-        }
-        BF_HIP(hipGetLastError());
-        c.read_back(tail, (const void*)L.tail, sizeof tail);
-    } catch (...) {
-        (void)hipStreamSynchronize(c.stream);
-        (void)hipFree(scratch);
-        throw;
+    DeviceScratch owner(c);
+    uint4* scratch = nullptr;
+    if (hipError_t e = owner.try_alloc(&scratch, bytes); e != hipSuccess)
+        throw HipError(me + ": cannot allocate " + std::to_string(bytes) + " bytes of scratch (" + hipGetErrorString(e) + ")");
+    L.v = (u64)scratch; L.wloc = (u64)(scratch + N); L.totals = (u64)(scratch + N + H); L.tail = (u64)(scratch + N + H + nb + 1);
+    L.n_instr = lp->n_instr; L.n_m = lp->n_m; L.log_size = log_size; L.n_logup_cols = lp->n_logup_cols; L.nb = (u32)nb;
+    c.stage_checkpoint();
+    BF_HIP(hipMemsetAsync((void*)L.tail, 0xFF, 2 * sizeof(uint4), c.stream));
+    {
+        StageBatch sb(c);
+        L.code = (u64)c.stage(lp->code.data(), lp->code.size());
+        in.stage(c, L.cols, L.params);
+        const LogupProgLaunch* d_launch = c.stage(&L, 1);
+        sb.end();
+        const size_t lds = sizeof(u32) * PROGRAM_LANES * (lp->n_m + 4 * lp->n_q);
+        { ProfScope ps(c.stream, "k_logup_program", 0); hipLaunchKernelGGL(k_logup_program, dim3((u32)((N + PROGRAM_LANES - 1) / PROGRAM_LANES)), dim3(PROGRAM_LANES), lds, c.stream, d_launch); }
+        ProfScope ps(c.stream, "k_logup_program_scan", 0);
+        hipLaunchKernelGGL(k_logup_program_scan, dim3((u32)nb), dim3(256), 0, c.stream, d_launch);
+        hipLaunchKernelGGL(k_logup_program_totals, dim3(1), dim3(LP_CHUNK), 0, c.stream, d_launch);
+        hipLaunchKernelGGL(k_logup_program_last, dim3((u32)((N + 255) / 256)), dim3(256), 0, c.stream, d_launch);
     }
-    BF_HIP(hipFree(scratch));
+    BF_HIP(hipGetLastError());
+    c.read_back(tail, (const void*)L.tail, sizeof tail);
     const u64 key = ((u64)tail[1].y << 32) | tail[1].x;
     if (key != ~u64(0)) throw HipError(me + ": fraction " + std::to_string(key & 0xFF) + " has a zero denominator at cell " + std::to_string(key >> 8));
     claimed_sum_h[0] = tail[0].x; claimed_sum_h[1] = tail[0].y; claimed_sum_h[2] = tail[0].z; claimed_sum_h[3] = tail[0].w;

@@ -80,7 +80,7 @@ void HipProver::preflight(const TraceInput& in) {
     const u32* const* tables[N_COMPONENTS];
     for (int k = 0; k < N_COMPONENTS; k++) { tables[k] = rows[k]; for (u32 j = 0; j < n_main_cols(k); j++) rows[k][j] = in.rows[k][j].ptr; }
 
-    const Arena::Mark arena_mark = c.arena.mark();
+    ArenaBorrow borrow(c);      // the logUp columns and scans: given back behind the read-back, or by a throw before it
     CheckReadback h_out{};
     for (int k = 0; k < N_COMPONENTS; k++) h_out.report[k] = check_report_init();
     const u32* inter[N_COMPONENTS][12] = {};
@@ -127,7 +127,7 @@ void HipProver::preflight(const TraceInput& in) {
     }
     BF_HIP(hipGetLastError());
     c.read_back(&h_out, d_out, sizeof h_out);      // the one host synchronisation of a passing preflight
-    c.arena.rewind(arena_mark);
+    borrow.end();      // relations_in_proof, below, borrows from the same mark on its own
     mark("preflight read back");
 
     int32_t n_bad = 0;
@@ -150,7 +150,6 @@ void HipProver::preflight(const TraceInput& in) {
         } catch (...) {
             for (auto& rr : rep.relations) rr = bfhip_relation_report{};
             rep.n_entries = 0;
-            c.arena.rewind(arena_mark);
             rep.seconds = now() - t_begin;
             throw;
         }

@@ -176,65 +176,59 @@ extern "C" int32_t bfhip_relation_program_summary(bfhip_ctx* ctx, const bfhip_re
     hipStream_t s = c.stream;
     // like a proof: nothing of this context is in flight, and its per-proof memory starts empty; the bookkeeping is put back at the end
     c.sync();
-    const Arena::Mark arena_mark = c.arena.mark();
-    try {
-        RpStaged staged;
-        rp_stage_tables(c, tables, n_tables, n_relations, staged);
-        const bf_u32x4* const* d_code = staged.code;
-        const bf_u32x4* const* d_cols = staged.cols;
-        for (u32 r = 0; r < n_relations; r++) {
-            bfhip_relation_report& rep = out[r];
-            rep = bfhip_relation_report{};
-            rep.relation = r; rep.n_words = first.relation_words[r];
-            u32 N = 0, row0[64] = {};
-            for (u32 t = 0; t < n_tables; t++) if (tables[t].program->entries_of[r]) { row0[t] = N; N += 1u << (tables[t].log_size - tables[t].row_shift); }
-            if (N == 0) continue;
-            c.sync();
-            c.arena.reset();
-            u32* counts = c.alloc_u32(N); u32* pos = c.alloc_u32(N); u32* tot = c.alloc_u32(N / RP_SCAN_TILE + 3);
-            RelProgLaunch L[64];
-            u32 n_part = 0;
-            for (u32 t = 0; t < n_tables; t++) {
-                const bfhip_relation_program& p = *tables[t].program;
-                if (!p.entries_of[r]) continue;
-                RelProgLaunch& l = L[n_part++];
-                l = RelProgLaunch{};
-                l.code = (u64)d_code[t]; l.cols = (u64)d_cols[t]; l.counts = (u64)(counts + row0[t]); l.pos = (u64)(pos + row0[t]);
-                l.n_instr = p.n_instr; l.rows = 1u << (tables[t].log_size - tables[t].row_shift); l.relation = r; l.n_words = rep.n_words; l.table = t;
-                l.n_m = p.n_m;
-            }
-            const u32* d_n;
-            {
-                ProfScope ps(s, "relation_program_count", 0);
-                const RelProgLaunch* d_L = c.stage(L, n_part);
-                for (u32 i = 0; i < n_part; i++)
-                    hipLaunchKernelGGL((k_relation_program<false, false>), dim3((L[i].rows + PROGRAM_LANES - 1) / PROGRAM_LANES), dim3(PROGRAM_LANES), sizeof(u32) * PROGRAM_LANES * L[i].n_m, s, d_L + i);
-                d_n = exclusive_scan_u32(s, counts, pos, tot, N);
-            }
-            u32 n = 0;
-            c.read_back(&n, d_n, sizeof n);
-            rep.n_entries = n;
-            if (n == 0) continue;
-            relation_aggregate(c, r, rep.n_words, n, cap_per_relation, rep, entries_h ? entries_h + size_t(r) * cap_per_relation : nullptr,
-                               [&](const RelEntries& e) {
-                                   for (u32 i = 0; i < n_part; i++) {
-                                       for (u32 k = 0; k < rep.n_words; k++) L[i].w[k] = (u64)e.w[k];
-                                       L[i].num = (u64)e.num; L[i].origin = (u64)e.origin;
-                                   }
-                                   const RelProgLaunch* d_L = c.stage(L, n_part);
-                                   for (u32 i = 0; i < n_part; i++)
-                                       hipLaunchKernelGGL((k_relation_program<true, false>), dim3((L[i].rows + PROGRAM_LANES - 1) / PROGRAM_LANES), dim3(PROGRAM_LANES), sizeof(u32) * PROGRAM_LANES * L[i].n_m, s, d_L + i);
-                               },
-                               "relation_program_emit");
-        }
+    ArenaBorrow borrow(c);
+    RpStaged staged;
+    rp_stage_tables(c, tables, n_tables, n_relations, staged);
+    const bf_u32x4* const* d_code = staged.code;
+    const bf_u32x4* const* d_cols = staged.cols;
+    for (u32 r = 0; r < n_relations; r++) {
+        bfhip_relation_report& rep = out[r];
+        rep = bfhip_relation_report{};
+        rep.relation = r; rep.n_words = first.relation_words[r];
+        u32 N = 0, row0[64] = {};
+        for (u32 t = 0; t < n_tables; t++) if (tables[t].program->entries_of[r]) { row0[t] = N; N += 1u << (tables[t].log_size - tables[t].row_shift); }
+        if (N == 0) continue;
         c.sync();
-        BF_HIP(hipGetLastError());
-    } catch (...) {
-        (void)hipStreamSynchronize(c.stream);
-        c.arena.rewind(arena_mark);
-        throw;
+        c.arena.reset();
+        u32* counts = c.alloc_u32(N); u32* pos = c.alloc_u32(N); u32* tot = c.alloc_u32(N / RP_SCAN_TILE + 3);
+        RelProgLaunch L[64];
+        u32 n_part = 0;
+        for (u32 t = 0; t < n_tables; t++) {
+            const bfhip_relation_program& p = *tables[t].program;
+            if (!p.entries_of[r]) continue;
+            RelProgLaunch& l = L[n_part++];
+            l = RelProgLaunch{};
+            l.code = (u64)d_code[t]; l.cols = (u64)d_cols[t]; l.counts = (u64)(counts + row0[t]); l.pos = (u64)(pos + row0[t]);
+            l.n_instr = p.n_instr; l.rows = 1u << (tables[t].log_size - tables[t].row_shift); l.relation = r; l.n_words = rep.n_words; l.table = t;
+            l.n_m = p.n_m;
+        }
+        const u32* d_n;
+        {
+            ProfScope ps(s, "relation_program_count", 0);
+            const RelProgLaunch* d_L = c.stage(L, n_part);
+            for (u32 i = 0; i < n_part; i++)
+                hipLaunchKernelGGL((k_relation_program<false, false>), dim3((L[i].rows + PROGRAM_LANES - 1) / PROGRAM_LANES), dim3(PROGRAM_LANES), sizeof(u32) * PROGRAM_LANES * L[i].n_m, s, d_L + i);
+            d_n = exclusive_scan_u32(s, counts, pos, tot, N);
+        }
+        u32 n = 0;
+        c.read_back(&n, d_n, sizeof n);
+        rep.n_entries = n;
+        if (n == 0) continue;
+        relation_aggregate(c, r, rep.n_words, n, cap_per_relation, rep, entries_h ? entries_h + size_t(r) * cap_per_relation : nullptr,
+                           [&](const RelEntries& e) {
+                               for (u32 i = 0; i < n_part; i++) {
+                                   for (u32 k = 0; k < rep.n_words; k++) L[i].w[k] = (u64)e.w[k];
+                                   L[i].num = (u64)e.num; L[i].origin = (u64)e.origin;
+                               }
+                               const RelProgLaunch* d_L = c.stage(L, n_part);
+                               for (u32 i = 0; i < n_part; i++)
+                                   hipLaunchKernelGGL((k_relation_program<true, false>), dim3((L[i].rows + PROGRAM_LANES - 1) / PROGRAM_LANES), dim3(PROGRAM_LANES), sizeof(u32) * PROGRAM_LANES * L[i].n_m, s, d_L + i);
+                           },
+                           "relation_program_emit");
     }
-    c.arena.rewind(arena_mark);
+    c.sync();
+    BF_HIP(hipGetLastError());
+    borrow.end();
     return 0;
     API_CATCH
 }
@@ -261,66 +255,60 @@ extern "C" int32_t bfhip_relation_program_multiplicities(bfhip_ctx* ctx, const b
     const u32 n_rows = 1u << (tables[target_table].log_size - tables[target_table].row_shift);
     // like a proof: nothing of this context is in flight, and its per-proof memory starts empty; the bookkeeping is put back at the end
     c.sync();
-    const Arena::Mark arena_mark = c.arena.mark();
-    try {
-        RpStaged staged;
-        rp_stage_tables(c, tables, n_tables, n_relations, staged);
-        bfhip_multiplicity_report rep{};
-        rep.relation = r; rep.n_words = n_words; rep.target_table = target_table; rep.target_entry = target_entry; rep.n_rows = n_rows;
-        u32 N = 0, row0[64] = {};
-        for (u32 t = 0; t < n_tables; t++) if (tables[t].program->entries_of[r]) { row0[t] = N; N += 1u << (tables[t].log_size - tables[t].row_shift); }
-        c.arena.reset();
-        u32* counts = c.alloc_u32(N); u32* pos = c.alloc_u32(N); u32* tot = c.alloc_u32(N / RP_SCAN_TILE + 3);
-        RelProgLaunch L[64];
-        u32 n_part = 0, target_part = 0;
-        for (u32 t = 0; t < n_tables; t++) {
-            const bfhip_relation_program& p = *tables[t].program;
-            if (!p.entries_of[r]) continue;
-            if (t == target_table) target_part = n_part;
-            RelProgLaunch& l = L[n_part++];
-            l = RelProgLaunch{};
-            l.code = (u64)staged.code[t]; l.cols = (u64)staged.cols[t]; l.counts = (u64)(counts + row0[t]); l.pos = (u64)(pos + row0[t]);
-            l.n_instr = p.n_instr; l.rows = 1u << (tables[t].log_size - tables[t].row_shift); l.relation = r; l.n_words = n_words; l.table = t;
-            l.n_m = p.n_m; l.target = target_entry;
-        }
-        auto launch = [&](bool emit) {
-            const RelProgLaunch* d_L = c.stage(L, n_part);
-            for (u32 i = 0; i < n_part; i++) {
-                const dim3 grid((L[i].rows + PROGRAM_LANES - 1) / PROGRAM_LANES);
-                const size_t lds = sizeof(u32) * PROGRAM_LANES * L[i].n_m;
-                if (i == target_part) {
-                    if (emit) hipLaunchKernelGGL((k_relation_program<true, true>), grid, dim3(PROGRAM_LANES), lds, s, d_L + i);
-                    else hipLaunchKernelGGL((k_relation_program<false, true>), grid, dim3(PROGRAM_LANES), lds, s, d_L + i);
-                } else {
-                    if (emit) hipLaunchKernelGGL((k_relation_program<true, false>), grid, dim3(PROGRAM_LANES), lds, s, d_L + i);
-                    else hipLaunchKernelGGL((k_relation_program<false, false>), grid, dim3(PROGRAM_LANES), lds, s, d_L + i);
-                }
-            }
-        };
-        const u32* d_n;
-        {
-            ProfScope ps(s, "relation_multiplicities_count", 0);
-            launch(false);
-            d_n = exclusive_scan_u32(s, counts, pos, tot, N);
-        }
-        u32 n = 0;
-        c.read_back(&n, d_n, sizeof n);      // n >= n_rows >= 1: the table side gives an entry at every row
-        relation_multiplicities(c, r, n_words, n, n_rows, out_d, cap, rep, missing_h, [&](const RelEntries& e) {
-            for (u32 i = 0; i < n_part; i++) {
-                for (u32 k = 0; k < n_words; k++) L[i].w[k] = (u64)e.w[k];
-                L[i].num = (u64)e.num; L[i].origin = (u64)e.origin;
-            }
-            launch(true);
-        });
-        c.sync();
-        BF_HIP(hipGetLastError());
-        *report = rep;
-    } catch (...) {
-        (void)hipStreamSynchronize(c.stream);
-        c.arena.rewind(arena_mark);
-        throw;
+    ArenaBorrow borrow(c);
+    RpStaged staged;
+    rp_stage_tables(c, tables, n_tables, n_relations, staged);
+    bfhip_multiplicity_report rep{};
+    rep.relation = r; rep.n_words = n_words; rep.target_table = target_table; rep.target_entry = target_entry; rep.n_rows = n_rows;
+    u32 N = 0, row0[64] = {};
+    for (u32 t = 0; t < n_tables; t++) if (tables[t].program->entries_of[r]) { row0[t] = N; N += 1u << (tables[t].log_size - tables[t].row_shift); }
+    c.arena.reset();
+    u32* counts = c.alloc_u32(N); u32* pos = c.alloc_u32(N); u32* tot = c.alloc_u32(N / RP_SCAN_TILE + 3);
+    RelProgLaunch L[64];
+    u32 n_part = 0, target_part = 0;
+    for (u32 t = 0; t < n_tables; t++) {
+        const bfhip_relation_program& p = *tables[t].program;
+        if (!p.entries_of[r]) continue;
+        if (t == target_table) target_part = n_part;
+        RelProgLaunch& l = L[n_part++];
+        l = RelProgLaunch{};
+        l.code = (u64)staged.code[t]; l.cols = (u64)staged.cols[t]; l.counts = (u64)(counts + row0[t]); l.pos = (u64)(pos + row0[t]);
+        l.n_instr = p.n_instr; l.rows = 1u << (tables[t].log_size - tables[t].row_shift); l.relation = r; l.n_words = n_words; l.table = t;
+        l.n_m = p.n_m; l.target = target_entry;
     }
-    c.arena.rewind(arena_mark);
+    auto launch = [&](bool emit) {
+        const RelProgLaunch* d_L = c.stage(L, n_part);
+        for (u32 i = 0; i < n_part; i++) {
+            const dim3 grid((L[i].rows + PROGRAM_LANES - 1) / PROGRAM_LANES);
+            const size_t lds = sizeof(u32) * PROGRAM_LANES * L[i].n_m;
+            if (i == target_part) {
+                if (emit) hipLaunchKernelGGL((k_relation_program<true, true>), grid, dim3(PROGRAM_LANES), lds, s, d_L + i);
+                else hipLaunchKernelGGL((k_relation_program<false, true>), grid, dim3(PROGRAM_LANES), lds, s, d_L + i);
+            } else {
+                if (emit) hipLaunchKernelGGL((k_relation_program<true, false>), grid, dim3(PROGRAM_LANES), lds, s, d_L + i);
+                else hipLaunchKernelGGL((k_relation_program<false, false>), grid, dim3(PROGRAM_LANES), lds, s, d_L + i);
+            }
+        }
+    };
+    const u32* d_n;
+    {
+        ProfScope ps(s, "relation_multiplicities_count", 0);
+        launch(false);
+        d_n = exclusive_scan_u32(s, counts, pos, tot, N);
+    }
+    u32 n = 0;
+    c.read_back(&n, d_n, sizeof n);      // n >= n_rows >= 1: the table side gives an entry at every row
+    relation_multiplicities(c, r, n_words, n, n_rows, out_d, cap, rep, missing_h, [&](const RelEntries& e) {
+        for (u32 i = 0; i < n_part; i++) {
+            for (u32 k = 0; k < n_words; k++) L[i].w[k] = (u64)e.w[k];
+            L[i].num = (u64)e.num; L[i].origin = (u64)e.origin;
+        }
+        launch(true);
+    });
+    c.sync();
+    BF_HIP(hipGetLastError());
+    borrow.end();
+    *report = rep;
     return 0;
     API_CATCH
 }

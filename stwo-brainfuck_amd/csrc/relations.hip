@@ -18,6 +18,7 @@
 // the scan, and writes each tuple's net into the looked-up table's column instead of reporting it.
 #include "../../include/bfhip.h"
 #include <cstring>
+#include <optional>
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 #include "kernels.h"
@@ -403,7 +404,9 @@ static void relations_run(Ctx& c, const RelTable* tables, u32 n_tables, bfhip_re
     if (total_rows > (u64(1) << 31)) throw HipError("more than 2^31 table rows in total");
     static const u32 N_WORDS[3] = {3, 3, 7};
     if (!in_proof) c.refuse_in_session("relation summary");
-    const Arena::Mark arena_mark = c.arena.mark();
+    // in a proof each relation's scratch is borrowed and given back on every path; outside one the arena is reset and left as it is
+    std::optional<ArenaBorrow> borrow;
+    if (in_proof) borrow.emplace(c);
     for (u32 r = 0; r < 3; r++) {
         RelSources S{};
         S.n_words = N_WORDS[r];
@@ -434,11 +437,11 @@ static void relations_run(Ctx& c, const RelTable* tables, u32 n_tables, bfhip_re
         }
         // like a proof: nothing of this context is in flight, and its per-proof memory starts empty
         c.sync();
-        if (in_proof) c.arena.rewind(arena_mark);
+        if (borrow) borrow->rewind_now();
         else { c.arena.reset(); c.stage_checkpoint(); }
         relation_run(c, r, S, N, cap, out[r], entries_h ? entries_h + size_t(r) * cap : nullptr);
     }
-    if (in_proof) { c.sync(); c.arena.rewind(arena_mark); }
+    if (borrow) { c.sync(); borrow->end(); }
     BF_HIP(hipGetLastError());
 }
 
