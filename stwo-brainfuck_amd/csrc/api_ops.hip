@@ -1,0 +1,306 @@
+// C ABI (include/bfhip.h): the backend-trait operations, one stwo `*Ops` call each over the gfx950 kernels. Plain pointers and sizes.
+#include "../../include/bfhip.h"
+#include "api_guard.h"
+#include "api_args.h"
+#include "pcs_types.h"
+#include "host/quotients.h"
+#include "host/hash.h"
+#include <algorithm>
+#include <vector>
+
+using namespace bf;
+
+// What bfhip_interpolate and bfhip_evaluate share behind their argument checks: the job's column lists staged, one plan, its launches
+static void fft_columns(Ctx& c, bool inverse, FftJob job, uint32_t* const* src_cols_h, uint32_t* const* dst_cols_h) {
+    c.stage_checkpoint();
+    StageBatch sb(c);
+    job.d_src = (const u32* const*)c.stage(src_cols_h, job.ncols);
+    job.d_dst = (u32* const*)c.stage(dst_cols_h, job.ncols);
+    FftPlan plan;
+    fft_plan(plan, inverse, &job, 1, c.d_tw, c.d_itw, c.tw_root_log);
+    plan.d_groups = c.stage(plan.groups.data(), plan.groups.size());
+    sb.end();
+    fft_run(c.stream, plan);
+    BF_HIP(hipGetLastError());
+}
+// The destination columns of bfhip_is_first_coeffs / bfhip_is_first_lde behind the checks the two share
+static IsFirstCols is_first_cols(const char* who, uint32_t log_min, uint32_t log_max, uint32_t* const* dst_cols_h) {
+    if (!dst_cols_h) throw HipError("null argument");
+    if (log_min < 4 || log_max < log_min || log_max - log_min >= 28) throw HipError(std::string(who) + ": need 4 <= log_min <= log_max < log_min + 28");
+    IsFirstCols a{}; a.log_min = log_min; a.log_max = log_max;
+    for (u32 n = log_min; n <= log_max; n++) a.ptr[n - log_min] = dst_cols_h[n - log_min];
+    return a;
+}
+// The 32 factors of a fold-by-halves evaluation at point_h = (x, y), staged: y, then x and its images under the doubling map x -> 2 x^2 - 1
+static const uint4* stage_point_factors(Ctx& c, const uint32_t point_h[8]) {
+    uint4 factors[32];
+    Q31 x = q_make(point_h[0], point_h[1], point_h[2], point_h[3]);
+    factors[0] = make_uint4(point_h[4], point_h[5], point_h[6], point_h[7]);
+    for (u32 b = 1; b < 32; b++) { factors[b] = make_uint4(x.a.a, x.a.b, x.b.a, x.b.b); Q31 s = q_mul(x, x); x = q_subm(q_add(s, s), 1); }
+    return c.stage(factors, 32);
+}
+// Column descriptors of (pointer, shift) lists; no shifts = every column at full size
+static std::vector<ColDesc> col_descs(const uint32_t* const* cols_h, const uint32_t* col_shifts_h, uint32_t n_cols) {
+    std::vector<ColDesc> d(n_cols);
+    for (u32 k = 0; k < n_cols; k++) d[k] = ColDesc{cols_h[k], col_shifts_h ? col_shifts_h[k] : 0u, 0};
+    return d;
+}
+// One Merkle layer over the previous layer and this size's columns, by the context's Blake2s convention or by Poseidon252
+static void merkle_commit_layer(Ctx& c, bool poseidon, uint32_t log_size, const void* prev_layer_d, const uint32_t* const* cols_h, const uint32_t* col_shifts_h, uint32_t n_cols,
+                                void* out_hashes_d) {
+    c.stage_checkpoint();
+    const std::vector<ColDesc> d = col_descs(cols_h, col_shifts_h, n_cols);
+    const ColDesc* dd = n_cols ? c.stage(d.data(), n_cols) : nullptr;
+    if (poseidon) merkle_layer_poseidon(c.stream, out_hashes_d, prev_layer_d, dd, n_cols, log_size);
+    else merkle_layer(c.stream, out_hashes_d, prev_layer_d, dd, n_cols, log_size, 0.0, 0, 0, c.conv.merkle_node_hash);
+    BF_HIP(hipGetLastError());
+}
+static const u32* stage_alpha(Ctx& c, const uint32_t alpha_h[4]) {
+    const Q31 a = q_from_h(alpha_h);
+    u32 w[8];
+    q31_words(a, w); q31_words(q_mul(a, a), w + 4);
+    c.stage_checkpoint();
+    return c.stage(w, 8);
+}
+
+extern "C" {
+
+int32_t bfhip_interpolate(bfhip_ctx* ctx, uint32_t* const* src_cols_h, uint32_t* const* dst_cols_h, uint32_t n_cols, uint32_t log_size, int32_t replicated) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    if (replicated && log_size < 4) throw HipError("replicated columns need log_size >= 4");
+    if (!replicated && log_size < 3) throw HipError("circle transforms need log_size >= 3");
+    if (log_size > c.tw_root_log + 1) throw HipError("log_size exceeds the context's twiddle tree");
+    u32 log = replicated ? log_size - 4 : log_size;
+    fft_columns(c, true, FftJob{nullptr, nullptr, n_cols, log, log, !replicated}, src_cols_h, dst_cols_h);
+    return 0;
+    API_CATCH
+}
+
+int32_t bfhip_evaluate(bfhip_ctx* ctx, uint32_t* const* coeff_cols_h, uint32_t* const* dst_cols_h, uint32_t n_cols, uint32_t log_size, uint32_t log_eval, int32_t replicated) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    if (log_eval < log_size) throw HipError("log_eval < log_size");
+    if (replicated && log_size < 4) throw HipError("replicated columns need log_size >= 4");
+    if (!replicated && log_eval < 3) throw HipError("circle transforms need log_eval >= 3");
+    if (log_eval > c.tw_root_log + 1) throw HipError("log_eval exceeds the context's twiddle tree");
+    u32 sh = replicated ? 4 : 0;
+    fft_columns(c, false, FftJob{nullptr, nullptr, n_cols, log_eval - sh, log_size - sh, !replicated}, coeff_cols_h, dst_cols_h);
+    return 0;
+    API_CATCH
+}
+
+int32_t bfhip_is_first_coeffs(bfhip_ctx* ctx, uint32_t log_min, uint32_t log_max, uint32_t* const* dst_cols_h) {
+    API_CTX(ctx)
+    const IsFirstCols a = is_first_cols("is_first_coeffs", log_min, log_max, dst_cols_h);
+    if (log_max > ctx->c.tw_root_log + 1) throw HipError("log_max exceeds the context's twiddle tree");
+    is_first_coeffs(ctx->c.stream, a, ctx->c.d_itw, ctx->c.tw_root_log);
+    BF_HIP(hipGetLastError());
+    return 0;
+    API_CATCH
+}
+int32_t bfhip_is_first_lde(bfhip_ctx* ctx, uint32_t log_min, uint32_t log_max, uint32_t log_blowup, uint32_t* const* dst_cols_h) {
+    API_CTX(ctx)
+    const IsFirstCols a = is_first_cols("is_first_lde", log_min, log_max, dst_cols_h);
+    if (log_blowup > 31 || log_max + log_blowup > ctx->c.tw_root_log + 1 || log_max + log_blowup > 31) throw HipError("log_max + log_blowup exceeds the context's twiddle tree");
+    is_first_lde(ctx->c.stream, a, log_blowup, ctx->c.d_tw, ctx->c.d_itw, ctx->c.tw_root_log);
+    BF_HIP(hipGetLastError());
+    return 0;
+    API_CATCH
+}
+int32_t bfhip_is_first_eval_at_point(bfhip_ctx* ctx, uint32_t log_size, const uint32_t point_h[8], uint32_t out_h[4]) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    if (!point_h || !out_h) throw HipError("null argument");
+    if (log_size < 4 || log_size > 31 || log_size > c.tw_root_log + 1) throw HipError("is_first_eval_at_point: need 4 <= log_size within the context's twiddle tree");
+    c.stage_checkpoint();
+    IsFirstSample job{log_size, 0, 0};
+    const IsFirstSample* dj = c.stage(&job, 1);
+    const uint4* df = stage_point_factors(c, point_h);
+    uint4 r;      // declared before the guard: the copy into it has completed when it goes
+    DeviceScratch scratch(c);
+    uint4* dout = nullptr;
+    scratch.alloc(&dout, sizeof(uint4));
+    is_first_samples(c.stream, dj, 1, df, dout, c.d_itw, c.tw_root_log);
+    read_q31(c, dout, r, out_h);
+    return 0;
+    API_CATCH
+}
+int32_t bfhip_broadcast16(bfhip_ctx* ctx, const uint32_t* rows_d, uint32_t* dst_d, size_t n_rows) {
+    API_CTX(ctx) broadcast16(ctx->c.stream, rows_d, dst_d, (u32)(n_rows * 16)); BF_HIP(hipGetLastError()); return 0; API_CATCH
+}
+int32_t bfhip_bit_reverse(bfhip_ctx* ctx, const uint32_t* src_d, uint32_t* dst_d, uint32_t log_size) {
+    API_CTX(ctx) if (src_d == dst_d) throw HipError("bit_reverse is out of place"); bit_reverse(ctx->c.stream, src_d, dst_d, log_size); BF_HIP(hipGetLastError()); return 0; API_CATCH
+}
+int32_t bfhip_batch_inverse_m31(bfhip_ctx* ctx, const uint32_t* src_d, uint32_t* dst_d, size_t n) {
+    API_CTX(ctx) batch_inverse_m31(ctx->c.stream, src_d, dst_d, (u32)n); BF_HIP(hipGetLastError()); return 0; API_CATCH
+}
+int32_t bfhip_batch_inverse_qm31(bfhip_ctx* ctx, const uint32_t* const src_d[4], uint32_t* const dst_d[4], size_t n) {
+    API_CTX(ctx) batch_inverse_qm31(ctx->c.stream, src_d, dst_d, (u32)n); BF_HIP(hipGetLastError()); return 0; API_CATCH
+}
+int32_t bfhip_accumulate(bfhip_ctx* ctx, uint32_t* dst_d, const uint32_t* src_d, size_t n) {
+    API_CTX(ctx) accumulate(ctx->c.stream, dst_d, src_d, (u32)n); BF_HIP(hipGetLastError()); return 0; API_CATCH
+}
+int32_t bfhip_eval_at_point(bfhip_ctx* ctx, const uint32_t* coeffs_d, uint32_t log_size, int32_t replicated, const uint32_t point_h[8], uint32_t out_h[4]) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    if (replicated && log_size < 4) throw HipError("replicated columns need log_size >= 4");
+    c.stage_checkpoint();
+    EvalJob job{coeffs_d, replicated ? log_size - 4 : log_size, 0, replicated ? 4u : 0u, 0};
+    const EvalJob* dj = c.stage(&job, 1);
+    const uint4* df = stage_point_factors(c, point_h);
+    u32 nchunks = job.log_n > 12 ? 1u << (job.log_n - 12) : 1u;
+    uint4 r;      // declared before the guard: the copy into it has completed when it goes
+    DeviceScratch scratch(c);
+    uint4* partials = nullptr;
+    scratch.alloc(&partials, sizeof(uint4) * (nchunks + 1));
+    uint4* dout = partials + nchunks;
+    eval_at_points(c.stream, dj, 1, nchunks, df, partials, dout);
+    read_q31(c, dout, r, out_h);
+    return 0;
+    API_CATCH
+}
+int32_t bfhip_merkle_commit_layer(bfhip_ctx* ctx, uint32_t log_size, const void* prev_layer_d, const uint32_t* const* cols_h, const uint32_t* col_shifts_h,
+                                  uint32_t n_cols, void* out_hashes_d) {
+    API_CTX(ctx) merkle_commit_layer(ctx->c, false, log_size, prev_layer_d, cols_h, col_shifts_h, n_cols, out_hashes_d); return 0; API_CATCH
+}
+int32_t bfhip_merkle_commit_layer_poseidon252(bfhip_ctx* ctx, uint32_t log_size, const void* prev_layer_d, const uint32_t* const* cols_h, const uint32_t* col_shifts_h,
+                                             uint32_t n_cols, void* out_hashes_d) {
+    API_CTX(ctx) merkle_commit_layer(ctx->c, true, log_size, prev_layer_d, cols_h, col_shifts_h, n_cols, out_hashes_d); return 0; API_CATCH
+}
+int32_t bfhip_hades_permutation(bfhip_ctx* ctx, const uint32_t in_h[24], uint32_t out_h[24]) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    c.stage_checkpoint();
+    u32* din = (u32*)c.stage(in_h, 24);
+    u32* dout = (u32*)c.stage(in_h, 24);
+    hades_once(c.stream, din, dout);
+    BF_HIP(hipMemcpyAsync(out_h, dout, 24 * sizeof(u32), hipMemcpyDeviceToHost, c.stream));
+    c.sync();
+    return 0;
+    API_CATCH
+}
+int32_t bfhip_fold_line(bfhip_ctx* ctx, const uint32_t* const src_d[4], uint32_t* const dst_d[4], uint32_t log_size, const uint32_t alpha_h[4]) {
+    API_CTX(ctx)
+    if (log_size < 1 || log_size > ctx->c.tw_root_log) throw HipError("fold_line: log_size outside the twiddle tree");
+    fold_line(ctx->c.stream, dst_d, src_d, stage_alpha(ctx->c, alpha_h), ctx->c.d_itw, ctx->c.tw_root_log, log_size); BF_HIP(hipGetLastError()); return 0;
+    API_CATCH
+}
+int32_t bfhip_fold_circle_into_line(bfhip_ctx* ctx, uint32_t* const dst_d[4], const uint32_t* const src_d[4], uint32_t log_size, const uint32_t alpha_h[4]) {
+    API_CTX(ctx)
+    if (log_size < 3 || log_size > ctx->c.tw_root_log + 1) throw HipError("fold_circle_into_line: log_size outside the twiddle tree");
+    fold_circle_into_line(ctx->c.stream, dst_d, src_d, stage_alpha(ctx->c, alpha_h), ctx->c.d_itw, ctx->c.tw_root_log, log_size); BF_HIP(hipGetLastError()); return 0;
+    API_CATCH
+}
+int32_t bfhip_fri_fold_leaf(bfhip_ctx* ctx, const uint32_t* const src_d[4], const uint32_t* const quot_d[4], uint32_t* const dst_d[4], uint32_t log_size,
+                            const uint32_t alpha_h[4], void* out_hashes_d) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    if (!src_d && !quot_d) throw HipError("fri_fold_leaf: neither a line source nor a circle evaluation");
+    if (!dst_d || !alpha_h || !out_hashes_d) throw HipError("fri_fold_leaf: null argument");
+    if (log_size < 2 || log_size + 1 > c.tw_root_log + (src_d ? 0u : 1u)) throw HipError("fri_fold_leaf: log_size outside the twiddle tree");
+    FriFoldLeafArgs fa{};
+    for (int w = 0; w < 4; w++) { fa.src[w] = src_d ? src_d[w] : nullptr; fa.quot[w] = quot_d ? quot_d[w] : nullptr; fa.dst[w] = dst_d[w]; }
+    fa.alpha8 = stage_alpha(c, alpha_h); fa.itw = c.d_itw; fa.tw_total = 1u << c.tw_root_log; fa.log = log_size;
+    fri_fold_leaf(c.stream, out_hashes_d, fa, !src_d ? FF_CIRCLE : quot_d ? FF_LINE_CIRCLE : FF_LINE, c.conv.merkle_node_hash);
+    BF_HIP(hipGetLastError());
+    return 0;
+    API_CATCH
+}
+int32_t bfhip_grind(bfhip_ctx* ctx, const uint8_t digest_h[32], uint32_t pow_bits, uint64_t* nonce) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    c.stage_checkpoint();
+    u32* d_digest = (u32*)c.stage(digest_h, 32);
+    unsigned long long init = ~0ull, best = ~0ull;
+    unsigned long long* d_best = c.stage(&init, 1);
+    const u32 span = 1u << 20;
+    for (u64 base = 0; best == ~0ull; base += span) {
+        grind_span(c.stream, d_digest, base, span, pow_bits, d_best, c.conv.mix_u64);
+        BF_HIP(hipMemcpyAsync(&best, d_best, 8, hipMemcpyDeviceToHost, c.stream));
+        c.sync();
+        if (base > (u64(1) << 40)) throw HipError("grind: no nonce found below 2^40");
+    }
+    *nonce = best;
+    return 0;
+    API_CATCH
+}
+// Spans start at start_nonce and are scanned in order, so the first span with a hit holds the smallest nonce. Span per launch: 2^clamp(pow_bits - 4, 12, 20)
+// — twice the expected 2^(pow_bits - 5) tries, at least 64 waves, at most ~1.4 ms of the GPU per launch.
+int32_t bfhip_grind_poseidon252(bfhip_ctx* ctx, const uint8_t digest_h[32], uint32_t pow_bits, uint64_t start_nonce, uint64_t* nonce, uint64_t* tried) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    if (!digest_h || !nonce) throw HipError("grind_poseidon252: null argument");
+    if (pow_bits > BFHIP_MAX_POW_BITS) throw HipError("grind_poseidon252: pow_bits must be at most 32, got " + std::to_string(pow_bits));
+    if (!fe252::canonical_bytes_in_range(digest_h)) throw HipError("grind_poseidon252: digest is not a canonical felt252");
+    c.stage_checkpoint();
+    u32* d_digest = (u32*)c.stage(digest_h, 32);
+    unsigned long long init = ~0ull, best = ~0ull;
+    unsigned long long* d_best = c.stage(&init, 1);
+    const u32 log_span = std::min(std::max(pow_bits, 16u) - 4u, 20u);
+    const u64 span = u64(1) << log_span, limit = u64(64) << (std::max(pow_bits, 8u) - 5u);      // a legitimate miss of `limit` nonces: e^-64
+    u64 scanned = 0;
+    while (best == ~0ull) {
+        if (scanned >= limit) throw HipError("grind_poseidon252: no nonce found");
+        const u64 base = start_nonce + scanned;
+        if (base < start_nonce || base + (span - 1) < base) throw HipError("grind_poseidon252: the scan would wrap past 2^64");
+        grind_poseidon_span(c.stream, d_digest, base, (u32)span, pow_bits, d_best);
+        BF_HIP(hipGetLastError());
+        BF_HIP(hipMemcpyAsync(&best, d_best, 8, hipMemcpyDeviceToHost, c.stream));
+        c.sync();
+        scanned += span;
+    }
+    *nonce = best;
+    if (tried) *tried = scanned;
+    return 0;
+    API_CATCH
+}
+int32_t bfhip_gather(bfhip_ctx* ctx, const uint32_t* col_d, const uint64_t* idx_h, size_t n, uint32_t* out_h) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    std::vector<GatherReq> req(n);
+    for (size_t i = 0; i < n; i++) req[i] = GatherReq{col_d, idx_h[i], (u32)i, 1u};
+    DeviceScratch scratch(c);      // behind req: the copy from it has completed when the guard goes
+    GatherReq* dreq = nullptr; u32* dout = nullptr;
+    scratch.alloc(&dreq, sizeof(GatherReq) * (n + 1));
+    scratch.alloc(&dout, sizeof(u32) * (n + 1));
+    BF_HIP(hipMemcpyAsync(dreq, req.data(), sizeof(GatherReq) * n, hipMemcpyHostToDevice, c.stream));
+    gather_u32(c.stream, dreq, (u32)n, dout);
+    BF_HIP(hipMemcpyAsync(out_h, dout, sizeof(u32) * n, hipMemcpyDeviceToHost, c.stream));
+    BF_HIP(hipStreamSynchronize(c.stream));
+    return 0;
+    API_CATCH
+}
+int32_t bfhip_accumulate_quotients(bfhip_ctx* ctx, uint32_t log_size, const uint32_t* const* cols_h, const uint32_t* col_shifts_h, uint32_t n_cols,
+                                   const uint32_t* n_samples_h, const uint32_t* sample_points_h, const uint32_t* sample_values_h,
+                                   const uint32_t random_coeff_h[4], uint32_t* const out_d[4]) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    if (log_size < 3 || log_size > c.tw_root_log + 1) throw HipError("accumulate_quotients: log_size outside the twiddle tree");
+    const std::vector<ColDesc> descs = col_descs(cols_h, col_shifts_h, n_cols);
+    std::vector<std::vector<ColumnSample>> samples(n_cols);
+    size_t si = 0;
+    for (u32 k = 0; k < n_cols; k++) {
+        if (descs[k].shift == 1) throw HipError("accumulate_quotients: column shift must be 0 or >= 2");
+        for (u32 s = 0; s < n_samples_h[k]; s++, si++) {
+            const uint32_t* p = sample_points_h + 8 * si;
+            samples[k].push_back({PtQ{q_from_h(p), q_from_h(p + 4)}, q_from_h(sample_values_h + 4 * si)});
+        }
+    }
+    std::vector<QuotientBatch> batches; std::vector<QuotientEntry> entries;
+    build_quotient_batches(samples, q_from_h(random_coeff_h), batches, entries);
+    quotient_entries_finish(batches.data(), batches.size(), entries.data(), descs.data());
+    c.stage_checkpoint();
+    QuotientArgs a{};
+    a.batches = batches.empty() ? nullptr : c.stage(batches.data(), batches.size());
+    a.entries = entries.empty() ? nullptr : c.stage(entries.data(), entries.size());
+    a.n_batches = (u32)batches.size(); a.log = log_size; a.tw = c.d_tw; a.tw_total = 1u << c.tw_root_log;
+    for (int w = 0; w < 4; w++) a.out[w] = out_d[w];
+    const u32 blocks = quotient_groups_layout(&a, 1);
+    accumulate_quotients(c.stream, c.stage(&a, 1), 1, blocks);
+    BF_HIP(hipGetLastError());
+    return 0;
+    API_CATCH
+}
+
+}  // extern "C"

@@ -409,6 +409,6 @@ struct ArenaBorrow {
 
 struct bfhip_ctx { bf::Ctx c; };
 void bfhip_set_error(const std::string& s);
-// api.hip: a bfhip_pcs_config checked against the accepted ranges (throws with the reason); NULL = the defaults.
+// pcs_host.hip: a bfhip_pcs_config checked against the accepted ranges (throws with the reason); NULL = the defaults.
 struct bfhip_pcs_config;
 bf::PcsConfig pcs_config_from(const bfhip_pcs_config* p);

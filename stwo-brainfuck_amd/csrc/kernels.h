@@ -241,7 +241,7 @@ void check_batch_init(CheckBatch& b, const u32 log_sizes[N_COMPONENTS], CheckRea
 // k_check_batch (cells of all 13 components) followed by k_check_first_batch (13 waves + one for the total); d_launches: 13 CheckLaunch
 void check_batch_run(hipStream_t stream, const CheckBatch* d_batch, const CheckBatch& h_batch, const CheckLaunch* d_launches);
 
-// prover.hip — the row-granular main-trace columns and the log sizes of a resident trace (for bfhip_trace_check in api.hip)
+// prover.hip — the row-granular main-trace columns and the log sizes of a resident trace (for bfhip_trace_check in api_air.hip)
 void trace_columns(const bfhip_trace* t, const u32* cols[N_COMPONENTS][13], u32 log_sizes[N_COMPONENTS]);
 
 // tables.hip — u32 exclusive scan over tiles of 2048 (wraps mod 2^32): out[i] = sum_{j<i} in[j], in == out allowed; returns a device pointer

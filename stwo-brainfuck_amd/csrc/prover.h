@@ -104,7 +104,7 @@ struct SharedPreprocessed {
     }
 };
 
-// ---- the AIRs asserted on the trace domain (check.hip): what bfhip_check_constraints / bfhip_trace_check (api.hip) and a proof's preflight
+// ---- the AIRs asserted on the trace domain (check.hip): what bfhip_check_constraints / bfhip_trace_check (api_air.hip) and a proof's preflight
 // (prover_preflight.hip) share --------------------------------------------------------------------------------------------------------------
 inline CheckReportDev check_report_init() { CheckReportDev r{}; r.first_bad_cell = ~u64(0); r.first_bad_constraint = 0xffffffffu; return r; }
 inline void check_report_fill(bfhip_check_report& out, const CheckReportDev& r, int component, u32 log_size, Q31 claimed) {
@@ -124,6 +124,31 @@ inline CheckLaunch check_launch_of(int component, u32 log_size, const u32* const
     for (u32 j = 0; j < n_inter; j++) L.inter[j] = ColDesc{logup_cols[j], j + 4 < n_inter ? LOG_N_LANES : 0u, 0};
     L.el = el; L.total_sum = total_sum; L.log_size = log_size; L.report = d_report;
     return L;
+}
+// The logUp pass of a whole-trace check: the 13 launches of logup_batch_init over the row-granular tables, their storage taken from the
+// arena — per component the logUp coordinate columns (inter[k][j]; the last logUp column full size, earlier ones row-granular), then vrow,
+// wloc and totals. d_claimed: the device address of the 13 claimed-sum slots. Every log size lies in [LOG_N_LANES, 29].
+static inline std::vector<LogupLaunch> check_logup_launches(Ctx& c, const u32* rows[N_COMPONENTS][13], const u32 log_sizes[N_COMPONENTS], uint4* d_claimed,
+                                                     const u32* inter[N_COMPONENTS][12]) {
+    std::vector<LogupLaunch> logups(N_COMPONENTS);
+    for (int k = 0; k < N_COMPONENTS; k++) {
+        const u32 log_rows = log_sizes[k] - LOG_N_LANES, nl = n_logup_cols(k);
+        const size_t M = size_t(1) << log_rows;
+        LogupLaunch L{};
+        for (u32 j = 0; j < n_main_cols(k); j++) L.cols[j] = rows[k][j];
+        for (u32 j = 0; j < 4 * nl; j++) {
+            u32* p = c.alloc_u32(j + 4 < 4 * nl ? M : 16 * M);
+            inter[k][j] = p;
+            if (j + 4 < 4 * nl) L.out_rep[j] = p; else L.out_last[j - 4 * (nl - 1)] = p;
+        }
+        L.vrow = c.arena.alloc(sizeof(uint4) * M);
+        L.wloc = c.arena.alloc(sizeof(uint4) * M);
+        L.totals = c.arena.alloc(sizeof(uint4) * (M / 1024 + 2));
+        L.claimed = d_claimed + k;
+        L.log_rows = log_rows; L.comp = k;
+        logups[k] = L;
+    }
+    return logups;
 }
 // The lookup elements of bfhip_trace_check(.., NULL, ..): MemoryElements::draw, InstructionElements::draw, ProcessorElements::draw
 // (mod.rs:589-597) on Blake2sChannel::default()

@@ -515,7 +515,7 @@ BrainfuckProof HipProver::prove(const std::function<const TraceInput&()>& get_in
 
 }  // namespace bf
 
-// api.hip (bfhip_trace_check): the row-granular main-trace columns and the log sizes of a resident trace
+// api_air.hip (bfhip_trace_check): the row-granular main-trace columns and the log sizes of a resident trace
 void bf::trace_columns(const bfhip_trace* t, const u32* cols[N_COMPONENTS][13], u32 log_sizes[N_COMPONENTS]) {
     for (int k = 0; k < N_COMPONENTS; k++) {
         log_sizes[k] = t->in.log_sizes[k];

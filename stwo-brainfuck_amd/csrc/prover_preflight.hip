@@ -84,28 +84,11 @@ void HipProver::preflight(const TraceInput& in) {
     CheckReadback h_out{};
     for (int k = 0; k < N_COMPONENTS; k++) h_out.report[k] = check_report_init();
     const u32* inter[N_COMPONENTS][12] = {};
-    std::vector<LogupLaunch> logups(N_COMPONENTS);
     CheckReadback* d_out = nullptr;
     {
         StageBatch sb(c);
         d_out = c.stage(&h_out, 1);
-        for (int k = 0; k < N_COMPONENTS; k++) {
-            const u32 log_rows = in.log_sizes[k] - LOG_N_LANES, nl = n_logup_cols(k);
-            const size_t M = size_t(1) << log_rows;
-            LogupLaunch L{};
-            for (u32 j = 0; j < n_main_cols(k); j++) L.cols[j] = rows[k][j];
-            for (u32 j = 0; j < 4 * nl; j++) {
-                u32* p = c.alloc_u32(j + 4 < 4 * nl ? M : 16 * M);
-                inter[k][j] = p;
-                if (j + 4 < 4 * nl) L.out_rep[j] = p; else L.out_last[j - 4 * (nl - 1)] = p;
-            }
-            L.vrow = c.arena.alloc(sizeof(uint4) * M);
-            L.wloc = c.arena.alloc(sizeof(uint4) * M);
-            L.totals = c.arena.alloc(sizeof(uint4) * (M / 1024 + 2));
-            L.claimed = &d_out->claimed[k];
-            L.log_rows = log_rows; L.comp = k;
-            logups[k] = L;
-        }
+        const std::vector<LogupLaunch> logups = check_logup_launches(c, rows, in.log_sizes, d_out->claimed, inter);
         LogupBatch lb;
         logup_batch_init(lb, el, logups.data(), N_COMPONENTS);
         const LogupBatch* d_lb = c.stage(&lb, 1);

@@ -23,6 +23,7 @@
 #include <rocprim/rocprim.hpp>
 #include "kernels.h"
 #include "api_guard.h"
+#include "api_args.h"
 #include "air.h"
 
 namespace bf {
@@ -394,9 +395,7 @@ static void relations_run(Ctx& c, const RelTable* tables, u32 n_tables, bfhip_re
     u64 total_rows = 0;
     for (u32 t = 0; t < n_tables; t++) {
         const RelTable& T = tables[t];
-        if (T.component < 0 || T.component >= N_COMPONENTS) throw HipError("unknown component");
-        if (T.log_size < LOG_N_LANES) throw HipError("component log_size below LOG_N_LANES (4)");
-        if (T.log_size > 29) throw HipError("component log_size above 29: columns hold at most 2^29 cells");
+        check_component(T.component, T.log_size);
         if (!T.cols) throw HipError("null main column array");
         for (u32 j = 0; j < n_main_cols(T.component); j++) if (!T.cols[j]) throw HipError("null main column pointer");
         total_rows += u64(1) << (T.log_size - LOG_N_LANES);

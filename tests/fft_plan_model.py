@@ -4,7 +4,7 @@ choose and to label test cases (tests/test_fft_plan_model_cpu.py holds every cas
 tests/test_gpu_pcs_commit_large.py to the property it is named for; one GPU test holds the model to the workgroup totals the library
 reports). It is never the reference of a value: values are compared with the CPU oracle.
 
-A job is (inverse, log, src_log, ncols) as api.hip builds it: interpolate(log) = (True, log, log, n), evaluate(log -> log_eval) =
+A job is (inverse, log, src_log, ncols) as api_ops.hip builds it: interpolate(log) = (True, log, log, n), evaluate(log -> log_eval) =
 (False, log_eval, log, n). Row-granular ("replicated") columns are the same job 4 levels lower in line mode, which changes no shape.
 
 Lines restated (fft.hip):

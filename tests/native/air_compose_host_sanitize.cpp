@@ -15,7 +15,7 @@
 #include <string>
 #include <vector>
 
-// what api.hip provides inside the library
+// what api_ctx.hip provides inside the library
 static std::string g_error;
 void bfhip_set_error(const std::string& s) { g_error = s; }
 

@@ -27,7 +27,7 @@ def test_library_exports_every_declared_symbol(pkg):
 
 def test_default_library_has_no_test_hooks():
     """The release build must not contain the test hooks: no lookup of a mock's symbol, no environment variable that makes it
-    dlopen an arbitrary path, no host delay for the mailboxes. The hooks build (same sources, -DBFHIP_TEST_HOOKS in api.hip / comm.hip / prover_fri.hip) has them and
+    dlopen an arbitrary path, no host delay for the mailboxes. The hooks build (same sources, -DBFHIP_TEST_HOOKS in ctx.hip / api_ctx.hip / api_testhooks.hip / comm.hip / prover_fri.hip / prover_commit.hip / pcs.hip) has them and
     exports the same entry points."""
     pkg_dir = os.path.join(ROOT, "stwo-brainfuck_amd")
     blob = open(os.path.join(pkg_dir, "libbfhip.so"), "rb").read()
