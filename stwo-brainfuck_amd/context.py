@@ -1,6 +1,8 @@
 """One GPU as the library sees it: the device functions, the byte-level conventions and the PcsConfig (both by-value structs), shard
 groups, and Context — the stream, the twiddles and every per-operation entry point (stwo's backend trait surface)."""
+import contextlib
 import ctypes
+import json
 import weakref
 
 import numpy as np
@@ -208,6 +210,32 @@ class Context(Owned):
         out = (ctypes.c_uint64 * 4)()
         _check(abi().bfhip_ctx_memory(self._h, out))
         return dict(zip(("arena_reserved", "arena_peak", "twiddles", "arena_in_use"), [int(v) for v in out]))
+
+    # -- the per-kernel profiler (HIP events around every instrumented launch) ----------------------------------------------------------
+    def profile_enable(self, mode=1):
+        """bfhip_profile_enable: 0 off, 1 every instrumented kernel, 2 only k_merkle_layer (the dominant kernel; lowest overhead)."""
+        _check(abi().bfhip_profile_enable(self._h, int(mode)))
+
+    def profile_reset(self):
+        """bfhip_profile_reset: forgets the records so far; the mode stays."""
+        _check(abi().bfhip_profile_reset(self._h))
+
+    def profile_report(self):
+        """bfhip_profile_report as a dict: {scope: {"calls": n, "total_ms": t, "bytes": b, ...}, ...} since the last reset."""
+        js = ctypes.c_void_p()
+        _check(abi().bfhip_profile_report(self._h, ctypes.byref(js)))
+        return json.loads(_take_host_string(js))
+
+    @contextlib.contextmanager
+    def profiling(self, mode=1):
+        """with ctx.profiling(): the profiler on and reset for the block, off again behind it (also when the block raises). Read
+        profile_report() inside the block."""
+        self.profile_enable(mode)
+        try:
+            self.profile_reset()
+            yield self
+        finally:
+            self.profile_enable(0)
 
     def set_table_builder(self, on_gpu=True):
         """Where this context builds the 13 component tables: GPU kernels (default) or the host builders. Identical results."""

@@ -20,18 +20,14 @@ def main():
     out = []
 
     def report():
-        js = ctypes.c_void_p()
-        pkg._check(lib.bfhip_profile_report(ctx._h, ctypes.byref(js)))
-        rep = json.loads(ctypes.string_at(js).decode())
-        lib.bfhip_free_host(js)
-        return {k: v["calls"] for k, v in rep.items() if k.startswith("k_fft")}
+        return {k: v["calls"] for k, v in ctx.profile_report().items() if k.startswith("k_fft")}
 
     def run(inverse, log, src_log, ncols):
         src = [ctx.malloc(4 << src_log) for _ in range(ncols)]
         dst = src if inverse else [ctx.malloc(4 << log) for _ in range(ncols)]
         for p in src:
             pkg._check(lib.bfhip_memset_zero(ctx._h, ctypes.c_void_p(p), ctypes.c_size_t(4 << src_log)))
-        pkg._check(lib.bfhip_profile_reset(ctx._h))
+        ctx.profile_reset()
         if inverse:
             ctx.interpolate(src, dst, log)
         else:
@@ -42,14 +38,14 @@ def main():
             ctx.free(p)
 
     try:
-        pkg._check(lib.bfhip_profile_enable(ctx._h, 1))
+        ctx.profile_enable(1)
         for log, n in fm.MANY_COLUMNS:
             run(True, log, log, n)
         for log, n in fm.MANY_COLUMNS:
             run(False, log + 1, log, n)
         for log, log_eval, n in fm.LARGER_BLOWUPS:
             run(False, log_eval, log, n)
-        pkg._check(lib.bfhip_profile_enable(ctx._h, 0))
+        ctx.profile_enable(0)
     finally:
         ctx.close()
     print(json.dumps(out))

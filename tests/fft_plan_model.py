@@ -108,7 +108,7 @@ def ragged(p, ncols):
 
 
 def launch_names(inverse, passes):
-    """What bfhip_profile_report lists for the job run alone under BFHIP_FFT_PROF_DETAIL=1: {"<kernel><inverse>/b<workgroups>/g1": calls}."""
+    """What Context.profile_report lists for the job run alone under BFHIP_FFT_PROF_DETAIL=1: {"<kernel><inverse>/b<workgroups>/g1": calls}."""
     tag = "<true>" if inverse else "<false>"
     return dict(Counter("%s%s/b%d/g1" % (KERNEL[p.kind], tag, p.workgroups) for p in passes if KERNEL[p.kind]))
 
@@ -153,7 +153,7 @@ SESSIONS = {"b1": (1, 20, 17), "b2": (2, 21, 9), "b4": (4, 22, 5), "b1_top22": (
 
 
 def session_kernels(log_blowup, tree_logs, forms):
-    """The kernel names bfhip_profile_report lists after the commits of a session (BFHIP_FFT_PROF_DETAIL unset): a tree of evaluations
+    """The kernel names Context.profile_report lists after the commits of a session (BFHIP_FFT_PROF_DETAIL unset): a tree of evaluations
     (form 0) is one inverse plan over its size classes, every tree one forward plan to log + log_blowup. Single-pass transforms below 2^12
     cells and tiny ones ride in the plan's first k_fft_tile12 launch when it has one (fft.hip :724-:733) and leave no name of their own."""
     names = set()

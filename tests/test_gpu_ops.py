@@ -180,3 +180,28 @@ def test_grind_finds_smallest_nonce(ctx, oracle, pow_bits):
     oracle.L.orc_grind_digest.restype = ctypes.c_uint64
     want = oracle.L.orc_grind_digest(digest, pow_bits)
     assert ctx.grind(digest, pow_bits) == want
+
+
+@pytest.mark.single_conv
+def test_profiler_in_the_mirror(pkg, ctx):
+    """Context.profiling / profile_report / profile_reset / profile_enable around bfhip_interpolate of one column at log_size 6, which
+    tests/fft_plan_model.py says is one timed launch."""
+    import fft_plan_model as fm
+    log = 6
+    per_call = len([p for p in fm.interpolate(log, 1) if fm.KERNEL[p.kind]])
+    assert per_call == 1
+    timed = lambda: sum(v["calls"] for v in ctx.profile_report().values() if isinstance(v, dict) and "calls" in v)
+    col = ctx.upload(splitmix_column(31, 1 << log))
+    try:
+        with ctx.profiling():
+            ctx.interpolate([col], [col], log)
+            ctx.interpolate([col], [col], log)
+            assert timed() == 2 * per_call
+            ctx.profile_reset()
+            assert timed() == 0
+        ctx.interpolate([col], [col], log)      # the profiler is off again: nothing is recorded
+        assert timed() == 0
+        with pytest.raises(pkg.BfhipError):
+            ctx.profile_enable(3)
+    finally:
+        ctx.free(col)

@@ -10,7 +10,6 @@ Integers and bytes only. tests/test_fft_plan_model_cpu.py holds the trees to wha
 
 Oracle time per session on a 16-core host: see the printed line of each case (pytest -s)."""
 import ctypes
-import json
 import random
 import time
 
@@ -52,14 +51,6 @@ def lctx(pkg):
     c.close()
 
 
-def _report(pkg, ctx):
-    js = ctypes.c_void_p()
-    pkg._check(pkg.lib().bfhip_profile_report(ctx._h, ctypes.byref(js)))
-    rep = json.loads(ctypes.string_at(js).decode())
-    pkg.lib().bfhip_free_host(js)
-    return rep
-
-
 def _same(got, want, what, tree, k, col):
     if not np.array_equal(got, want):
         i = int(np.nonzero(got != want)[0][0])
@@ -80,11 +71,10 @@ def _run_session(pkg, ctx, oracle, name, conv):
     ctx.set_pcs_config(pkg.PcsConfig(pow_bits=4, log_blowup_factor=b, n_queries=6))
     oracle.set_conventions(*conv)
     ch, ch_ref = pkg.Channel(conv), pkg.Channel(conv)
-    lib = pkg.lib()
     dev, t_oracle = [], 0.0
     try:
-        pkg._check(lib.bfhip_profile_enable(ctx._h, 1))
-        pkg._check(lib.bfhip_profile_reset(ctx._h))
+        ctx.profile_enable(1)
+        ctx.profile_reset()
         with pkg.PcsSession(ctx) as s:
             for t, tree in enumerate(trees):
                 logs = [c[0] for c in tree]
@@ -115,9 +105,9 @@ def _run_session(pkg, ctx, oracle, name, conv):
                 ch_ref.mix_root(want_root)
                 assert ch.state() == ch_ref.state(), "tree %d: the channel was not given the root" % t
         ctx.sync()
-        rep = _report(pkg, ctx)
+        rep = ctx.profile_report()
     finally:
-        lib.bfhip_profile_enable(ctx._h, 0)
+        ctx.profile_enable(0)
         ctx.sync()
         for p in dev:
             ctx.free(p)

@@ -7,37 +7,25 @@ compiled-in kernels) on the same resident tables, in one run on one GPU.
   tables     the 13 component tables of one execution (fib19, or the synthetic 2^k-row trace with --program sweep20 .. sweep22), row-granular
              in HBM; the logUp columns are bfhip_logup_generate's. Both calls read the same buffers: main columns and the earlier logUp
              columns at shift 4, the last logUp column full size; the program also reads an IsFirst column.
-  time       ms per pass = host clock around `passes` back-to-back calls divided by `passes`; every call ends in its own read-back, so a pass
-             is what a caller waits for. The two calls alternate, `rounds` rounds after one warm-up round; median and range. Beside it the GPU
-             time per pass by HIP events (bfhip_profile_enable mode 1) of one further round.
+  time       ms per pass: the two calls alternate in windows of `passes` back-to-back calls, `rounds` rounds, and by HIP events
+             (tools/ratelib.py has the scheme). Every call ends in its own read-back, so a pass is what a caller waits for.
   check      before the timing: both report a valid trace, with the same counters.
 
 The interpreter is expected to be slower; no threshold is attached. A run without a GPU fails: nothing here is measured on the host."""
 import argparse
-import ctypes
-import json
 import os
 import statistics
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from tools.benchlib.workloads import FIB19, load_package, sweep_program      # noqa: E402
-
-
-def profile_report(pkg, ctx):
-    js = ctypes.c_void_p()
-    assert pkg.lib().bfhip_profile_report(ctx._h, ctypes.byref(js)) == 0
-    rep = json.loads(ctypes.string_at(js).decode())
-    pkg.lib().bfhip_free_host(js)
-    return rep
+from tools.benchlib.workloads import FIB19, sweep_program                 # noqa: E402
+from ratelib import alternate, cell, emit, events, load_package, require_gpu      # noqa: E402
 
 
 def measure(pkg, ctx, tr, comp, elems, passes, rounds):
-    L = pkg.lib()
     program, _, columns = pkg.brainfuck_air_program(comp)
     n_main, n_logup = len([c for c in columns if c.startswith("main")]), len([c for c in columns if c.startswith("logup")]) // 4
     log_size = tr.log_sizes[comp]
@@ -56,24 +44,12 @@ def measure(pkg, ctx, tr, comp, elems, passes, rounds):
         if not (want["ok"] and got["ok"] and got["bad_per_constraint"] == want["bad_per_constraint"][: got["n_constraints"]]):
             raise SystemExit("air_check_rate: component %d is not reported valid by both: %r / %r" % (comp, want, got))
 
-        def window(call):
-            ctx.sync()
-            t0 = time.perf_counter()
-            for _ in range(passes):
-                call()
-            return 1e3 * (time.perf_counter() - t0) / passes
-
-        ms = {"compiled": [], "program": []}
-        for r in range(rounds + 1):
-            for name, call in (("compiled", compiled), ("program", interpreted)):
-                t = window(call)
-                if r:
-                    ms[name].append(t)
-        assert L.bfhip_profile_enable(ctx._h, 1) == 0 and L.bfhip_profile_reset(ctx._h) == 0
-        window(compiled); window(interpreted)
-        rep = profile_report(pkg, ctx)
-        assert L.bfhip_profile_enable(ctx._h, 0) == 0
-        ev = {"compiled": rep["k_check_cells"]["total_ms"] / rep["k_check_cells"]["calls"], "program": rep["k_air_check"]["total_ms"] / rep["k_air_check"]["calls"]}
+        calls = {"compiled": compiled, "program": interpreted}
+        ms = alternate(ctx, calls, passes, rounds)
+        ev = {}
+        for name, scope in (("compiled", "k_check_cells"), ("program", "k_air_check")):
+            gpu_ms, timed = events(ctx, calls[name], passes)[scope]
+            ev[name] = gpu_ms / timed
     finally:
         for p in main + logup + [first]:
             ctx.free(p)
@@ -86,8 +62,7 @@ def main():
     ap.add_argument("--passes", type=int, default=200); ap.add_argument("--rounds", type=int, default=5); ap.add_argument("--out")
     a = ap.parse_args()
     pkg = load_package()
-    if pkg.device_count() < 1:
-        raise SystemExit("air_check_rate: no GPU")
+    require_gpu(pkg, "air_check_rate")
     code = FIB19 if a.program == "fib19" else sweep_program(int(a.program[5:]))
     ctx = pkg.Context(0, max_log_domain=26)
     try:
@@ -106,12 +81,9 @@ def main():
     for r in rows:
         c, p, s = r["ms"]["compiled"], r["ms"]["program"], r["shape"]
         lines.append(f"{r['name']} | {r['log_size']} | {r['columns']} | {s['n_instr']}, {s['m_regs']} / {s['q_regs']}, {256 * (s['m_regs'] + 4 * s['q_regs'])} | "
-                     f"{statistics.median(c):.4f} ({min(c):.4f}-{max(c):.4f}) | {statistics.median(p):.4f} ({min(p):.4f}-{max(p):.4f}) | "
+                     f"{cell(c, 4)} | {cell(p, 4)} | "
                      f"{statistics.median(p) / statistics.median(c):.2f}x | {r['events_ms']['compiled']:.4f}, {r['events_ms']['program']:.4f}")
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    if a.out:
-        open(a.out, "w").write(text)
+    emit("\n".join(lines) + "\n", a.out)
 
 
 if __name__ == "__main__":

@@ -6,33 +6,24 @@ interpreter (bfhip_air_eval_domain) and the built-in per-component kernels (bfhi
 
   columns    full size (shift 0: bfhip_eval_constraints then takes its per-row kernel, one lane per row like the other two), splitmix values;
              the constraint domain is CanonicCoset(log_size + 1). All three calls accumulate into four coordinate columns.
-  time       ms per launch = host clock around `launches` back-to-back calls that end in a context synchronise, divided by `launches`; the
-             three kernels alternate, `rounds` rounds after one warm-up round; median and range (the scheme of tools/air_program_rate.py).
-             Beside it the GPU time per launch by HIP events (bfhip_profile_enable mode 1) of one further round.
+  time       ms per launch: the three kernels alternate in windows of `launches` back-to-back calls, `rounds` rounds, and by HIP events
+             (tools/ratelib.py has the scheme).
   check      before the timing: from the same starting accumulator the three calls leave the same bytes.
   compile    once, for each of the 13 programs: generate + compile + load time and bfhip_air_kernel_info's figures.
 
 No threshold is attached. A run without a GPU fails: nothing here is measured on the host."""
 import argparse
-import os
 import statistics
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-from conftest import load_package, splitmix_column      # noqa: E402
-from air_program_rate import profile_report             # noqa: E402
+from ratelib import alternate, cell, emit, events, load_package, require_gpu, splitmix_column
 
 KINDS = ("builtin", "interpreter", "compiled")
 SCOPES = {"builtin": "k_constraints", "interpreter": "k_air_program", "compiled": "bfhip_air_generated"}
 
 
 def measure(pkg, ctx, comp, log_size, launches, rounds):
-    L = pkg.lib()
     program, _, columns = pkg.brainfuck_air_program(comp)
     kernel = ctx.air_compile(program)
     n_main, n_logup = len([c for c in columns if c.startswith("main")]), len([c for c in columns if c.startswith("logup")]) // 4
@@ -57,26 +48,12 @@ def measure(pkg, ctx, comp, log_size, launches, rounds):
         if not all(np.array_equal(a, b) and np.array_equal(a, c) for a, b, c in zip(*[got[k] for k in KINDS])):
             raise SystemExit("air_compiled_rate: the three kernels disagree on component %d" % comp)
 
-        def window(k):
-            ctx.sync()
-            t0 = time.perf_counter()
-            for _ in range(launches):
-                calls[k](accs["builtin"])
-            ctx.sync()
-            return 1e3 * (time.perf_counter() - t0) / launches
-
-        ms = {k: [] for k in KINDS}
-        for r in range(rounds + 1):
-            for k in KINDS:
-                t = window(k)
-                if r:
-                    ms[k].append(t)
-        assert L.bfhip_profile_enable(ctx._h, 1) == 0 and L.bfhip_profile_reset(ctx._h) == 0
+        timed = {k: (lambda k=k: calls[k](accs["builtin"])) for k in KINDS}
+        ms = alternate(ctx, timed, launches, rounds)
+        ev = {}
         for k in KINDS:
-            window(k)
-        rep = profile_report(pkg, ctx)
-        assert L.bfhip_profile_enable(ctx._h, 0) == 0
-        ev = {k: rep[SCOPES[k]]["total_ms"] / rep[SCOPES[k]]["calls"] for k in KINDS}
+            gpu_ms, n_timed = events(ctx, timed[k], launches)[SCOPES[k]]
+            ev[k] = gpu_ms / n_timed
     finally:
         kernel.close()
         for p in cols + [p for k in KINDS for p in accs[k]]:
@@ -102,8 +79,7 @@ def main():
     ap.add_argument("--launches", type=int, default=500); ap.add_argument("--rounds", type=int, default=5); ap.add_argument("--out")
     a = ap.parse_args()
     pkg = load_package()
-    if pkg.device_count() < 1:
-        raise SystemExit("air_compiled_rate: no GPU")
+    require_gpu(pkg, "air_compiled_rate")
     ctx = pkg.Context(0, max_log_domain=a.log_size + 1)
     try:
         compiled = compile_report(pkg, ctx)      # first: the first compile of the process also loads libhiprtc and its compiler
@@ -116,14 +92,10 @@ def main():
              "component | columns | ms per launch, median (min-max): built-in | interpreter | compiled | interpreter / compiled | compiled / built-in | by HIP events: built-in, interpreter, compiled ms"]
     for r in rows:
         med = {k: statistics.median(r["ms"][k]) for k in KINDS}
-        cell = lambda k: f"{med[k]:.4f} ({min(r['ms'][k]):.4f}-{max(r['ms'][k]):.4f})"
-        lines.append(f"{r['name']} | {r['columns']} | {cell('builtin')} | {cell('interpreter')} | {cell('compiled')} | {med['interpreter'] / med['compiled']:.2f}x | "
+        lines.append(f"{r['name']} | {r['columns']} | {cell(r['ms']['builtin'], 4)} | {cell(r['ms']['interpreter'], 4)} | {cell(r['ms']['compiled'], 4)} | {med['interpreter'] / med['compiled']:.2f}x | "
                      f"{med['compiled'] / med['builtin']:.2f}x | {r['events_ms']['builtin']:.4f}, {r['events_ms']['interpreter']:.4f}, {r['events_ms']['compiled']:.4f}")
     lines += ["", "compiled once each, in this process (the first line includes loading libhiprtc and its compiler):"] + compiled
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    if a.out:
-        open(a.out, "w").write(text)
+    emit("\n".join(lines) + "\n", a.out)
 
 
 if __name__ == "__main__":

@@ -14,27 +14,20 @@ columns, in one run on one GPU.
   (c)        the sequence: a zero fill of every accumulator, bfhip_air_eval_domain per component under its slice of
              bfhip_air_compose_coeffs, bfhip_interpolate per size, bfhip_accumulate per smaller size and coordinate
   check      before the timing the three leave the same words in all four coefficient columns.
-  events     one further round of each under the library's profiler (HIP events around every launch): GPU ms per call by kernel, and the
-             LDS bytes per wave of every program beside what the shared launch asks for.
-  time       ms per call = host clock around `calls` back-to-back calls that end in a context synchronise, divided by `calls`; the three
-             alternate, `rounds` rounds after one warm-up round; median and range. (a) and (b) end every call with their own wait when
-             the list has more than one bucket (they free their scratch); (c) keeps its accumulators allocated across calls.
+  events     GPU ms per call by kernel, and the LDS bytes per wave of every program beside what the shared launch asks for.
+  time       ms per call: the three alternate in windows of `calls` back-to-back calls, `rounds` rounds (tools/ratelib.py has the scheme).
+             (a) and (b) end every call with their own wait when the list has more than one bucket (they free their scratch); (c) keeps
+             its accumulators allocated across calls.
 
 No threshold is attached. A run without a GPU fails: nothing here is measured on the host."""
 import argparse
 import ctypes
 import os
 import statistics
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-from conftest import Oracle, load_package, splitmix_column      # noqa: E402
-from air_program_rate import profile_report                      # noqa: E402
+from ratelib import ROOT, Oracle, alternate, cell, emit, events, load_package, require_gpu, splitmix_column
 
 KINDS = ("compose", "compose_compiled", "sequence")
 R = [0x1234567, 0x7654321, 3, 0x2468ACE]
@@ -101,28 +94,10 @@ class Case:
         assert any(w.any() for w in want)
 
     def measure(self, calls, rounds):
-        def window(kind):
-            self.ctx.sync()
-            t0 = time.perf_counter()
-            for _ in range(calls):
-                self.call(kind)
-            self.ctx.sync()
-            return 1e3 * (time.perf_counter() - t0) / calls
-        ms = {k: [] for k in KINDS}
-        for r in range(rounds + 1):
-            for k in KINDS:
-                t = window(k)
-                if r:
-                    ms[k].append(t)
-        # one further round under the library's profiler (HIP events around every launch): where the GPU time of a call goes
-        L, events = self.pkg.lib(), {}
-        for k in KINDS:
-            assert L.bfhip_profile_enable(self.ctx._h, 1) == 0 and L.bfhip_profile_reset(self.ctx._h) == 0
-            window(k)
-            rep = profile_report(self.pkg, self.ctx)
-            assert L.bfhip_profile_enable(self.ctx._h, 0) == 0
-            events[k] = {name: v["total_ms"] / calls for name, v in rep.items() if isinstance(v, dict) and "total_ms" in v}
-        return ms, events
+        paths = {k: (lambda k=k: self.call(k)) for k in KINDS}
+        ms = alternate(self.ctx, paths, calls, rounds)
+        # where the GPU time of a call goes
+        return ms, {k: {name: t for name, (t, _) in events(self.ctx, paths[k], calls).items()} for k in KINDS}
 
     def bytes_moved(self):
         """(a)'s and (c)'s HBM bytes of the sweep and the finalize by count: columns read once; accumulator words written (a: once per row;
@@ -146,8 +121,7 @@ def main():
     ap.add_argument("--calls", type=int, default=10); ap.add_argument("--rounds", type=int, default=5); ap.add_argument("--out")
     a = ap.parse_args()
     pkg = load_package()
-    if pkg.device_count() < 1:
-        raise SystemExit("air_compose_rate: no GPU")
+    require_gpu(pkg, "air_compose_rate")
     log_sizes, steps = Oracle().log_sizes(open(a.program).read(), a.input.encode())
     log_sizes = [l - a.shrink if l >= 4 + a.shrink else l for l in log_sizes]
     top = max(max(log_sizes), a.equal_log) + 1
@@ -166,9 +140,8 @@ def main():
                 case.check()
                 ms, events = case.measure(a.calls, a.rounds)
                 med = {k: statistics.median(ms[k]) for k in KINDS}
-                cell = lambda k: f"{med[k]:.3f} ({min(ms[k]):.3f}-{max(ms[k]):.3f})"
                 ba, bc = case.bytes_moved()
-                lines.append(f"{name} | {len(comps)} | {len(case.sizes)} | 2^{case.dst_log} | {cell('compose')} | {cell('compose_compiled')} | {cell('sequence')} | "
+                lines.append(f"{name} | {len(comps)} | {len(case.sizes)} | 2^{case.dst_log} | {cell(ms['compose'], 3)} | {cell(ms['compose_compiled'], 3)} | {cell(ms['sequence'], 3)} | "
                              f"{med['sequence'] / med['compose']:.2f}x | {med['sequence'] / med['compose_compiled']:.2f}x | {ba / 2**20:.0f} MiB, {bc / 2**20:.0f} MiB")
                 for k, label in zip(KINDS, ("(a)", "(b)", "(c)")):
                     detail.append(f"  {name.split(',')[0].split(':')[0]} {label} GPU ms per call by HIP events (one profiled round): " +
@@ -180,10 +153,7 @@ def main():
                 case.close()
     finally:
         ctx.close()
-    text = "\n".join(lines + [""] + detail) + "\n"
-    print(text, end="")
-    if a.out:
-        open(a.out, "w").write(text)
+    emit("\n".join(lines + [""] + detail) + "\n", a.out)
 
 
 if __name__ == "__main__":

@@ -6,37 +6,20 @@ per-component kernels (bfhip_eval_constraints) on the same columns, in one run o
 
   columns    full size (shift 0: bfhip_eval_constraints then takes its per-row kernel, one lane per row like the interpreter), splitmix values;
              the constraint domain is CanonicCoset(log_size + 1). Both calls accumulate into the same four coordinate columns.
-  time       ms per launch = host clock around `launches` back-to-back calls that end in a context synchronise, divided by `launches`; the two
-             kernels alternate, `rounds` rounds after one warm-up round; median and range. Beside it the GPU time per launch by HIP events
-             (bfhip_profile_enable mode 1) of one further round.
+  time       ms per launch: the two kernels alternate in windows of `launches` back-to-back calls, `rounds` rounds, and by HIP events
+             (tools/ratelib.py has the scheme).
   check      before the timing: from the same starting accumulator the two calls leave the same bytes.
 
 The interpreter is expected to be slower; no threshold is attached. A run without a GPU fails: nothing here is measured on the host."""
 import argparse
-import ctypes
-import json
-import os
 import statistics
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-from conftest import load_package, splitmix_column      # noqa: E402
-
-
-def profile_report(pkg, ctx):
-    js = ctypes.c_void_p()
-    assert pkg.lib().bfhip_profile_report(ctx._h, ctypes.byref(js)) == 0
-    rep = json.loads(ctypes.string_at(js).decode())
-    pkg.lib().bfhip_free_host(js)
-    return rep
+from ratelib import alternate, cell, emit, events, load_package, require_gpu, splitmix_column
 
 
 def measure(pkg, ctx, comp, log_size, launches, rounds):
-    L = pkg.lib()
     program, _, columns = pkg.brainfuck_air_program(comp)
     n_main, n_logup = len([c for c in columns if c.startswith("main")]), len([c for c in columns if c.startswith("logup")]) // 4
     n = 2 << log_size
@@ -49,33 +32,20 @@ def measure(pkg, ctx, comp, log_size, launches, rounds):
     zero = np.zeros(n, dtype=np.uint32)
     acc_a, acc_b = [ctx.upload(zero) for _ in range(4)], [ctx.upload(zero) for _ in range(4)]
     main, inter, first = cols[:n_main], cols[n_main: n_main + 4 * n_logup], cols[-1]
-    compiled = lambda acc: ctx.eval_constraints(comp, log_size, first, main, inter, elems, claimed, coeffs, acc)
-    interpreted = lambda acc: ctx.air_eval_domain(program, log_size, 1, cols, params, coeffs.reshape(n_cons, 4).tolist(), acc)
+    compiled = lambda acc=acc_a: ctx.eval_constraints(comp, log_size, first, main, inter, elems, claimed, coeffs, acc)
+    interpreted = lambda acc=acc_a: ctx.air_eval_domain(program, log_size, 1, cols, params, coeffs.reshape(n_cons, 4).tolist(), acc)
     try:
-        compiled(acc_a); interpreted(acc_b)
+        compiled(); interpreted(acc_b)
         same = all(np.array_equal(ctx.download(a, n), ctx.download(b, n)) for a, b in zip(acc_a, acc_b))
         if not same:
             raise SystemExit("air_program_rate: the two kernels disagree on component %d" % comp)
 
-        def window(call):
-            ctx.sync()
-            t0 = time.perf_counter()
-            for _ in range(launches):
-                call(acc_a)
-            ctx.sync()
-            return 1e3 * (time.perf_counter() - t0) / launches
-
-        ms = {"compiled": [], "program": []}
-        for r in range(rounds + 1):
-            for name, call in (("compiled", compiled), ("program", interpreted)):
-                t = window(call)
-                if r:
-                    ms[name].append(t)
-        assert L.bfhip_profile_enable(ctx._h, 1) == 0 and L.bfhip_profile_reset(ctx._h) == 0
-        window(compiled); window(interpreted)
-        rep = profile_report(pkg, ctx)
-        assert L.bfhip_profile_enable(ctx._h, 0) == 0
-        ev = {"compiled": rep["k_constraints"]["total_ms"] / rep["k_constraints"]["calls"], "program": rep["k_air_program"]["total_ms"] / rep["k_air_program"]["calls"]}
+        calls = {"compiled": compiled, "program": interpreted}
+        ms = alternate(ctx, calls, launches, rounds)
+        ev = {}
+        for name, scope in (("compiled", "k_constraints"), ("program", "k_air_program")):
+            gpu_ms, timed = events(ctx, calls[name], launches)[scope]
+            ev[name] = gpu_ms / timed
     finally:
         for p in cols + acc_a + acc_b:
             ctx.free(p)
@@ -88,8 +58,7 @@ def main():
     ap.add_argument("--launches", type=int, default=500); ap.add_argument("--rounds", type=int, default=5); ap.add_argument("--out")
     a = ap.parse_args()
     pkg = load_package()
-    if pkg.device_count() < 1:
-        raise SystemExit("air_program_rate: no GPU")
+    require_gpu(pkg, "air_program_rate")
     ctx = pkg.Context(0, max_log_domain=a.log_size + 1)
     try:
         rows = [measure(pkg, ctx, int(c), a.log_size, a.launches, a.rounds) for c in a.components.split(",")]
@@ -102,12 +71,9 @@ def main():
     for r in rows:
         c, p, s = r["ms"]["compiled"], r["ms"]["program"], r["shape"]
         lines.append(f"{r['name']} | {r['columns']} | {s['n_instr']}, {s['m_regs']} / {s['q_regs']}, {256 * (s['m_regs'] + 4 * s['q_regs'])} | "
-                     f"{statistics.median(c):.4f} ({min(c):.4f}-{max(c):.4f}) | {statistics.median(p):.4f} ({min(p):.4f}-{max(p):.4f}) | "
+                     f"{cell(c, 4)} | {cell(p, 4)} | "
                      f"{statistics.median(p) / statistics.median(c):.2f}x | {r['events_ms']['compiled']:.4f}, {r['events_ms']['program']:.4f}")
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    if a.out:
-        open(a.out, "w").write(text)
+    emit("\n".join(lines) + "\n", a.out)
 
 
 if __name__ == "__main__":

@@ -14,27 +14,21 @@
   (d)        brainfuck only, for orientation: Trace.prove (bfhip_prove_trace), the built-in path on the same trace (row-granular columns,
              compiled-in kernels, its own launch order)
   check      before the timing: (a), (b) and (c) return the same proof bytes, and on the brainfuck case (d)'s proof member is those bytes.
-  time       ms per proof = host clock around `calls` back-to-back proofs divided by `calls` (every path returns with the GPU idle); the
-             paths alternate, `rounds` windows each after one warm-up round; median and range. Beside it one further window under HIP
-             events (bfhip_profile_enable mode 1): GPU ms per proof and timed launches per proof, in all and by kernel.
+  time       ms per proof: the paths alternate in windows of `calls` back-to-back proofs, `rounds` windows each (every path returns with
+             the GPU idle), and by HIP events: GPU ms per proof and timed launches per proof, in all and by kernel (tools/ratelib.py has
+             the scheme).
 
 No threshold is attached. A run without a GPU fails: nothing here is measured on the host."""
 import argparse
 import os
 import statistics
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-from conftest import load_package                                 # noqa: E402
+from ratelib import ROOT, alternate, cell, emit, events, load_package, require_gpu      # first: it puts tests/ on the path
 import pcs_replay                                                 # noqa: E402
 import test_gpu_air_prove as hand                                 # noqa: E402
 from bfprove import generic_columns                               # noqa: E402
-from logup_program_rate import profile_report                     # noqa: E402
 
 CONV = (0, 0, 0, 0)
 
@@ -64,26 +58,8 @@ class Case:
         return len(proofs["interpreted"])
 
     def measure(self, calls, rounds):
-        def window(kind):
-            self.ctx.sync()
-            t0 = time.perf_counter()
-            for _ in range(calls):
-                self.call(kind)
-            return 1e3 * (time.perf_counter() - t0) / calls
-        ms = {k: [] for k in self.kinds}
-        for r in range(rounds + 1):
-            for k in self.kinds:
-                t = window(k)
-                if r:
-                    ms[k].append(t)
-        L, events = self.pkg.lib(), {}
-        for k in self.kinds:
-            assert L.bfhip_profile_enable(self.ctx._h, 1) == 0 and L.bfhip_profile_reset(self.ctx._h) == 0
-            window(k)
-            rep = profile_report(self.pkg, self.ctx)
-            assert L.bfhip_profile_enable(self.ctx._h, 0) == 0
-            events[k] = {name: (v["total_ms"] / calls, v["calls"] / calls) for name, v in rep.items() if isinstance(v, dict) and "total_ms" in v}
-        return ms, events
+        paths = {k: (lambda k=k: self.call(k)) for k in self.kinds}
+        return alternate(self.ctx, paths, calls, rounds), {k: events(self.ctx, paths[k], calls) for k in self.kinds}
 
     def close(self):
         for k in self.kernels:
@@ -112,8 +88,7 @@ def main():
     ap.add_argument("--calls", type=int, default=10); ap.add_argument("--rounds", type=int, default=5); ap.add_argument("--out")
     a = ap.parse_args()
     pkg = load_package()
-    if pkg.device_count() < 1:
-        raise SystemExit("air_prove_rate: no GPU")
+    require_gpu(pkg, "air_prove_rate")
     code = open(a.program).read()
     probe = pkg.Context(0, max_log_domain=24)
     tr = pkg.Trace(probe, code, b"")
@@ -134,10 +109,10 @@ def main():
                 n_bytes = case.check()
                 ms, events = case.measure(a.calls, a.rounds)
                 four = case.kinds + [None] * (4 - len(case.kinds))
-                cell = lambda k: "-" if k is None else f"{statistics.median(ms[k]):.3f} ({min(ms[k]):.3f}-{max(ms[k]):.3f})"
+                path = lambda k: "-" if k is None else cell(ms[k], 3)
                 gpu = lambda k: "-" if k is None else "%.3f" % sum(t for t, _ in events[k].values())
                 launches = lambda k: "-" if k is None else "%g" % sum(c for _, c in events[k].values())
-                lines.append(f"{name} | {n_bytes} | " + " | ".join(cell(k) for k in four) + f" | {statistics.median(ms['by hand']) - statistics.median(ms['interpreted']):.3f} | " +
+                lines.append(f"{name} | {n_bytes} | " + " | ".join(path(k) for k in four) + f" | {statistics.median(ms['by hand']) - statistics.median(ms['interpreted']):.3f} | " +
                              " | ".join(gpu(k) for k in four) + " | " + " | ".join(launches(k) for k in four))
                 short = name.split(",")[0].split(" at ")[0]
                 for k, label in zip(case.kinds, ("(a)", "(b)", "(c)", "(d)")):
@@ -148,10 +123,7 @@ def main():
                 case.close()
     finally:
         ctx.close()
-    text = "\n".join(lines + [""] + detail) + "\n"
-    print(text, end="")
-    if a.out:
-        open(a.out, "w").write(text)
+    emit("\n".join(lines + [""] + detail) + "\n", a.out)
 
 
 if __name__ == "__main__":

@@ -6,7 +6,7 @@
   search     per pow_bits: `reps` fixed digests (sha256("grind_poseidon_rate <pow_bits> <i>") mod p) after `warmup` calls on other digests.
              ms per call = host clock around the whole call (every span's launch and read-back; the context is synchronised before the
              clock starts): median and range. Permutations per second = nonces scanned (`tried`, launches x span) / GPU time of the
-             launches by HIP events (bfhip_profile_enable mode 1, one event pair per launch), summed over the `reps` calls.
+             launches by HIP events (Context.profiling, one event pair per launch), summed over the `reps` calls.
   yardstick  Hades permutations per second with the state in registers: `k_hades` of tools/ubench_poseidon.hip, the same field code with no
              conversion, no test and no read-back. The program is run 5 times before the search and 5 times after it (median and range).
              --ubench names a built binary; without it the source is compiled with hipcc into a temporary directory.
@@ -16,32 +16,20 @@ A run without a GPU fails: nothing here is measured on the host except the CPU o
 import argparse
 import ctypes
 import hashlib
-import json
 import os
 import re
 import statistics
 import subprocess
-import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-from conftest import load_package, Oracle      # noqa: E402
+from ratelib import ROOT, Oracle, cell, emit, load_package, require_gpu
 
 P252 = 2**251 + 17 * 2**192 + 1
 
 
 def digest(pow_bits, i):
     return (int.from_bytes(hashlib.sha256(b"grind_poseidon_rate %d %d" % (pow_bits, i)).digest(), "big") % P252).to_bytes(32, "little")
-
-
-def profile_report(pkg, ctx):
-    js = ctypes.c_void_p()
-    assert pkg.lib().bfhip_profile_report(ctx._h, ctypes.byref(js)) == 0
-    rep = json.loads(ctypes.string_at(js).decode())
-    pkg.lib().bfhip_free_host(js)
-    return rep
 
 
 def yardstick(binary, runs=5):
@@ -53,20 +41,18 @@ def yardstick(binary, runs=5):
 
 
 def search(pkg, ctx, pow_bits, reps, warmup):
-    L = pkg.lib()
     for i in range(warmup):
         ctx.grind_poseidon252(digest(pow_bits, 1000 + i), pow_bits)
     ms, nonces, tried_all = [], [], 0
-    assert L.bfhip_profile_enable(ctx._h, 1) == 0 and L.bfhip_profile_reset(ctx._h) == 0
-    for i in range(reps):
-        d = digest(pow_bits, i)
-        ctx.sync()
-        t0 = time.perf_counter()
-        nonce, tried = ctx.grind_poseidon252(d, pow_bits, with_tried=True)
-        ms.append(1e3 * (time.perf_counter() - t0))
-        nonces.append(nonce); tried_all += tried
-    rec = profile_report(pkg, ctx)["k_grind_poseidon"]
-    assert L.bfhip_profile_enable(ctx._h, 0) == 0
+    with ctx.profiling(1):      # every call is another digest and is timed on its own; one report over the `reps` calls
+        for i in range(reps):
+            d = digest(pow_bits, i)
+            ctx.sync()
+            t0 = time.perf_counter()
+            nonce, tried = ctx.grind_poseidon252(d, pow_bits, with_tried=True)
+            ms.append(1e3 * (time.perf_counter() - t0))
+            nonces.append(nonce); tried_all += tried
+        rec = ctx.profile_report()["k_grind_poseidon"]
     assert rec["units"] == tried_all, (rec, tried_all)
     return {"pow_bits": pow_bits, "ms": ms, "nonces": nonces, "tried": tried_all, "launches": rec["calls"], "gpu_ms": rec["total_ms"],
             "perm_per_s": tried_all / (rec["total_ms"] * 1e-3)}
@@ -93,8 +79,7 @@ def main():
     ap.add_argument("--pows", default="12,16,20,24,28"); ap.add_argument("--ubench"); ap.add_argument("--out")
     a = ap.parse_args()
     pkg = load_package()
-    if pkg.device_count() < 1:
-        raise SystemExit("grind_poseidon_rate: no GPU")
+    require_gpu(pkg, "grind_poseidon_rate")
     tmp = None
     binary = a.ubench
     if not binary:
@@ -116,7 +101,7 @@ def main():
              f"(before the search {min(before):.4g}-{max(before):.4g}, after it {min(after):.4g}-{max(after):.4g})", "",
              "pow_bits | ms per call: median (min-max) | launches | nonces scanned | GPU ms by HIP events | permutations/s | of the yardstick"]
     for r in rows:
-        lines.append(f"{r['pow_bits']:8d} | {statistics.median(r['ms']):.3f} ({min(r['ms']):.3f}-{max(r['ms']):.3f}) | {r['launches']} | {r['tried']} | "
+        lines.append(f"{r['pow_bits']:8d} | {cell(r['ms'], 3)} | {r['launches']} | {r['tried']} | "
                      f"{r['gpu_ms']:.3f} | {r['perm_per_s']:.4g} | {r['perm_per_s'] / yard:.3f}")
     lines.append("")
     for r in rows:
@@ -127,10 +112,7 @@ def main():
         res = cpu_oracle(pw)
         lines.append(f"CPU oracle orc_grind_digest, pow_bits {pw}: " + ", ".join(f"nonce {n} in {ms:.1f} ms" for n, ms in res)
                      + f"  ({1e3 * sum(n + 1 for n, _ in res) / sum(ms for _, ms in res):.4g} permutations/s, one thread)")
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    if a.out:
-        open(a.out, "w").write(text)
+    emit("\n".join(lines) + "\n", a.out)
     if tmp:
         tmp.cleanup()
 

@@ -18,25 +18,19 @@ compiled path, on the same tables, in one run on one GPU.
              orientation
   check      before the timing: (a) and (b) leave the same words in every column and the same claimed sums; (c)'s earlier columns broadcast
              16-fold, its last column and its claimed sums are (a)'s.
-  time       ms per call of the whole list = host clock around `calls` back-to-back runs divided by `calls` (every path returns with the GPU
-             idle: each call reads its claimed sums back); the three alternate, `rounds` windows each after one warm-up round; median and
-             range. Beside it the GPU time of one further window by HIP events (bfhip_profile_enable mode 1), by kernel.
+  time       ms per call of the whole list: the three alternate in windows of `calls` back-to-back runs, `rounds` windows each (every path
+             returns with the GPU idle: each call reads its claimed sums back), and by HIP events, by kernel (tools/ratelib.py has the
+             scheme).
 
 No threshold is attached. A run without a GPU fails: nothing here is measured on the host."""
 import argparse
 import os
 import statistics
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-from conftest import Oracle, load_package, splitmix_column      # noqa: E402
-import logup_model                                               # noqa: E402
-from logup_program_rate import profile_report                    # noqa: E402
+from ratelib import ROOT, Oracle, alternate, cell, emit, events, load_package, require_gpu, splitmix_column      # first: it puts tests/ on the path
+import logup_model
 
 KINDS = ("batch", "singles", "compiled")
 
@@ -93,26 +87,8 @@ class Case:
                     raise SystemExit("logup_batch_rate: the three paths disagree on component %d" % k)
 
     def measure(self, calls, rounds):
-        def window(kind):
-            self.ctx.sync()
-            t0 = time.perf_counter()
-            for _ in range(calls):
-                self.call(kind)
-            return 1e3 * (time.perf_counter() - t0) / calls
-        ms = {k: [] for k in KINDS}
-        for r in range(rounds + 1):
-            for k in KINDS:
-                t = window(k)
-                if r:
-                    ms[k].append(t)
-        L, events = self.pkg.lib(), {}
-        for k in KINDS:
-            assert L.bfhip_profile_enable(self.ctx._h, 1) == 0 and L.bfhip_profile_reset(self.ctx._h) == 0
-            window(k)
-            rep = profile_report(self.pkg, self.ctx)
-            assert L.bfhip_profile_enable(self.ctx._h, 0) == 0
-            events[k] = {name: (v["total_ms"] / calls, v["calls"] / calls) for name, v in rep.items() if isinstance(v, dict) and "total_ms" in v}
-        return ms, events
+        paths = {k: (lambda k=k: self.call(k)) for k in KINDS}
+        return alternate(self.ctx, paths, calls, rounds), {k: events(self.ctx, paths[k], calls) for k in KINDS}
 
     def close(self):
         for p in self.ptrs:
@@ -126,8 +102,7 @@ def main():
     ap.add_argument("--out"); ap.add_argument("--append", action="store_true", help="add to --out instead of replacing it")
     a = ap.parse_args()
     pkg = load_package()
-    if pkg.device_count() < 1:
-        raise SystemExit("logup_batch_rate: no GPU")
+    require_gpu(pkg, "logup_batch_rate")
     log_sizes, steps = Oracle().log_sizes(open(a.program).read(), a.input.encode())
     ctx = pkg.Context(0, max_log_domain=max(max(log_sizes), a.equal_log) + 1)
     lines = [f"BFHIP_LOGUP_BATCH_LAUNCH={os.environ.get('BFHIP_LOGUP_BATCH_LAUNCH', '(unset)')}: bfhip_logup_program_generate_batch beside the 13 calls of bfhip_logup_program_generate it replaces and "
@@ -144,9 +119,8 @@ def main():
                 case.check()
                 ms, events = case.measure(a.calls, a.rounds)
                 med = {k: statistics.median(ms[k]) for k in KINDS}
-                cell = lambda k: f"{med[k]:.3f} ({min(ms[k]):.3f}-{max(ms[k]):.3f})"
                 gpu = {k: "%.3f" % sum(t for t, _ in events[k].values()) if events[k] else "- (its launches are not timed scopes)" for k in KINDS}
-                lines.append(f"{name} | {sum(1 << i['log'] for i in case.items)} |{cell('batch')} | {cell('singles')} | {cell('compiled')} | {med['singles'] - med['batch']:.3f} | "
+                lines.append(f"{name} | {sum(1 << i['log'] for i in case.items)} |{cell(ms['batch'], 3)} | {cell(ms['singles'], 3)} | {cell(ms['compiled'], 3)} | {med['singles'] - med['batch']:.3f} | "
                              f"{med['singles'] / med['batch']:.2f}x | {gpu['batch']} | {gpu['singles']} | {gpu['compiled']}")
                 short = name.split(",")[0].split(":")[0]
                 for k, label in zip(KINDS, ("(a)", "(b)", "(c)")):
@@ -158,10 +132,7 @@ def main():
                 case.close()
     finally:
         ctx.close()
-    text = "\n".join(lines + [""] + detail) + "\n\n"
-    print(text, end="")
-    if a.out:
-        open(a.out, "a" if a.append else "w").write(text)
+    emit("\n".join(lines + [""] + detail) + "\n\n", a.out, a.append)
 
 
 if __name__ == "__main__":

@@ -7,40 +7,23 @@ AIR) beside the compiled, replication-aware path (bfhip_logup_generate) on the s
   tables     row-granular main columns of 2^(log_size - 4) rows, splitmix values. bfhip_logup_generate reads them as rows;
              bfhip_logup_program_generate reads them at shift 4 and writes every logUp column full size. A third row per component runs the
              same program on full-size columns of 2^log_size distinct cells (shift 0), which has no compiled counterpart.
-  time       ms per call = host clock around `calls` back-to-back calls divided by `calls` (each call allocates its scratch, launches, reads
-             its claimed sum back and frees: a call returns with the GPU idle); the paths alternate, `rounds` windows each after one warm-up
-             round; median and range, and cells per second = 2^log_size / median. Beside it the GPU time of the row stage and of the scan
-             stage by HIP events (bfhip_profile_enable mode 1) of one further window.
+  time       ms per call: the paths alternate in windows of `calls` back-to-back calls, `rounds` windows each (each call allocates its
+             scratch, launches, reads its claimed sum back and frees: a call returns with the GPU idle), and cells per second =
+             2^log_size / median; the row stage and the scan stage by HIP events (tools/ratelib.py has the scheme).
   check      before the timing: the program's earlier columns are the 16-fold broadcast of the compiled path's, the last column and the
              claimed sum are equal.
 
 The generic path scans 16 times the entries and writes 16 times the cells of the replicated one; no threshold is attached. A run without
 a GPU fails: nothing here is measured on the host."""
 import argparse
-import ctypes
-import json
-import os
 import statistics
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-from conftest import load_package, splitmix_column      # noqa: E402
-
-
-def profile_report(pkg, ctx):
-    js = ctypes.c_void_p()
-    assert pkg.lib().bfhip_profile_report(ctx._h, ctypes.byref(js)) == 0
-    rep = json.loads(ctypes.string_at(js).decode())
-    pkg.lib().bfhip_free_host(js)
-    return rep
+from ratelib import alternate, cell, emit, events, load_package, require_gpu, splitmix_column
 
 
 def measure(pkg, ctx, comp, log_size, calls, rounds):
-    L = pkg.lib()
     program, _ = pkg.brainfuck_logup_program(comp)
     n_main, n_logup = program.shape["n_cols"], program.shape["n_logup_cols"]
     n, M = 1 << log_size, 1 << (log_size - 4)
@@ -58,27 +41,13 @@ def measure(pkg, ctx, comp, log_size, calls, rounds):
         if not same:
             raise SystemExit("logup_program_rate: the two paths disagree on component %d" % comp)
 
-        def window(call):
-            ctx.sync()
-            t0 = time.perf_counter()
-            for _ in range(calls):
-                call()
-            return 1e3 * (time.perf_counter() - t0) / calls
-
-        ms = {"compiled": [], "program": [], "distinct": []}
-        for r in range(rounds + 1):
-            for name, call in (("compiled", compiled), ("program", shifted), ("distinct", distinct)):
-                t = window(call)
-                if r:
-                    ms[name].append(t)
-        # GPU time of the two stages by HIP events (bfhip_profile_enable mode 1), one further window each
+        paths = {"compiled": compiled, "program": shifted, "distinct": distinct}
+        ms = alternate(ctx, paths, calls, rounds)
+        # GPU time of the two stages, per timed scope
         ev = {}
-        for name, call in (("program", shifted), ("distinct", distinct)):
-            assert L.bfhip_profile_enable(ctx._h, 1) == 0 and L.bfhip_profile_reset(ctx._h) == 0
-            window(call)
-            rep = profile_report(pkg, ctx)
-            assert L.bfhip_profile_enable(ctx._h, 0) == 0
-            ev[name] = tuple(rep[k]["total_ms"] / rep[k]["calls"] for k in ("k_logup_program", "k_logup_program_scan"))
+        for name in ("program", "distinct"):
+            rep = events(ctx, paths[name], calls)
+            ev[name] = tuple(rep[k][0] / rep[k][1] for k in ("k_logup_program", "k_logup_program_scan"))
     finally:
         for p in rows + full + out_c + out_p:
             ctx.free(p)
@@ -93,8 +62,7 @@ def main():
     ap.add_argument("--append", action="store_true", help="add to --out instead of replacing it")
     a = ap.parse_args()
     pkg = load_package()
-    if pkg.device_count() < 1:
-        raise SystemExit("logup_program_rate: no GPU")
+    require_gpu(pkg, "logup_program_rate")
     ctx = pkg.Context(0, max_log_domain=a.log_size + 1)
     try:
         rows = [measure(pkg, ctx, int(c), a.log_size, a.calls, a.rounds) for c in a.components.split(",")]
@@ -110,12 +78,9 @@ def main():
         s, c = r["shape"], statistics.median(r["ms"]["compiled"])
         for path, what in (("compiled", "bfhip_logup_generate, rows"), ("program", "program, the same rows at shift 4"), ("distinct", "program, full-size distinct cells")):
             v = r["ms"][path]
-            lines.append(f"{r['name']} | {s['n_logup_cols']}, {s['n_instr']}, {s['m_regs']} / {s['q_regs']} | {what} | {statistics.median(v):.4f} ({min(v):.4f}-{max(v):.4f}) | "
+            lines.append(f"{r['name']} | {s['n_logup_cols']}, {s['n_instr']}, {s['m_regs']} / {s['q_regs']} | {what} | {cell(v, 4)} | "
                          f"{n / statistics.median(v) / 1e3:.1f} | {statistics.median(v) / c:.2f}x | " + ("%.4f, %.4f" % r["events_ms"][path] if path in r["events_ms"] else "-"))
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    if a.out:
-        open(a.out, "a" if a.append else "w").write(text)
+    emit("\n".join(lines) + "\n", a.out, a.append)
 
 
 if __name__ == "__main__":

@@ -26,20 +26,12 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 os.environ.setdefault("BFHIP_LIBRARY", os.path.join(ROOT, "stwo-brainfuck_amd", "libbfhip_testhooks.so"))
-from tools.benchlib.workloads import FIB19, load_package, sweep_program      # noqa: E402
-import pcs_replay                                                             # noqa: E402
+from tools.benchlib.workloads import FIB19, sweep_program                 # noqa: E402
+from ratelib import emit, load_package, repeated, require_gpu            # noqa: E402  (first: it puts tests/ on the path)
+import pcs_replay                                                         # noqa: E402
 
 PCS_PHASES = ("preprocessed", "main_trace", "interaction", "composition", "oods", "quotients", "fri", "decommit")
-
-
-def profile_ms(pkg, ctx):
-    js = ctypes.c_void_p()
-    assert pkg.lib().bfhip_profile_report(ctx._h, ctypes.byref(js)) == 0
-    rep = json.loads(ctypes.string_at(js).decode())
-    pkg.lib().bfhip_free_host(js)
-    return {k: v["total_ms"] for k, v in rep.items()}
 
 
 def capture(pkg, ctx, tr, log_max_rows):
@@ -93,23 +85,17 @@ def session(pkg, ctx, full, logs, ptrs, log_sizes, log_max_rows):
 
 
 def measure(pkg, name, code, log_max_rows, reps, warmup):
-    L = pkg.lib()
     ctx = pkg.Context(0, max_log_domain=log_max_rows + 2)
     tr = pkg.Trace(ctx, code)
     raw, full, logs, ptrs = capture(pkg, ctx, tr, log_max_rows)
     want = pcs_replay.proof_member(raw)
     # the caller's share of a proof, by HIP events: logUp generation (as bfhip_trace_check times the same four launches) and k_constraints
-    assert L.bfhip_profile_enable(ctx._h, 1) == 0
-    logup, sweep = [], []
-    for i in range(3):
-        assert L.bfhip_profile_reset(ctx._h) == 0
+    def check_then_prove():
         assert tr.check().ok
-        logup.append(profile_ms(pkg, ctx)["trace_check_logup"])
-        assert L.bfhip_profile_reset(ctx._h) == 0
         tr.prove(log_max_rows, want_json=False)
-        sweep.append(profile_ms(pkg, ctx)["k_constraints"])
-    assert L.bfhip_profile_enable(ctx._h, 0) == 0
-    logup_ms, sweep_ms = statistics.median(logup), statistics.median(sweep)
+
+    priced = [ms for _, ms in repeated(ctx, check_then_prove, 3, 0)]
+    logup_ms, sweep_ms = statistics.median(ms["trace_check_logup"] for ms in priced), statistics.median(ms["k_constraints"] for ms in priced)
     ses, prf, tot = [], [], []
     for i in range(warmup + reps):
         dt, proof = session(pkg, ctx, full, logs, ptrs, tr.log_sizes, log_max_rows)
@@ -138,15 +124,14 @@ def main():
     ap.add_argument("--only", choices=("fib19", "2p22"))
     a = ap.parse_args()
     pkg = load_package()
+    require_gpu(pkg, "pcs_session_rate")
     lines = []
     for key, name, code, lmr in (("fib19", "fib19", FIB19, 24), ("2p22", "synthetic 2^22 rows", sweep_program(22), 22)):
         if a.only in (None, key):
             lines += measure(pkg, name, code, lmr, a.reps, a.warmup) + [""]
-    text = "\n".join(lines)
-    print(text)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        open(a.out, "w").write(text)
+    emit("\n".join(lines) + "\n", a.out)
 
 
 if __name__ == "__main__":

@@ -4,9 +4,9 @@ traces of tools/benchlib/workloads.py (LOG_MAX_ROWS 22 and 20), one process, one
 
   proof      the same resident trace proved with the preflight off and on, ALTERNATING, median of 5 after 2 warm-ups each: the total of
              phase_seconds, and the preflight's own host wall time (bfhip_preflight_report.seconds).
-  preflight  GPU time by HIP events (bfhip_profile_enable mode 1: one event pair around the four logUp launches, one around the launch pair
-             k_check_batch + k_check_first_batch), same protocol. 6 launches, ONE host synchronisation (the read-back of 13 reports,
-             13 claimed sums and the total).
+  preflight  GPU time by HIP events (one event pair around the four logUp launches, one around the launch pair k_check_batch +
+             k_check_first_batch), every proof timed on its own (`repeated` of tools/ratelib.py), same counts. 6 launches, ONE host
+             synchronisation (the read-back of 13 reports, 13 claimed sums and the total).
   check      the unbatched Trace.check() of the same trace, same protocol: its two event pairs and the wall time of the call. 4 + 26
              launches, TWO host synchronisations (the claimed sums, then the reports).
   rejection  the trace's register rows with one mv altered, as a resident trace: wall time from the call to the TraceRejected (median of 5
@@ -15,8 +15,6 @@ traces of tools/benchlib/workloads.py (LOG_MAX_ROWS 22 and 20), one process, one
 
 A diagnostic: no threshold. Output: one block of text per workload (--out FILE also writes it to a file)."""
 import argparse
-import ctypes
-import json
 import os
 import statistics
 import sys
@@ -24,34 +22,16 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from tools.benchlib.workloads import FIB19, load_package, sweep_program      # noqa: E402
+from tools.benchlib.workloads import FIB19, sweep_program      # noqa: E402
+from ratelib import emit, load_package, repeated, require_gpu      # noqa: E402
 
 med = statistics.median
 
 
-def profile_ms(pkg, ctx):
-    js = ctypes.c_void_p()
-    assert pkg.lib().bfhip_profile_report(ctx._h, ctypes.byref(js)) == 0
-    rep = json.loads(ctypes.string_at(js).decode())
-    pkg.lib().bfhip_free_host(js)
-    return {k: v["total_ms"] for k, v in rep.items()}
-
-
-def events(pkg, ctx, call, names, reps, warmup):
-    """([GPU ms per name], [wall ms]) of `call` under the per-kernel profiler, one sample per repetition."""
-    L = pkg.lib()
-    gpu, wall = [], []
-    assert L.bfhip_profile_enable(ctx._h, 1) == 0
-    for i in range(warmup + reps):
-        assert L.bfhip_profile_reset(ctx._h) == 0
-        t0 = time.perf_counter()
-        call()
-        dt = time.perf_counter() - t0
-        ms = profile_ms(pkg, ctx)
-        if i >= warmup:
-            gpu.append([ms.get(n, 0.0) for n in names]); wall.append(1e3 * dt)
-    assert L.bfhip_profile_enable(ctx._h, 0) == 0
-    return gpu, wall
+def timed(ctx, call, names, reps, warmup):
+    """([GPU ms per name], [wall ms]) of `call`, one sample per repetition."""
+    kept = repeated(ctx, call, reps, warmup)
+    return [[ms.get(n, 0.0) for n in names] for _, ms in kept], [wall for wall, _ in kept]
 
 
 def arena_peak(pkg, tr_args, log_max_rows, on):
@@ -92,9 +72,9 @@ def measure(pkg, name, code, log_max_rows, reps, warmup):
         assert ctx.last_proof_flags()["preflight"]
         if i >= warmup:
             off.append(1e3 * ph0["total"]); on.append(1e3 * ph1["total"]); pre_wall.append(1e3 * ctx.last_preflight()[0].seconds)
-    pre_gpu, _ = events(pkg, ctx, lambda: tr.prove(log_max_rows, want_json=False), ("preflight_logup", "preflight_check"), reps, warmup)
+    pre_gpu, _ = timed(ctx, lambda: tr.prove(log_max_rows, want_json=False), ("preflight_logup", "preflight_check"), reps, warmup)
     ctx.set_preflight(False)
-    chk_gpu, chk_wall = events(pkg, ctx, lambda: tr.check(), ("trace_check_logup", "k_check_cells"), reps, warmup)
+    chk_gpu, chk_wall = timed(ctx, lambda: tr.check(), ("trace_check_logup", "k_check_cells"), reps, warmup)
     bad_rows = rows.copy()
     bad_rows[1, 5] = (int(bad_rows[1, 5]) + 4) % ((1 << 31) - 1)
     bad = pkg.Trace.from_registers(ctx, bad_rows, words)
@@ -128,15 +108,13 @@ def main():
     ap.add_argument("--append", action="store_true", help="append to --out instead of replacing it (one workload per run)")
     a = ap.parse_args()
     pkg = load_package()
+    require_gpu(pkg, "preflight_rate")
     loads = (("fib19", FIB19, 24), ("synthetic 2^22 rows", sweep_program(22), 22), ("synthetic 2^20 rows", sweep_program(20), 20))
     lines = []
     for k, (name, code, lmr) in enumerate(loads):
         if a.only in (-1, k):
             lines += measure(pkg, name, code, lmr, a.reps, a.warmup) + [""]
-    text = "\n".join(lines)
-    print(text)
-    if a.out:
-        open(a.out, "a" if a.append else "w").write(text)
+    emit("\n".join(lines) + "\n", a.out, a.append)
 
 
 if __name__ == "__main__":

@@ -13,26 +13,18 @@ In one run on one GPU.
   host       bfhip_download of the consumer's and the table's word columns, the tuples packed to one key per row (a 4 w-byte void view),
              np.unique(return_counts) over the consumer's keys, np.searchsorted of the table's keys, bfhip_upload of the column into a fresh
              buffer. Pageable numpy memory, one host thread: what a caller without this entry point writes.
-  time       ms per call = host clock around `passes` back-to-back calls divided by `passes`, the context synchronised first; every call
-             ends in its own read-backs or copies, so a call is what a caller waits for. The three alternate, `rounds` rounds (at least
-             five) after one warm-up round; median and range. Beside it the GPU time per call by HIP events (bfhip_profile_enable mode 1) of
-             one further round for the two device paths, by profiler scope.
+  time       ms per call: the three alternate in windows of `passes` back-to-back calls, `rounds` rounds (at least five); the two device
+             paths also by HIP events, by profiler scope (tools/ratelib.py has the scheme). Every call ends in its own read-backs or
+             copies, so a call is what a caller waits for.
   check      before the timing: the three columns are equal, and the summary says balanced.
 
 No threshold is attached. A run without a GPU fails: nothing here is measured on the host alone."""
 import argparse
-import ctypes
-import json
-import os
 import statistics
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from tools.benchlib.workloads import load_package      # noqa: E402
+from ratelib import alternate, cell, emit, events, load_package, require_gpu
 
 P = (1 << 31) - 1
 
@@ -44,21 +36,12 @@ def splitmix(seed, n):
     return z ^ (z >> np.uint64(31))
 
 
-def profile_report(pkg, ctx):
-    js = ctypes.c_void_p()
-    assert pkg.lib().bfhip_profile_report(ctx._h, ctypes.byref(js)) == 0
-    rep = json.loads(ctypes.string_at(js).decode())
-    pkg.lib().bfhip_free_host(js)
-    return rep
-
-
 def keys_of(cols):
     rows = np.ascontiguousarray(np.stack(cols, axis=1))
     return rows.view(np.dtype((np.void, 4 * len(cols)))).ravel()
 
 
 def measure(pkg, ctx, a, width):
-    L = pkg.lib()
     n, m = 1 << a.log_consumer, 1 << a.log_table
     # 2^log_table distinct tuples: word 0 is a permutation of odd multiples, the other words hang on the row
     ids = np.argsort(splitmix(11 * width, m), kind="stable").astype(np.uint32)
@@ -99,28 +82,9 @@ def measure(pkg, ctx, a, width):
         if not (res.ok and np.array_equal(on_device, want) and np.array_equal(host.last, want) and summary().balanced):
             raise SystemExit("relation_multiplicities_rate: the paths disagree at width %d: %r" % (width, res.report))
 
-        def window(call):
-            ctx.sync()
-            t0 = time.perf_counter()
-            for _ in range(a.passes):
-                call()
-            ctx.sync()
-            return 1e3 * (time.perf_counter() - t0) / a.passes
-
-        calls = (("device", device), ("summary", summary), ("host", host))
-        ms = {name: [] for name, _ in calls}
-        for r in range(a.rounds + 1):
-            for name, call in calls:
-                t = window(call)
-                if r:
-                    ms[name].append(t)
-        ev = {}
-        for name, call in calls[:2]:
-            assert L.bfhip_profile_enable(ctx._h, 1) == 0 and L.bfhip_profile_reset(ctx._h) == 0
-            window(call)
-            rep = profile_report(pkg, ctx)
-            assert L.bfhip_profile_enable(ctx._h, 0) == 0
-            ev[name] = {s: v["total_ms"] / a.passes for s, v in sorted(rep.items())}
+        calls = {"device": device, "summary": summary, "host": host}
+        ms = alternate(ctx, calls, a.passes, a.rounds)
+        ev = {name: {s: t for s, (t, _) in sorted(events(ctx, calls[name], a.passes).items())} for name in ("device", "summary")}
         return ms, ev, res.report
     finally:
         for p in ptrs:
@@ -135,8 +99,7 @@ def main():
     if a.rounds < 5:
         raise SystemExit("relation_multiplicities_rate: at least five rounds")
     pkg = load_package()
-    if pkg.device_count() < 1:
-        raise SystemExit("relation_multiplicities_rate: no GPU")
+    require_gpu(pkg, "relation_multiplicities_rate")
     ctx = pkg.Context(0, max_log_domain=26)
     lines = [f"bfhip_relation_program_multiplicities (device) beside bfhip_relation_program_summary on the same tables with the column filled (summary) and beside "
              f"download + np.unique / np.searchsorted + upload (host): 2^{a.log_consumer} consumer rows, each looking one tuple up with multiplicity 1 in a table of "
@@ -150,16 +113,12 @@ def main():
                       f"n_missing {report['n_missing']}",
                       "path | ms per call: median (min-max) | by HIP events per call: all scopes; by scope"]
             for name in ("device", "summary", "host"):
-                v = ms[name]
-                events = "-" if name == "host" else "%.4f; %s" % (sum(ev[name].values()), ", ".join("%s %.4f" % kv for kv in ev[name].items()))
-                lines.append(f"{name} | {med[name]:.4f} ({min(v):.4f}-{max(v):.4f}) | {events}")
+                by_events = "-" if name == "host" else "%.4f; %s" % (sum(ev[name].values()), ", ".join("%s %.4f" % kv for kv in ev[name].items()))
+                lines.append(f"{name} | {cell(ms[name], 4)} | {by_events}")
             lines += [f"device / summary | {med['device'] / med['summary']:.2f}x", f"host / device | {med['host'] / med['device']:.2f}x", ""]
     finally:
         ctx.close()
-    text = "\n".join(lines)
-    print(text, end="")
-    if a.out:
-        open(a.out, "w").write(text)
+    emit("\n".join(lines), a.out)
 
 
 if __name__ == "__main__":

@@ -8,35 +8,24 @@ calls) beside bfhip_trace_relations (the three compiled-in Brainfuck relations) 
              in HBM. The compiled call reads the resident trace's own columns; the 13 brainfuck_relation_programs read copies of the same
              columns at row_shift 4 (one word per table row, NULL column shifts). Sort, segments, reduction and report are the same launches
              (relation_aggregate) in both: what differs is the extraction.
-  time       ms per pass = host clock around `passes` back-to-back calls divided by `passes`, the context synchronised first; every call ends
-             in its own read-backs, so a pass is what a caller waits for. The two calls alternate, `rounds` rounds (at least five) after one
-             warm-up round; median and range. Beside it the GPU time per pass by HIP events (bfhip_profile_enable mode 1) of one further
-             round, the extraction launches alone: relations_extract (k_rel_flags + scan; k_rel_emit is timed inside relations_sort) against
-             relation_program_count + relation_program_emit (both interpreter launches per table and relation, and the scan).
+  time       ms per pass: the two calls alternate in windows of `passes` back-to-back calls, `rounds` rounds (at least five), and by HIP
+             events (tools/ratelib.py has the scheme); every call ends in its own read-backs, so a pass is what a caller waits for. By
+             events also the extraction launches alone: relations_extract (k_rel_flags + scan; k_rel_emit is timed inside relations_sort)
+             against relation_program_count + relation_program_emit (both interpreter launches per table and relation, and the scan).
   check      before the timing: both give the same three reports and the same entries.
 
 The interpreter is expected to be slower; no threshold is attached. A run without a GPU fails: nothing here is measured on the host."""
 import argparse
-import ctypes
-import json
 import os
 import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from tools.benchlib.workloads import FIB19, load_package, sweep_program      # noqa: E402
+from tools.benchlib.workloads import FIB19, sweep_program                 # noqa: E402
+from ratelib import alternate, cell, emit, events, load_package, require_gpu      # noqa: E402
 
 N_MAIN = (8, 8, 4, 9, 13, 13, 11, 11, 11, 11, 11, 11, 7)
-
-
-def profile_report(pkg, ctx):
-    js = ctypes.c_void_p()
-    assert pkg.lib().bfhip_profile_report(ctx._h, ctypes.byref(js)) == 0
-    rep = json.loads(ctypes.string_at(js).decode())
-    pkg.lib().bfhip_free_host(js)
-    return rep
 
 
 def main():
@@ -47,9 +36,7 @@ def main():
     if a.rounds < 5:
         raise SystemExit("relation_program_rate: at least five rounds")
     pkg = load_package()
-    if pkg.device_count() < 1:
-        raise SystemExit("relation_program_rate: no GPU")
-    L = pkg.lib()
+    require_gpu(pkg, "relation_program_rate")
     code = FIB19 if a.program == "fib19" else sweep_program(int(a.program[5:]))
     ctx = pkg.Context(0, max_log_domain=26)
     ptrs = []
@@ -68,28 +55,13 @@ def main():
             if not (got.reports == want.reports and got.entries == want.entries):
                 raise SystemExit("relation_program_rate: the two paths disagree: %r / %r" % (want.reports, got.reports))
 
-            def window(call):
-                ctx.sync()
-                t0 = time.perf_counter()
-                for _ in range(a.passes):
-                    call()
-                ctx.sync()
-                return 1e3 * (time.perf_counter() - t0) / a.passes
-
-            ms = {"compiled": [], "program": []}
-            for r in range(a.rounds + 1):
-                for name, call in (("compiled", compiled), ("program", interpreted)):
-                    t = window(call)
-                    if r:
-                        ms[name].append(t)
+            calls = {"compiled": compiled, "program": interpreted}
+            ms = alternate(ctx, calls, a.passes, a.rounds)
             ev = {}
-            for name, call, scopes in (("compiled", compiled, ("relations_extract",)), ("program", interpreted, ("relation_program_count", "relation_program_emit"))):
-                assert L.bfhip_profile_enable(ctx._h, 1) == 0 and L.bfhip_profile_reset(ctx._h) == 0
-                window(call)
-                rep = profile_report(pkg, ctx)
-                assert L.bfhip_profile_enable(ctx._h, 0) == 0
-                ev[name] = {s: rep[s]["total_ms"] / a.passes for s in scopes}
-                ev[name]["all"] = sum(v["total_ms"] for v in rep.values()) / a.passes
+            for name, scopes in (("compiled", ("relations_extract",)), ("program", ("relation_program_count", "relation_program_emit"))):
+                rep = events(ctx, calls[name], a.passes)
+                ev[name] = {s: rep[s][0] for s in scopes}
+                ev[name]["all"] = sum(t for t, _ in rep.values())
             reports, log_sizes = want.reports, list(tr.log_sizes)
         finally:
             tr.close()
@@ -109,14 +81,11 @@ def main():
              f"programs: {sum(s['n_instr'] for s in shapes)} instructions in all, at most {max(s['m_regs'] for s in shapes)} m registers "
              f"({256 * max(s['m_regs'] for s in shapes)} bytes of LDS per wave), 15 entries; 30 interpreter launches per pass against 6 compiled ones", "",
              "path | ms per pass: median (min-max) | by HIP events per pass: all scopes, extraction alone",
-             f"compiled | {statistics.median(c):.4f} ({min(c):.4f}-{max(c):.4f}) | {ev['compiled']['all']:.4f}, {ext_c:.4f} (relations_extract; k_rel_emit is inside relations_sort)",
-             f"program | {statistics.median(p):.4f} ({min(p):.4f}-{max(p):.4f}) | {ev['program']['all']:.4f}, {ext_p:.4f} "
+             f"compiled | {cell(c, 4)} | {ev['compiled']['all']:.4f}, {ext_c:.4f} (relations_extract; k_rel_emit is inside relations_sort)",
+             f"program | {cell(p, 4)} | {ev['program']['all']:.4f}, {ext_p:.4f} "
              f"(relation_program_count {ev['program']['relation_program_count']:.4f} + relation_program_emit {ev['program']['relation_program_emit']:.4f})",
              f"program / compiled | {statistics.median(p) / statistics.median(c):.2f}x | {ev['program']['all'] / ev['compiled']['all']:.2f}x all scopes"]
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    if a.out:
-        open(a.out, "w").write(text)
+    emit("\n".join(lines) + "\n", a.out)
 
 
 if __name__ == "__main__":

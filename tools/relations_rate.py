@@ -2,51 +2,30 @@
 """What bfhip_trace_relations costs beside bfhip_trace_check and a proof of the same trace: fib19 (LOG_MAX_ROWS 24) and the synthetic
 2^22-row trace of tools/benchlib/workloads.py (LOG_MAX_ROWS 22), in one process each workload.
 
-  relations  median of 5 after 2 warm-ups. GPU time by HIP events (bfhip_profile_enable mode 1: one event pair around each stage of each of
-             the three relations — extract, sort, reduce, report; the host's three small read-backs per relation lie between the pairs) and the
-             wall time of the whole call.
+  relations  median of 5 after 2 warm-ups, every call timed on its own (`repeated` of tools/ratelib.py). GPU time by HIP events (one event
+             pair around each stage of each of the three relations — extract, sort, reduce, report; the host's three small read-backs per
+             relation lie between the pairs) and the wall time of the whole call.
   check      the same protocol for Trace.check(): its two event pairs and its wall time.
   proof      median of 5 after 2 warm-ups of the same resident trace with the profiler off: the total of phase_seconds.
 
 A diagnostic: no threshold. Output: one block of text per workload (--out FILE also writes it to a file)."""
 import argparse
-import ctypes
-import json
 import os
 import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from tools.benchlib.workloads import FIB19, load_package, sweep_program      # noqa: E402
+from tools.benchlib.workloads import FIB19, sweep_program      # noqa: E402
+from ratelib import emit, load_package, repeated, require_gpu      # noqa: E402
 
 STAGES = ("relations_extract", "relations_sort", "relations_reduce", "relations_report")
 
 
-def profile_ms(pkg, ctx):
-    js = ctypes.c_void_p()
-    assert pkg.lib().bfhip_profile_report(ctx._h, ctypes.byref(js)) == 0
-    rep = json.loads(ctypes.string_at(js).decode())
-    pkg.lib().bfhip_free_host(js)
-    return {k: v["total_ms"] for k, v in rep.items()}
-
-
-def timed(pkg, ctx, call, names, reps, warmup):
+def timed(ctx, call, names, reps, warmup):
     """(GPU ms per stage, wall ms) of `call`, one sample per repetition."""
-    L = pkg.lib()
-    gpu, wall = [], []
-    assert L.bfhip_profile_enable(ctx._h, 1) == 0
-    for i in range(warmup + reps):
-        assert L.bfhip_profile_reset(ctx._h) == 0
-        t0 = time.perf_counter()
-        call()
-        dt = time.perf_counter() - t0
-        ms = profile_ms(pkg, ctx)
-        if i >= warmup:
-            gpu.append([ms.get(n, 0.0) for n in names]); wall.append(1e3 * dt)
-    assert L.bfhip_profile_enable(ctx._h, 0) == 0
-    return gpu, wall
+    kept = repeated(ctx, call, reps, warmup)
+    return [[ms.get(n, 0.0) for n in names] for _, ms in kept], [wall for wall, _ in kept]
 
 
 def measure(pkg, name, code, log_max_rows, reps, warmup):
@@ -54,8 +33,8 @@ def measure(pkg, name, code, log_max_rows, reps, warmup):
     tr = pkg.Trace(ctx, code)
     res = tr.relations()
     assert res.balanced, res.lines()
-    rel_gpu, rel_wall = timed(pkg, ctx, lambda: tr.relations(), STAGES, reps, warmup)
-    chk_gpu, chk_wall = timed(pkg, ctx, lambda: tr.check(), ("trace_check_logup", "k_check_cells"), reps, warmup)
+    rel_gpu, rel_wall = timed(ctx, lambda: tr.relations(), STAGES, reps, warmup)
+    chk_gpu, chk_wall = timed(ctx, lambda: tr.check(), ("trace_check_logup", "k_check_cells"), reps, warmup)
     total = []
     for i in range(warmup + reps):
         _, ph = tr.prove(log_max_rows, want_json=False)
@@ -81,13 +60,11 @@ def main():
     ap.add_argument("--reps", type=int, default=5); ap.add_argument("--warmup", type=int, default=2); ap.add_argument("--out")
     a = ap.parse_args()
     pkg = load_package()
+    require_gpu(pkg, "relations_rate")
     lines = []
     for name, code, lmr in (("fib19", FIB19, 24), ("synthetic 2^22 rows", sweep_program(22), 22)):
         lines += measure(pkg, name, code, lmr, a.reps, a.warmup) + [""]
-    text = "\n".join(lines)
-    print(text)
-    if a.out:
-        open(a.out, "w").write(text)
+    emit("\n".join(lines) + "\n", a.out)
 
 
 if __name__ == "__main__":

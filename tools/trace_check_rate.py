@@ -2,50 +2,35 @@
 """What bfhip_trace_check costs beside a proof of the same trace: fib19 (LOG_MAX_ROWS 24) and the synthetic 2^22-row trace of
 tools/benchlib/workloads.py (LOG_MAX_ROWS 22), in one process each workload.
 
-  check   median of 5 after 2 warm-ups. GPU time by HIP events (bfhip_profile_enable mode 1: one event pair around the four logUp launches,
-          one around the 26 check launches) and the wall time of the whole call (staging, two read-backs).
+  check   median of 5 after 2 warm-ups, every call timed on its own (`repeated` of tools/ratelib.py). GPU time by HIP events (one event
+          pair around the four logUp launches, one around the 26 check launches) and the wall time of the whole call (staging, two
+          read-backs).
   proof   median of 5 after 2 warm-ups of the same resident trace with the profiler off: the `interaction` entry of phase_seconds (logUp
           generation + interaction tree + the round trip) and the total.
 
 The check shares the logUp generation with that phase and adds one read of the row-granular main columns and two reads of the last logUp
 column; it does no transform and no hashing. Output: one block of text per workload (--out FILE also writes it to a file)."""
 import argparse
-import ctypes
-import json
 import os
 import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from tools.benchlib.workloads import FIB19, load_package, sweep_program      # noqa: E402
-
-
-def profile_ms(pkg, ctx):
-    js = ctypes.c_void_p()
-    assert pkg.lib().bfhip_profile_report(ctx._h, ctypes.byref(js)) == 0
-    rep = json.loads(ctypes.string_at(js).decode())
-    pkg.lib().bfhip_free_host(js)
-    return {k: v["total_ms"] for k, v in rep.items()}
+from tools.benchlib.workloads import FIB19, sweep_program      # noqa: E402
+from ratelib import emit, load_package, repeated, require_gpu      # noqa: E402
 
 
 def measure(pkg, name, code, log_max_rows, reps, warmup):
-    L = pkg.lib()
     ctx = pkg.Context(0, max_log_domain=log_max_rows + 2)
     tr = pkg.Trace(ctx, code)
-    gpu, wall, parts = [], [], []
-    assert L.bfhip_profile_enable(ctx._h, 1) == 0
-    for i in range(warmup + reps):
-        assert L.bfhip_profile_reset(ctx._h) == 0
-        t0 = time.perf_counter()
-        res = tr.check()
-        dt = time.perf_counter() - t0
+    results = []
+    kept = repeated(ctx, lambda: results.append(tr.check()), reps, warmup)
+    for res in results:
         assert res.ok, res.failures()
-        ms = profile_ms(pkg, ctx)
-        if i >= warmup:
-            gpu.append(ms["trace_check_logup"] + ms["k_check_cells"]); wall.append(1e3 * dt); parts.append((ms["trace_check_logup"], ms["k_check_cells"]))
-    assert L.bfhip_profile_enable(ctx._h, 0) == 0
+    wall = [w for w, _ in kept]
+    parts = [(ms["trace_check_logup"], ms["k_check_cells"]) for _, ms in kept]
+    gpu = [a + b for a, b in parts]
     inter, total = [], []
     for i in range(warmup + reps):
         _, ph = tr.prove(log_max_rows, want_json=False)
@@ -70,13 +55,11 @@ def main():
     ap.add_argument("--reps", type=int, default=5); ap.add_argument("--warmup", type=int, default=2); ap.add_argument("--out")
     a = ap.parse_args()
     pkg = load_package()
+    require_gpu(pkg, "trace_check_rate")
     lines = []
     for name, code, lmr in (("fib19", FIB19, 24), ("synthetic 2^22 rows", sweep_program(22), 22)):
         lines += measure(pkg, name, code, lmr, a.reps, a.warmup) + [""]
-    text = "\n".join(lines)
-    print(text)
-    if a.out:
-        open(a.out, "w").write(text)
+    emit("\n".join(lines) + "\n", a.out)
 
 
 if __name__ == "__main__":
