@@ -258,10 +258,14 @@ impl PolyOps for HipBackend {
     type Twiddles = HipTwiddles;
 
     fn new_canonical_ordered(coset: CanonicCoset, values: Col<Self, BaseField>) -> CircleEvaluation<Self, BaseField, BitReversedOrder> {
-        // canonic-coset order -> circle-domain order -> bit-reversed: a host permutation of indices, one upload (cold path: tests only)
-        let host = values.to_cpu();
-        let eval = stwo_prover::core::backend::CpuBackend::new_canonical_ordered(coset, host);
-        CircleEvaluation::new(coset.circle_domain(), eval.values.into_iter().collect())
+        // canonic-coset (row) order -> bit-reversed circle-domain order on the device: bfhip_columns_from_rows over the column itself as a
+        // column-major table of one column (one launch, every word checked for canonicity; include/bfhip.h "Row order")
+        let out = HipColumn::<BaseField>::alloc(values.len);
+        let (src, dst) = ([values.ptr as *const u32], [out.ptr]);
+        let table = sys::BfhipRowsTable { layout: sys::BFHIP_ROWS_COLUMN_MAJOR, n_cols: 1, rows_d: std::ptr::null(), cols_h: src.as_ptr(), n_rows: values.len as u64,
+                                          row_stride: 0, flags: 0, reserved: 0 };
+        check(unsafe { sys::bfhip_columns_from_rows(ctx().p(), &table, coset.log_size(), std::ptr::null(), std::ptr::null(), dst.as_ptr(), 1) });
+        CircleEvaluation::new(coset.circle_domain(), out)
     }
     fn precompute_twiddles(coset: Coset) -> TwiddleTree<Self> {
         let (mut tw, mut itw, mut root_log) = (std::ptr::null(), std::ptr::null(), 0u32);

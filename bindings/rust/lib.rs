@@ -646,6 +646,52 @@ pub fn logup_program_generate_batch(ctx: &Context, comps: &[LogupComponent]) -> 
     Ok((claimed, total))
 }
 
+// ---- row order <-> storage order (`include/bfhip.h` "Row order") --------------------------------------------------------------------------------
+/// A device table in row order: row-major (`word (r, c)` at `rows[r * row_stride + c]`, `row_stride >= n_cols` words) or one device
+/// pointer per source column.
+pub enum RowsTable<'a> {
+    RowMajor { rows: *const u32, n_rows: u64, n_cols: u32, row_stride: u64 },
+    ColumnMajor { cols: &'a [*const u32], n_rows: u64 },
+}
+
+/// `bfhip_columns_from_rows`: a trace in ROW order (row r + 1 = the row at offset +1) to storage-order columns of `2^log_size` words, one
+/// launch. `src_cols` empty = the identity; otherwise the source column of every output column (subset, permutation, repeats). Rows from
+/// `n_rows` on hold `pad[k]` (`pad` empty = 0), or with `repeat_last` a copy of the last row. Every word read is checked: a non-canonical
+/// one is an `Err` naming the lowest row, then the lowest output column. Takes nothing from the arena; works while a session is open.
+pub fn columns_from_rows(ctx: &Context, table: &RowsTable, log_size: u32, src_cols: &[u32], pad: &[u32], repeat_last: bool, out: &[*mut u32]) -> Result<(), String> {
+    if !src_cols.is_empty() && src_cols.len() != out.len() { return Err("one source column per output column".into()); }
+    if !pad.is_empty() && pad.len() != out.len() { return Err("one pad value per output column".into()); }
+    let flags = if repeat_last { sys::BFHIP_ROWS_REPEAT_LAST } else { 0 };
+    let raw = match *table {
+        RowsTable::RowMajor { rows, n_rows, n_cols, row_stride } =>
+            sys::BfhipRowsTable { layout: sys::BFHIP_ROWS_ROW_MAJOR, n_cols, rows_d: rows, cols_h: std::ptr::null(), n_rows, row_stride, flags, reserved: 0 },
+        RowsTable::ColumnMajor { cols, n_rows } =>
+            sys::BfhipRowsTable { layout: sys::BFHIP_ROWS_COLUMN_MAJOR, n_cols: cols.len() as u32, rows_d: std::ptr::null(), cols_h: cols.as_ptr(), n_rows, row_stride: 0, flags, reserved: 0 },
+    };
+    check(unsafe { sys::bfhip_columns_from_rows(ctx.0, &raw, log_size, if src_cols.is_empty() { std::ptr::null() } else { src_cols.as_ptr() },
+                                                if pad.is_empty() { std::ptr::null() } else { pad.as_ptr() }, out.as_ptr(), out.len() as u32) })
+}
+
+/// `bfhip_rows_from_columns`: the inverse — storage-order columns to words `(r, c)`, `r < n_rows`, `c < cols.len()`, of a row-major device
+/// table; the rest of each row is left untouched. Enqueued on the context's stream; no canonicity check.
+pub fn rows_from_columns(ctx: &Context, cols: &[*const u32], log_size: u32, rows: *mut u32, n_rows: u64, row_stride: u64) -> Result<(), String> {
+    check(unsafe { sys::bfhip_rows_from_columns(ctx.0, cols.as_ptr(), cols.len() as u32, log_size, rows, n_rows, row_stride, 0) })
+}
+
+/// `bfhip_cell_of_row` (host only): the storage index of coset index `row`.
+pub fn cell_of_row(log_size: u32, row: u64) -> Result<u64, String> {
+    let mut cell = 0u64;
+    check(unsafe { sys::bfhip_cell_of_row(log_size, row, &mut cell) })?;
+    Ok(cell)
+}
+
+/// `bfhip_row_of_cell` (host only): the row an author wrote for the cell that `AirProgram::check` or a logUp generation reports.
+pub fn row_of_cell(log_size: u32, cell: u64) -> Result<u64, String> {
+    let mut row = 0u64;
+    check(unsafe { sys::bfhip_row_of_cell(log_size, cell, &mut row) })?;
+    Ok(row)
+}
+
 // ---- the protocol driver (`include/bfhip.h` "Proving an AIR given as programs") ----------------------------------------------------------------
 // `prover::prove` / `verify` for an AIR given as a statement: trees, relations, components with their column bindings and parameter rules.
 // `air_prove` orders the session, the mixes and draws, the batched interaction trace, `air_compose`, the mask and `prove_values`;

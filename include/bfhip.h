@@ -673,7 +673,7 @@ int32_t bfhip_brainfuck_composition_at_point(const uint32_t log_sizes_h[13], con
  *   and a second bfhip_pcs_create.
  * Everything else keeps working, which is what the caller's constraint sweep needs: bfhip_malloc / bfhip_free / bfhip_upload / bfhip_download /
  * bfhip_memset_zero, bfhip_interpolate, bfhip_evaluate, bfhip_is_first_coeffs, bfhip_is_first_lde, bfhip_eval_at_point, bfhip_logup_generate, bfhip_eval_constraints,
- * bfhip_air_eval_domain, bfhip_air_kernel_eval_domain (and bfhip_air_compile), bfhip_logup_program_generate, bfhip_accumulate, the Merkle / fold / grind / gather single operations, resident traces' getters and the profiler.
+ * bfhip_air_eval_domain, bfhip_air_kernel_eval_domain (and bfhip_air_compile), bfhip_logup_program_generate, bfhip_columns_from_rows, bfhip_rows_from_columns, bfhip_accumulate, the Merkle / fold / grind / gather single operations, resident traces' getters and the profiler.
  * Not supported: a context in a shard group (create refuses; joining refuses while a session is open); a pool's sub-context while anything
  * is queued, running or not yet taken on the pool.
  * Launch order: the plain one only (wait, draw, copy, launch). No mailbox order, and the overlap mask (bfhip_ctx_set_overlap) is ignored.
@@ -1113,6 +1113,69 @@ int32_t bfhip_air_verify(const bfhip_air_statement* statement, const bfhip_conve
  * the rules are checked under (NULL = defaults), with max_log_domain 30. Refusals are the validator's, in this function's name. */
 int32_t bfhip_air_statement_samples(const bfhip_air_statement* statement, const bfhip_pcs_config* pcs, uint32_t counts[4], uint32_t* tree_n_cols,
                                     uint32_t* point_log_sizes, int32_t* point_offsets, uint32_t* n_samples, uint32_t* point_idx);
+
+/* ---- Row order: a trace as its author writes it -> the storage-order columns of ANY AIR, and back ------------------------------------------
+ * Every entry point above takes device columns in STORAGE order: CanonicCoset(log_size).circle_domain() bit-reversed. An AIR author writes a
+ * witness in ROW order — row r + 1 is "the row at offset +1", the coset order. stwo's step between the two is
+ * CircleEvaluation::new_canonical_ordered plus the bit reversal; here it is one launch, the first step of the generic pipeline
+ * (INTEGRATION.md section 2e), in front of bfhip_pcs_commit / bfhip_air_check / bfhip_logup_program_generate(_batch) / bfhip_relation_program_* /
+ * bfhip_air_prove.
+ * The order (normative). n = 2^log_size. Cell (storage index) s holds row (coset index) i:
+ *     d = bit_reverse(s, log_size);   i = 2 d if d < n / 2, else 2 (n - 1 - d) + 1.
+ * Equivalently, for every d < n / 2 with s = bit_reverse(d, log_size): row 2 d lives in cell s, row 2 d + 1 in cell ~s & (n - 1).
+ *
+ * bfhip_cell_of_row / bfhip_row_of_cell (host only): that map and its inverse, 1 <= log_size <= 30, argument below 2^log_size; otherwise -1 with
+ *   "bfhip_cell_of_row: <rule>" / "bfhip_row_of_cell: <rule>". bfhip_air_check and bfhip_logup_program_generate report CELLS: with
+ *   bfhip_row_of_cell "first at cell 37" becomes the row the author wrote.
+ *
+ * bfhip_columns_from_rows: a table of n_rows rows and n_cols source columns of u32 words, in row order, to n_out storage-order columns.
+ *   table->layout BFHIP_ROWS_ROW_MAJOR: word (r, c) at rows_d[r * row_stride + c]; row_stride in words, >= n_cols (a table of structs with
+ *     trailing fields works); r * row_stride may exceed 2^32: source offsets are 64-bit. cols_h is ignored.
+ *   table->layout BFHIP_ROWS_COLUMN_MAJOR: cols_h = host array of n_cols device pointers, each to n_rows words in row order. rows_d and
+ *     row_stride are ignored.
+ *   0 <= n_rows <= 2^log_size, 1 <= log_size <= 30, n_cols >= 1.
+ *   src_cols_h[k] = the source column of output column k; NULL = the identity (then n_out <= n_cols). A subset, a permutation, the same
+ *     source column more than once: one row table can feed several trees.
+ *   out_cols_h: n_out device pointers, each to 2^log_size words, written in storage order. 1 <= n_out <= 256 = BFHIP_AIR_MAX_COLUMNS.
+ *   Padding, rows n_rows .. 2^log_size - 1: the constant pad_h[k] of output column k (NULL = 0; a value >= p = 2^31 - 1 is refused on the
+ *     host), or with BFHIP_ROWS_REPEAT_LAST in table->flags a copy of row n_rows - 1 (refused with n_rows = 0; pad_h is then ignored).
+ *   Canonicity: every word read is checked on the way. A word >= 2^31 - 1 makes the call return -1 with
+ *     "bfhip_columns_from_rows: row <r>, column <k>: <v> is not a canonical M31 value" — the lowest row, then the lowest OUTPUT column k
+ *     (a 64-bit integer atomicMin over row * 256 + k). The outputs are then unspecified; nothing faults and the context stays usable.
+ *   One launch on the context's stream and one read-back (the bad-word record: the call returns when the columns are written); a refused
+ *     word costs a second, 4-byte one to quote its value. The table is borrowed for the call and not modified.
+ *   Memory: nothing from the arena (bfhip_ctx_memory out[3] is unchanged) and no allocation — column descriptors and the record come from
+ *     the staging ring. Works while a commitment-scheme session is open.
+ *   Refused, -1 with "bfhip_columns_from_rows: <rule>", nothing enqueued, the context usable: null pointers (ctx aside: "null context");
+ *     log_size out of range; n_rows > 2^log_size; row_stride < n_cols; a column index not below n_cols; n_out of 0 or above
+ *     BFHIP_AIR_MAX_COLUMNS; an unknown layout or flag bit; reserved != 0; pad >= p; REPEAT_LAST with n_rows = 0; an output column whose byte
+ *     range shares a byte with the source (row-major: the whole table from word (0, 0) to the last word of the last row; column-major: any
+ *     source column) or with another output column — the message names the two; a context in a shard group.
+ * bfhip_rows_from_columns: the inverse. n_cols storage-order columns of 2^log_size words -> words (r, c), r < n_rows, c < n_cols, of the
+ *   row-major device table rows_d with row_stride >= n_cols; the rest of each row is left untouched. No canonicity check, no read-back: the
+ *   launch is enqueued on the context's stream (bfhip_download behind it is ordered). What a caller uses to read a generated column back in
+ *   row order: multiplicities, a logUp column. Refused in its own name: null pointers, log_size, n_rows, row_stride, n_cols of 0 or above
+ *   BFHIP_AIR_MAX_COLUMNS, reserved != 0, the table sharing a byte with a column, a context in a shard group.
+ * Kernel (csrc/rows.hip): tiles of 1024 rows through LDS, 8 or 16 columns per pass; log_size below 10: one thread per cell.
+ * Not built: shard groups, row-granular (shifted) outputs, host-pointer sources streamed in chunks, pool jobs for generic statements.
+ * Layout (natural alignment, declaration order):
+ *   bfhip_rows_table  48 bytes: layout 0, n_cols 4, rows_d 8, cols_h 16, n_rows 24, row_stride 32, flags 40, reserved 44 */
+enum { BFHIP_ROWS_ROW_MAJOR = 0, BFHIP_ROWS_COLUMN_MAJOR = 1, BFHIP_ROWS_REPEAT_LAST = 1 };
+typedef struct bfhip_rows_table {
+    uint32_t layout;                  /* BFHIP_ROWS_ROW_MAJOR or BFHIP_ROWS_COLUMN_MAJOR */
+    uint32_t n_cols;                  /* source columns */
+    const uint32_t* rows_d;           /* row-major: device table */
+    const uint32_t* const* cols_h;    /* column-major: host array of n_cols device pointers */
+    uint64_t n_rows;
+    uint64_t row_stride;              /* row-major: words from one row to the next */
+    uint32_t flags, reserved;         /* flags: BFHIP_ROWS_REPEAT_LAST; reserved must be 0 */
+} bfhip_rows_table;
+int32_t bfhip_columns_from_rows(bfhip_ctx* ctx, const bfhip_rows_table* table, uint32_t log_size, const uint32_t* src_cols_h, const uint32_t* pad_h,
+                                uint32_t* const* out_cols_h, uint32_t n_out);
+int32_t bfhip_rows_from_columns(bfhip_ctx* ctx, const uint32_t* const* cols_h, uint32_t n_cols, uint32_t log_size, uint32_t* rows_d, uint64_t n_rows,
+                                uint64_t row_stride, uint32_t reserved);
+int32_t bfhip_cell_of_row(uint32_t log_size, uint64_t row, uint64_t* cell);
+int32_t bfhip_row_of_cell(uint32_t log_size, uint64_t cell, uint64_t* row);
 
 /* ---- Relation programs: the lookup tuples of ANY AIR that do not cancel ------------------------------------------------------------------------
  * bfhip_relation_summary / bfhip_trace_relations know the three Brainfuck relations and the 13 table layouts. An AIR proved through bfhip_pcs_* +

@@ -11,6 +11,7 @@ from ._abi import BfhipError, Owned, _check, _ptr_array, _qm31s, _take_host_stri
 from ._abi_gen import (BFHIP_CHANNEL_BLAKE2S as CHANNEL_BLAKE2S, BFHIP_CHANNEL_POSEIDON252 as CHANNEL_POSEIDON252, BFHIP_LOGUP_MASK_CUR_PREV as LOGUP_MASK_CUR_PREV,
                        BFHIP_LOGUP_MASK_PREV_CUR as LOGUP_MASK_PREV_CUR, BFHIP_MERKLE_RFC7693 as MERKLE_RFC7693, BFHIP_MERKLE_STWO_COMPRESS as MERKLE_STWO_COMPRESS,
                        BFHIP_MIX_U64_COMPRESS as MIX_U64_COMPRESS, BFHIP_MIX_U64_HASH as MIX_U64_HASH)
+from . import columns as _columns
 from .programs import AIR_PROVE_CHECK, AirComponent, CompiledAir, LogupComponent
 from .reports import (COMPONENT_NAMES, AirCheckReport, CheckReport, MultiplicityReport, MultiplicityResult, PreflightReport, RelationEntry, RelationProgramTable,
                       RelationTable, _relation_result)
@@ -308,6 +309,22 @@ class Context(Owned):
         out = np.empty(n, dtype=dtype)
         _check(abi().bfhip_download(self._h, out.ctypes.data, ptr, out.nbytes))
         return out
+
+    # -- row order <-> storage order ----------------------------------------------------------------------------------------------------
+    def columns_from_rows(self, table, log_size, columns=None, pad=None, repeat_last=False, out=None):
+        """bfhip_columns_from_rows: a trace in ROW order (row r + 1 = the row at offset +1) to storage-order device columns of 2^log_size
+        words, in one launch; every word read is checked to be a canonical M31 value (BfhipError naming the lowest row, then column).
+        table: a (n_rows, n_src) uint32 array (uploaded into a temporary device buffer, freed before return), a DeviceRows(ptr, n_rows,
+        n_cols, row_stride) or a DeviceRowColumns(ptrs, n_rows). columns: the source column of every output column (None = all, in
+        order; subsets, permutations and repeats are fine). Rows n_rows .. 2^log_size - 1 hold pad[k] (None = 0), or with repeat_last a
+        copy of the last row. out: device pointers to write instead of new columns. Returns a Columns handle (closable, a context
+        manager) whose pointers go wherever column pointers are taken."""
+        return _columns.columns_from_rows(self, table, log_size, columns, pad, repeat_last, out)
+
+    def rows_from_columns(self, col_ptrs, log_size, n_rows=None):
+        """bfhip_rows_from_columns: storage-order device columns (pointers, or a Columns handle) back in row order, as a (n_rows,
+        n_cols) uint32 array; n_rows None = all 2^log_size. What reads a generated column — multiplicities, a logUp column — by row."""
+        return _columns.rows_from_columns(self, col_ptrs, log_size, n_rows)
 
     # -- PolyOps ---------------------------------------------------------------------------------------------------
     def interpolate(self, src_ptrs, dst_ptrs, log_size, replicated=False):

@@ -5,6 +5,9 @@
 #include "pcs_types.h"
 #include "host/quotients.h"
 #include "host/hash.h"
+#include "rows.h"
+#include "rows_index.h"
+#include <string>
 #include <algorithm>
 #include <vector>
 
@@ -61,6 +64,25 @@ static const u32* stage_alpha(Ctx& c, const uint32_t alpha_h[4]) {
     q31_words(a, w); q31_words(q_mul(a, a), w + 4);
     c.stage_checkpoint();
     return c.stage(w, 8);
+}
+// ---- what the two row-order entry points share (rows.hip) ----
+struct ByteRange {
+    u64 base, bytes; std::string name;
+    bool overlaps(const ByteRange& o) const { return bytes && o.bytes && base < o.base + o.bytes && o.base < base + bytes; }
+};
+static void rows_check_index(const char* who, uint32_t log_size, uint64_t index, const uint64_t* out) {
+    if (!out) throw HipError(std::string(who) + ": null argument");
+    if (log_size < 1 || log_size > ROWS_MAX_LOG) throw HipError(std::string(who) + ": log_size " + std::to_string(log_size) + " is outside 1..30");
+    if (index >> log_size) throw HipError(std::string(who) + ": index " + std::to_string(index) + " is not below 2^" + std::to_string(log_size));
+}
+static void rows_check_shape(const std::string& who, uint32_t log_size, uint64_t n_rows, uint32_t n_cols, const char* n_cols_name) {
+    if (log_size < 1 || log_size > ROWS_MAX_LOG) throw HipError(who + "log_size " + std::to_string(log_size) + " is outside 1..30");
+    if (n_rows > (u64(1) << log_size)) throw HipError(who + "n_rows " + std::to_string(n_rows) + " exceeds 2^" + std::to_string(log_size));
+    if (n_cols == 0 || n_cols > BFHIP_AIR_MAX_COLUMNS)
+        throw HipError(who + n_cols_name + " " + std::to_string(n_cols) + " is outside 1.." + std::to_string((int)BFHIP_AIR_MAX_COLUMNS) + " (BFHIP_AIR_MAX_COLUMNS)");
+}
+static void rows_not_sharded(const Ctx& c, const std::string& who) {
+    if (c.shard.count > 1) throw HipError(who + "a context in a shard group is not supported (bfhip_ctx_leave_group first)");
 }
 
 extern "C" {
@@ -298,6 +320,112 @@ int32_t bfhip_accumulate_quotients(bfhip_ctx* ctx, uint32_t log_size, const uint
     for (int w = 0; w < 4; w++) a.out[w] = out_d[w];
     const u32 blocks = quotient_groups_layout(&a, 1);
     accumulate_quotients(c.stream, c.stage(&a, 1), 1, blocks);
+    BF_HIP(hipGetLastError());
+    return 0;
+    API_CATCH
+}
+
+// ---- row order <-> storage order (include/bfhip.h "Row order"; rows.hip) ----
+int32_t bfhip_cell_of_row(uint32_t log_size, uint64_t row, uint64_t* cell) {
+    API_TRY
+    rows_check_index("bfhip_cell_of_row", log_size, row, cell);
+    *cell = rows_cell_of_row(log_size, (u32)row);
+    return 0;
+    API_CATCH
+}
+int32_t bfhip_row_of_cell(uint32_t log_size, uint64_t cell, uint64_t* row) {
+    API_TRY
+    rows_check_index("bfhip_row_of_cell", log_size, cell, row);
+    *row = rows_row_of_cell(log_size, (u32)cell);
+    return 0;
+    API_CATCH
+}
+int32_t bfhip_columns_from_rows(bfhip_ctx* ctx, const bfhip_rows_table* table, uint32_t log_size, const uint32_t* src_cols_h, const uint32_t* pad_h,
+                                uint32_t* const* out_cols_h, uint32_t n_out) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    const std::string who = "bfhip_columns_from_rows: ";
+    if (!table || !out_cols_h) throw HipError(who + "null argument");
+    if (table->reserved != 0) throw HipError(who + "reserved must be 0");
+    if (table->layout != BFHIP_ROWS_ROW_MAJOR && table->layout != BFHIP_ROWS_COLUMN_MAJOR) throw HipError(who + "unknown layout " + std::to_string(table->layout));
+    if (table->flags & ~uint32_t(BFHIP_ROWS_REPEAT_LAST)) throw HipError(who + "unknown flag bits " + std::to_string(table->flags));
+    const bool col_major = table->layout == BFHIP_ROWS_COLUMN_MAJOR, repeat = (table->flags & BFHIP_ROWS_REPEAT_LAST) != 0;
+    const u64 n_rows = table->n_rows, stride = col_major ? 1 : table->row_stride;
+    rows_check_shape(who, log_size, n_rows, n_out, "n_out");
+    if (table->n_cols == 0) throw HipError(who + "the table has no columns");
+    if (!col_major && table->row_stride < table->n_cols) throw HipError(who + "row_stride " + std::to_string(table->row_stride) + " is below n_cols " + std::to_string(table->n_cols));
+    if (repeat && n_rows == 0) throw HipError(who + "BFHIP_ROWS_REPEAT_LAST needs at least one row");
+    if (col_major ? !table->cols_h : (n_rows && !table->rows_d)) throw HipError(who + "null table pointer");
+    rows_not_sharded(c, who);
+    const u64 col_bytes = sizeof(u32) << log_size;
+    std::vector<RowsCol> cols(n_out);
+    std::vector<ByteRange> used;      // the source first, then the output columns accepted so far
+    if (col_major) {
+        for (u32 j = 0; j < table->n_cols; j++) {
+            if (n_rows && !table->cols_h[j]) throw HipError(who + "source column " + std::to_string(j) + " is a null pointer");
+            used.push_back({(u64)(uintptr_t)table->cols_h[j], n_rows * sizeof(u32), "source column " + std::to_string(j)});
+        }
+    } else if (n_rows) {
+        used.push_back({(u64)(uintptr_t)table->rows_d, (rows_src_offset(n_rows - 1, stride, table->n_cols - 1) + 1) * sizeof(u32), "the source table"});
+    }
+    for (u32 k = 0; k < n_out; k++) {
+        const u32 j = src_cols_h ? src_cols_h[k] : k;
+        if (j >= table->n_cols) throw HipError(who + "column index " + std::to_string(j) + " is not below n_cols " + std::to_string(table->n_cols));
+        if (!out_cols_h[k]) throw HipError(who + "output column " + std::to_string(k) + " is a null pointer");
+        if (!repeat && pad_h && pad_h[k] >= P31) throw HipError(who + "pad value " + std::to_string(pad_h[k]) + " of output column " + std::to_string(k) + " is not a canonical M31 value");
+        const ByteRange out{(u64)(uintptr_t)out_cols_h[k], col_bytes, "output column " + std::to_string(k)};
+        for (const ByteRange& u : used) if (out.overlaps(u)) throw HipError(who + out.name + " overlaps " + u.name);
+        used.push_back(out);
+        const u64 table_word = col_major ? (u64)(uintptr_t)table->cols_h[j] : (u64)(uintptr_t)(table->rows_d + j);
+        cols[k] = RowsCol{table_word, out.base, pad_h && !repeat ? pad_h[k] : 0u, 0};
+    }
+    c.stage_checkpoint(Ctx::stage_round(sizeof(RowsCol) * n_out) + 256);
+    const unsigned long long none = ~0ull;
+    RowsArgs a{};
+    {
+        StageBatch sb(c);
+        a.cols = c.stage(cols.data(), n_out);
+        a.first_bad = c.stage(&none, 1);
+        sb.end();
+    }
+    a.n_rows = n_rows; a.row_stride = stride; a.log_size = log_size; a.n_cols = n_out; a.repeat_last = repeat;
+    rows_launch(c.stream, a, false, col_major);
+    BF_HIP(hipGetLastError());
+    unsigned long long bad = ~0ull;
+    c.read_back(&bad, a.first_bad, sizeof bad);
+    if (bad != ~0ull) {
+        const u64 row = bad >> 8; const u32 k = (u32)(bad & 255u);
+        u32 v = 0;
+        c.read_back(&v, (const u32*)(uintptr_t)cols[k].table + row * stride, sizeof v);
+        throw HipError(who + "row " + std::to_string(row) + ", column " + std::to_string(k) + ": " + std::to_string(v) + " is not a canonical M31 value");
+    }
+    return 0;
+    API_CATCH
+}
+int32_t bfhip_rows_from_columns(bfhip_ctx* ctx, const uint32_t* const* cols_h, uint32_t n_cols, uint32_t log_size, uint32_t* rows_d, uint64_t n_rows,
+                                uint64_t row_stride, uint32_t reserved) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    const std::string who = "bfhip_rows_from_columns: ";
+    if (!cols_h || (n_rows && !rows_d)) throw HipError(who + "null argument");
+    if (reserved != 0) throw HipError(who + "reserved must be 0");
+    rows_check_shape(who, log_size, n_rows, n_cols, "n_cols");
+    if (row_stride < n_cols) throw HipError(who + "row_stride " + std::to_string(row_stride) + " is below n_cols " + std::to_string(n_cols));
+    rows_not_sharded(c, who);
+    const ByteRange dst{(u64)(uintptr_t)rows_d, n_rows ? (rows_src_offset(n_rows - 1, row_stride, n_cols - 1) + 1) * sizeof(u32) : 0, "the table"};
+    std::vector<RowsCol> cols(n_cols);
+    for (u32 k = 0; k < n_cols; k++) {
+        if (!cols_h[k]) throw HipError(who + "column " + std::to_string(k) + " is a null pointer");
+        const ByteRange col{(u64)(uintptr_t)cols_h[k], sizeof(u32) << log_size, "column " + std::to_string(k)};
+        if (col.overlaps(dst)) throw HipError(who + col.name + " overlaps " + dst.name);
+        cols[k] = RowsCol{(u64)(uintptr_t)(rows_d + k), col.base, 0, 0};
+    }
+    if (n_rows == 0) return 0;
+    c.stage_checkpoint(Ctx::stage_round(sizeof(RowsCol) * n_cols));
+    RowsArgs a{};
+    a.cols = c.stage(cols.data(), n_cols);
+    a.n_rows = n_rows; a.row_stride = row_stride; a.log_size = log_size; a.n_cols = n_cols;
+    rows_launch(c.stream, a, true, false);
     BF_HIP(hipGetLastError());
     return 0;
     API_CATCH
