@@ -14,21 +14,16 @@
 // whose every value is replicated 16x (the reference broadcasts each table row into 16 SIMD lanes, memory/table.rs:95-104)
 // reduces to, on the 16x smaller row-granular column. See DESIGN.md "replicated columns".
 #include "kernels.h"
-#include <cstdio>
 #include <cstdlib>
 #include <stdexcept>
-#include <algorithm>
-#include <vector>
 #include <mutex>
+#include <optional>
 #include <set>
 #include <string>
 
 namespace bf {
 
-static constexpr int TILE_LOG = 12;          // 4096 elements = 16 KiB of LDS
-static constexpr int TILE = 1 << TILE_LOG;
-static constexpr int CHUNK_LOG = 5;          // 32 x u32 = 128 B contiguous per strided row
-static constexpr int STRIDED_K = TILE_LOG - CHUNK_LOG;  // 7 layers per strided pass
+static constexpr int TILE = 1 << TILE_LOG;   // TILE_LOG, CHUNK_LOG, STRIDED_K and the kernel kinds: fft_plan.h
 static constexpr int FFT_THREADS = 256;
 // PassArgs::scale of an inverse transform is 2^-n = a power of two (m31.h: m_inv_pow2): its exponent, for m_mul_pow2 (uniform: scalar unit)
 __device__ __forceinline__ u32 scale_shift(u32 scale) { return (u32)__builtin_ctz(scale); }
@@ -194,13 +189,10 @@ void is_first_lde(hipStream_t stream, const IsFirstCols& a, u32 log_blowup, cons
 
 // ---------------------------------------------------------------------------------------------------------------------
 // One pass = layers [lo, lo+k) of a size-2^log transform, for the columns cols[by * cpb .. +cpb) of one GROUP (columns of one size and
-// storage). A launch covers several groups (PassArgs table in HBM, kernels.h): workgroup b belongs to the group g with
+// storage). A launch covers several groups (PassArgs table in HBM, fft_plan.h): workgroup b belongs to the group g with
 // groups[g].block0 <= b < groups[g + 1].block0 and is its (tile, column block) = ((b - block0) % grid_x, (b - block0) / grid_x). The 13
 // components of a proof have ~10 distinct sizes: one launch per pass and kernel kind instead of one per size.
 // ---------------------------------------------------------------------------------------------------------------------
-// kernel kinds of a launch. PassArgs::kind != 0 marks a group that rides in ANOTHER kind's launch: the single-pass transforms of 2^6..2^11 cells (K_PASS) and the tiny
-// ones (K_TINY) of a plan join its contiguous-tile launch (r06: a proof issued ~24 separate 5-18 us launches for them, each a latency chain on an otherwise idle GPU)
-enum { K_TILE12 = 0, K_STRIDED5 = 1, K_STRIDED6 = 2, K_PASS = 3, K_TINY = 4, K_STRIDED_K8 = 5, K_STRIDED_K9 = 6, K_STRIDED_K10 = 7, K_KINDS = 8 };
 struct BlockOfGroup { u32 g, tile, by; };
 template <bool INV> __device__ __forceinline__ void fft_tiny_body(const PassArgs& a, const BlockOfGroup& bg);      // defined with k_fft_tiny below
 __device__ __forceinline__ BlockOfGroup find_group(const PassArgs* __restrict__ groups, u32 ngroups) {
@@ -709,140 +701,6 @@ __global__ void __launch_bounds__(256) k_fft_tiny(const PassArgs* __restrict__ g
     fft_tiny_body<INV>(a, bg);
 }
 
-// Host-side pass planner. Inverse: contiguous pass first then strided passes upward; forward: mirror image.
-// fft_plan lays out the passes of every job (one job = the columns of one size and storage); the pass a job executes pi-th goes into
-// the launch (pi, kernel kind), so a batch of jobs costs at most (passes of the largest job) x (kinds in use) launches.
-
-void fft_plan(FftPlan& plan, bool inverse, const FftJob* jobs, size_t njobs, const u32* tw, const u32* itw, u32 tw_root_log) {
-    plan.inverse = inverse; plan.groups.clear(); plan.launches.clear(); plan.d_groups = nullptr;
-    struct Item { int pi, kind; PassArgs a; double bytes, alg; bool single = false; double bfly() const { return 0.5 * a.ncols * (double)(1u << a.log) * a.k; } };      // butterflies of the pass
-    std::vector<Item> items;
-    int max_np = 0;
-    for (size_t ji = 0; ji < njobs; ji++) {
-        const FftJob& job = jobs[ji];
-        const u32 ncols = job.ncols, log = job.log, src_log = job.src_log;
-        if (ncols == 0) continue;
-        PassArgs a{};
-        a.ncols = ncols; a.log = log; a.circle = job.circle ? 1 : 0; a.tw = inverse ? itw : tw; a.tw_total = 1u << tw_root_log; a.scale = 1;
-        // forward: the layers >= src_log only duplicate (zero extension) = wrap-around load. Past 32 cells a lane loads 4 cells at once: a polynomial of 1 or 2
-        // coefficients (the row-granular columns of a 2^4- or 2^5-row component under a large blowup) is zero-padded to 4 by the load (fft_pass_body) and runs 2 layers
-        const u32 nl = inverse ? log : (log > 5 && src_log < 2) ? 2u : src_log;
-        if (log <= 5) {
-            a.dst = job.d_dst; a.src = job.d_src; a.src_mask = (1u << src_log) - 1; a.lo = 0; a.k = nl;
-            a.scale = inverse ? m_inv(1u << log) : 1;
-            a.grid_x = (ncols + (256u >> log) - 1) / (256u >> log); a.cols_per_block = 1;      // k_fft_tiny: a lane per cell, 64 >> log columns per wave, 4 waves per workgroup
-            items.push_back({0, K_TINY, a, 0.0, 0.0, true});
-            max_np = std::max(max_np, 1);
-            continue;
-        }
-        // ---- fast path: 2^12-cell contiguous pass with k0 in [6,12] layers + strided passes of exactly 7 layers ----------------
-        if (log >= 12 && nl >= 6) {
-            u32 ns = nl > 12 ? (nl - 12 + 6) / 7 : 0;
-            u32 k0 = nl - 7 * ns;
-            // 20..22 layers: 12 contiguous + ONE strided pass of 8..10 layers through LDS (two passes instead of three)
-            static const bool two_pass = [] { const char* v = getenv("BFHIP_FFT_TWO_PASS"); return !v || v[0] != '0'; }();
-            const u32 big_k = (two_pass && nl >= 20 && nl <= 22) ? nl - 12 : 0;
-            if (big_k) { ns = 1; k0 = 12; }
-            int np = 1 + (int)ns;
-            max_np = std::max(max_np, np);
-            // profiler accounting: `bytes` = what this pass moves (4 B in + 4 B out per cell), `alg` = this pass's share of the transform's
-            // ALGORITHMIC bytes (iFFT 8N, LDE 12N per column = read the input once, write the output once)
-            const double alg = 4.0 * ncols * ((double)(1u << src_log) + (double)(1u << log)) / np;
-            for (int pi = 0; pi < np; pi++) {
-                int p = inverse ? pi : np - 1 - pi;
-                bool first = pi == 0, last = pi == np - 1;
-                a.src = first ? job.d_src : (const u32* const*)job.d_dst;
-                a.dst = job.d_dst;
-                a.src_mask = first ? ((1u << src_log) - 1) : 0xffffffffu;
-                a.scale = (inverse && last) ? m_inv(1u << log) : 1;
-                u32 ntiles = 1u << (log - 12);
-                // one workgroup walks as many columns as possible per tile (twiddles staged once), as long as >= 2048 workgroups remain
-                u32 cpb = ncols;
-                while (cpb > 1 && (u64)ntiles * ((ncols + cpb - 1) / cpb) < 2048) cpb = (cpb + 1) / 2;
-                a.cols_per_block = cpb;
-                const u32 gy = (ncols + cpb - 1) / cpb;
-                const double bytes = 8.0 * ncols * (double)(1u << log);
-                if (p == 0) {
-                    a.lo = 0; a.k = k0; a.tile_log = 12; a.grid_x = ntiles;
-                    PassArgs b = a; b.block0 = gy;      // block0 temporarily holds the group's grid_y
-                    items.push_back({pi, K_TILE12, b, bytes, alg});
-                } else if (big_k) {
-                    a.lo = 12; a.k = big_k;
-                    const u32 cl = big_k == 10 ? 4 : 5;                       // 64-byte rows at 10 layers (64 KiB of LDS), 128-byte rows otherwise
-                    PassArgs b = a; b.grid_x = 1u << (log - big_k - cl); b.block0 = gy;
-                    items.push_back({pi, big_k == 8 ? K_STRIDED_K8 : big_k == 9 ? K_STRIDED_K9 : K_STRIDED_K10, b, bytes, alg});
-                } else {
-                    a.lo = k0 + 7 * (p - 1); a.k = 7;
-#ifndef BF_STRIDED_WIDE_MIN_LOG
-#define BF_STRIDED_WIDE_MIN_LOG 20
-#endif
-                    // 256-byte rows for big transforms (enough tiles to fill the chip twice over), 128-byte rows otherwise
-                    const bool wide = a.lo >= 6 && log >= BF_STRIDED_WIDE_MIN_LOG;
-                    PassArgs b = a; b.grid_x = wide ? ntiles / 2 : ntiles; b.block0 = gy;
-                    items.push_back({pi, wide ? K_STRIDED6 : K_STRIDED5, b, bytes, alg});
-                }
-            }
-            continue;
-        }
-        // pass boundaries: [0, k0) contiguous, then strided passes [k0, k0 + k1), ...
-        u32 bounds[8]; int np = 0;
-        bounds[0] = 0;
-        a.tile_log = log < (u32)TILE_LOG ? log : (u32)TILE_LOG;
-        u32 k0 = nl < a.tile_log ? nl : a.tile_log;
-        bounds[++np] = k0;
-        while (bounds[np] < nl) {
-            u32 rem = nl - bounds[np];
-            u32 passes_left = (rem + STRIDED_K - 1) / STRIDED_K;
-            u32 kk = (rem + passes_left - 1) / passes_left;  // balance the strided passes
-            bounds[np + 1] = bounds[np] + kk; np++;
-        }
-        max_np = std::max(max_np, np);
-        const double alg = 4.0 * ncols * ((double)(1u << src_log) + (double)(1u << log)) / np;
-        for (int pi = 0; pi < np; pi++) {
-            int p = inverse ? pi : np - 1 - pi;
-            bool first = pi == 0, last = pi == np - 1;
-            a.lo = bounds[p]; a.k = bounds[p + 1] - bounds[p];
-            u32 tl = a.lo == 0 ? a.tile_log : a.k + CHUNK_LOG;
-            u32 ntiles = 1u << (log - tl);
-            a.src = first ? job.d_src : (const u32* const*)job.d_dst;
-            a.dst = job.d_dst;
-            a.src_mask = first ? ((1u << src_log) - 1) : 0xffffffffu;
-            a.scale = (inverse && last) ? m_inv(1u << log) : 1;
-            // columns per block: enough blocks to fill the chip, as few twiddle re-loads as possible
-            u32 cpb = 1;
-            while ((u64)ntiles * ((ncols + cpb - 1) / cpb) > 8192 && cpb < ncols) cpb *= 2;
-            a.cols_per_block = cpb;
-            PassArgs b = a; b.grid_x = ntiles; b.block0 = (ncols + cpb - 1) / cpb;
-            items.push_back({pi, K_PASS, b, 8.0 * ncols * (double)(1u << log), alg, np == 1 && log < (u32)TILE_LOG});
-        }
-    }
-    // The small fry rides along: single-pass transforms of < 2^12 cells and the tiny ones touch columns of their own, so they can join ANY launch of the plan — the
-    // first contiguous-tile launch takes them as guest groups (PassArgs::kind). BFHIP_FFT_FUSE_SMALL=0: A/B knob (separate launches as before; same bytes).
-    {
-        static const bool fuse = [] { const char* v = getenv("BFHIP_FFT_FUSE_SMALL"); return !v || v[0] != '0'; }();
-        int host_pi = -1;
-        for (auto& it : items) if (it.kind == K_TILE12 && (host_pi < 0 || it.pi < host_pi)) host_pi = it.pi;
-        if (fuse && host_pi >= 0)
-            for (auto& it : items)
-                if (it.single && (it.kind == K_PASS || it.kind == K_TINY)) { it.a.kind = (u32)it.kind; it.kind = K_TILE12; it.pi = host_pi; }
-    }
-    for (int pi = 0; pi < max_np; pi++)
-        for (int kind = 0; kind < K_KINDS; kind++) {
-            FftLaunch L{}; L.kind = kind; L.first_group = (u32)plan.groups.size();
-            u32 blocks = 0;
-            for (auto& it : items) {
-                if (it.pi != pi || it.kind != kind) continue;
-                PassArgs a = it.a;
-                const u32 gy = (kind == K_TINY || a.kind == K_TINY) ? 1u : a.block0;
-                a.block0 = blocks; blocks += a.grid_x * gy;
-                plan.groups.push_back(a);
-                L.bytes += it.bytes; L.alg += it.alg; L.bfly += it.bfly();
-            }
-            L.ngroups = (u32)plan.groups.size() - L.first_group; L.total_blocks = blocks;
-            if (L.ngroups) plan.launches.push_back(L);
-        }
-}
-
 // BFHIP_FFT_PROF_DETAIL=1 (tools/fft_inproof.py): the profiler's record of an FFT launch carries its shape — "name/b<workgroups>/g<size groups>" — so that
 // the in-proof launches can be priced one by one (butterflies and bytes per launch against its time) instead of per kernel name.
 static const char* fft_prof_name(const char* base, const FftLaunch& L) {
@@ -853,54 +711,35 @@ static const char* fft_prof_name(const char* base, const FftLaunch& L) {
     return names.insert(std::string(base) + "/b" + std::to_string(L.total_blocks) + "/g" + std::to_string(L.ngroups)).first->c_str();
 }
 
+// The kernel of every launch kind: forward and inverse entry point, workgroup size (what the kernel's __launch_bounds__ says, from the same template
+// arguments) and the profiler's names. k_fft_tile12 takes one argument more (generic); k_fft_tiny is launched without a profiler record.
+using FftKernel = void (*)(const PassArgs*, u32); using FftKernelTile12 = void (*)(const PassArgs*, u32, u32);
+struct FftKernelEntry { FftKernel fn[2]; FftKernelTile12 tile12[2]; u32 threads; const char* name[2]; };      // [inverse]
+template <int CL> constexpr FftKernelEntry strided7_entry() { return {{k_fft_strided7<false, CL>, k_fft_strided7<true, CL>}, {}, 4u << CL, {"k_fft_strided7<false>", "k_fft_strided7<true>"}}; }
+template <int K, int CL> constexpr FftKernelEntry stridedK_entry() { return {{k_fft_stridedK<false, K, CL>, k_fft_stridedK<true, K, CL>}, {}, (1u << (K + CL)) / 32, {"k_fft_stridedK<false>", "k_fft_stridedK<true>"}}; }
+static constexpr FftKernelEntry FFT_KERNELS[K_KINDS] = {
+    /* K_TILE12      */ {{}, {k_fft_tile12<false>, k_fft_tile12<true>}, 256, {"k_fft_tile12<false>", "k_fft_tile12<true>"}},
+    /* K_STRIDED5    */ strided7_entry<5>(),
+    /* K_STRIDED6    */ strided7_entry<6>(),
+    /* K_PASS        */ {{k_fft_pass<false>, k_fft_pass<true>}, {}, FFT_THREADS, {"k_fft_pass<false>", "k_fft_pass<true>"}},
+    /* K_TINY        */ {{k_fft_tiny<false>, k_fft_tiny<true>}, {}, 256, {nullptr, nullptr}},
+    /* K_STRIDED_K8  */ stridedK_entry<8, FFT_STRIDED_K_CHUNK_LOG>(),
+    /* K_STRIDED_K9  */ stridedK_entry<9, FFT_STRIDED_K_CHUNK_LOG>(),
+    /* K_STRIDED_K10 */ stridedK_entry<10, FFT_STRIDED_K10_CHUNK_LOG>(),
+};
 void fft_run(hipStream_t stream, const FftPlan& plan) {
     if (plan.launches.empty()) return;
     if (!plan.d_groups) throw std::runtime_error("fft_run: the plan's group table has not been staged");
-    const bool inverse = plan.inverse;
+    static const u32 generic = [] { const char* v = getenv("BFHIP_FFT_TILE12_GENERIC"); return (v && v[0] == '1') ? 1u : 0u; }();
+    const int inv = plan.inverse ? 1 : 0;
     for (const FftLaunch& L : plan.launches) {
+        const FftKernelEntry& e = FFT_KERNELS[L.kind];
         const PassArgs* g = plan.d_groups + L.first_group;
-        const dim3 grid(L.total_blocks);
-        switch (L.kind) {
-            case K_TILE12: {
-                ProfScope ps(stream, fft_prof_name(inverse ? "k_fft_tile12<true>" : "k_fft_tile12<false>", L), L.bytes, L.alg, false, L.bfly);
-                static const u32 generic = [] { const char* v = getenv("BFHIP_FFT_TILE12_GENERIC"); return (v && v[0] == '1') ? 1u : 0u; }();
-                if (inverse) hipLaunchKernelGGL(k_fft_tile12<true>, grid, dim3(256), 0, stream, g, L.ngroups, generic);
-                else hipLaunchKernelGGL(k_fft_tile12<false>, grid, dim3(256), 0, stream, g, L.ngroups, generic);
-                break; }
-            case K_STRIDED5: {
-                ProfScope ps(stream, fft_prof_name(inverse ? "k_fft_strided7<true>" : "k_fft_strided7<false>", L), L.bytes, L.alg, false, L.bfly);
-                if (inverse) hipLaunchKernelGGL((k_fft_strided7<true, 5>), grid, dim3(128), 0, stream, g, L.ngroups);
-                else hipLaunchKernelGGL((k_fft_strided7<false, 5>), grid, dim3(128), 0, stream, g, L.ngroups);
-                break; }
-            case K_STRIDED6: {
-                ProfScope ps(stream, fft_prof_name(inverse ? "k_fft_strided7<true>" : "k_fft_strided7<false>", L), L.bytes, L.alg, false, L.bfly);
-                if (inverse) hipLaunchKernelGGL((k_fft_strided7<true, 6>), grid, dim3(256), 0, stream, g, L.ngroups);
-                else hipLaunchKernelGGL((k_fft_strided7<false, 6>), grid, dim3(256), 0, stream, g, L.ngroups);
-                break; }
-            case K_STRIDED_K8: {
-                ProfScope ps(stream, fft_prof_name(inverse ? "k_fft_stridedK<true>" : "k_fft_stridedK<false>", L), L.bytes, L.alg, false, L.bfly);
-                if (inverse) hipLaunchKernelGGL((k_fft_stridedK<true, 8, 5>), grid, dim3(256), 0, stream, g, L.ngroups);
-                else hipLaunchKernelGGL((k_fft_stridedK<false, 8, 5>), grid, dim3(256), 0, stream, g, L.ngroups);
-                break; }
-            case K_STRIDED_K9: {
-                ProfScope ps(stream, fft_prof_name(inverse ? "k_fft_stridedK<true>" : "k_fft_stridedK<false>", L), L.bytes, L.alg, false, L.bfly);
-                if (inverse) hipLaunchKernelGGL((k_fft_stridedK<true, 9, 5>), grid, dim3(512), 0, stream, g, L.ngroups);
-                else hipLaunchKernelGGL((k_fft_stridedK<false, 9, 5>), grid, dim3(512), 0, stream, g, L.ngroups);
-                break; }
-            case K_STRIDED_K10: {
-                ProfScope ps(stream, fft_prof_name(inverse ? "k_fft_stridedK<true>" : "k_fft_stridedK<false>", L), L.bytes, L.alg, false, L.bfly);
-                if (inverse) hipLaunchKernelGGL((k_fft_stridedK<true, 10, 4>), grid, dim3(512), 0, stream, g, L.ngroups);
-                else hipLaunchKernelGGL((k_fft_stridedK<false, 10, 4>), grid, dim3(512), 0, stream, g, L.ngroups);
-                break; }
-            case K_PASS: {
-                ProfScope ps(stream, fft_prof_name(inverse ? "k_fft_pass<true>" : "k_fft_pass<false>", L), L.bytes, L.alg, false, L.bfly);
-                if (inverse) hipLaunchKernelGGL(k_fft_pass<true>, grid, dim3(FFT_THREADS), 0, stream, g, L.ngroups);
-                else hipLaunchKernelGGL(k_fft_pass<false>, grid, dim3(FFT_THREADS), 0, stream, g, L.ngroups);
-                break; }
-            default:
-                if (inverse) hipLaunchKernelGGL(k_fft_tiny<true>, grid, dim3(256), 0, stream, g, L.ngroups);
-                else hipLaunchKernelGGL(k_fft_tiny<false>, grid, dim3(256), 0, stream, g, L.ngroups);
-        }
+        const dim3 grid(L.total_blocks), block(e.threads);
+        std::optional<ProfScope> ps;
+        if (e.name[inv]) ps.emplace(stream, fft_prof_name(e.name[inv], L), L.bytes, L.alg, false, L.bfly);
+        if (e.tile12[inv]) hipLaunchKernelGGL(e.tile12[inv], grid, block, 0, stream, g, L.ngroups, generic);
+        else hipLaunchKernelGGL(e.fn[inv], grid, block, 0, stream, g, L.ngroups);
     }
 }
 

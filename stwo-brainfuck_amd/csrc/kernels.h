@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "m31.h"
 #include "air.h"
+#include "fft_plan.h"
 #include <string>
 #include <vector>
 
@@ -73,33 +74,7 @@ __device__ __forceinline__ u32 ld_col(const ColDesc& d, u32 i) {
 
 // fft.hip
 void gen_twiddles(hipStream_t stream, u32* d_tw, u32* d_itw, u32 R, const uint2* d_tlo, const uint2* d_thi);
-// Transforms of columns of 2^log cells, batched over JOBS (one job = the columns of one size and storage).
-// inverse: evaluations (bit-reversed) -> coefficients, scaled by 2^-log.
-// forward: coefficients of 2^src_log (zero-extended to 2^log) -> evaluations on the canonic domain of size 2^log.
-// circle = false selects "line mode" (no circle layer) used for 16x-replicated columns stored row-granular.
-// d_src / d_dst: DEVICE arrays of column pointers.
-struct FftJob { const u32* const* d_src; u32* const* d_dst; u32 ncols, log, src_log; bool circle; };
-// One pass of one job (fft.hip). A launch covers several of them: workgroups [block0, block0 + grid_x * grid_y) belong to this one.
-struct PassArgs {
-    u32* const* dst;          // device array of column pointers (output / in-place)
-    const u32* const* src;    // device array of column pointers (input of this pass)
-    u32 ncols, cols_per_block;
-    u32 log;                  // transform size
-    u32 lo, k;                // layers [lo, lo + k)
-    u32 tile_log;             // contiguous pass (lo == 0): tile = 2^tile_log >= 2^k cells; strided: tile = 2^(k + CHUNK_LOG)
-    u32 src_mask;             // input index mask (2^src_log - 1): forward zero-extension = wrap-around load
-    u32 circle;               // 1: layer 0 is the circle layer; 0: line mode
-    u32 scale;                // inverse: multiply outputs by this (1 = none)
-    u32 tw_total;             // 2^R
-    const u32* tw;            // twiddle (forward) or inverse-twiddle (inverse) layered buffer
-    u32 block0, grid_x;       // first workgroup of this group within its launch; tiles per column block
-    u32 kind;                 // 0: the launch's own kernel; else the kind (fft.hip: K_PASS, K_TINY) of a small transform that rides in a contiguous-tile launch
-};
-struct FftLaunch { int kind; u32 first_group, ngroups, total_blocks; double bytes, alg, bfly; };
-// fft_plan: host-side layout of every pass of every job; the caller copies plan.groups to device memory the stream can read (the
-// staging ring: one copy together with the pointer arrays) and sets d_groups; fft_run issues the launches.
-struct FftPlan { bool inverse = false; std::vector<PassArgs> groups; std::vector<FftLaunch> launches; const PassArgs* d_groups = nullptr; };
-void fft_plan(FftPlan& plan, bool inverse, const FftJob* jobs, size_t njobs, const u32* tw, const u32* itw, u32 tw_root_log);
+// The jobs, the pass descriptors and the planner (fft_plan) are host-only: fft_plan.h. fft_run issues the launches of a plan whose group table has been staged.
 void fft_run(hipStream_t stream, const FftPlan& plan);
 
 // Coefficients of IsFirst(n) (indicator of cell 0 of the 2^n-cell canonic domain), n = log_min..log_max, written in closed form by one

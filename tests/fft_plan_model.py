@@ -1,30 +1,32 @@
-"""A plain-Python restatement of the SHAPE decisions of fft_plan (stwo-brainfuck_amd/csrc/fft.hip) for one job = the columns of one size:
+"""A plain-Python restatement of the SHAPE decisions of fft_plan (stwo-brainfuck_amd/csrc/fft_plan.h) for one job = the columns of one size:
 which kernel runs each pass, over which layers, how many columns one workgroup walks and how many workgroups the launch has. It exists to
 choose and to label test cases (tests/test_fft_plan_model_cpu.py holds every case of tests/test_gpu_fft.py and
-tests/test_gpu_pcs_commit_large.py to the property it is named for; one GPU test holds the model to the workgroup totals the library
-reports). It is never the reference of a value: values are compared with the CPU oracle.
+tests/test_gpu_pcs_commit_large.py to the property it is named for). It is never the reference of a value: values are compared with the CPU oracle.
+
+tests/test_fft_plan_cpu.py holds the model to the planner: it compiles fft_plan.h into a stand-alone program (tests/native/fft_plan_host.cpp) and
+compares every pass of 11 136 single-job plans, and the constants below, with what the header itself computes. One GPU test
+(tests/test_gpu_fft.py::test_library_launches_what_the_plan_model_says) holds it to the workgroup totals the library launches.
 
 A job is (inverse, log, src_log, ncols) as api_ops.hip builds it: interpolate(log) = (True, log, log, n), evaluate(log -> log_eval) =
 (False, log_eval, log, n). Row-granular ("replicated") columns are the same job 4 levels lower in line mode, which changes no shape.
 
-Lines restated (fft.hip):
-  :634       nl, the layers that run: all of them inverse; forward the source's (the layers above only duplicate), at least 2 past 32 cells
-  :635-:642  log <= 5: k_fft_tiny, 256 >> log columns per workgroup, no column loop
-  :644-:652  the fast path (log >= 12, nl >= 6): ns strided passes of 7 layers behind a contiguous pass of k0 = nl - 7 ns in [6, 12];
-             20 <= nl <= 22 (BFHIP_FFT_TWO_PASS unset): ONE strided pass of nl - 12 layers behind k0 = 12
-  :657       execution order: inverse = contiguous pass first, forward = mirrored
-  :663-:668  ntiles = 2^(log - 12); cols_per_block starts at ncols and halves, rounding up, while cpb > 1 and ntiles * ceil(ncols / cpb) < 2048;
-             gy = ceil(ncols / cpb)
-  :671       k_fft_tile12: grid_x = ntiles
-  :675-:678  k_fft_stridedK<K>: rows of 2^cl cells, cl = 4 at K = 10 and 5 otherwise; grid_x = 2^(log - K - cl)
-  :680-:687  k_fft_strided7: lo = k0 + 7 (p - 1); wide (256-byte rows) when lo >= 6 and log >= 20: grid_x = ntiles / 2, else ntiles
-  :693-:722  everything else (k_fft_pass): a contiguous pass of min(nl, min(log, 12)) layers, strided passes of balanced length <= 7 in tiles of
-             2^(k + 5) cells; cols_per_block doubles from 1 while ntiles * ceil(ncols / cpb) > 8192 and cpb < ncols
-  :741-:742  a launch has grid_x * gy workgroups per group (tiny: grid_x)
-The symbolic constants: TILE_LOG = 12, CHUNK_LOG = 5, STRIDED_K = 7 (:28-:31), BF_STRIDED_WIDE_MIN_LOG = 20 (:682)."""
+Rules restated (fft_plan.h):
+  fft_layers          nl, the layers that run: all of them inverse; forward the source's (the layers above only duplicate), at least 2 past 32 cells
+  fft_passes_tiny     log <= FFT_TINY_MAX_LOG: k_fft_tiny, 256 >> log columns per workgroup, no column loop
+  fft_passes_fast     log >= TILE_LOG and nl >= FFT_FAST_MIN_LAYERS: ns strided passes of 7 layers behind a contiguous pass of k0 = nl - 7 ns in [6, 12];
+                      FFT_TWO_PASS_MIN_LAYERS <= nl <= FFT_TWO_PASS_MAX_LAYERS (BFHIP_FFT_TWO_PASS unset): ONE strided pass of nl - 12 layers behind k0 = 12.
+                      ntiles = 2^(log - 12); cols_per_block starts at ncols and halves, rounding up, while cpb > 1 and ntiles * ceil(ncols / cpb) <
+                      FFT_MIN_BLOCKS; gy = ceil(ncols / cpb). k_fft_tile12: grid_x = ntiles. k_fft_stridedK<K>: rows of 2^cl cells, cl =
+                      FFT_STRIDED_K10_CHUNK_LOG at K = 10 and FFT_STRIDED_K_CHUNK_LOG otherwise; grid_x = 2^(log - K - cl). k_fft_strided7: lo = k0 + 7 (p - 1);
+                      wide (256-byte rows) when lo >= 6 and log >= FFT_STRIDED_WIDE_MIN_LOG: grid_x = ntiles / 2, else ntiles
+  fft_passes_generic  everything else (k_fft_pass): a contiguous pass of min(nl, min(log, 12)) layers, strided passes of balanced length <= 7 in tiles of
+                      2^(k + 5) cells; cols_per_block doubles from 1 while ntiles * ceil(ncols / cpb) > FFT_MAX_BLOCKS_GENERIC and cpb < ncols
+  fft_plan            execution order: inverse = contiguous pass first, forward = mirrored; a launch has grid_x * gy workgroups per group (tiny: grid_x);
+                      single-pass transforms below 2^12 cells and tiny ones ride in the plan's first k_fft_tile12 launch when it has one"""
 from collections import Counter, namedtuple
 
 TILE_LOG, CHUNK_LOG, STRIDED_K, WIDE_MIN_LOG, MIN_BLOCKS, MAX_BLOCKS_GENERIC = 12, 5, 7, 20, 2048, 8192
+TINY_MAX_LOG, FAST_MIN_LAYERS, TWO_PASS_MIN_LAYERS, TWO_PASS_MAX_LAYERS, STRIDED_K_CHUNK_LOG, STRIDED_K10_CHUNK_LOG = 5, 6, 20, 22, 5, 4
 
 # kind: "tile12" | "strided7_narrow" | "strided7_wide" | "stridedK8" | "stridedK9" | "stridedK10" | "pass" | "tiny"; lo, k: the layers [lo, lo + k)
 Pass = namedtuple("Pass", "kind lo k cols_per_block grid_x gy workgroups")
@@ -41,15 +43,15 @@ def _ceil_div(a, b):
 def plan(inverse, log, src_log, ncols):
     """The passes of the job in execution order."""
     assert ncols >= 1 and src_log <= log
-    nl = log if inverse else (2 if log > 5 and src_log < 2 else src_log)
-    if log <= 5:
+    nl = log if inverse else (2 if log > TINY_MAX_LOG and src_log < 2 else src_log)
+    if log <= TINY_MAX_LOG:
         gx = _ceil_div(ncols, 256 >> log)
         return [Pass("tiny", 0, nl, 1, gx, 1, gx)]
     out = []
-    if log >= 12 and nl >= 6:
+    if log >= TILE_LOG and nl >= FAST_MIN_LAYERS:
         ns = (nl - 12 + 6) // 7 if nl > 12 else 0
         k0 = nl - 7 * ns
-        big_k = nl - 12 if 20 <= nl <= 22 else 0
+        big_k = nl - 12 if TWO_PASS_MIN_LAYERS <= nl <= TWO_PASS_MAX_LAYERS else 0
         if big_k:
             ns, k0 = 1, 12
         np_ = 1 + ns
@@ -63,7 +65,7 @@ def plan(inverse, log, src_log, ncols):
             if p == 0:
                 kind, lo, k, gx = "tile12", 0, k0, ntiles
             elif big_k:
-                cl = 4 if big_k == 10 else 5
+                cl = STRIDED_K10_CHUNK_LOG if big_k == 10 else STRIDED_K_CHUNK_LOG
                 kind, lo, k, gx = "stridedK%d" % big_k, 12, big_k, 1 << (log - big_k - cl)
             else:
                 lo = k0 + 7 * (p - 1)
@@ -155,7 +157,7 @@ SESSIONS = {"b1": (1, 20, 17), "b2": (2, 21, 9), "b4": (4, 22, 5), "b1_top22": (
 def session_kernels(log_blowup, tree_logs, forms):
     """The kernel names Context.profile_report lists after the commits of a session (BFHIP_FFT_PROF_DETAIL unset): a tree of evaluations
     (form 0) is one inverse plan over its size classes, every tree one forward plan to log + log_blowup. Single-pass transforms below 2^12
-    cells and tiny ones ride in the plan's first k_fft_tile12 launch when it has one (fft.hip :724-:733) and leave no name of their own."""
+    cells and tiny ones ride in the plan's first k_fft_tile12 launch when it has one (fft_plan.h: fft_plan) and leave no name of their own."""
     names = set()
     for logs, form in zip(tree_logs, forms):
         plans = [(False, [plan(False, log + log_blowup, log, logs.count(log)) for log in sorted(set(logs))])]

@@ -1,17 +1,13 @@
 """CPU: every case of the many-columns tests of tests/test_gpu_fft.py and of tests/test_gpu_pcs_commit_large.py still has the property it is
 named for, by tests/fft_plan_model.py: the kernel kind of every pass, k0, cols_per_block >= 2, a shorter last column block, one block walking
 every column. A case that stops reaching its path (a planner threshold moved, a column count changed) fails here instead of passing for
-nothing on the GPU; that the model is the library's planner is the GPU test test_library_launches_what_the_plan_model_says.
-The model is also held to the text of fft_plan it restates: the constants are read from fft.hip."""
-import os
-import re
-
+nothing on the GPU. That the model is the library's planner is held elsewhere: tests/test_fft_plan_cpu.py compares it, constants and plans, with
+csrc/fft_plan.h compiled into a stand-alone program, and the GPU test test_library_launches_what_the_plan_model_says with what the library launches."""
 import pytest
 
 import fft_plan_model as fm
 import pcs_generic_cases as gc
 import test_gpu_pcs_commit_large as large
-from conftest import ROOT
 
 
 def _check(passes, ncols, want, what):
@@ -129,16 +125,3 @@ def test_wide20_has_a_many_column_class_above_level_18():
     assert small & {4, 5} and any(6 <= l <= 11 for l in small) and len({l for l in small if 12 <= l <= 18}) >= 2
     assert len(case.points) == 2 and any(len(c) == 2 for t in case.samples for c in t) and all(c for t in case.samples for c in t)
     assert any(len(c) == 2 for l, c in zip(case.logs[0], case.samples[0]) if l == 19)
-
-
-def test_constants_are_those_of_the_planner():
-    """The numbers the model restates, read from the planner's text: a changed threshold makes the model stale, and says so here."""
-    src = open(os.path.join(ROOT, "stwo-brainfuck_amd", "csrc", "fft.hip")).read()
-    num = lambda pattern: int(re.search(pattern, src).group(1))
-    assert num(r"constexpr int TILE_LOG = (\d+);") == fm.TILE_LOG and num(r"constexpr int CHUNK_LOG = (\d+);") == fm.CHUNK_LOG
-    assert fm.STRIDED_K == fm.TILE_LOG - fm.CHUNK_LOG and "STRIDED_K = TILE_LOG - CHUNK_LOG" in src
-    assert num(r"#define BF_STRIDED_WIDE_MIN_LOG (\d+)") == fm.WIDE_MIN_LOG
-    assert num(r"while \(cpb > 1 && \(u64\)ntiles \* \(\(ncols \+ cpb - 1\) / cpb\) < (\d+)\) cpb = \(cpb \+ 1\) / 2;") == fm.MIN_BLOCKS
-    assert num(r"while \(\(u64\)ntiles \* \(\(ncols \+ cpb - 1\) / cpb\) > (\d+) && cpb < ncols\) cpb \*= 2;") == fm.MAX_BLOCKS_GENERIC
-    assert "(two_pass && nl >= 20 && nl <= 22) ? nl - 12 : 0" in src and "const u32 cl = big_k == 10 ? 4 : 5;" in src
-    assert "const bool wide = a.lo >= 6 && log >= BF_STRIDED_WIDE_MIN_LOG;" in src
