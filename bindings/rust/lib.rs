@@ -219,6 +219,32 @@ impl<'a> Pool<'a> {
         if rc != 0 { Err(last_error()) } else { Ok(ticket) }
     }
 
+    /// `bfhip_pool_submit_air`: what `air_prove` takes, as a job; the result's proof is `air_prove`'s bytes. The library copies the statement,
+    /// the table of column pointers and the channel's state at submit: `channel` is not advanced. It borrows the programs and the kernels
+    /// until the job's result has been taken — the lifetime `'a` keeps them alive as long as the pool — and the device columns behind
+    /// `tree_cols`, which the caller must not free before then. `kernels`: empty, or `n_in_flight * n_components` entries, row w = the
+    /// kernels compiled on sub-context w. `Err` = the submit itself was refused (the validator's rule, other conventions, 4096 outstanding).
+    pub fn submit_air(&self, statement: &AirStatement<'a>, tree_cols: &[&[*const u32]], kernels: &[Option<&'a AirKernel>], channel: &Channel, check_trace: bool,
+                      tag: u64) -> Result<u64, String> {
+        if tree_cols.len() != statement.trees.len() || tree_cols.iter().zip(statement.trees.iter()).any(|(c, t)| c.len() != t.log_sizes.len()) {
+            return Err("one device column per column of every caller tree".into());
+        }
+        let mut n_in_flight = 0u32;
+        check(unsafe { sys::bfhip_pool_size(self.ptr, &mut n_in_flight) })?;
+        if !kernels.is_empty() && kernels.len() != n_in_flight as usize * statement.components.len() {
+            return Err("n_in_flight rows of one kernel (or None) per component".into());
+        }
+        let raw = statement.raw();
+        let trees: Vec<*const *const u32> = tree_cols.iter().map(|c| c.as_ptr()).collect();
+        let ks: Vec<*mut sys::BfhipAirKernel> = kernels.iter().map(|k| k.map_or(std::ptr::null_mut(), |k| k.0)).collect();
+        let mut ticket = 0u64;
+        let rc = unsafe {
+            sys::bfhip_pool_submit_air(self.ptr, &raw.st, trees.as_ptr(), if ks.is_empty() { std::ptr::null() } else { ks.as_ptr() }, channel.0 as *const sys::BfhipChannel,
+                                       if check_trace { sys::BFHIP_AIR_PROVE_CHECK } else { 0 }, tag, &mut ticket)
+        };
+        if rc != 0 { Err(last_error()) } else { Ok(ticket) }
+    }
+
     /// `bfhip_pool_wait`: `Ok(Some(result))`, `Ok(None)` when nothing is outstanding, `Err("timeout")` when `timeout_ms` (`u32::MAX` = no
     /// limit, 0 = poll) ran out with jobs outstanding.
     pub fn wait(&self, timeout_ms: u32) -> Result<Option<JobResult>, String> {

@@ -88,6 +88,20 @@ int32_t bfhip_ctx_set_overlap(bfhip_ctx* ctx, uint32_t mask);
 /* Device memory of this context in bytes: out[0] = reserved by its per-proof arena (1 GiB chunks, kept until the context is destroyed),
  * out[1] = the arena's high-water mark over all proofs so far, out[2] = twiddle tree + inverse, out[3] = arena bytes in use now. */
 int32_t bfhip_ctx_memory(bfhip_ctx* ctx, uint64_t out[4]);
+/* The scratch reserve. Call-scoped device memory outside the arena — the driver's buffer of bfhip_air_prove, the scan buffers of
+ * bfhip_logup_program_generate_batch, the staging of bfhip_air_compose and of the other generic entry points — is by default one
+ * hipMalloc on entry and one hipFree on exit per call, and hipFree waits for the WHOLE device, not for one stream: with k proofs in flight
+ * on one GPU every proof would stall on the others' kernels. bfhip_ctx_set_scratch_reserve makes ONE hipMalloc of `bytes`, kept until it
+ * is set again or the context is destroyed; a call-scoped request is then placed in it when it fits behind what is in use (256-byte
+ * aligned) and goes to hipMalloc exactly as before when it does not. The scopes of one context nest, so the reserve is a stack: a scope
+ * rewinds to where it found it, behind the same wait for the context's stream as before. Results are the same bytes either way.
+ * bytes = 0: no reserve, the default. Refused (-1) while a commitment-scheme session is open on the context; a failed allocation is -1 and
+ * leaves the context without a reserve.
+ * bfhip_ctx_scratch_stats: out[0] = the reserve's bytes, out[1] = the high-water mark of its use since it was set — what a caller sizes
+ * the reserve by: set a generous one, run the largest shape, read the mark —, out[2] = the device allocations made by call-scoped scopes
+ * since the context was created, out[3] = the requests served from a reserve since the context was created. */
+int32_t bfhip_ctx_set_scratch_reserve(bfhip_ctx* ctx, uint64_t bytes);
+int32_t bfhip_ctx_scratch_stats(bfhip_ctx* ctx, uint64_t out[4]);
 /* Host waits of this context: 0 (default) = poll briefly, then yield / block; 1 = hipStreamSynchronize at once (hosts with more waiting
  * contexts than cores). Waits inside a shard group are always bounded polls (BFHIP_COMM_TIMEOUT_S, default 300 s).
  * Mailboxes (small proofs, LOG_MAX_ROWS <= 21: the launches behind a Fiat-Shamir point are enqueued before the host knows the challenge and a
@@ -555,7 +569,8 @@ int32_t bfhip_prove_batch_brainfuck(bfhip_pool* pool, const char* const* codes, 
  * (the caller of prove_brainfuck(&Machine), mod.rs:471-473) wants the first proof's bytes as soon as they exist and the workers never idle.
  *   submit    returns at once with a ticket (1, 2, 3, ... per pool). Jobs START in ticket order on whichever worker is free; results are
  *             delivered in COMPLETION order, each exactly once. Program text, input bytes and program words are copied at submit; register
- *             rows and traces are BORROWED until that ticket's result has been taken. What needs no GPU to check fails the submit itself
+ *             rows and traces are BORROWED until that ticket's result has been taken (an AIR statement's rule: bfhip_pool_submit_air,
+ *             below the generic entry points). What needs no GPU to check fails the submit itself
  *             (-1, no ticket): null pointers, zero rows, n_rows >= 2^31, more than BFHIP_POOL_MAX_OUTSTANDING jobs outstanding (queued +
  *             running + finished and not taken), a batch call in progress. Everything else fails the JOB.
  *   traces    for bfhip_pool_submit_trace may come from ANY context on the pool's device, e.g. one the caller owns: a trace is plain device
@@ -1057,8 +1072,8 @@ int32_t bfhip_logup_program_generate_batch(bfhip_ctx* ctx, const bfhip_logup_com
  *     more than BFHIP_PCS_MAX_SAMPLES_PER_COLUMN points (the message names it); more than BFHIP_PCS_MAX_POINTS points. A failure of a
  *     call the driver makes comes back as "bfhip_air_prove: " + that call's message (in the batch's, a component index counts the
  *     components with a fraction program).
- *   Memory: the driver's own buffers (interaction columns, composition columns, constraint-domain scratch) are ONE hipMalloc, not the
- *     session's arena, freed before return on every path after a wait for the context's streams; the session is destroyed on every
+ *   Memory: the driver's own buffers (interaction columns, composition columns, constraint-domain scratch) are ONE hipMalloc (or one
+ *     request to the context's scratch reserve, bfhip_ctx_set_scratch_reserve), not the session's arena, freed before return on every path after a wait for the context's streams; the session is destroyed on every
  *     path: bfhip_ctx_memory out[3] is what it was before the call. A failed allocation is -1 with "bfhip_air_prove: cannot allocate <n> bytes
  *     ...", before the session opens. After a failure behind that point the channel has advanced: replay with a fresh one.
  * bfhip_air_verify (host only, plain C++): replays steps 2 to 8 with the roots of proof.commitments (bfhip_pcs_verifier_commit, trace-domain
@@ -1113,6 +1128,34 @@ int32_t bfhip_air_verify(const bfhip_air_statement* statement, const bfhip_conve
  * the rules are checked under (NULL = defaults), with max_log_domain 30. Refusals are the validator's, in this function's name. */
 int32_t bfhip_air_statement_samples(const bfhip_air_statement* statement, const bfhip_pcs_config* pcs, uint32_t counts[4], uint32_t* tree_n_cols,
                                     uint32_t* point_log_sizes, int32_t* point_offsets, uint32_t* n_samples, uint32_t* point_idx);
+
+/* ---- AIR statements as jobs of a pool's queue -----------------------------------------------------------------------------------------------
+ * bfhip_pool_submit_air: what bfhip_air_prove takes, as a job of the queue above ("the pool as a QUEUE"): the worker that takes the job runs
+ * bfhip_air_prove on its sub-context, the launches are exactly that call's and the bytes are its bytes. bfhip_pool_wait delivers
+ * {"claimed_sums":...,"proof":...} in proof_json; log_max_rows and flags of such a result are 0. Brainfuck jobs and these may be interleaved
+ * in one queue; cancel, outstanding, destroy and the "jobs outstanding" refusals apply unchanged. flags: BFHIP_AIR_PROVE_CHECK or 0.
+ *   copied    at submit: the statement (trees, log sizes, mix words, components, bindings, parameter rules), the table tree_cols_h down to
+ *             the device pointers, the kernel table, and the channel's STATE: the caller's channel object is not advanced by the job and may
+ *             be reused or destroyed at once. Every host array behind the statement may be freed when the submit returns.
+ *   borrowed  until that ticket's result has been taken: the program handles (bfhip_air, bfhip_logup; immutable), the device columns, and
+ *             the kernels.
+ *   kernels   kernels_h is NULL, or n_in_flight x n_components entries: row w holds component k's bfhip_air_kernel as compiled on
+ *             bfhip_pool_ctx(pool, w), or NULL = interpreted. A job uses the row of the worker that runs it. A kernel of another context
+ *             fails the job by name, as in bfhip_air_prove. Compile while nothing is outstanding: no compiler runs inside a worker.
+ *   submit    fails (-1, no ticket, nothing queued, "bfhip_pool_submit_air: ...") on: null arguments; whatever the validator of
+ *             bfhip_air_prove refuses, under the pool's current PcsConfig and max_log_domain, word for word; a channel created under other
+ *             conventions (merkle_channel, mix_u64) than the pool's; more than BFHIP_POOL_MAX_OUTSTANDING jobs outstanding; a batch call in
+ *             progress.
+ *   the job   fails on everything else — status -1, "job <ticket>: bfhip_air_prove: ...": ConstraintsNotSatisfied, a zero denominator, the
+ *             line of BFHIP_AIR_PROVE_CHECK, a null column pointer, unknown flags. The worker and the other jobs are unaffected.
+ *   sessions  the job's session is the worker's own; the caller's bfhip_pcs_create (and bfhip_air_prove) on a sub-context stays refused while
+ *             anything is outstanding. Such a job takes no shared preprocessed tree — a statement's preprocessed columns are a tree like
+ *             any other — and creates no stream: the session, the batch and the composition enqueue on the sub-context's one stream.
+ * bfhip_pool_set_scratch_reserve: bfhip_ctx_set_scratch_reserve(bytes_per_worker) on every sub-context, so that a job of a shape its
+ * worker has seen makes no device allocation; refused ("jobs outstanding") while anything is queued, running or not yet taken. */
+int32_t bfhip_pool_submit_air(bfhip_pool* pool, const bfhip_air_statement* statement, const uint32_t* const* const* tree_cols_h,
+                              bfhip_air_kernel* const* kernels_h, const bfhip_channel* ch, uint32_t flags, uint64_t user_tag, uint64_t* ticket);
+int32_t bfhip_pool_set_scratch_reserve(bfhip_pool* pool, uint64_t bytes_per_worker);
 
 /* ---- Row order: a trace as its author writes it -> the storage-order columns of ANY AIR, and back ------------------------------------------
  * Every entry point above takes device columns in STORAGE order: CanonicCoset(log_size).circle_domain() bit-reversed. An AIR author writes a

@@ -212,6 +212,20 @@ class Context(Owned):
         _check(abi().bfhip_ctx_memory(self._h, out))
         return dict(zip(("arena_reserved", "arena_peak", "twiddles", "arena_in_use"), [int(v) for v in out]))
 
+    def set_scratch_reserve(self, nbytes):
+        """bfhip_ctx_set_scratch_reserve: ONE device block of nbytes that the call-scoped memory of air_prove, logup_program_generate_batch,
+        air_compose and the other generic calls is served from where it fits, instead of one device allocation and release per call (a
+        release waits for the whole device). 0 = none, the default. Same results either way. Size it from scratch_stats()["high_water"].
+        Refused while a PcsSession is open."""
+        _check(abi().bfhip_ctx_set_scratch_reserve(self._h, int(nbytes)))
+
+    def scratch_stats(self):
+        """bfhip_ctx_scratch_stats: {reserve (bytes), high_water (of its use since it was set), device_allocations (made by call-scoped
+        memory since the context was created), served (requests placed in a reserve since then)}."""
+        out = (ctypes.c_uint64 * 4)()
+        _check(abi().bfhip_ctx_scratch_stats(self._h, out))
+        return dict(zip(("reserve", "high_water", "device_allocations", "served"), [int(v) for v in out]))
+
     # -- the per-kernel profiler (HIP events around every instrumented launch) ----------------------------------------------------------
     def profile_enable(self, mode=1):
         """bfhip_profile_enable: 0 off, 1 every instrumented kernel, 2 only k_merkle_layer (the dominant kernel; lowest overhead)."""

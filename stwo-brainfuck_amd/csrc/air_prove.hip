@@ -30,6 +30,8 @@ extern "C" int32_t bfhip_air_prove(bfhip_ctx* ctx, const bfhip_air_statement* st
     auto ok = [&](int32_t rc) { if (rc != 0) throw HipError(me + ": " + bfhip_last_error()); };
     if (!st || !tree_cols_h || !ch || !proof_json) throw HipError(me + ": null argument");
     if (flags & ~(uint32_t)BFHIP_AIR_PROVE_CHECK) throw HipError(me + ": unknown flags " + std::to_string(flags));
+    // step 1's refusal on a pool's sub-context, in its words and before this context's own state is read: a worker may be inside a job
+    if (c.pool_refuses_this_thread()) throw HipError(me + ": bfhip_pcs_create: not supported on a pool's sub-context while jobs are outstanding on the pool");
     if (c.pcs_session_open) throw HipError(me + ": a commitment-scheme session is open on this context (bfhip_pcs_destroy first)");
     if (c.shard.count > 1) throw HipError(me + ": a context in a shard group is not supported (bfhip_ctx_leave_group first)");
     const u32 blowup = c.pcs.log_blowup, max_log_domain = c.tw_root_log + 1;

@@ -108,6 +108,33 @@ int32_t bfhip_ctx_memory(bfhip_ctx* ctx, uint64_t out[4]) {
     return 0;
     API_CATCH
 }
+int32_t bfhip_ctx_set_scratch_reserve(bfhip_ctx* ctx, uint64_t bytes) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    c.refuse_in_session("bfhip_ctx_set_scratch_reserve");
+    c.sync();
+    if (!c.reserve.idle()) throw HipError("bfhip_ctx_set_scratch_reserve: a call of this context is using the reserve");
+    if (bytes > (uint64_t)SIZE_MAX) throw HipError("bfhip_ctx_set_scratch_reserve: cannot allocate " + std::to_string(bytes) + " bytes");
+    if (c.d_reserve) { BF_HIP(hipFree(c.d_reserve)); c.d_reserve = nullptr; }
+    c.reserve.set(0);
+    if (bytes == 0) return 0;
+    if (hipMalloc((void**)&c.d_reserve, (size_t)bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        c.d_reserve = nullptr;
+        throw HipError("bfhip_ctx_set_scratch_reserve: cannot allocate " + std::to_string(bytes) + " bytes (the context now has no reserve)");
+    }
+    c.reserve.set((size_t)bytes);
+    return 0;
+    API_CATCH
+}
+int32_t bfhip_ctx_scratch_stats(bfhip_ctx* ctx, uint64_t out[4]) {
+    API_CTX(ctx)
+    if (!out) throw HipError("null argument");
+    const ScratchReserve& r = ctx->c.reserve;
+    out[0] = r.bytes; out[1] = r.high_water; out[2] = r.device_allocs; out[3] = r.served;
+    return 0;
+    API_CATCH
+}
 int32_t bfhip_ctx_get_conventions(bfhip_ctx* ctx, bfhip_conventions* out) {
     API_CTX(ctx)
     if (!out) throw HipError("null argument");

@@ -5,6 +5,9 @@
 #include <chrono>
 #include "kernels.h"
 #include "comm.h"
+#include "scratch_reserve.h"
+#include <atomic>
+#include <cassert>
 #include <functional>
 #include <memory>
 #include <vector>
@@ -129,6 +132,17 @@ struct Ctx {
     }
     // set by a pool on its sub-contexts: is anything queued, running or not yet taken on that pool? (a session on a sub-context needs it idle)
     std::function<bool()> pool_busy;
+    // set by a pool's worker around a job that opens a session of its own (pool.hip: an AIR statement, bfhip_air_prove): the one thread
+    // whose bfhip_pcs_create passes the check above while jobs are outstanding. Any other thread stays refused.
+    std::atomic<std::thread::id> pool_job_thread{std::thread::id()};
+    // what bfhip_pcs_create refuses with "not supported on a pool's sub-context while jobs are outstanding on the pool"; asked before the
+    // context's own state is looked at, which a worker may be changing
+    bool pool_refuses_this_thread() const { return pool_busy && pool_job_thread.load() != std::this_thread::get_id() && pool_busy(); }
+    // The scratch reserve (bfhip_ctx_set_scratch_reserve; scratch_reserve.h): ONE device block that DeviceScratch serves requests from, so
+    // that a call of a shape this context has seen makes no device allocation — hipFree waits for the whole device, which k proofs in
+    // flight on one GPU would each pay three times per proof. d_reserve null = none: every request goes to hipMalloc.
+    char* d_reserve = nullptr;
+    ScratchReserve reserve;
     // test-hooks build only (prover_commit.hip: bfhip_test_capture_polys): where the next proof's polynomials are copied to; always null in
     // the default library. A member of every build so that the two builds share one layout of this struct.
     struct PolyCapture* capture = nullptr;
@@ -367,27 +381,36 @@ struct StageBatch {
     ~StageBatch() { if (open) { if (--c.stage_batch_depth < 0) c.stage_batch_depth = 0; } }
 };
 
-// Device memory that lives for one call, from hipMalloc (the arena may belong to an open session). Going out of scope waits for the context's
-// stream — a launch of a call that failed half way may still use the memory — and frees. A guard declared before another owner is destroyed
-// after it: a call that also uses a second stream, or a session, declares the guard first and lets the other owner quiesce its own work.
+// Device memory that lives for one call, outside the arena (which may belong to an open session): from the context's scratch reserve where
+// one is set and the request fits behind what is in use (scratch_reserve.h), otherwise from hipMalloc. Going out of scope waits for the
+// context's stream — a launch of a call that failed half way may still use the memory —, rewinds the reserve to where the guard found it and
+// frees what it took from the device. A guard declared before another owner is destroyed after it: a call that also uses a second stream,
+// or a session, declares the guard first and lets the other owner quiesce its own work. The guards of one context nest.
 struct DeviceScratch {
-    Ctx& c; std::vector<void*> owned;
-    explicit DeviceScratch(Ctx& c_) : c(c_) {}
+    Ctx& c; std::vector<void*> owned; const ScratchReserve::Mark mark; bool from_reserve = false;
+    explicit DeviceScratch(Ctx& c_) : c(c_), mark(c_.reserve.open()) {}
     DeviceScratch(const DeviceScratch&) = delete; DeviceScratch& operator=(const DeviceScratch&) = delete;
     // a failure leaves *p null and the thread's last error clear (as BF_HIP does): the caller words its own message
     template <class T> hipError_t try_alloc(T** p, size_t bytes) {
         *p = nullptr;
+        if (c.d_reserve) {
+            const size_t at = c.reserve.take(bytes);
+            if (at != ScratchReserve::kNone) { *p = reinterpret_cast<T*>(c.d_reserve + at); from_reserve = true; return hipSuccess; }
+        }
         owned.reserve(owned.size() + 1);
         hipError_t e = hipMalloc((void**)p, bytes);
         if (e != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return e; }
         owned.push_back(*p);
+        if (bytes) c.reserve.device_allocs++;      // an empty request is answered with a null pointer: nothing was allocated
         return e;
     }
     template <class T> void alloc(T** p, size_t bytes) { BF_HIP(try_alloc(p, bytes)); }
     ~DeviceScratch() {
-        if (owned.empty()) return;
-        (void)hipStreamSynchronize(c.stream);
+        if (!owned.empty() || from_reserve) (void)hipStreamSynchronize(c.stream);
         for (void* p : owned) (void)hipFree(p);
+        const bool innermost = c.reserve.close(mark);
+        assert(innermost && "DeviceScratch guards of one context close in reverse order");
+        (void)innermost;
     }
 };
 

@@ -89,6 +89,7 @@ void Ctx::destroy() {
     arena.release();
     auto dfree = [](auto*& p) { if (p) (void)hipFree(p); p = nullptr; };
     dfree(d_counters); dfree(d_stage);
+    dfree(d_reserve); reserve.set(0);
     if (owns_tables) { dfree(d_tw); dfree(d_itw); dfree(d_tlo); dfree(d_thi); }
     else d_tw = d_itw = nullptr, d_tlo = d_thi = nullptr;
     if (h_stage) { (void)hipHostFree(h_stage); h_stage = nullptr; }

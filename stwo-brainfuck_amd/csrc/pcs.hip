@@ -42,9 +42,11 @@ int32_t bfhip_pcs_create(bfhip_ctx* ctx, bfhip_pcs** out) {
     API_CTX(ctx)
     if (!out) throw HipError("null argument");
     Ctx& c = ctx->c;
+    // a pool's own worker opens the session of the job it runs (pool.hip: bfhip_pool_submit_air); the caller's threads stay refused, and
+    // are refused first: the session that is open may be a worker's
+    if (c.pool_refuses_this_thread()) throw HipError("bfhip_pcs_create: not supported on a pool's sub-context while jobs are outstanding on the pool");
     if (c.pcs_session_open) throw HipError("bfhip_pcs_create: a commitment-scheme session is open on this context (one session per context)");
     if (c.shard.count > 1) throw HipError("bfhip_pcs_create: not supported on a member of a shard group (bfhip_ctx_leave_group first)");
-    if (c.pool_busy && c.pool_busy()) throw HipError("bfhip_pcs_create: not supported on a pool's sub-context while jobs are outstanding on the pool");
     auto* s = new bfhip_pcs(ctx);
     try {
         // like a proof: nothing of this context is in flight, its per-proof memory starts empty, no mailbox order

@@ -18,9 +18,17 @@
 // and a submit is refused while a batch runs. In queue use the pool keeps up to two shared preprocessed trees (two values of LOG_MAX_ROWS
 // interleaved in one stream both find theirs), each in an arena of its own that the builder context borrows for the commitment; a tree is
 // recommitted only while no running job reads it.
+//
+// A fourth kind of job is an AIR given as a statement (bfhip_pool_submit_air): the worker runs bfhip_air_prove on its sub-context. The
+// statement, the table of column pointers and the channel's state are copied at submit (air_statement_copy.h); program handles, device
+// columns and kernels are borrowed. Such a job opens a commitment-scheme session, which a sub-context refuses while jobs are outstanding:
+// the worker names itself in Ctx::pool_job_thread around the call, and only that thread passes. It takes no shared preprocessed tree and
+// creates no stream: session, batch and composition all enqueue on the sub-context's one stream.
 #include "../../include/bfhip.h"
 #include "api_guard.h"
 #include "prover.h"
+#include "pcs_types.h"
+#include "air_statement_copy.h"
 #include <atomic>
 #include <deque>
 #include <new>
@@ -49,10 +57,13 @@ struct Job {
 // One job of the queue. What the caller may free after submit (program text, input, program words) is copied; register rows and traces are borrowed.
 struct QJob {
     uint64_t ticket = 0, tag = 0; uint32_t log_max_rows = 0;
-    int kind = 0;                                            // 0 resident trace, 1 program text, 2 register rows
+    int kind = 0;                                            // 0 resident trace, 1 program text, 2 register rows, 3 AIR statement
     const bfhip_trace* trace = nullptr;
     std::string code; std::vector<uint8_t> input;
     const uint32_t* rows = nullptr; size_t n_rows = 0; std::vector<uint32_t> words;
+    // kind 3: the statement and the column pointers (copied), the channel's state (copied), row w of the caller's kernels for worker w (copied
+    // pointers, n_in_flight x n_components, or empty)
+    AirStatementCopy air; std::unique_ptr<bfhip_channel> channel; std::vector<bfhip_air_kernel*> kernels; uint32_t air_flags = 0;
     std::chrono::steady_clock::time_point submitted;
 };
 
@@ -130,13 +141,19 @@ struct bfhip_pool {
         PreSlot* tree = nullptr;
         char* js = nullptr; size_t n = 0;
         try {
-            tree = acquire_tree(w, q.log_max_rows);
+            if (q.kind != 3) tree = acquire_tree(w, q.log_max_rows);
             subs[w]->c.shared_pre = tree ? tree->sp : nullptr;
             int32_t rc;
-            if (q.kind == 0) rc = bfhip_prove_trace(subs[w], q.trace, q.log_max_rows, &js, &n, nullptr, nullptr);
+            if (q.kind == 3) {
+                // the session this call opens is the worker's own: bfhip_pcs_create lets this thread pass while jobs are outstanding
+                struct Own { Ctx& c; explicit Own(Ctx& c_) : c(c_) { c.pool_job_thread = std::this_thread::get_id(); } ~Own() { c.pool_job_thread = std::thread::id(); } } own(subs[w]->c);
+                const size_t nk = q.air.st.n_components;
+                rc = bfhip_air_prove(subs[w], &q.air.st, q.air.tree_cols.data(), q.kernels.empty() ? nullptr : q.kernels.data() + nk * w, q.channel.get(), q.air_flags, &js, &n);
+            }
+            else if (q.kind == 0) rc = bfhip_prove_trace(subs[w], q.trace, q.log_max_rows, &js, &n, nullptr, nullptr);
             else if (q.kind == 1) rc = bfhip_prove_brainfuck(subs[w], q.code.c_str(), q.input.data(), q.input.size(), q.log_max_rows, &js, &n, nullptr, nullptr);
             else rc = bfhip_prove_registers(subs[w], q.rows, q.n_rows, q.words.data(), q.words.size(), q.log_max_rows, &js, &n, nullptr, nullptr);
-            if (rc == 0) { r.status = 0; r.proof_json = js; r.proof_len = n; r.flags = subs[w]->c.last_proof_flags; js = nullptr; }
+            if (rc == 0) { r.status = 0; r.proof_json = js; r.proof_len = n; r.flags = q.kind == 3 ? 0 : subs[w]->c.last_proof_flags; js = nullptr; }
             else { if (rc == BFHIP_TRACE_REJECTED) r.status = rc; err = bfhip_last_error(); }      // bad input, not an internal failure
         } catch (const std::exception& e) { err = e.what(); } catch (...) { err = "unknown error"; }
         subs[w]->c.shared_pre = nullptr;
@@ -359,11 +376,11 @@ int32_t bfhip_prove_batch_brainfuck(bfhip_pool* pool, const char* const* codes, 
 }
 
 // ---- the queue ---------------------------------------------------------------------------------------------------------------------------
-static int32_t pool_submit(bfhip_pool* pool, QJob* raw, uint64_t* ticket) {
+static int32_t pool_submit(bfhip_pool* pool, QJob* raw, uint64_t* ticket, const std::string& me = "bfhip_pool_submit") {
     std::unique_ptr<QJob> q(raw);
     bfhip_pool::CallScope call(pool);
-    if (pool->batch_active) throw HipError("bfhip_pool_submit: a batch call is in progress");
-    if (pool->outstanding() >= BFHIP_POOL_MAX_OUTSTANDING) throw HipError("bfhip_pool_submit: more than BFHIP_POOL_MAX_OUTSTANDING (4096) jobs outstanding");
+    if (pool->batch_active) throw HipError(me + ": a batch call is in progress");
+    if (pool->outstanding() >= BFHIP_POOL_MAX_OUTSTANDING) throw HipError(me + ": more than BFHIP_POOL_MAX_OUTSTANDING (4096) jobs outstanding");
     q->ticket = pool->next_ticket; q->submitted = std::chrono::steady_clock::now();
     pool->queued.push_back(q.get());
     *ticket = q.release()->ticket;
@@ -399,6 +416,33 @@ int32_t bfhip_pool_submit_registers(bfhip_pool* pool, const uint32_t* trace7_h, 
     std::unique_ptr<QJob> q(new QJob()); q->kind = 2; q->rows = trace7_h; q->n_rows = n_rows; q->log_max_rows = log_max_rows; q->tag = user_tag;
     q->words.assign(code_words_h, code_words_h + n_code);      // n_code == 0 fails the job ("empty program"), like the one-call entry
     return pool_submit(pool, q.release(), ticket);
+    API_CATCH
+}
+
+int32_t bfhip_pool_submit_air(bfhip_pool* pool, const bfhip_air_statement* statement, const uint32_t* const* const* tree_cols_h, bfhip_air_kernel* const* kernels_h,
+                              const bfhip_channel* ch, uint32_t flags, uint64_t user_tag, uint64_t* ticket) {
+    API_TRY
+    const std::string me = "bfhip_pool_submit_air";
+    if (!pool || !statement || !tree_cols_h || !ch || !ticket) throw HipError(me + ": null argument");
+    // settings change only while nothing is outstanding, and jobs read them: the first sub-context's are the pool's
+    const Ctx& c0 = pool->subs[0]->c;
+    (void)air_statement_plan(me, statement, c0.pcs.log_blowup, c0.tw_root_log + 1);
+    if (ch->conv.merkle_channel != c0.conv.merkle_channel || (c0.conv.merkle_channel == 0 && ch->conv.mix_u64 != c0.conv.mix_u64))
+        throw HipError(me + ": the channel was created under other conventions (merkle_channel, mix_u64) than the pool's");
+    std::unique_ptr<QJob> q(new QJob()); q->kind = 3; q->tag = user_tag; q->air_flags = flags;
+    q->air.assign(me, statement, tree_cols_h);
+    q->channel.reset(new bfhip_channel(*ch));
+    if (kernels_h) q->kernels.assign(kernels_h, kernels_h + (size_t)pool->k * statement->n_components);
+    return pool_submit(pool, q.release(), ticket, me);
+    API_CATCH
+}
+
+int32_t bfhip_pool_set_scratch_reserve(bfhip_pool* pool, uint64_t bytes_per_worker) {
+    API_POOL(pool)
+    std::lock_guard<std::mutex> call(pool->call_mu);
+    pool->require_idle("bfhip_pool_set_scratch_reserve");
+    for (auto* s : pool->subs) if (bfhip_ctx_set_scratch_reserve(s, bytes_per_worker) != 0) return -1;
+    return 0;
     API_CATCH
 }
 

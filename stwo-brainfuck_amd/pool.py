@@ -3,9 +3,10 @@ import ctypes
 
 import numpy as np
 
-from ._abi import TRACE_REJECTED, Owned, _check, _last_error, _take_host_string, abi, struct_fields
+from ._abi import TRACE_REJECTED, BfhipError, Owned, _check, _last_error, _ptr_array, _take_host_string, abi, struct_fields
 from ._abi_gen import BFHIP_JOB_CANCELLED as JOB_CANCELLED, BFHIP_POOL_MAX_OUTSTANDING as POOL_MAX_OUTSTANDING
 from .context import Context, Conventions, _default_conventions, _pcs_ref
+from .programs import AIR_PROVE_CHECK, CompiledAir
 
 
 class PoolResult(ctypes.Structure):
@@ -34,10 +35,34 @@ class JobResult:
                                                                              "%d proof bytes" % len(self.proof) if self.ok else self.error)
 
 
+class PoolCompiledAir:
+    """Pool.air_compile: one AirProgram compiled on every sub-context of a pool — .kernels[w] is the CompiledAir of sub-context w, the
+    one a job that runs on worker w uses. close() closes them all; .shape is the program's."""
+
+    def __init__(self, pool, program):
+        self.shape, self.kernels = dict(program.shape), []
+        try:
+            for w in range(pool.n_in_flight):
+                self.kernels.append(CompiledAir(pool.ctx(w), program))
+        except Exception:
+            self.close()
+            raise
+
+    def close(self):
+        for k in self.kernels:
+            k.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class Pool(Owned):
     """bfhip_pool_create: `n_in_flight` sub-contexts on one GPU behind ONE caller thread — prove_batch() hands the library a batch of resident
     traces and returns when all are proved, n_in_flight at a time on the library's own worker threads; submit_trace / submit_program /
-    submit_registers + wait() / as_completed() use the same workers as a queue (results as they complete; not while a batch runs). The sub-contexts share one twiddle
+    submit_registers / submit_air + wait() / as_completed() use the same workers as a queue (results as they complete; not while a batch runs). The sub-contexts share one twiddle
     tree and (preprocessed=1, default) one preprocessed commitment per batch; 0 = every proof recommits it like the reference
     (mod.rs:495-500), 2 = kept across batches."""
     _destroy = "bfhip_pool_destroy"
@@ -83,6 +108,44 @@ class Pool(Owned):
         code = np.ascontiguousarray(code_words, dtype=np.uint32)
         t = ctypes.c_uint64()
         return self._submitted(abi().bfhip_pool_submit_registers(self._h, tr.ctypes.data, tr.shape[0], code.ctypes.data, code.size, log_max_rows, tag, ctypes.byref(t)), t, tr)
+
+    def submit_air(self, statement, tree_cols, channel, kernels=None, check=False, tag=0):
+        """bfhip_pool_submit_air: what Context.air_prove takes, as a job; the result's proof is air_prove's bytes. The statement, the table
+        of column pointers and the channel's state are copied by the library at submit: `channel` is not advanced and may be reused or
+        closed at once. kernels: per component None or the PoolCompiledAir of its program (Pool.air_compile, while nothing is
+        outstanding). The pool holds the programs, the kernels and tree_cols until the result is taken; the device columns behind
+        tree_cols stay the caller's to keep alive until then."""
+        st = statement._c()
+        if len(tree_cols) != len(statement.trees) or any(len(cols) != len(tree[0]) for cols, tree in zip(tree_cols, statement.trees)):
+            raise ValueError("one device column per column of every caller tree")
+        if kernels is not None and len(kernels) != len(statement.components):
+            raise ValueError("one kernel (or None) per component")
+        per_tree = [_ptr_array(cols) for cols in tree_cols]
+        trees = (ctypes.c_void_p * max(1, len(per_tree)))(*[ctypes.cast(a, ctypes.c_void_p) for a in per_tree])
+        ks = None
+        if kernels is not None:
+            ks = (ctypes.c_void_p * (self.n_in_flight * len(kernels)))(*[None if k is None else k.kernels[w]._h for w in range(self.n_in_flight) for k in kernels])
+        t = ctypes.c_uint64()
+        rc = abi().bfhip_pool_submit_air(self._h, ctypes.byref(st), trees, ks, channel._h, AIR_PROVE_CHECK if check else 0, tag, ctypes.byref(t))
+        keep = ([c[0] for c in statement.components], [c[5] for c in statement.components], list(kernels or ()), tree_cols)
+        return self._submitted(rc, t, keep)
+
+    def air_compile(self, program):
+        """bfhip_air_compile on every sub-context: a PoolCompiledAir for submit_air's `kernels`. Call it while nothing is outstanding."""
+        return PoolCompiledAir(self, program)
+
+    def prove_batch_air(self, jobs, timeout_s=None):
+        """Submits every job — (statement, tree_cols, channel) or (statement, tree_cols, channel, kernels[, check]) — and returns the
+        JobResults in SUBMIT order once all are done. Needs an empty queue (results of other jobs would be taken with these)."""
+        if any(self.outstanding().values()):
+            raise BfhipError("prove_batch_air: jobs outstanding")
+        tickets = [self.submit_air(*job[:3], kernels=job[3] if len(job) > 3 else None, check=bool(job[4]) if len(job) > 4 else False, tag=i) for i, job in enumerate(jobs)]
+        by_ticket = {r.ticket: r for r in self.as_completed(timeout_s)}
+        return [by_ticket[t] for t in tickets]
+
+    def set_scratch_reserve(self, bytes_per_worker):
+        """bfhip_pool_set_scratch_reserve: Context.set_scratch_reserve on every sub-context; refused while jobs are outstanding."""
+        _check(abi().bfhip_pool_set_scratch_reserve(self._h, int(bytes_per_worker)))
 
     def wait(self, timeout_s=None):
         """bfhip_pool_wait: the next finished job as a JobResult; None when nothing is outstanding; TimeoutError when timeout_s (None = no limit,

@@ -7,7 +7,7 @@ tracker for it:
                     [--log-max-rows 24] [--conventions a,b,c,d | --poseidon252] [--all-sets DIR] [PCS options]
                     [--preflight] [--set-register ROW:NAME=VALUE ...] [--set-word INDEX=VALUE ...] [--generic]
   bfprove.py prove  --queue N --programs a.bf b.bf ... --output-dir DIR [--input-file in.bin] [--ram-size N] [--log-max-rows 24]
-                    [--conventions a,b,c,d | --poseidon252] [PCS options] [--preflight] [--set-register ...]
+                    [--conventions a,b,c,d | --poseidon252] [PCS options] [--preflight] [--set-register ...] [--generic]
   bfprove.py verify proof.json [--log-max-rows 24] [--conventions a,b,c,d | --poseidon252 | --try-all] [PCS options] [--generic]
   bfprove.py check  (--file prog.bf | --code '++>,<[>+.<-]') [--input-file in.bin] [--ram-size N] [--set-register ROW:NAME=VALUE ...]
   bfprove.py relations (--file prog.bf | --code ...) [--input-file in.bin] [--ram-size N] [--set-register ROW:NAME=VALUE ...]
@@ -39,7 +39,8 @@ prove --generic proves the same trace through bfhip_air_prove: the 13 components
 brainfuck_air_statement, the main trace handed over as full-size device columns, IsFirst as coefficients. The file it writes is the same
 BrainfuckProof (claim and interaction claim put around the driver's claimed sums and proof member) — byte for byte the file of the
 built-in path, which plain `verify` accepts. verify --generic checks a BrainfuckProof file through bfhip_air_verify under the statement
-that its claim describes. Neither works with --all-sets, --queue or --preflight.
+that its claim describes. Neither works with --all-sets or --preflight. prove --generic --queue N --programs ... sends every program's trace
+through the pool's queue as an AIR statement (bfhip_pool_submit_air), N in flight, and writes the same files as --queue alone.
 
 PCS options (stwo's PcsConfig; the defaults are PcsConfig::default()): --pow-bits 5 --log-blowup-factor 1 --n-queries 3. The proof file does
 not record them: verify with the values the proof was made with. prove prints the config and its security bits (pow + blowup x queries).
@@ -284,12 +285,79 @@ def generic_prove(pkg, ctx, tr, log_max_rows, conv, kernels=None, columns=None):
         if columns is None:
             for p in ptrs:
                 ctx.free(p)
+    return brainfuck_proof_of(raw, tr.log_sizes), raw
+
+
+def brainfuck_proof_of(raw, log_sizes):
+    """The BrainfuckProof bytes around air_prove's result: claim and interaction claim put around its claimed sums and proof member"""
     head, at = b'{"claimed_sums":[', raw.index(b'],"proof":')
     sums = raw[len(head): at].replace(b"]],[[", b"]]\n[[").split(b"\n")
     assert raw.startswith(head) and len(sums) == 13
-    claim = b",".join(b'"%s":{"log_size":%d,"_marker":null}' % (n.encode(), l) for n, l in zip(pcs_replay.NAMES, tr.log_sizes))
+    claim = b",".join(b'"%s":{"log_size":%d,"_marker":null}' % (n.encode(), l) for n, l in zip(pcs_replay.NAMES, log_sizes))
     inter = b",".join(b'"%s":{"claimed_sum":%s}' % (n.encode(), c) for n, c in zip(pcs_replay.NAMES, sums))
-    return b'{"claim":{' + claim + b'},"interaction_claim":{' + inter + b'},"proof":' + raw[at + len(b'],"proof":'):], raw
+    return b'{"claim":{' + claim + b'},"interaction_claim":{' + inter + b'},"proof":' + raw[at + len(b'],"proof":'):]
+
+
+def prove_queue_generic(pkg, a, ap):
+    """prove --generic --queue N: every program's trace as a brainfuck_air_statement job of the pool's queue (bfhip_pool_submit_air), each
+    proof written as it completes. The traces are made resident by a context of the caller's; the columns of every program stay on the
+    device until its result has been taken."""
+    if not a.programs or not a.output_dir:
+        ap.error("prove --queue needs --programs FILE... and --output-dir DIR")
+    if not 1 <= a.queue <= 16:
+        ap.error("--queue takes 1..16 proofs in flight")
+    if a.set_register or a.set_word:
+        ap.error("--generic --queue does not go with --set-register / --set-word")
+    inp = open(a.input_file, "rb").read() if a.input_file else (b"" if sys.stdin.isatty() else sys.stdin.buffer.read())
+    os.makedirs(a.output_dir, exist_ok=True)
+    pcs, conv = parse_pcs(pkg, a), parse_conventions(a)
+    max_log_domain = a.log_max_rows + pcs.log_blowup_factor + 1
+    ctx = pkg.Context(0, max_log_domain=max_log_domain)
+    pool = pkg.Pool(0, n_in_flight=a.queue, max_log_domain=max_log_domain)
+    failed, held = 0, {}
+    try:
+        pool.set_pcs_config(pcs)
+        pool.set_conventions(*conv)
+        t0 = time.time()
+        with pkg.Channel(conv) as ch:
+            for i, path in enumerate(a.programs):
+                try:
+                    tr = pkg.Trace(ctx, open(path).read(), inp, ram_size=a.ram_size)
+                except pkg.BfhipError as e:            # the VM refused the program: nothing was submitted
+                    failed += 1
+                    print(f"{path}: error: {e}", file=sys.stderr)
+                    continue
+                cols, ptrs = generic_columns(pkg, ctx, tr, a.log_max_rows)
+                held[i] = (tr.log_sizes, ptrs)
+                tr.close()
+                try:
+                    pool.submit_air(pkg.brainfuck_air_statement(held[i][0], a.log_max_rows, conv[2]), cols, ch, tag=i)
+                except pkg.BfhipError as e:            # the validator refused the statement (a trace too large for --log-max-rows)
+                    failed += 1
+                    print(f"{path}: error: {e}", file=sys.stderr)
+                    for p in held.pop(i)[1]:
+                        ctx.free(p)
+        for r in pool.as_completed(timeout_s=3600.0):
+            path = a.programs[r.tag]
+            log_sizes, ptrs = held.pop(r.tag)
+            for p in ptrs:
+                ctx.free(p)
+            if not r.ok:
+                failed += 1
+                print(f"{path}: error: {r.error}", file=sys.stderr)
+                continue
+            proof = brainfuck_proof_of(r.proof, log_sizes)
+            out = os.path.join(a.output_dir, os.path.splitext(os.path.basename(path))[0] + ".proof.json")
+            open(out, "wb").write(proof)
+            print(f"{out}  {len(proof)} bytes; queued {1e3 * r.seconds_queued:.1f} ms, proving {1e3 * r.seconds_proving:.1f} ms on worker {r.worker}; "
+                  f"{time.time() - t0:.3f}s after the first submit", flush=True)
+    finally:
+        pool.close()
+        for _, ptrs in held.values():
+            for p in ptrs:
+                ctx.free(p)
+        ctx.close()
+    return 1 if failed else 0
 
 
 def generic_verify(pkg, proof, log_max_rows, conv, pcs):
@@ -310,10 +378,10 @@ def generic_verify(pkg, proof, log_max_rows, conv, pcs):
 
 
 def run(pkg, a, ap):
-    if a.cmd == "prove" and a.generic and (a.queue or a.all_sets or a.preflight):
-        ap.error("--generic does not go with --queue, --all-sets or --preflight")
+    if a.cmd == "prove" and a.generic and (a.all_sets or a.preflight):
+        ap.error("--generic does not go with --all-sets or --preflight")
     if a.cmd == "prove" and a.queue:
-        return prove_queue(pkg, a, ap)
+        return prove_queue_generic(pkg, a, ap) if a.generic else prove_queue(pkg, a, ap)
     if a.cmd == "check":
         return check(pkg, a, ap)
     if a.cmd == "relations":
