@@ -943,3 +943,54 @@ impl Drop for RelationProgram {
         unsafe { sys::bfhip_relation_program_destroy(self.0) };
     }
 }
+
+// ---- witness programs (`include/bfhip.h` "Witness programs"): the columns an author computes row by row, derived on the device ----------------
+// The base-field opcodes of a constraint program, M_COL at trace offsets, plus `sys::BFHIP_WIT_ARG` .. `sys::BFHIP_WIT_STORE`: run once per
+// row of CanonicCoset(log_size), a program reads input columns and stores output columns — an inverse, a padding flag, the bits of a byte, a
+// "next" value. The step between `Context::columns_from_rows` and the first commitment.
+
+/// `bfhip_witness_program_shape`.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct WitnessShape { pub n_cols: u32, pub n_out: u32, pub n_args: u32, pub n_instr: u32, pub m_regs: u32, pub min_offset: i32, pub max_offset: i32 }
+
+/// A validated witness program (`bfhip_witness_program`). Host only to create, inspect and evaluate over a row-order table.
+pub struct WitnessProgram(*mut sys::BfhipWitnessProgram);
+
+impl WitnessProgram {
+    /// `bfhip_witness_program_create`. A refusal names the instruction index and the rule.
+    pub fn new(code: &[u32], n_cols: u32, n_out: u32, n_args: u32) -> Result<Self, String> {
+        let mut p = std::ptr::null_mut();
+        check(unsafe { sys::bfhip_witness_program_create(code.as_ptr(), code.len(), n_cols, n_out, n_args, &mut p) })?;
+        Ok(WitnessProgram(p))
+    }
+    pub fn shape(&self) -> Result<WitnessShape, String> {
+        let mut o = [0u32; 8];
+        check(unsafe { sys::bfhip_witness_program_shape(self.0, o.as_mut_ptr()) })?;
+        Ok(WitnessShape { n_cols: o[0], n_out: o[1], n_args: o[2], n_instr: o[3], m_regs: o[4], min_offset: o[5] as i32, max_offset: o[6] as i32 })
+    }
+    /// `bfhip_witness_program_eval_table` (host only): the program over a row-major table of 2^log_size rows in ROW order; returns the
+    /// 2^log_size x n_out outputs, row-major. The definition `generate` is held to.
+    pub fn eval_table(&self, log_size: u32, table: &[u32], args: &[u32]) -> Result<Vec<u32>, String> {
+        let s = self.shape()?;
+        if log_size < 1 || log_size > 30 || table.len() != (s.n_cols as usize) << log_size { return Err("a table is 2^log_size x n_cols words".into()); }
+        let mut out = vec![0u32; (s.n_out as usize) << log_size];
+        let table_ptr = if table.is_empty() { std::ptr::null() } else { table.as_ptr() };
+        let args_ptr = if args.is_empty() { std::ptr::null() } else { args.as_ptr() };
+        check(unsafe { sys::bfhip_witness_program_eval_table(self.0, log_size, table_ptr, args_ptr, args.len() as u32, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+    /// `bfhip_witness_program_generate`: the program at every cell of the trace domain, one launch on the context's stream, no read-back.
+    /// `cols` and `out_cols`: device columns of 2^log_size words in storage order. Works while a commitment-scheme session is open.
+    pub fn generate(&self, ctx: &Context, log_size: u32, cols: &[*const u32], args: &[u32], out_cols: &[*mut u32]) -> Result<(), String> {
+        if cols.len() != self.shape()?.n_cols as usize { return Err("one column pointer per program column".into()); }
+        let cols_ptr = if cols.is_empty() { std::ptr::null() } else { cols.as_ptr() };
+        let args_ptr = if args.is_empty() { std::ptr::null() } else { args.as_ptr() };
+        check(unsafe { sys::bfhip_witness_program_generate(ctx.0, self.0, log_size, cols_ptr, args_ptr, args.len() as u32, out_cols.as_ptr(), out_cols.len() as u32) })
+    }
+}
+
+impl Drop for WitnessProgram {
+    fn drop(&mut self) {
+        unsafe { sys::bfhip_witness_program_destroy(self.0) };
+    }
+}

@@ -1331,6 +1331,68 @@ int32_t bfhip_relation_program_multiplicities(bfhip_ctx* ctx, const bfhip_relati
                                               uint32_t relation, uint32_t target_table, uint32_t target_entry, uint32_t* out_d,
                                               bfhip_multiplicity_report* report, bfhip_relation_entry* missing_h, uint32_t cap);
 
+/* ---- Witness programs: derive the columns an author does not have, row by row, on the device ------------------------------------------------
+ * Between bfhip_columns_from_rows and the first commitment stand the columns an AIR's author does not hold but can compute from the ones they
+ * do: the inverse of an is-zero gadget, a padding flag, a selector, the bits of a byte, and every "next" value — fraction and relation
+ * programs read a row's own cells only, so a "next" value is a column, and in storage order row r + 1 is not pointer + 1. A witness program
+ * is a constraint program's bytecode (same four-word {op, dst, a, b} instructions, same m[] register file, same caps: 96 m registers, 4096
+ * instructions, 256 columns, offsets -16..16), base field only, run ONCE PER ROW of CanonicCoset(log_size): it reads input columns at trace
+ * offsets and stores output columns. Admitted from the shared set: M_COL at any offset in -BFHIP_AIR_MAX_OFFSET..BFHIP_AIR_MAX_OFFSET (the
+ * coset-order move, cyclic over 2^log_size: exactly what bfhip_air_check reads for that mask entry), M_CONST, M_ADD, M_SUB, M_MUL, M_NEG.
+ * Opcodes that exist only here:
+ *   BFHIP_WIT_ARG      dst, k       m[dst] = args[k]: a per-call array of canonical M31 words — what differs from trace to trace, such as
+ *                                   the number of real rows
+ *   BFHIP_WIT_ROW      dst          m[dst] = the row's coset index: the r of bfhip_columns_from_rows (bfhip_row_of_cell of the cell)
+ *   BFHIP_WIT_INV0     dst, a       m[dst] = m[a]^-1, and 0 for 0 (the convention of the VM's mvi)
+ *   BFHIP_WIT_IS_ZERO  dst, a       m[dst] = 1 if m[a] == 0, else 0
+ *   BFHIP_WIT_LT       dst, a, b    m[dst] = 1 if m[a] < m[b] as integers in [0, p), else 0
+ *   BFHIP_WIT_AND      dst, a, imm  m[dst] = m[a] & imm; imm < 2^31 in the b word
+ *   BFHIP_WIT_SHR      dst, a, imm  m[dst] = m[a] >> imm; imm in 0..30
+ *   BFHIP_WIT_STORE    out, a       output column `out` (the dst word) of this row receives m[a]
+ * Every value a program produces is a canonical M31 word when its inputs are (bfhip_columns_from_rows checks that on the way in): there is
+ * no run-time failure and no report.
+ *
+ * bfhip_witness_program_create (host only): every rule of bfhip_air_create that applies (opcode, register range, read before write, column
+ *   within n_cols, offset, v < p, the instruction and column caps), and: every Q_* opcode, C_BASE, C_EXT, FRAC, END_COL, REL_WORD and
+ *   REL_ENTRY are refused; an ARG index not below n_args; n_args above BFHIP_AIR_MAX_PARAMS; an AND immediate of 2^31 or more; a SHR
+ *   immediate above 30; n_out outside 1 .. 256; a STORE index not below n_out; an output stored a second time ("STORE: output <k> is stored
+ *   a second time"); an output no STORE writes ("the program ends with output <k> never stored"). Each refusal is -1 with
+ *   "bfhip_witness_program_create: instruction <i>: <rule>" (rules about the program as a whole name the instruction count). bfhip_air_create,
+ *   bfhip_logup_create and bfhip_relation_program_create keep refusing opcodes 19 and up.
+ * bfhip_witness_program_shape: out = {columns, outputs, args, instructions, m registers used, min offset, max offset, 0}; the offsets are
+ *   int32 in uint32 words.
+ * bfhip_witness_program_eval_table (host only): the whole program over a row-major table in ROW order — table_h = 2^log_size x n_cols words,
+ *   out_h = 2^log_size x n_out words; row r reads column c at offset `off` in row (r + off) mod 2^log_size. The definition the kernel is held
+ *   to. 1 <= log_size <= 30. Refused, -1 with "bfhip_witness_program_eval_table: <rule>": null arguments, log_size, n_args other than the
+ *   program's, an arg or a table word that is not canonical (the word's row and column are named).
+ * bfhip_witness_program_generate: the program at every cell of the trace domain. cols_h: the program's n_cols device columns, out_cols_h:
+ *   n_out device columns; all of them full size — 2^log_size words in storage order, shift 0. args_h: n_args host words. ONE launch on the
+ *   context's stream and no read-back: ordered like bfhip_rows_from_columns, so bfhip_download behind it sees the result. The inputs are not
+ *   checked for canonicity (they come from bfhip_columns_from_rows or from an entry point that wrote canonical words); output columns are
+ *   written whole.
+ *   Memory: descriptors, args and code go through the staging ring; nothing from the arena (bfhip_ctx_memory out[3] is unchanged) and no
+ *     allocation. Works while a commitment-scheme session is open.
+ *   Refused, -1 with "bfhip_witness_program_generate: <rule>", nothing enqueued, the context usable: null arguments ("null argument"; a null
+ *     column names itself: "input column <j> is a null pointer", "output column <k> is a null pointer"); a context in a shard group; log_size
+ *     outside [1, max_log_domain]; n_out or n_args other than the program's ("<n> output columns, the program has <m>", "<n> args, the
+ *     program has <m>"); "arg <k>: <v> is not a canonical M31 value"; an output column sharing a byte with an input or with another output:
+ *     "output column <k> overlaps input column <j>" / "output column <k> overlaps output column <j>".
+ * Kernel (csrc/witness_program.hip): the instruction core of the four program kernels on the row of bfhip_air_check;
+ *   one lane per cell, one wave per workgroup, the register file in LDS.
+ * Not built: tables that need a sort or a row filter (the Memory, Instruction and per-instruction Brainfuck tables), extension-field values,
+ *   shifted (row-granular) columns, reading an output of the same call at an offset (run a second program), witness programs compiled with
+ *   hiprtc, pool jobs, shard groups. */
+enum { BFHIP_WIT_ARG = 19, BFHIP_WIT_ROW = 20, BFHIP_WIT_INV0 = 21, BFHIP_WIT_IS_ZERO = 22, BFHIP_WIT_LT = 23, BFHIP_WIT_AND = 24, BFHIP_WIT_SHR = 25,
+       BFHIP_WIT_STORE = 26 };
+typedef struct bfhip_witness_program bfhip_witness_program;
+int32_t bfhip_witness_program_create(const uint32_t* code, size_t n_words, uint32_t n_cols, uint32_t n_out, uint32_t n_args, bfhip_witness_program** out);
+int32_t bfhip_witness_program_destroy(bfhip_witness_program* wp);
+int32_t bfhip_witness_program_shape(const bfhip_witness_program* wp, uint32_t out[8]);
+int32_t bfhip_witness_program_eval_table(const bfhip_witness_program* wp, uint32_t log_size, const uint32_t* table_h, const uint32_t* args_h, uint32_t n_args,
+                                         uint32_t* out_h);
+int32_t bfhip_witness_program_generate(bfhip_ctx* ctx, const bfhip_witness_program* wp, uint32_t log_size, const uint32_t* const* cols_h,
+                                       const uint32_t* args_h, uint32_t n_args, uint32_t* const* out_cols_h, uint32_t n_out);
+
 /* Host-only pieces of the drop-in (usable without a GPU): the Brainfuck compiler (crates/brainfuck_vm/src/compiler.rs:17-37), the VM
  * (crates/brainfuck_vm/src/machine.rs:141-238; trace rows are 7 u32: clk, ip, ci, ni, mp, mv, mvi) and the 13 table builders
  * (`XTable::from`, the table.rs files under crates/brainfuck_prover/src/components; component index = claim order of mod.rs:85-99), row-major out. */

@@ -233,3 +233,33 @@ def brainfuck_relation_program(component):
     else:
         b.relation_entry(2, t(7)[0] - one, t(0, 1, 2, 3, 4, 5, 6))
     return b.relation_program(BRAINFUCK_RELATION_WORDS, n_cols=n_main), RELATION_NAMES
+
+
+def brainfuck_witness_program(table):
+    """A Brainfuck table derived from the VM's registers as a witness program — the worked example of include/bfhip.h "Witness programs".
+    "processor": the 9 columns of the Processor table (host/tables.h processor_table; components/processor/table.rs: clk, ip, ci, ni, mp,
+    mv, mvi, d, next_clk) from the six register columns clk, ip, ci, ni, mp, mv, ingested with Context.columns_from_rows(...,
+    repeat_last=True), so that a padding row holds the last real row. args = [the number of real rows]. Per row: d = 1 - lt(row, n); a
+    padding row's clk counts on from the last real one; ci..mv are zeroed under d; mvi = inv0(mv); next_clk is the padded clk of the row at
+    offset +1, except on the last row, which takes its own clk + 1 (the extra dummy's) instead of wrapping to row 0. The last row is the
+    one whose neighbour at +1 has clk 0: the VM starts at clk 0 and counts up. Returns (WitnessProgram, output column names)."""
+    if table != "processor":
+        raise ValueError("witness programs are written for: 'processor' (Memory, Instruction and the sub-tables need a sort or a row filter)")
+    b = AirBuilder()
+    row, n = b.row(), b.arg(0)
+    real = b.lt(row, n)
+    d = 1 - real
+    clk = b.col(0) + d * (row + 1 - n)
+    b.store(0, clk)
+    b.store(1, b.col(1))
+    for j in (2, 3, 4):
+        b.store(j, b.col(j) * real)
+    mv = b.col(5) * real
+    b.store(5, mv)
+    b.store(6, b.inv0(mv))
+    b.store(7, d)
+    d_next = 1 - b.lt(row + 1, n)
+    following = b.col(0, 1) + d_next * (row + 2 - n)
+    last = b.is_zero(b.col(0, 1))
+    b.store(8, following + last * (clk + 1 - following))
+    return b.witness_program(9, n_cols=6, n_args=1), ("clk", "ip", "ci", "ni", "mp", "mv", "mvi", "d", "next_clk")

@@ -121,6 +121,26 @@ def columns_from_rows(ctx, table, log_size, columns=None, pad=None, repeat_last=
             ctx.free(tmp)
 
 
+def witness_program_generate(ctx, program, log_size, col_ptrs, args=(), out=None):
+    """Context.witness_program_generate (see there)."""
+    col_ptrs, args = list(col_ptrs), [int(a) for a in args]
+    n_out = program.shape()["n_out"] if out is None else len(out)
+    owned = []
+    try:
+        ptrs = list(out) if out is not None else None
+        if ptrs is None:
+            for _ in range(n_out):
+                owned.append(ctx.malloc(4 << log_size))
+            ptrs = owned
+        _check(abi().bfhip_witness_program_generate(ctx._h, program._h, int(log_size), _ptr_array(col_ptrs) if col_ptrs else None,
+                                                    _u32s(args) if args else None, len(args), _ptr_array(ptrs) if ptrs else None, n_out))
+    except Exception:
+        for p in owned:
+            ctx.free(p)
+        raise
+    return Columns(ctx, ptrs, log_size, owned)
+
+
 def rows_from_columns(ctx, col_ptrs, log_size, n_rows=None):
     """Context.rows_from_columns (see there)."""
     col_ptrs = list(col_ptrs)

@@ -340,6 +340,13 @@ class Context(Owned):
         n_cols) uint32 array; n_rows None = all 2^log_size. What reads a generated column — multiplicities, a logUp column — by row."""
         return _columns.rows_from_columns(self, col_ptrs, log_size, n_rows)
 
+    def witness_program_generate(self, program, log_size, col_ptrs, args=(), out=None):
+        """bfhip_witness_program_generate: a WitnessProgram at every row of CanonicCoset(log_size), in one launch and without a read-back.
+        col_ptrs: one full-size storage-order device column per program column (pointers, or a Columns handle); args: the program's
+        per-call canonical words; out: device pointers to write instead of new columns. Returns a Columns handle of the n_out output
+        columns that owns what it allocated. Nothing comes from the arena: it works inside an open PcsSession."""
+        return _columns.witness_program_generate(self, program, log_size, col_ptrs, args, out)
+
     # -- PolyOps ---------------------------------------------------------------------------------------------------
     def interpolate(self, src_ptrs, dst_ptrs, log_size, replicated=False):
         _check(abi().bfhip_interpolate(self._h, _ptr_array(src_ptrs), _ptr_array(dst_ptrs), len(src_ptrs), log_size, int(replicated)))

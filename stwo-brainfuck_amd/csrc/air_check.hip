@@ -6,10 +6,11 @@
 // cells of CanonicCoset(log_size) are non-zero.
 //
 // The interpreter is the core of program_interp.h, which k_air_program runs too: one lane per cell, one wave per workgroup (at the caps the
-// register file is 48 KiB per wave: four waves would not fit a workgroup's LDS). This file adds what a cell of the trace domain is
-// (AirTraceRow) and what C_BASE / C_EXT do here (AirCheckSink).
+// register file is 48 KiB per wave: four waves would not fit a workgroup's LDS). A cell of the trace domain is AirTraceRow (trace_row.h,
+// shared with witness_program.hip); this file adds what C_BASE / C_EXT do here (AirCheckSink).
 #include "api_guard.h"
 #include "program_interp.h"
+#include "trace_row.h"
 #include "../../include/bfhip.h"
 #include <cstddef>
 #include <cstring>
@@ -32,15 +33,6 @@ struct AirCheckLaunch {
     u64 params;          // bf_u32x4[n_params]
     u64 report;          // AirCheckReportDev*
     u32 n_instr, n_m, log_size, n_constraints;
-};
-
-// A cell of the trace domain CanonicCoset(log_size) itself; a column of shift s holds the cell's own value at cell >> s. The offset map is
-// air.h's trace_offset_cell, not air_offset_row of air_program.hip.
-struct AirTraceRow {
-    static constexpr bool OFFSETS = true;
-    u32 self, log_size;
-    __device__ __forceinline__ u32 at0(const bf_u32x4 col) const { return self >> col.z; }
-    __device__ __forceinline__ u32 at(int off) const { return trace_offset_cell(self, off, log_size); }
 };
 
 // C_BASE / C_EXT set bit j of the lane's 64-bit mask when constraint j is non-zero; nothing leaves early, so the wave stays uniform.

@@ -1,4 +1,5 @@
-// Argument conversions that more than one file of the C ABI needs (api_ops.hip, api_air.hip, relations.hip). Internal to the library.
+// Argument conversions and checks that more than one file of the C ABI needs (api_ops.hip, api_air.hip, relations.hip, witness_program.hip).
+// Internal to the library.
 #pragma once
 #include "ctx.h"
 
@@ -14,6 +15,13 @@ static inline void check_component(int32_t component, uint32_t log_size, const C
     if (!tree && log_size > 29) throw HipError("component log_size above 29: columns hold at most 2^29 cells");
     if (tree && log_size + extra_log > tree->tw_root_log + 1) throw HipError("log_size exceeds the context's twiddle tree");
 }
+
+// A named range of device bytes: how bfhip_columns_from_rows, bfhip_rows_from_columns and bfhip_witness_program_generate refuse an output
+// that shares a byte with something the same launch reads or writes
+struct ByteRange {
+    u64 base, bytes; std::string name;
+    bool overlaps(const ByteRange& o) const { return bytes && o.bytes && base < o.base + o.bytes && o.base < base + bytes; }
+};
 
 // One QM31 result read back: a copy on the context's stream into pageable memory, then a wait for the stream (not Ctx::read_back's pinned
 // bounce). r is the caller's, declared before the DeviceScratch that owns `src`: on every path the copy into it has completed when it goes.

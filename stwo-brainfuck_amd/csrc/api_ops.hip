@@ -65,11 +65,7 @@ static const u32* stage_alpha(Ctx& c, const uint32_t alpha_h[4]) {
     c.stage_checkpoint();
     return c.stage(w, 8);
 }
-// ---- what the two row-order entry points share (rows.hip) ----
-struct ByteRange {
-    u64 base, bytes; std::string name;
-    bool overlaps(const ByteRange& o) const { return bytes && o.bytes && base < o.base + o.bytes && o.base < base + bytes; }
-};
+// ---- what the two row-order entry points share (rows.hip); ByteRange is api_args.h's ----
 static void rows_check_index(const char* who, uint32_t log_size, uint64_t index, const uint64_t* out) {
     if (!out) throw HipError(std::string(who) + ": null argument");
     if (log_size < 1 || log_size > ROWS_MAX_LOG) throw HipError(std::string(who) + ": log_size " + std::to_string(log_size) + " is outside 1..30");

@@ -1,5 +1,6 @@
-"""Any AIR given as programs (include/bfhip.h "Constraint programs", "Fraction programs", "Relation programs"): the validated handles
-AirProgram, CompiledAir, LogupProgram and RelationProgram, and AirBuilder, which writes their bytecode from expressions."""
+"""Any AIR given as programs (include/bfhip.h "Constraint programs", "Fraction programs", "Relation programs", "Witness programs"): the
+validated handles AirProgram, CompiledAir, LogupProgram, RelationProgram and WitnessProgram, and AirBuilder, which writes their bytecode from
+expressions."""
 import ctypes
 
 import numpy as np
@@ -17,7 +18,9 @@ from ._abi_gen import (BFHIP_AIR_C_BASE as AIR_C_BASE, BFHIP_AIR_C_EXT as AIR_C_
                        BFHIP_LOGUP_MAX_COLUMNS as LOGUP_MAX_COLUMNS,
                        BFHIP_LOGUP_MAX_FRACTIONS as LOGUP_MAX_FRACTIONS, BFHIP_REL_ENTRY as REL_ENTRY, BFHIP_REL_WORD as REL_WORD,
                        BFHIP_RELATION_PROGRAM_MAX_ENTRIES as RELATION_PROGRAM_MAX_ENTRIES, BFHIP_RELATION_PROGRAM_MAX_RELATIONS as RELATION_PROGRAM_MAX_RELATIONS,
-                       BFHIP_RELATION_PROGRAM_MAX_WORDS as RELATION_PROGRAM_MAX_WORDS)
+                       BFHIP_RELATION_PROGRAM_MAX_WORDS as RELATION_PROGRAM_MAX_WORDS, BFHIP_WIT_AND as WIT_AND, BFHIP_WIT_ARG as WIT_ARG,
+                       BFHIP_WIT_INV0 as WIT_INV0, BFHIP_WIT_IS_ZERO as WIT_IS_ZERO, BFHIP_WIT_LT as WIT_LT, BFHIP_WIT_ROW as WIT_ROW, BFHIP_WIT_SHR as WIT_SHR,
+                       BFHIP_WIT_STORE as WIT_STORE)
 
 AIR_OPS = ("M_COL", "M_CONST", "M_ADD", "M_SUB", "M_MUL", "M_NEG", "Q_COL", "Q_PARAM", "Q_FROM_M", "Q_ADD", "Q_SUB", "Q_MUL", "Q_MULM", "C_BASE", "C_EXT")
 
@@ -308,6 +311,38 @@ class RelationProgram(_Program):
         return [(int(rels[e]), int(mults[e]), tuple(int(v) for v in tups[7 * e: 7 * e + self.relation_words[rels[e]]])) for e in range(n.value)]
 
 
+class WitnessProgram(_Program):
+    """bfhip_witness_program: a validated witness program (include/bfhip.h "Witness programs") — the base-field opcodes of a constraint
+    program, M_COL at trace offsets, with ARG, ROW, INV0, IS_ZERO, LT, AND, SHR and STORE: run once per row, it reads input columns and
+    stores n_out output columns. Host only to create and for eval_table; Context.witness_program_generate runs it on the trace domain. A
+    refused program raises BfhipError naming the instruction index and the rule."""
+    _destroy = "bfhip_witness_program_destroy"
+
+    def __init__(self, code, n_cols, n_out, n_args):
+        self._out = self._create(code, lambda words, n, h: abi().bfhip_witness_program_create(words, n, int(n_cols), int(n_out), int(n_args), h),
+                                 abi().bfhip_witness_program_shape)
+
+    def shape(self):
+        """bfhip_witness_program_shape as a dict."""
+        out = self._out
+        signed = lambda v: v - (1 << 32) if v >= 1 << 31 else v
+        return {"n_cols": out[0], "n_out": out[1], "n_args": out[2], "n_instr": out[3], "m_regs": out[4], "min_offset": signed(out[5]), "max_offset": signed(out[6])}
+
+    def eval_table(self, table, args=()):
+        """bfhip_witness_program_eval_table (host only): the program over a (2^log_size, n_cols) uint32 table in ROW order; returns the
+        (2^log_size, n_out) outputs. The definition Context.witness_program_generate is held to."""
+        shape = self.shape()
+        table = np.ascontiguousarray(table, dtype=np.uint32)
+        n = table.shape[0] if table.ndim == 2 else 0
+        if table.ndim != 2 or table.shape[1] != shape["n_cols"] or n < 2 or n & (n - 1):
+            raise ValueError("a table is a (2^log_size, n_cols) uint32 array with log_size >= 1")
+        args = [int(a) for a in args]
+        out = np.zeros((n, shape["n_out"]), dtype=np.uint32)
+        _check(abi().bfhip_witness_program_eval_table(self._h, n.bit_length() - 1, table.ctypes.data_as(ctypes.c_void_p) if table.size else None,
+                                                      _u32s(args) if args else None, len(args), out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+
 class AirExpr:
     """A value of an AirBuilder: kind 'm' (M31, a base-field column expression) or 'q' (QM31). Operators + - * and unary -; a Python int
     stands for const(int). m op q promotes the m side (Q_FROM_M), except a product, which is Q_MULM."""
@@ -331,7 +366,9 @@ class AirBuilder:
     col(i, off) / secure_col(i, off) (coordinates in columns i..i+3) / param(i) / const(v) give values; every value is computed once, in
     the order it was created (so the order of first use of a column's offsets — the mask order — is the order of the col() calls that are
     used); other values no constraint depends on are dropped, but a column read stays (like stwo's next_trace_mask, it is part of the mask
-    whether or not a constraint uses it); a register is reused after its value's last use."""
+    whether or not a constraint uses it); a register is reused after its value's last use. The same builder writes the other families:
+    frac() / end_column() (logup_program), relation_entry() (relation_program), and arg() / row() / inv0() / is_zero() / lt() / bit_and() /
+    shr() / store() (witness_program)."""
 
     def __init__(self):
         self._ops = []        # [op, kind of the result or None, sources (value ids), immediates]
@@ -409,6 +446,44 @@ class AirBuilder:
         # the words are sources of the ENTRY too: the interpreters read them there, so their registers live until then
         self._emit(REL_ENTRY, None, (mult.id,) + tuple(v.id for v in values), imm=(int(relation),))
 
+    def _m(self, x, what):
+        x = self._value(x)
+        if x.kind != "m":
+            raise ValueError(what + " takes a base-field value (kind 'm')")
+        return x
+
+    def arg(self, k):
+        """BFHIP_WIT_ARG: the k-th per-call argument of a witness program (see witness_program())."""
+        return self._emit(WIT_ARG, "m", imm=(int(k),), key=("arg", int(k)))
+
+    def row(self):
+        """BFHIP_WIT_ROW: the row's coset index — the r of Context.columns_from_rows. Witness programs only."""
+        return self._emit(WIT_ROW, "m", key=("row",))
+
+    def inv0(self, x):
+        """BFHIP_WIT_INV0: 1 / x, and 0 for 0. Witness programs only."""
+        return self._emit(WIT_INV0, "m", (self._m(x, "inv0").id,))
+
+    def is_zero(self, x):
+        """BFHIP_WIT_IS_ZERO: 1 if x == 0, else 0. Witness programs only."""
+        return self._emit(WIT_IS_ZERO, "m", (self._m(x, "is_zero").id,))
+
+    def lt(self, x, y):
+        """BFHIP_WIT_LT: 1 if x < y as integers in [0, p), else 0. Witness programs only."""
+        return self._emit(WIT_LT, "m", (self._m(x, "lt").id, self._m(y, "lt").id))
+
+    def bit_and(self, x, imm):
+        """BFHIP_WIT_AND: x & imm, imm < 2^31. Witness programs only."""
+        return self._emit(WIT_AND, "m", (self._m(x, "bit_and").id,), imm=(int(imm),))
+
+    def shr(self, x, imm):
+        """BFHIP_WIT_SHR: x >> imm, imm in 0..30. Witness programs only."""
+        return self._emit(WIT_SHR, "m", (self._m(x, "shr").id,), imm=(int(imm),))
+
+    def store(self, out, x):
+        """BFHIP_WIT_STORE: output column `out` of the row receives x. Witness programs only."""
+        self._emit(WIT_STORE, None, (self._m(x, "store").id,), imm=(int(out),))
+
     def code(self):
         """The bytecode (a flat list of u32 words). Raises ValueError if the program needs more registers than the caps."""
         import heapq
@@ -441,8 +516,8 @@ class AirBuilder:
                     heapq.heappush(free[kind], dst)
             if op in (AIR_M_COL, AIR_Q_COL):
                 words += [op, dst, imm[0], imm[1] & 0xFFFFFFFF]
-            elif op in (AIR_M_CONST, AIR_Q_PARAM):
-                words += [op, dst, imm[0], 0]
+            elif op in (AIR_M_CONST, AIR_Q_PARAM, WIT_ARG):
+                words += [op, dst, imm[0] & 0xFFFFFFFF, 0]
             elif op in (AIR_C_BASE, AIR_C_EXT):
                 words += [op, 0, regs[0], 0]
             elif op == LOGUP_END_COL:
@@ -451,6 +526,12 @@ class AirBuilder:
                 words += [op, 0, regs[0], 0]
             elif op == REL_ENTRY:
                 words += [op, imm[0] & 0xFFFFFFFF, regs[0], 0]
+            elif op in (WIT_AND, WIT_SHR):
+                words += [op, dst, regs[0], imm[0] & 0xFFFFFFFF]
+            elif op == WIT_STORE:
+                words += [op, imm[0] & 0xFFFFFFFF, regs[0], 0]
+            elif op == WIT_ROW:
+                words += [op, dst, 0, 0]
             else:
                 words += [op, dst, regs[0], regs[1] if len(regs) > 1 else 0]
         return words
@@ -473,3 +554,9 @@ class AirBuilder:
         """RelationProgram of the bytecode (relation_entry() instead of constraint()); relation_words[r] = the width of relation r; n_cols
         defaults as for program()."""
         return RelationProgram(self.code(), self._counts(n_cols)[0], relation_words)
+
+    def witness_program(self, n_out, n_cols=None, n_args=None):
+        """WitnessProgram of the bytecode (store() instead of constraint()); n_cols defaults as for program(), n_args to one more than the
+        highest argument any arg() named."""
+        args = [imm[0] + 1 for op, _, _, imm in self._ops if op == WIT_ARG]
+        return WitnessProgram(self.code(), self._counts(n_cols)[0], n_out, max(args, default=0) if n_args is None else n_args)

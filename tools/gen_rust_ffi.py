@@ -30,7 +30,8 @@ DOCS = {
                               "first_cell_per_constraint[j] = u64::MAX and first_bad_constraint = -1 where nothing fails. (No Default: arrays of 64.)",
     "bfhip_logup": "A validated fraction program (include/bfhip.h \"Fraction programs\"): a constraint program's opcodes without C_BASE / C_EXT, plus BFHIP_LOGUP_FRAC and BFHIP_LOGUP_END_COL.",
     "bfhip_relation_program": "A validated relation program (include/bfhip.h \"Relation programs\"): the base-field opcodes of a constraint program, plus BFHIP_REL_WORD and BFHIP_REL_ENTRY.",
-    "bfhip_rows_table": "`bfhip_rows_table`: a table in row order for bfhip_columns_from_rows (include/bfhip.h \"Row order\"), 48 bytes. layout 0: rows_d and row_stride; layout 1: cols_h.",
+    "bfhip_witness_program": "A validated witness program (include/bfhip.h \"Witness programs\"): the base-field opcodes of a constraint program at trace offsets, plus BFHIP_WIT_*.",
+    "bfhip_rows_table":"`bfhip_rows_table`: a table in row order for bfhip_columns_from_rows (include/bfhip.h \"Row order\"), 48 bytes. layout 0: rows_d and row_stride; layout 1: cols_h.",
     "bfhip_relation_program_table": "`bfhip_relation_program_table`: one table of bfhip_relation_program_summary, 32 bytes. cols_h = host array of device pointers; col_shifts_h may be null.",
     "bfhip_multiplicity_report": "`bfhip_multiplicity_report`: the counts of bfhip_relation_program_multiplicities (include/bfhip.h \"Lookup multiplicities\"), 80 bytes.",
 }
