@@ -698,6 +698,34 @@ pub fn columns_from_rows(ctx: &Context, table: &RowsTable, log_size: u32, src_co
                                                 if pad.is_empty() { std::ptr::null() } else { pad.as_ptr() }, out.as_ptr(), out.len() as u32) })
 }
 
+fn raw_rows_table(table: &RowsTable, flags: u32) -> sys::BfhipRowsTable {
+    match *table {
+        RowsTable::RowMajor { rows, n_rows, n_cols, row_stride } =>
+            sys::BfhipRowsTable { layout: sys::BFHIP_ROWS_ROW_MAJOR, n_cols, rows_d: rows, cols_h: std::ptr::null(), n_rows, row_stride, flags, reserved: 0 },
+        RowsTable::ColumnMajor { cols, n_rows } =>
+            sys::BfhipRowsTable { layout: sys::BFHIP_ROWS_COLUMN_MAJOR, n_cols: cols.len() as u32, rows_d: std::ptr::null(), cols_h: cols.as_ptr(), n_rows, row_stride: 0, flags, reserved: 0 },
+    }
+}
+
+/// `bfhip_rows_select` (`include/bfhip.h` "Row selection"): `columns_from_rows` of a selection of the table's rows. A candidate row
+/// `rows.0 .. rows.1` is selected iff every term holds (`word(row, col) <op> value` as integers, `op` = `sys::BFHIP_SELECT_EQ` ..
+/// `BFHIP_SELECT_GE`); the selected rows are sorted by `keys`, most significant first, stably; output row `i` of output column `k` is the
+/// source word `(order[i] + outs[k].offset, outs[k].col)`, rows past the selected ones hold `outs[k].pad`, or with `repeat_last` the last
+/// selected row. `out` empty with `log_size` 0 is the count-only form. `order`: null, or `rows.1 - rows.0` device words for the source row
+/// of every selected row. Returns the number of selected rows. Takes nothing from the arena; works while a session is open.
+/// Source only, like the rest of this file: it has never been compiled.
+pub fn rows_select(ctx: &Context, table: &RowsTable, terms: &[sys::BfhipSelectTerm], keys: &[sys::BfhipSelectKey], rows: (u64, u64), log_size: u32,
+                   outs: &[sys::BfhipSelectOut], repeat_last: bool, out: &[*mut u32], order: *mut u32) -> Result<u64, String> {
+    if outs.len() != out.len() { return Err("one output pointer per output column".into()); }
+    let raw = raw_rows_table(table, if repeat_last { sys::BFHIP_ROWS_REPEAT_LAST } else { 0 });
+    let sel = sys::BfhipRowsSelectDesc { terms: if terms.is_empty() { std::ptr::null() } else { terms.as_ptr() }, keys: if keys.is_empty() { std::ptr::null() } else { keys.as_ptr() },
+                                         n_terms: terms.len() as u32, n_keys: keys.len() as u32, row_begin: rows.0, row_end: rows.1, reserved: [0; 2] };
+    let mut n_selected = 0u64;
+    check(unsafe { sys::bfhip_rows_select(ctx.0, &raw, &sel, log_size, if outs.is_empty() { std::ptr::null() } else { outs.as_ptr() },
+                                          if out.is_empty() { std::ptr::null() } else { out.as_ptr() }, out.len() as u32, order, &mut n_selected) })?;
+    Ok(n_selected)
+}
+
 /// `bfhip_rows_from_columns`: the inverse — storage-order columns to words `(r, c)`, `r < n_rows`, `c < cols.len()`, of a row-major device
 /// table; the rest of each row is left untouched. Enqueued on the context's stream; no canonicity check.
 pub fn rows_from_columns(ctx: &Context, cols: &[*const u32], log_size: u32, rows: *mut u32, n_rows: u64, row_stride: u64) -> Result<(), String> {

@@ -1220,6 +1220,76 @@ int32_t bfhip_rows_from_columns(bfhip_ctx* ctx, const uint32_t* const* cols_h, u
 int32_t bfhip_cell_of_row(uint32_t log_size, uint64_t row, uint64_t* cell);
 int32_t bfhip_row_of_cell(uint32_t log_size, uint64_t cell, uint64_t* row);
 
+/* ---- Row selection: filter and sort a row-order table on the device, straight into storage-order columns ---------------------------------------
+ * Most tables of a VM-shaped AIR are not the register trace itself but a selection of it: an instruction sub-table is "the rows where
+ * ci == opcode, beside their successor", a memory-consistency table is "the rows sorted by (address, clk)". bfhip_rows_select is
+ * bfhip_columns_from_rows with a row filter, a stable sort and per-output row offsets in front: the selected, reordered rows are written where
+ * bfhip_columns_from_rows would put the same rows, without a trip through the host.
+ * Source: a bfhip_rows_table, unchanged, both layouts. Candidates: source rows sel->row_begin .. sel->row_end - 1.
+ * Selected rows (normative):
+ *   A candidate row r is selected iff every term holds: word(r, term.col) <op> term.value as unsigned integers, op one of BFHIP_SELECT_EQ, NE,
+ *     LT, LE, GT, GE. The terms are a conjunction; n_terms = 0 selects every candidate.
+ *   The selected rows are ordered by the keys, keys[0] most significant: ascending in word(r, key.col), or descending with
+ *     BFHIP_SELECT_DESCENDING in key.flags. The sort is stable — equal keys keep source-row order —; n_keys = 0 is source-row order.
+ *   *n_selected = their number S; order[i] = the source row of output row i, i < S.
+ * Outputs: output row i < S of output column k is the source word (order[i] + outs_h[k].offset, outs_h[k].col): a sub-table's "next" values
+ *   are offset +1 of the same selection, without a pass of their own. Rows S .. 2^log_size - 1 hold outs_h[k].pad, or with
+ *   BFHIP_ROWS_REPEAT_LAST in table->flags a copy of output row S - 1 (pads are then ignored). out_cols_h: n_out device pointers, each to
+ *   2^log_size words, written whole in storage order (the order of "Row order" above). 1 <= n_out <= 256, 1 <= log_size <= 30.
+ * order_d: NULL, or row_end - row_begin device words of which the first S receive order[] (32-bit: row_end <= 2^32 when given) — which
+ *   register row a table row is.
+ * Count-only form: out_cols_h == NULL with n_out == 0 and log_size == 0 returns *n_selected and writes no column (order_d still, if given):
+ *   how a caller sizes the domain. Otherwise S > 2^log_size is -1 with "bfhip_rows_select: <S> rows selected, the domain has <2^log_size>",
+ *   and REPEAT_LAST with S = 0 is -1 with "bfhip_rows_select: BFHIP_ROWS_REPEAT_LAST needs at least one selected row"; both are found after
+ *   the count (*n_selected is set) and before any column is written.
+ * Canonicity: checked are the term words of EVERY candidate row, and the key words and the output words (offsets applied) of every selected
+ *   row; the key words only where the sort runs (not in the count-only form without order_d). A word >= 2^31 - 1 makes the call return -1 with
+ *   "bfhip_rows_select: row <r>, column <c>: <v> is not a canonical M31 value" — the lowest SOURCE row, then the lowest SOURCE column (a 64-bit
+ *   integer atomicMin over row * 2^24 + column). The outputs are then unspecified; nothing faults and the context stays usable. The two
+ *   refusals by the count come first.
+ * Launches: flags, a scan and a compaction; per pair of keys one key gather and one stable radix sort (rocPRIM), least significant pair
+ *   first; the gather (csrc/rows_select.hip, DESIGN.md section 9t: tiles of 1024 output rows through LDS as csrc/rows.hip, the tile's
+ *   permutation kept in LDS; log_size below 10: one thread per cell). Two read-backs: S, which the sort and the gather need on the host, and
+ *   the bad-word record at the end (the call returns when the columns are written); a refused word costs a third, 4-byte one.
+ * Memory: nothing from the arena (bfhip_ctx_memory out[3] is unchanged): works while a commitment-scheme session is open. Descriptors come
+ *   from the staging ring; flags, positions, two permutations, two key arrays and rocPRIM's temporary are call-scoped scratch, served from the
+ *   scratch reserve where one is set (bfhip_ctx_set_scratch_reserve: no device allocation on the second call of a shape).
+ * Refused, -1 with "bfhip_rows_select: <rule>", nothing enqueued, the context usable — the rule names the term, key or output index where
+ *   there is one: everything bfhip_columns_from_rows refuses about the table (null pointers, unknown layout or flag bit, reserved != 0,
+ *   row_stride < n_cols, no columns), the outputs (log_size, n_out, a null output column, pad >= p unless REPEAT_LAST) and overlaps (an output
+ *   column or order_d sharing a byte with the source or with an earlier output; the message names the two); out_cols_h NULL with n_out or
+ *   log_size not 0; n_terms above BFHIP_SELECT_MAX_TERMS or n_keys above BFHIP_SELECT_MAX_KEYS, either non-zero with a null array; an unknown
+ *   op or key flag bit; a term value >= p; a term, key or output column index not below n_cols; row_begin > row_end; row_end > n_rows; more
+ *   than 2^30 candidates; an output offset with row_begin + offset < 0 or row_end + offset > n_rows, so that no read can leave the table;
+ *   sel->reserved != 0; n_rows above 2^40 or n_cols above 2^24 (the bad-word record's fields); a context in a shard group.
+ * bfhip_rows_select_host (host only, no GPU): the same definition over a host row-major table, the result in ROW order — out_rows_h = 2^log_size
+ *   x n_out words, order_h = row_end - row_begin words or NULL; out_rows_h NULL with n_out 0 and log_size 0 is the count-only form.
+ *   repeat_last is 0 or 1. The kernels are held to it word for word. The same refusals and failures under "bfhip_rows_select_host: ".
+ * Not built: several source tables concatenated (the Instruction table's program rows beside the trace's), row insertion (the Memory
+ *   table's clk-gap dummy rows), disjunctions and column-to-column terms, pool jobs, shard groups, row-granular (shifted) outputs.
+ * Layout (natural alignment, declaration order):
+ *   bfhip_select_term  12 bytes: col 0, op 4, value 8
+ *   bfhip_select_key    8 bytes: col 0, flags 4
+ *   bfhip_select_out   12 bytes: col 0, offset 4, pad 8
+ *   bfhip_rows_select_desc  48 bytes: terms 0, keys 8, n_terms 16, n_keys 20, row_begin 24, row_end 32, reserved 40 */
+enum { BFHIP_SELECT_EQ = 0, BFHIP_SELECT_NE = 1, BFHIP_SELECT_LT = 2, BFHIP_SELECT_LE = 3, BFHIP_SELECT_GT = 4, BFHIP_SELECT_GE = 5,
+       BFHIP_SELECT_DESCENDING = 1, BFHIP_SELECT_MAX_TERMS = 8, BFHIP_SELECT_MAX_KEYS = 4 };
+typedef struct bfhip_select_term { uint32_t col, op, value; } bfhip_select_term;      /* word(row, col) <op> value, as integers */
+typedef struct bfhip_select_key { uint32_t col, flags; } bfhip_select_key;            /* flags: BFHIP_SELECT_DESCENDING */
+typedef struct bfhip_select_out { uint32_t col; int32_t offset; uint32_t pad; } bfhip_select_out;
+typedef struct bfhip_rows_select_desc {
+    const bfhip_select_term* terms;   /* host array of n_terms */
+    const bfhip_select_key* keys;     /* host array of n_keys, most significant first */
+    uint32_t n_terms, n_keys;
+    uint64_t row_begin, row_end;      /* candidates: source rows row_begin .. row_end - 1 */
+    uint32_t reserved[2];             /* must be 0 */
+} bfhip_rows_select_desc;
+int32_t bfhip_rows_select(bfhip_ctx* ctx, const bfhip_rows_table* table, const bfhip_rows_select_desc* sel, uint32_t log_size,
+                          const bfhip_select_out* outs_h, uint32_t* const* out_cols_h, uint32_t n_out, uint32_t* order_d, uint64_t* n_selected);
+int32_t bfhip_rows_select_host(const uint32_t* table_h, uint64_t n_rows, uint32_t n_cols, uint64_t row_stride, uint32_t repeat_last,
+                               const bfhip_rows_select_desc* sel, uint32_t log_size, const bfhip_select_out* outs_h, uint32_t n_out,
+                               uint32_t* out_rows_h, uint32_t* order_h, uint64_t* n_selected);
+
 /* ---- Relation programs: the lookup tuples of ANY AIR that do not cancel ------------------------------------------------------------------------
  * bfhip_relation_summary / bfhip_trace_relations know the three Brainfuck relations and the 13 table layouts. An AIR proved through bfhip_pcs_* +
  * bfhip_air_* + bfhip_logup_* whose lookups do not balance learns only that its claimed sums do not add up to zero; a
@@ -1379,7 +1449,8 @@ int32_t bfhip_relation_program_multiplicities(bfhip_ctx* ctx, const bfhip_relati
  *     "output column <k> overlaps input column <j>" / "output column <k> overlaps output column <j>".
  * Kernel (csrc/witness_program.hip): the instruction core of the four program kernels on the row of bfhip_air_check;
  *   one lane per cell, one wave per workgroup, the register file in LDS.
- * Not built: tables that need a sort or a row filter (the Memory, Instruction and per-instruction Brainfuck tables), extension-field values,
+ * Not built: tables that need row insertion or several concatenated sources (the Memory table's clk-gap dummy rows, the Instruction table's
+ *   program rows beside the trace's; a sort or a row filter alone is bfhip_rows_select, "Row selection" above), extension-field values,
  *   shifted (row-granular) columns, reading an output of the same call at an offset (run a second program), witness programs compiled with
  *   hiprtc, pool jobs, shard groups. */
 enum { BFHIP_WIT_ARG = 19, BFHIP_WIT_ROW = 20, BFHIP_WIT_INV0 = 21, BFHIP_WIT_IS_ZERO = 22, BFHIP_WIT_LT = 23, BFHIP_WIT_AND = 24, BFHIP_WIT_SHR = 25,

@@ -244,7 +244,9 @@ def brainfuck_witness_program(table):
     offset +1, except on the last row, which takes its own clk + 1 (the extra dummy's) instead of wrapping to row 0. The last row is the
     one whose neighbour at +1 has clk 0: the VM starts at clk 0 and counts up. Returns (WitnessProgram, output column names)."""
     if table != "processor":
-        raise ValueError("witness programs are written for: 'processor' (Memory, Instruction and the sub-tables need a sort or a row filter)")
+        raise ValueError("witness programs are written for: 'processor' (the sub-tables' real rows and the Memory table's sorted entries come from "
+                         "brainfuck_rows_select; what remains is row insertion and concatenated sources: the Memory table's clk-gap dummies and the "
+                         "Instruction table's program rows)")
     b = AirBuilder()
     row, n = b.row(), b.arg(0)
     real = b.lt(row, n)
@@ -263,3 +265,26 @@ def brainfuck_witness_program(table):
     last = b.is_zero(b.col(0, 1))
     b.store(8, following + last * (clk + 1 - following))
     return b.witness_program(9, n_cols=6, n_args=1), ("clk", "ip", "ci", "ni", "mp", "mv", "mvi", "d", "next_clk")
+
+
+# the opcode of each per-instruction component (claim order of include/bfhip.h's component indices 4..11)
+_BF_SUB_TABLE_OPCODES = {"jump_if_not_zero": "]", "jump_if_zero": "[", "input_instruction": ",", "left_instruction": "<", "minus_instruction": "-",
+                         "output_instruction": ".", "plus_instruction": "+", "right_instruction": ">"}
+
+
+def brainfuck_rows_select(table, n_rows):
+    """The selections that derive Brainfuck tables from the VM's 7 register columns clk, ip, ci, ni, mp, mv, mvi (n_rows rows) — the worked
+    example of include/bfhip.h "Row selection". Returns (keyword arguments of Context.rows_select / rows_select_host, output column names).
+    A per-instruction component ("plus_instruction", "jump_if_zero", ...): the REAL rows of its sub-table (host/tables.h sub_intermediate;
+    instructions/table.rs, jump/table.rs) — the steps with ci == opcode that have a successor (rows 0 .. n_rows - 2), clk .. mvi of the step
+    beside ip, mp, mv of the step at offset +1, in trace order. "memory": the (mp, clk)-sorted entries the Memory table starts from
+    (memory/table.rs: clk, mp, mv of every step). What the tables hold beyond these rows is not a selection: the sub-tables' dummy rows, d and
+    the jumps' next_clk and is_mv_zero columns are row-by-row work (a witness program over these columns), the Memory table's clk-gap dummies
+    are inserted rows."""
+    if table == "memory":
+        return dict(order_by=(4, 0), columns=(0, 4, 5)), ("clk", "mp", "mv")
+    if table not in _BF_SUB_TABLE_OPCODES:
+        raise ValueError("selections are written for 'memory' and the per-instruction components: " + ", ".join(sorted(_BF_SUB_TABLE_OPCODES)))
+    names = ("clk", "ip", "ci", "ni", "mp", "mv", "mvi", "next_ip", "next_mp", "next_mv")
+    return dict(where=((2, "==", ord(_BF_SUB_TABLE_OPCODES[table])),), rows=(0, max(0, int(n_rows) - 1)),
+                columns=(0, 1, 2, 3, 4, 5, 6, (1, 1), (4, 1), (5, 1))), names

@@ -6,7 +6,9 @@ import ctypes
 import numpy as np
 
 from ._abi import _check, _ptr_array, _u32s, abi, struct_fields
-from ._abi_gen import (BFHIP_ROWS_COLUMN_MAJOR as ROWS_COLUMN_MAJOR, BFHIP_ROWS_REPEAT_LAST as ROWS_REPEAT_LAST, BFHIP_ROWS_ROW_MAJOR as ROWS_ROW_MAJOR)
+from ._abi_gen import (BFHIP_ROWS_COLUMN_MAJOR as ROWS_COLUMN_MAJOR, BFHIP_ROWS_REPEAT_LAST as ROWS_REPEAT_LAST, BFHIP_ROWS_ROW_MAJOR as ROWS_ROW_MAJOR,
+                       BFHIP_SELECT_DESCENDING as SELECT_DESCENDING, BFHIP_SELECT_EQ, BFHIP_SELECT_GE, BFHIP_SELECT_GT, BFHIP_SELECT_LE, BFHIP_SELECT_LT,
+                       BFHIP_SELECT_MAX_KEYS as SELECT_MAX_KEYS, BFHIP_SELECT_MAX_TERMS as SELECT_MAX_TERMS, BFHIP_SELECT_NE)
 
 
 class RowsTable(ctypes.Structure):
@@ -154,3 +156,174 @@ def rows_from_columns(ctx, col_ptrs, log_size, n_rows=None):
         return ctx.download(dst, n_rows * n_cols).reshape(n_rows, n_cols)
     finally:
         ctx.free(dst)
+
+
+# ---- bfhip_rows_select (include/bfhip.h "Row selection") -------------------------------------------------------------------------------
+SELECT_OPS = {"==": BFHIP_SELECT_EQ, "!=": BFHIP_SELECT_NE, "<": BFHIP_SELECT_LT, "<=": BFHIP_SELECT_LE, ">": BFHIP_SELECT_GT, ">=": BFHIP_SELECT_GE}
+
+
+class SelectTerm(ctypes.Structure):
+    """include/bfhip.h `bfhip_select_term`."""
+    _fields_ = struct_fields("bfhip_select_term")
+
+
+class SelectKey(ctypes.Structure):
+    """include/bfhip.h `bfhip_select_key`."""
+    _fields_ = struct_fields("bfhip_select_key")
+
+
+class SelectOut(ctypes.Structure):
+    """include/bfhip.h `bfhip_select_out`."""
+    _fields_ = struct_fields("bfhip_select_out")
+
+
+class RowsSelectDesc(ctypes.Structure):
+    """include/bfhip.h `bfhip_rows_select_desc`."""
+    _fields_ = struct_fields("bfhip_rows_select_desc")
+
+
+# What rows_select_host returns: rows = (2^log_size, n_out) uint32 in ROW order (None in the count-only form), order = the source rows of the
+# selected rows (None unless asked for)
+SelectedRows = collections.namedtuple("SelectedRows", "rows n_selected order")
+
+
+def _select_desc(where, order_by, rows, n_rows):
+    """The bfhip_rows_select_desc of (where, order_by, rows) and the arrays it points into."""
+    for _, op, _ in where:
+        if isinstance(op, str) and op not in SELECT_OPS:
+            raise ValueError('a where entry is (column, "==" | "!=" | "<" | "<=" | ">" | ">=", value)')
+    terms = (SelectTerm * max(1, len(where)))(*[SelectTerm(int(c), SELECT_OPS[op] if isinstance(op, str) else int(op), int(v)) for c, op, v in where])
+    keys = (SelectKey * max(1, len(order_by)))()
+    for i, k in enumerate(order_by):
+        col, how = (k, "asc") if isinstance(k, (int, np.integer)) else k
+        if how not in ("asc", "desc"):
+            raise ValueError('an order_by entry is a column or (column, "asc" | "desc")')
+        keys[i] = SelectKey(int(col), SELECT_DESCENDING if how == "desc" else 0)
+    begin, end = (0, n_rows) if rows is None else rows
+    desc = RowsSelectDesc(ctypes.cast(terms, ctypes.c_void_p) if len(where) else None, ctypes.cast(keys, ctypes.c_void_p) if len(order_by) else None,
+                          len(where), len(order_by), int(begin), int(end), (ctypes.c_uint32 * 2)(0, 0))
+    return desc, (terms, keys)
+
+
+def _select_outs(columns, pad, n_cols):
+    columns = list(range(n_cols)) if columns is None else list(columns)
+    if pad is not None and len(pad) != len(columns):
+        raise ValueError("one pad value per output column")
+    outs = (SelectOut * max(1, len(columns)))()
+    for k, c in enumerate(columns):
+        col, off = (c, 0) if isinstance(c, (int, np.integer)) else c
+        outs[k] = SelectOut(int(col), int(off), 0 if pad is None else int(pad[k]))
+    return outs, len(columns)
+
+
+def _domain_for(n_selected):
+    """The smallest log_size whose domain holds n_selected rows, at least 1."""
+    return max(1, int(n_selected - 1).bit_length()) if n_selected > 1 else 1
+
+
+def _as_device_table(ctx, table):
+    """(table as DeviceRows / DeviceRowColumns, the temporary upload to free or None)."""
+    if isinstance(table, np.ndarray):
+        if table.ndim != 2 or table.dtype != np.uint32:
+            raise TypeError("a host table is a (n_rows, n_cols) uint32 array")
+        host = np.ascontiguousarray(table)
+        tmp = ctx.upload(host) if host.size else None
+        return DeviceRows(tmp, host.shape[0], host.shape[1], host.shape[1]), tmp
+    return table, None
+
+
+def rows_select_count(ctx, table, where=(), order_by=(), rows=None, want_order=False):
+    """Context.rows_select_count (see there)."""
+    table, tmp = _as_device_table(ctx, table)
+    order_d = None
+    try:
+        tdesc, keep = _rows_table(table, False)
+        sel, keep2 = _select_desc(list(where), list(order_by), rows, tdesc.n_rows)
+        n_cand = max(0, sel.row_end - sel.row_begin)
+        if want_order:
+            order_d = ctx.malloc(4 * max(1, n_cand))
+        n_sel = ctypes.c_uint64()
+        _check(abi().bfhip_rows_select(ctx._h, ctypes.byref(tdesc), ctypes.byref(sel), 0, None, None, 0, order_d, ctypes.byref(n_sel)))
+        del keep, keep2
+        order = None
+        if want_order:
+            order = ctx.download(order_d, n_sel.value) if n_sel.value else np.zeros(0, dtype=np.uint32)
+        return n_sel.value, order
+    finally:
+        if order_d is not None:
+            ctx.free(order_d)
+        if tmp is not None:
+            ctx.free(tmp)
+
+
+def rows_select(ctx, table, log_size=None, where=(), order_by=(), columns=None, rows=None, pad=None, repeat_last=False, out=None, want_order=False):
+    """Context.rows_select (see there)."""
+    table, tmp = _as_device_table(ctx, table)
+    order_d, owned = None, []
+    try:
+        tdesc, keep = _rows_table(table, repeat_last)
+        where, order_by = list(where), list(order_by)
+        sel, keep2 = _select_desc(where, order_by, rows, tdesc.n_rows)
+        outs, n_out = _select_outs(columns, pad, tdesc.n_cols)
+        if out is not None and len(out) != n_out:
+            raise ValueError("one output pointer per output column")
+        if log_size is None:
+            log_size = _domain_for(rows_select_count(ctx, table, where, (), rows)[0])
+        n_cand = max(0, sel.row_end - sel.row_begin)
+        if want_order:
+            order_d = ctx.malloc(4 * max(1, n_cand))
+        ptrs = list(out) if out is not None else None
+        if ptrs is None:
+            for _ in range(n_out):
+                owned.append(ctx.malloc(4 << log_size))
+            ptrs = owned
+        n_sel = ctypes.c_uint64()
+        _check(abi().bfhip_rows_select(ctx._h, ctypes.byref(tdesc), ctypes.byref(sel), int(log_size), outs, _ptr_array(ptrs) if ptrs else None, n_out, order_d,
+                                       ctypes.byref(n_sel)))
+        del keep, keep2
+        order = None
+        if want_order:
+            order = ctx.download(order_d, n_sel.value) if n_sel.value else np.zeros(0, dtype=np.uint32)
+        cols = Columns(ctx, ptrs, log_size, owned)      # from here on the handle owns the columns
+        owned = []
+        cols.n_selected, cols.order = n_sel.value, order
+        return cols
+    finally:
+        for p in owned:
+            ctx.free(p)
+        if order_d is not None:
+            ctx.free(order_d)
+        if tmp is not None:
+            ctx.free(tmp)
+
+
+def rows_select_host(table, log_size=None, where=(), order_by=(), columns=None, rows=None, pad=None, repeat_last=False, want_order=False, n_cols=None,
+                     count_only=False):
+    """bfhip_rows_select_host: the definition of a selection, on the host and without a GPU. table: a (n_rows, row_stride) uint32 array of
+    which the first n_cols words of a row are the table (None = all). The other arguments are rows_select's. Returns SelectedRows(rows,
+    n_selected, order): rows in ROW order, (2^log_size, n_out). count_only: the count (and the order, if wanted) without rows; log_size
+    None takes the smallest domain that holds the count, at least 1."""
+    table = np.ascontiguousarray(table, dtype=np.uint32)
+    if table.ndim != 2:
+        raise TypeError("a host table is a (n_rows, row_stride) uint32 array")
+    n_rows, stride = table.shape
+    n_cols = stride if n_cols is None else int(n_cols)
+    where, order_by = list(where), list(order_by)
+    sel, keep = _select_desc(where, order_by, rows, n_rows)
+    n_sel = ctypes.c_uint64()
+    order = np.zeros(max(1, sel.row_end - sel.row_begin), dtype=np.uint32) if want_order else None
+    data = table.ctypes.data if table.size else None
+
+    def call(log, outs, n_out, rows_out):
+        _check(abi().bfhip_rows_select_host(data, n_rows, n_cols, stride, int(bool(repeat_last)), ctypes.byref(sel), log, outs, n_out,
+                                            None if rows_out is None else rows_out.ctypes.data, None if order is None else order.ctypes.data, ctypes.byref(n_sel)))
+    if count_only or log_size is None:
+        call(0, None, 0, None)
+        if count_only:
+            return SelectedRows(None, n_sel.value, None if order is None else order[:n_sel.value].copy())
+        log_size = _domain_for(n_sel.value)
+    outs, n_out = _select_outs(columns, pad, n_cols)
+    rows_out = np.zeros((1 << log_size, n_out), dtype=np.uint32)
+    call(int(log_size), outs, n_out, rows_out)
+    del keep
+    return SelectedRows(rows_out, n_sel.value, None if order is None else order[:n_sel.value].copy())

@@ -335,6 +335,21 @@ class Context(Owned):
         manager) whose pointers go wherever column pointers are taken."""
         return _columns.columns_from_rows(self, table, log_size, columns, pad, repeat_last, out)
 
+    def rows_select(self, table, log_size=None, where=(), order_by=(), columns=None, rows=None, pad=None, repeat_last=False, out=None, want_order=False):
+        """bfhip_rows_select: columns_from_rows of a SELECTION of the table's rows — filtered, sorted, read at row offsets — without a trip
+        through the host. table: as columns_from_rows. where: (col, "==" | "!=" | "<" | "<=" | ">" | ">=", value) terms, all of which a
+        selected row satisfies (integer comparison). order_by: col or (col, "desc") keys, most significant first; the sort is stable and
+        without keys the order is the source's. columns: col or (col, offset) per output column (None = every source column): output row i
+        is the source row of selected row i plus the offset. rows: (begin, end) = the candidate rows, None = all; the offsets must stay
+        inside the table from every candidate. Rows past the selected ones hold pad[k] (None = 0), or with repeat_last the last selected
+        row. log_size None: a count-only call first, then the smallest domain that holds the selection (at least 1). Returns a Columns
+        handle that also carries .n_selected and, with want_order, .order — the source row of every selected row (else None)."""
+        return _columns.rows_select(self, table, log_size, where, order_by, columns, rows, pad, repeat_last, out, want_order)
+
+    def rows_select_count(self, table, where=(), order_by=(), rows=None, want_order=False):
+        """The count-only form of bfhip_rows_select: (the number of selected rows, their source rows in order if want_order else None)."""
+        return _columns.rows_select_count(self, table, where, order_by, rows, want_order)
+
     def rows_from_columns(self, col_ptrs, log_size, n_rows=None):
         """bfhip_rows_from_columns: storage-order device columns (pointers, or a Columns handle) back in row order, as a (n_rows,
         n_cols) uint32 array; n_rows None = all 2^log_size. What reads a generated column — multiplicities, a logUp column — by row."""

@@ -7,6 +7,7 @@
 #include "host/hash.h"
 #include "rows.h"
 #include "rows_index.h"
+#include "rows_select.h"
 #include <string>
 #include <algorithm>
 #include <vector>
@@ -423,6 +424,121 @@ int32_t bfhip_rows_from_columns(bfhip_ctx* ctx, const uint32_t* const* cols_h, u
     a.n_rows = n_rows; a.row_stride = row_stride; a.log_size = log_size; a.n_cols = n_cols;
     rows_launch(c.stream, a, true, false);
     BF_HIP(hipGetLastError());
+    return 0;
+    API_CATCH
+}
+
+// ---- filter and sort a row-order table (include/bfhip.h "Row selection"; rows_select.hip, the rules in rows_select.h) ----
+int32_t bfhip_rows_select(bfhip_ctx* ctx, const bfhip_rows_table* table, const bfhip_rows_select_desc* sel, uint32_t log_size, const bfhip_select_out* outs_h,
+                          uint32_t* const* out_cols_h, uint32_t n_out, uint32_t* order_d, uint64_t* n_selected) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    hipStream_t s = c.stream;
+    const std::string who = "bfhip_rows_select: ";
+    if (!table || !sel || !n_selected) throw HipError(who + "null argument");
+    if (table->reserved != 0) throw HipError(who + "reserved must be 0");
+    if (table->layout != BFHIP_ROWS_ROW_MAJOR && table->layout != BFHIP_ROWS_COLUMN_MAJOR) throw HipError(who + "unknown layout " + std::to_string(table->layout));
+    if (table->flags & ~uint32_t(BFHIP_ROWS_REPEAT_LAST)) throw HipError(who + "unknown flag bits " + std::to_string(table->flags));
+    const bool col_major = table->layout == BFHIP_ROWS_COLUMN_MAJOR, repeat = (table->flags & BFHIP_ROWS_REPEAT_LAST) != 0;
+    const u64 n_rows = table->n_rows, stride = col_major ? 1 : table->row_stride;
+    if (!col_major && table->row_stride < table->n_cols) throw HipError(who + "row_stride " + std::to_string(table->row_stride) + " is below n_cols " + std::to_string(table->n_cols));
+    const SelectPlan plan = select_validate(who, SelectShape{n_rows, table->n_cols, repeat}, sel, log_size, outs_h, n_out, out_cols_h != nullptr, order_d != nullptr);
+    if (col_major ? !table->cols_h : (n_rows && !table->rows_d)) throw HipError(who + "null table pointer");
+    rows_not_sharded(c, who);
+    const u32 n_cand = (u32)plan.n_candidates;
+    std::vector<ByteRange> used;      // the source first, then the outputs accepted so far
+    if (col_major) {
+        for (u32 j = 0; j < table->n_cols; j++) {
+            if (n_rows && !table->cols_h[j]) throw HipError(who + "source column " + std::to_string(j) + " is a null pointer");
+            used.push_back({(u64)(uintptr_t)table->cols_h[j], n_rows * sizeof(u32), "source column " + std::to_string(j)});
+        }
+    } else if (n_rows) {
+        used.push_back({(u64)(uintptr_t)table->rows_d, (rows_src_offset(n_rows - 1, stride, table->n_cols - 1) + 1) * sizeof(u32), "the source table"});
+    }
+    auto table_word = [&](u32 j) { return col_major ? (u64)(uintptr_t)table->cols_h[j] : (u64)(uintptr_t)(table->rows_d + j); };
+    auto accept = [&](const ByteRange& out) {
+        for (const ByteRange& u : used) if (out.overlaps(u)) throw HipError(who + out.name + " overlaps " + u.name);
+        used.push_back(out);
+    };
+    if (order_d) accept({(u64)(uintptr_t)order_d, u64(n_cand) * sizeof(u32), "the order"});
+    std::vector<SelectOutDev> outs(n_out);
+    for (u32 k = 0; k < n_out; k++) {
+        if (!out_cols_h[k]) throw HipError(who + "output column " + std::to_string(k) + " is a null pointer");
+        accept({(u64)(uintptr_t)out_cols_h[k], sizeof(u32) << log_size, "output column " + std::to_string(k)});
+        outs[k] = SelectOutDev{table_word(outs_h[k].col), (u64)(uintptr_t)out_cols_h[k], outs_h[k].offset, repeat ? 0u : outs_h[k].pad, outs_h[k].col, 0};
+    }
+    // ---- enqueued from here on ----
+    c.stage_checkpoint(Ctx::stage_round(sizeof(SelectOutDev) * n_out) + 256);
+    const unsigned long long none = ~0ull;
+    SelectSource src{sel->row_begin, stride, nullptr};
+    const SelectOutDev* d_outs = nullptr;
+    {
+        StageBatch sb(c);
+        if (n_out) d_outs = c.stage(outs.data(), n_out);
+        src.first_bad = c.stage(&none, 1);
+        sb.end();
+    }
+    DeviceScratch scratch(c);
+    // (1) flags, positions, the count
+    u32 S = 0;
+    u32 *flags = nullptr, *pos = nullptr, *tot = nullptr;
+    if (n_cand) {
+        scratch.alloc(&flags, sizeof(u32) * n_cand); scratch.alloc(&pos, sizeof(u32) * n_cand); scratch.alloc(&tot, sizeof(u32) * (n_cand / 2048 + 3));
+        SelectFlagsArgs fa{};
+        for (u32 i = 0; i < sel->n_terms; i++) fa.t[i] = SelectTermDev{table_word(sel->terms[i].col), sel->terms[i].op, sel->terms[i].value, sel->terms[i].col, 0};
+        fa.src = src; fa.n_terms = sel->n_terms; fa.n = n_cand; fa.flags = flags;
+        const u32* d_total;
+        {
+            ProfScope ps(s, "k_select_flags", 4.0 * double(n_cand) * double(sel->n_terms + 1));
+            select_flags_launch(s, fa);
+            d_total = exclusive_scan_u32(s, flags, pos, tot, n_cand);
+        }
+        BF_HIP(hipGetLastError());
+        c.read_back(&S, d_total, sizeof S);
+    }
+    *n_selected = S;
+    select_check_count(who, plan, repeat, S, log_size);
+    // (2) the permutation: source order, then the key passes
+    u32* perm[2] = {nullptr, nullptr};
+    int cur = 0;
+    const bool want_perm = !plan.count_only || order_d;
+    if (S && want_perm) {
+        const bool sorted = plan.n_passes != 0;
+        scratch.alloc(&perm[0], sizeof(u32) * S);
+        select_compact_launch(s, flags, pos, n_cand, perm[0]);
+        if (sorted) {
+            u64 *keys = nullptr, *keys_sorted = nullptr; void* tmp = nullptr;
+            const size_t tmp_bytes = select_sort_tmp_bytes(S);
+            scratch.alloc(&perm[1], sizeof(u32) * S);
+            scratch.alloc(&keys, sizeof(u64) * S); scratch.alloc(&keys_sorted, sizeof(u64) * S);
+            scratch.alloc(&tmp, tmp_bytes + 256);
+            ProfScope ps(s, "rows_select_sort", 0);
+            for (u32 p = 0; p < plan.n_passes; p++) {
+                const bfhip_select_key& lo = sel->keys[plan.lo[p]];
+                SelectKeyDev hi_d{0, 0, 0};
+                if (plan.hi[p] >= 0) { const bfhip_select_key& hi = sel->keys[plan.hi[p]]; hi_d = SelectKeyDev{table_word(hi.col), hi.col, hi.flags}; }
+                select_sort_pass(s, hi_d, SelectKeyDev{table_word(lo.col), lo.col, lo.flags}, src, perm[cur], perm[cur ^ 1], keys, keys_sorted, tmp, tmp_bytes, S);
+                cur ^= 1;
+            }
+        }
+        if (order_d) select_order_launch(s, perm[cur], sel->row_begin, S, order_d);
+        BF_HIP(hipGetLastError());
+    }
+    // (3) the columns
+    if (!plan.count_only) {
+        SelectGatherArgs ga{};
+        ga.outs = d_outs; ga.perm = perm[cur]; ga.src = src; ga.n_selected = S; ga.log_size = log_size; ga.n_out = n_out; ga.repeat_last = repeat;
+        select_gather_launch(s, ga, col_major);
+        BF_HIP(hipGetLastError());
+    }
+    unsigned long long bad = ~0ull;
+    c.read_back(&bad, src.first_bad, sizeof bad);
+    if (bad != ~0ull) {
+        const u64 row = bad >> SELECT_BAD_COL_BITS; const u32 j = (u32)(bad & ((1u << SELECT_BAD_COL_BITS) - 1));
+        u32 v = 0;
+        c.read_back(&v, (const u32*)(uintptr_t)table_word(j) + row * stride, sizeof v);
+        throw HipError(select_bad_word_message(who, bad, v));
+    }
     return 0;
     API_CATCH
 }

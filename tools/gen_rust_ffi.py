@@ -32,6 +32,10 @@ DOCS = {
     "bfhip_relation_program": "A validated relation program (include/bfhip.h \"Relation programs\"): the base-field opcodes of a constraint program, plus BFHIP_REL_WORD and BFHIP_REL_ENTRY.",
     "bfhip_witness_program": "A validated witness program (include/bfhip.h \"Witness programs\"): the base-field opcodes of a constraint program at trace offsets, plus BFHIP_WIT_*.",
     "bfhip_rows_table":"`bfhip_rows_table`: a table in row order for bfhip_columns_from_rows (include/bfhip.h \"Row order\"), 48 bytes. layout 0: rows_d and row_stride; layout 1: cols_h.",
+    "bfhip_select_term": "`bfhip_select_term`: word(row, col) <op> value as integers, op = BFHIP_SELECT_EQ .. BFHIP_SELECT_GE (include/bfhip.h \"Row selection\"), 12 bytes.",
+    "bfhip_select_key": "`bfhip_select_key`: one sort key of bfhip_rows_select, 8 bytes. flags: BFHIP_SELECT_DESCENDING.",
+    "bfhip_select_out": "`bfhip_select_out`: one output column of bfhip_rows_select: source column, row offset, pad value; 12 bytes.",
+    "bfhip_rows_select_desc": "`bfhip_rows_select_desc`: the filter, the keys and the candidate rows of bfhip_rows_select, 48 bytes. terms and keys are host arrays.",
     "bfhip_relation_program_table": "`bfhip_relation_program_table`: one table of bfhip_relation_program_summary, 32 bytes. cols_h = host array of device pointers; col_shifts_h may be null.",
     "bfhip_multiplicity_report": "`bfhip_multiplicity_report`: the counts of bfhip_relation_program_multiplicities (include/bfhip.h \"Lookup multiplicities\"), 80 bytes.",
 }
