@@ -726,6 +726,26 @@ pub fn rows_select(ctx: &Context, table: &RowsTable, terms: &[sys::BfhipSelectTe
     Ok(n_selected)
 }
 
+/// `bfhip_rows_fill` (`include/bfhip.h` "Row filling"): the entries of the table — source rows `order[0 .. n_entries]` (device words, as
+/// `rows_select` writes them), or with a null `order` the rows `row_begin .. row_begin + n_entries` — with the missing rows inserted. With
+/// `gaps` a row for every value of `step` (a source column) skipped between two consecutive entries that agree in every `group` column;
+/// behind the last entry inserted rows without end. Output row `i` of output column `k` is sequence element `i + outs[k].offset`; its value
+/// follows `outs[k].kind` (`sys::BFHIP_FILL_KEEP`, `SET`, `MARK`). `out` empty with `log_size` 0 is the count-only form. Returns the number
+/// of rows before the tail. Takes nothing from the arena; works while a session is open.
+/// Source only, like the rest of this file: it has never been compiled.
+pub fn rows_fill(ctx: &Context, table: &RowsTable, group: &[u32], step: Option<u32>, gaps: bool, order: *const u32, n_entries: u64, row_begin: u64, log_size: u32,
+                 outs: &[sys::BfhipFillOut], out: &[*mut u32]) -> Result<u64, String> {
+    if outs.len() != out.len() { return Err("one output pointer per output column".into()); }
+    let raw = raw_rows_table(table, 0);
+    let fill = sys::BfhipRowsFillDesc { group_cols: if group.is_empty() { std::ptr::null() } else { group.as_ptr() }, n_group: group.len() as u32,
+                                        step_col: step.unwrap_or(sys::BFHIP_FILL_NO_STEP), order_d: order, n_entries, row_begin,
+                                        flags: if gaps { sys::BFHIP_FILL_GAPS } else { 0 }, reserved: 0 };
+    let mut n_filled = 0u64;
+    check(unsafe { sys::bfhip_rows_fill(ctx.0, &raw, &fill, log_size, if outs.is_empty() { std::ptr::null() } else { outs.as_ptr() },
+                                        if out.is_empty() { std::ptr::null() } else { out.as_ptr() }, out.len() as u32, &mut n_filled) })?;
+    Ok(n_filled)
+}
+
 /// `bfhip_rows_from_columns`: the inverse — storage-order columns to words `(r, c)`, `r < n_rows`, `c < cols.len()`, of a row-major device
 /// table; the rest of each row is left untouched. Enqueued on the context's stream; no canonicity check.
 pub fn rows_from_columns(ctx: &Context, cols: &[*const u32], log_size: u32, rows: *mut u32, n_rows: u64, row_stride: u64) -> Result<(), String> {

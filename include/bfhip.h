@@ -1265,8 +1265,9 @@ int32_t bfhip_row_of_cell(uint32_t log_size, uint64_t cell, uint64_t* row);
  * bfhip_rows_select_host (host only, no GPU): the same definition over a host row-major table, the result in ROW order — out_rows_h = 2^log_size
  *   x n_out words, order_h = row_end - row_begin words or NULL; out_rows_h NULL with n_out 0 and log_size 0 is the count-only form.
  *   repeat_last is 0 or 1. The kernels are held to it word for word. The same refusals and failures under "bfhip_rows_select_host: ".
- * Not built: several source tables concatenated (the Instruction table's program rows beside the trace's), row insertion (the Memory
- *   table's clk-gap dummy rows), disjunctions and column-to-column terms, pool jobs, shard groups, row-granular (shifted) outputs.
+ * Not built: a multi-source selection (several source tables are concatenated by the caller's layout: the Instruction table's program rows
+ *   in front of the trace's, "Row filling" below), disjunctions and column-to-column terms, pool jobs, shard groups, row-granular (shifted)
+ *   outputs. Row insertion — the Memory table's clk-gap dummy rows, the dummies that pad a table — is bfhip_rows_fill, "Row filling" below.
  * Layout (natural alignment, declaration order):
  *   bfhip_select_term  12 bytes: col 0, op 4, value 8
  *   bfhip_select_key    8 bytes: col 0, flags 4
@@ -1289,6 +1290,76 @@ int32_t bfhip_rows_select(bfhip_ctx* ctx, const bfhip_rows_table* table, const b
 int32_t bfhip_rows_select_host(const uint32_t* table_h, uint64_t n_rows, uint32_t n_cols, uint64_t row_stride, uint32_t repeat_last,
                                const bfhip_rows_select_desc* sel, uint32_t log_size, const bfhip_select_out* outs_h, uint32_t n_out,
                                uint32_t* out_rows_h, uint32_t* order_h, uint64_t* n_selected);
+
+/* ---- Row filling: insert the missing rows of a table on the device, straight into storage-order columns ----------------------------------------
+ * A memory-consistency table is not a selection of the trace: it is the (address, clk)-sorted rows with a dummy row for every clk that is
+ * skipped inside one address, padded by dummies that keep counting, each row beside its successor — one pairing dummy past the end included
+ * (memory/table.rs:249-303, 121-151). bfhip_rows_fill is that step for any AIR: the entries of a bfhip_rows_table, in the order a
+ * bfhip_rows_select call wrote or in source order, with the missing rows inserted, written where bfhip_columns_from_rows would put the same rows.
+ * Entries (normative): entry i < n_entries is source row order_d[i]; with order_d == NULL it is source row row_begin + i. row_begin must be 0
+ *   when order_d is given.
+ * Gaps: filled only with BFHIP_FILL_GAPS in fill->flags, which needs a step_col. Before entry i >= 1, with prev = entry i - 1, there is a gap
+ *   iff every group word (group_cols, n_group of them) of the two is equal and step(i) > step(prev) + 1 as integers; it holds
+ *   g_i = step(i) - step(prev) - 1 inserted rows, numbered t = 1 .. g_i. Otherwise g_i = 0: equal or descending steps and a group change
+ *   insert nothing. g_0 = 0. With n_group = 0 every consecutive pair is one group.
+ * The sequence is infinite: the entries, each with its inserted rows in front — T = n_entries + sum g_i elements, counted in 64 bits —, then
+ *   the tail: inserted rows behind the last entry with t = 1, 2, ... without end.
+ * Values, by outs_h[k].kind:
+ *   BFHIP_FILL_KEEP  a real row holds word(row, col); an inserted row holds its predecessor entry's word(col), and if col == step_col that
+ *                    word + t as an M31 sum (only the tail can wrap past p - 1).
+ *   BFHIP_FILL_SET   a real row holds word(row, col); an inserted row holds `value`.
+ *   BFHIP_FILL_MARK  a real row holds 0; an inserted row holds `value`; col is ignored. The `d` column of a table.
+ * Outputs: output row i of output column k is sequence element i + outs_h[k].offset, 0 <= offset <= BFHIP_FILL_MAX_OFFSET = 16: a row's
+ *   successor is offset 1 of the same call. Every output row is defined, the pairing dummy at 2^log_size included: the call has no pad array.
+ *   out_cols_h: n_out device pointers, each to 2^log_size words, written whole in storage order. 1 <= n_out <= 256, 1 <= log_size <= 30.
+ * *n_filled = T. Count-only form: out_cols_h == NULL with n_out == 0 and log_size == 0 returns T and writes nothing: how a caller sizes the
+ *   domain. Otherwise T > 2^log_size is -1 with "bfhip_rows_fill: <T> rows after filling, the domain has <2^log_size>", found after the count
+ *   (*n_filled is set) and before any column is written — also when T exceeds 2^32: the total is a 64-bit sum, nothing wraps.
+ * Canonicity: checked are the group and step words of every entry (with BFHIP_FILL_GAPS) and every source word an output reads (an inserted
+ *   row of a SET column and a MARK column read nothing). A word >= 2^31 - 1 makes the call return -1 with
+ *   "bfhip_rows_fill: row <r>, column <c>: <v> is not a canonical M31 value" — the lowest SOURCE row, then the lowest SOURCE column. The
+ *   outputs are then unspecified; nothing faults and the context stays usable. The refusal by the count comes first.
+ * order_d: every word must be below n_rows, else -1 with "bfhip_rows_fill: order[<i>] = <r> is not a row of the table (<n_rows> rows)", the
+ *   lowest i — found by a launch that reads only order_d, before any launch reads the table through it: no read leaves the table, nothing
+ *   is written.
+ * Launches (csrc/rows_fill.hip): the order check; with BFHIP_FILL_GAPS the counts c_i = 1 + g_i with their 64-bit total
+ *   and a scan for the positions; the gather — tiles of 1024 output rows through LDS as bfhip_rows_select's, each run of 32 rows resolved to
+ *   (entry, t) once; log_size below 10: one thread per cell. Two read-backs: T together with the order record, and the bad-word record at
+ *   the end (the call returns when the columns are written); a refused word costs a third, 4-byte one.
+ * Memory: nothing from the arena (bfhip_ctx_memory out[3] is unchanged): works while a commitment-scheme session is open. Descriptors and
+ *   records come from the staging ring; counts and positions are call-scoped scratch, served from the scratch reserve where one is set.
+ * Refused, -1 with "bfhip_rows_fill: <rule>", nothing enqueued, the context usable: everything bfhip_rows_select refuses about the table
+ *   (null pointers, unknown layout or flag bit, reserved != 0, row_stride < n_cols, no columns, n_rows above 2^40, n_cols above 2^24), the
+ *   outputs (log_size, n_out, a null output column) and overlaps (an output column sharing a byte with the source, with order_d or with an
+ *   earlier output; the message names the two); out_cols_h NULL with n_out or log_size not 0; n_entries of 0 ("needs at least one entry")
+ *   or above 2^30; row_begin + n_entries > n_rows; row_begin != 0 with order_d; n_group above BFHIP_FILL_MAX_GROUP or non-zero with a null
+ *   array; a group, step or output column index not below n_cols; BFHIP_FILL_GAPS without a step column; an unknown kind or flag bit; a SET
+ *   or MARK value >= p; an offset above 16; fill->reserved != 0; BFHIP_ROWS_REPEAT_LAST in table->flags (the tail is this call's padding);
+ *   a context in a shard group.
+ * bfhip_rows_fill_host (host only, no GPU): the same definition over a host row-major table, fill->order_d a HOST array there, the result
+ *   in ROW order — out_rows_h = 2^log_size x n_out words; out_rows_h NULL with n_out 0 and log_size 0 is the count-only form. The kernels are
+ *   held to it word for word. The same refusals and failures under "bfhip_rows_fill_host: ".
+ * Not built: a multi-source bfhip_rows_select without the caller's layout (lay the row blocks into one device table, as the Instruction
+ *   table of brainfuck_rows_fill does); the per-instruction sub-tables' dummy rows (their padding counts from the SUCCESSOR entry, which a
+ *   witness program over the selected columns covers); an origin map per output row; pool jobs; shard groups; row-granular (shifted) outputs.
+ * Layout (natural alignment, declaration order):
+ *   bfhip_fill_out  16 bytes: col 0, kind 4, value 8, offset 12
+ *   bfhip_rows_fill_desc  48 bytes: group_cols 0, n_group 8, step_col 12, order_d 16, n_entries 24, row_begin 32, flags 40, reserved 44 */
+enum { BFHIP_FILL_KEEP = 0, BFHIP_FILL_SET = 1, BFHIP_FILL_MARK = 2,
+       BFHIP_FILL_GAPS = 1,
+       BFHIP_FILL_NO_STEP = 4294967295u /* 0xFFFFFFFF */, BFHIP_FILL_MAX_GROUP = 4, BFHIP_FILL_MAX_OFFSET = 16 };
+typedef struct bfhip_fill_out { uint32_t col, kind, value, offset; } bfhip_fill_out;
+typedef struct bfhip_rows_fill_desc {
+    const uint32_t* group_cols;       /* host array of n_group source columns */
+    uint32_t n_group, step_col;       /* step_col: a source column, or BFHIP_FILL_NO_STEP */
+    const uint32_t* order_d;          /* NULL, or n_entries device words: the source row of entry i, as bfhip_rows_select writes order_d */
+    uint64_t n_entries, row_begin;
+    uint32_t flags, reserved;         /* flags: BFHIP_FILL_GAPS; reserved must be 0 */
+} bfhip_rows_fill_desc;
+int32_t bfhip_rows_fill(bfhip_ctx* ctx, const bfhip_rows_table* table, const bfhip_rows_fill_desc* fill, uint32_t log_size,
+                        const bfhip_fill_out* outs_h, uint32_t* const* out_cols_h, uint32_t n_out, uint64_t* n_filled);
+int32_t bfhip_rows_fill_host(const uint32_t* table_h, uint64_t n_rows, uint32_t n_cols, uint64_t row_stride, const bfhip_rows_fill_desc* fill,
+                             uint32_t log_size, const bfhip_fill_out* outs_h, uint32_t n_out, uint32_t* out_rows_h, uint64_t* n_filled);
 
 /* ---- Relation programs: the lookup tuples of ANY AIR that do not cancel ------------------------------------------------------------------------
  * bfhip_relation_summary / bfhip_trace_relations know the three Brainfuck relations and the 13 table layouts. An AIR proved through bfhip_pcs_* +
@@ -1449,8 +1520,8 @@ int32_t bfhip_relation_program_multiplicities(bfhip_ctx* ctx, const bfhip_relati
  *     "output column <k> overlaps input column <j>" / "output column <k> overlaps output column <j>".
  * Kernel (csrc/witness_program.hip): the instruction core of the four program kernels on the row of bfhip_air_check;
  *   one lane per cell, one wave per workgroup, the register file in LDS.
- * Not built: tables that need row insertion or several concatenated sources (the Memory table's clk-gap dummy rows, the Instruction table's
- *   program rows beside the trace's; a sort or a row filter alone is bfhip_rows_select, "Row selection" above), extension-field values,
+ * Not built: row insertion and sorting inside a program (the Memory table's clk-gap dummy rows and the Instruction table's program rows
+ *   beside the trace's are bfhip_rows_fill, "Row filling" above; a sort or a row filter alone is bfhip_rows_select), extension-field values,
  *   shifted (row-granular) columns, reading an output of the same call at an offset (run a second program), witness programs compiled with
  *   hiprtc, pool jobs, shard groups. */
 enum { BFHIP_WIT_ARG = 19, BFHIP_WIT_ROW = 20, BFHIP_WIT_INV0 = 21, BFHIP_WIT_IS_ZERO = 22, BFHIP_WIT_LT = 23, BFHIP_WIT_AND = 24, BFHIP_WIT_SHR = 25,

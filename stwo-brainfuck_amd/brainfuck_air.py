@@ -245,8 +245,8 @@ def brainfuck_witness_program(table):
     one whose neighbour at +1 has clk 0: the VM starts at clk 0 and counts up. Returns (WitnessProgram, output column names)."""
     if table != "processor":
         raise ValueError("witness programs are written for: 'processor' (the sub-tables' real rows and the Memory table's sorted entries come from "
-                         "brainfuck_rows_select; what remains is row insertion and concatenated sources: the Memory table's clk-gap dummies and the "
-                         "Instruction table's program rows)")
+                         "brainfuck_rows_select; row insertion and concatenated sources — the Memory table's clk-gap dummies and the Instruction "
+                         "table's program rows — from brainfuck_rows_fill)")
     b = AirBuilder()
     row, n = b.row(), b.arg(0)
     real = b.lt(row, n)
@@ -288,3 +288,38 @@ def brainfuck_rows_select(table, n_rows):
     names = ("clk", "ip", "ci", "ni", "mp", "mv", "mvi", "next_ip", "next_mp", "next_mv")
     return dict(where=((2, "==", ord(_BF_SUB_TABLE_OPCODES[table])),), rows=(0, max(0, int(n_rows) - 1)),
                 columns=(0, 1, 2, 3, 4, 5, 6, (1, 1), (4, 1), (5, 1))), names
+
+
+def brainfuck_instruction_rows(code, regs):
+    """The source table of brainfuck_rows_fill("instruction"): the program's pseudo-register rows (clk = 0, ip = i, ci = code[i],
+    ni = code[i + 1] or 0, the rest 0) in front of the trace's register rows `regs` (n x 7) — two row blocks laid into one row-major table,
+    so that the stable (ip, clk) sort puts a program row before a trace row of equal key (instruction/table.rs:253-271)."""
+    import numpy as np
+    code = np.asarray(code, dtype=np.uint32)
+    rows = np.zeros((code.size, 7), dtype=np.uint32)
+    rows[:, 1] = np.arange(code.size)
+    rows[:, 2] = code
+    rows[:-1, 3] = code[1:]
+    return np.concatenate([rows, np.asarray(regs, dtype=np.uint32)])
+
+
+def brainfuck_rows_fill(table, n_rows):
+    """The whole Memory, Processor and Instruction tables from the VM's 7 register columns clk, ip, ci, ni, mp, mv, mvi — the worked example
+    of include/bfhip.h "Row filling". Returns (keyword arguments of Context.rows_select_count or None, keyword arguments of Context.rows_fill
+    / rows_fill_host, output column names): where the first is not None the table is sorted first (want_order=True) and the order it returns
+    is rows_fill's `order`. Every table equals bfhip_host_table in every row and column, dummy rows and the pairing dummy included.
+    "memory" (component 0; memory/table.rs:249-303, 121-151): the (mp, clk)-sorted steps with a dummy row for every clk skipped inside one mp.
+    "processor" (component 3): the trace in source order, rows = (0, n_rows); no gaps, the dummies behind it keep counting clk.
+    "instruction" (component 1): over brainfuck_instruction_rows(code, regs) — n_rows counts its rows —, sorted by (ip, clk); no step."""
+    if table == "memory":
+        cols = [("keep", 0), ("keep", 4), ("keep", 5), ("mark", 1)]
+        return (dict(order_by=(4, 0), want_order=True), dict(group=(4,), step=0, gaps=True, columns=cols + [c + (1,) for c in cols]),
+                ("clk", "mp", "mv", "d", "next_clk", "next_mp", "next_mv", "next_d"))
+    if table == "processor":
+        cols = [("keep", 0), ("keep", 1)] + [("set", j, 0) for j in (2, 3, 4, 5, 6)] + [("mark", 1), ("keep", 0, 1)]
+        return None, dict(step=0, columns=cols, rows=(0, int(n_rows))), ("clk", "ip", "ci", "ni", "mp", "mv", "mvi", "d", "next_clk")
+    if table == "instruction":
+        cols = [("keep", 1), ("set", 2, 0), ("set", 3, 0), ("mark", 1)]
+        return (dict(order_by=(1, 0), want_order=True), dict(columns=cols + [c + (1,) for c in cols]),
+                ("ip", "ci", "ni", "d", "next_ip", "next_ci", "next_ni", "next_d"))
+    raise ValueError("fillings are written for 'memory', 'processor' and 'instruction'")

@@ -6,7 +6,9 @@ import ctypes
 import numpy as np
 
 from ._abi import _check, _ptr_array, _u32s, abi, struct_fields
-from ._abi_gen import (BFHIP_ROWS_COLUMN_MAJOR as ROWS_COLUMN_MAJOR, BFHIP_ROWS_REPEAT_LAST as ROWS_REPEAT_LAST, BFHIP_ROWS_ROW_MAJOR as ROWS_ROW_MAJOR,
+from ._abi_gen import (BFHIP_FILL_GAPS as FILL_GAPS, BFHIP_FILL_KEEP as FILL_KEEP, BFHIP_FILL_MARK as FILL_MARK, BFHIP_FILL_MAX_GROUP as FILL_MAX_GROUP,
+                       BFHIP_FILL_MAX_OFFSET as FILL_MAX_OFFSET, BFHIP_FILL_NO_STEP as FILL_NO_STEP, BFHIP_FILL_SET as FILL_SET,
+                       BFHIP_ROWS_COLUMN_MAJOR as ROWS_COLUMN_MAJOR, BFHIP_ROWS_REPEAT_LAST as ROWS_REPEAT_LAST, BFHIP_ROWS_ROW_MAJOR as ROWS_ROW_MAJOR,
                        BFHIP_SELECT_DESCENDING as SELECT_DESCENDING, BFHIP_SELECT_EQ, BFHIP_SELECT_GE, BFHIP_SELECT_GT, BFHIP_SELECT_LE, BFHIP_SELECT_LT,
                        BFHIP_SELECT_MAX_KEYS as SELECT_MAX_KEYS, BFHIP_SELECT_MAX_TERMS as SELECT_MAX_TERMS, BFHIP_SELECT_NE)
 
@@ -232,7 +234,7 @@ def _as_device_table(ctx, table):
     return table, None
 
 
-def rows_select_count(ctx, table, where=(), order_by=(), rows=None, want_order=False):
+def rows_select_count(ctx, table, where=(), order_by=(), rows=None, want_order=False, order_out=None):
     """Context.rows_select_count (see there)."""
     table, tmp = _as_device_table(ctx, table)
     order_d = None
@@ -240,13 +242,13 @@ def rows_select_count(ctx, table, where=(), order_by=(), rows=None, want_order=F
         tdesc, keep = _rows_table(table, False)
         sel, keep2 = _select_desc(list(where), list(order_by), rows, tdesc.n_rows)
         n_cand = max(0, sel.row_end - sel.row_begin)
-        if want_order:
+        if want_order and order_out is None:
             order_d = ctx.malloc(4 * max(1, n_cand))
         n_sel = ctypes.c_uint64()
-        _check(abi().bfhip_rows_select(ctx._h, ctypes.byref(tdesc), ctypes.byref(sel), 0, None, None, 0, order_d, ctypes.byref(n_sel)))
+        _check(abi().bfhip_rows_select(ctx._h, ctypes.byref(tdesc), ctypes.byref(sel), 0, None, None, 0, order_d if order_out is None else order_out, ctypes.byref(n_sel)))
         del keep, keep2
         order = None
-        if want_order:
+        if want_order and order_out is None:
             order = ctx.download(order_d, n_sel.value) if n_sel.value else np.zeros(0, dtype=np.uint32)
         return n_sel.value, order
     finally:
@@ -327,3 +329,145 @@ def rows_select_host(table, log_size=None, where=(), order_by=(), columns=None, 
     call(int(log_size), outs, n_out, rows_out)
     del keep
     return SelectedRows(rows_out, n_sel.value, None if order is None else order[:n_sel.value].copy())
+
+
+# ---- bfhip_rows_fill (include/bfhip.h "Row filling") ------------------------------------------------------------------------------------
+FILL_KINDS = {"keep": FILL_KEEP, "set": FILL_SET, "mark": FILL_MARK}
+
+
+class FillOut(ctypes.Structure):
+    """include/bfhip.h `bfhip_fill_out`."""
+    _fields_ = struct_fields("bfhip_fill_out")
+
+
+class RowsFillDesc(ctypes.Structure):
+    """include/bfhip.h `bfhip_rows_fill_desc`."""
+    _fields_ = struct_fields("bfhip_rows_fill_desc")
+
+
+# What rows_fill_host returns: rows = (2^log_size, n_out) uint32 in ROW order (None in the count-only form), n_filled = T
+FilledRows = collections.namedtuple("FilledRows", "rows n_filled")
+
+
+def _fill_outs(columns):
+    """columns: ("keep", col[, offset]) | ("set", col, value[, offset]) | ("mark", value[, offset]) | a bare column (keep, offset 0)."""
+    columns = list(columns)
+    outs = (FillOut * max(1, len(columns)))()
+    for k, c in enumerate(columns):
+        if isinstance(c, (int, np.integer)):
+            c = ("keep", c)
+        kind, rest = c[0], [int(v) for v in c[1:]]
+        want = {"keep": (1, 2), "set": (2, 3), "mark": (1, 2)}.get(kind)
+        if want is None or len(rest) not in want:
+            raise ValueError('an output is ("keep", col[, offset]), ("set", col, value[, offset]) or ("mark", value[, offset])')
+        off = rest.pop() if len(rest) == want[1] else 0
+        col, value = (0, rest[0]) if kind == "mark" else (rest[0], rest[1] if kind == "set" else 0)
+        outs[k] = FillOut(col, FILL_KINDS[kind], value, off)
+    return outs, len(columns)
+
+
+def _fill_desc(group, step, gaps, order_ptr, n_entries, row_begin):
+    """The bfhip_rows_fill_desc and the array it points into."""
+    group = [int(g) for g in group]
+    garr = _u32s(group) if group else None
+    desc = RowsFillDesc(ctypes.cast(garr, ctypes.POINTER(ctypes.c_uint32)) if group else None, len(group), FILL_NO_STEP if step is None else int(step),
+                        ctypes.cast(order_ptr, ctypes.POINTER(ctypes.c_uint32)) if order_ptr else None, int(n_entries), int(row_begin), FILL_GAPS if gaps else 0, 0)
+    return desc, garr
+
+
+def _fill_entries(order, n_order, rows, n_rows):
+    """(n_entries, row_begin) of the (order, rows) arguments."""
+    if order is not None:
+        if rows is not None:
+            raise ValueError("give an order or a row range, not both")
+        return n_order, 0
+    begin, end = (0, n_rows) if rows is None else rows
+    return max(0, int(end) - int(begin)), int(begin)
+
+
+def _fill_call(ctx, table, log_size, group, step, gaps, columns, order, n_order, rows, out):
+    table, tmp = _as_device_table(ctx, table)
+    order_tmp, owned = None, []
+    try:
+        tdesc, keep = _rows_table(table, False)
+        if isinstance(order, np.ndarray):
+            n_order = order.size
+            if not order.size:
+                raise ValueError("an order has at least one entry")
+            order_tmp = order = ctx.upload(np.ascontiguousarray(order, dtype=np.uint32))
+        elif order is not None and n_order is None:
+            raise ValueError("a device order needs n_order, the number of entries")
+        n_entries, row_begin = _fill_entries(order, n_order, rows, tdesc.n_rows)
+        fill, keep2 = _fill_desc(group, step, gaps, order, n_entries, row_begin)
+        n_filled = ctypes.c_uint64()
+        if columns is None:
+            _check(abi().bfhip_rows_fill(ctx._h, ctypes.byref(tdesc), ctypes.byref(fill), 0, None, None, 0, ctypes.byref(n_filled)))
+            return n_filled.value
+        outs, n_out = _fill_outs(columns)
+        if out is not None and len(out) != n_out:
+            raise ValueError("one output pointer per output column")
+        if log_size is None:
+            _check(abi().bfhip_rows_fill(ctx._h, ctypes.byref(tdesc), ctypes.byref(fill), 0, None, None, 0, ctypes.byref(n_filled)))
+            log_size = _domain_for(n_filled.value)
+        ptrs = list(out) if out is not None else None
+        if ptrs is None:
+            for _ in range(n_out):
+                owned.append(ctx.malloc(4 << log_size))
+            ptrs = owned
+        _check(abi().bfhip_rows_fill(ctx._h, ctypes.byref(tdesc), ctypes.byref(fill), int(log_size), outs, _ptr_array(ptrs) if ptrs else None, n_out, ctypes.byref(n_filled)))
+        del keep, keep2
+        cols = Columns(ctx, ptrs, log_size, owned)      # from here on the handle owns the columns
+        owned = []
+        cols.n_filled = n_filled.value
+        return cols
+    finally:
+        for p in owned:
+            ctx.free(p)
+        if order_tmp is not None:
+            ctx.free(order_tmp)
+        if tmp is not None:
+            ctx.free(tmp)
+
+
+def rows_fill(ctx, table, log_size=None, group=(), step=None, gaps=False, columns=None, order=None, n_order=None, rows=None, out=None):
+    """Context.rows_fill (see there)."""
+    if columns is None:
+        raise ValueError("rows_fill needs its output columns (rows_fill_count is the count-only form)")
+    return _fill_call(ctx, table, log_size, group, step, gaps, columns, order, n_order, rows, out)
+
+
+def rows_fill_count(ctx, table, group=(), step=None, gaps=False, order=None, n_order=None, rows=None):
+    """Context.rows_fill_count (see there)."""
+    return _fill_call(ctx, table, None, group, step, gaps, None, order, n_order, rows, None)
+
+
+def rows_fill_host(table, log_size=None, group=(), step=None, gaps=False, columns=None, order=None, rows=None, n_cols=None, count_only=False):
+    """bfhip_rows_fill_host: the definition of a filled table, on the host and without a GPU. table: a (n_rows, row_stride) uint32 array of
+    which the first n_cols words of a row are the table (None = all); order: None or a uint32 array of source rows. The other arguments are
+    rows_fill's. Returns FilledRows(rows, n_filled): rows in ROW order, (2^log_size, n_out). count_only: the count without rows; log_size None
+    takes the smallest domain that holds the count, at least 1."""
+    table = np.ascontiguousarray(table, dtype=np.uint32)
+    if table.ndim != 2:
+        raise TypeError("a host table is a (n_rows, row_stride) uint32 array")
+    n_rows, stride = table.shape
+    n_cols = stride if n_cols is None else int(n_cols)
+    if order is not None:
+        order = np.ascontiguousarray(order, dtype=np.uint32)
+    n_entries, row_begin = _fill_entries(order, None if order is None else order.size, rows, n_rows)
+    fill, keep = _fill_desc(group, step, gaps, order.ctypes.data if order is not None and order.size else None, n_entries, row_begin)
+    n_filled = ctypes.c_uint64()
+    data = table.ctypes.data if table.size else None
+
+    def call(log, outs, n_out, rows_out):
+        _check(abi().bfhip_rows_fill_host(data, n_rows, n_cols, stride, ctypes.byref(fill), log, outs, n_out, None if rows_out is None else rows_out.ctypes.data,
+                                          ctypes.byref(n_filled)))
+    if count_only or log_size is None:
+        call(0, None, 0, None)
+        if count_only:
+            return FilledRows(None, n_filled.value)
+        log_size = _domain_for(n_filled.value)
+    outs, n_out = _fill_outs(columns if columns is not None else range(n_cols))
+    rows_out = np.zeros((1 << log_size, n_out), dtype=np.uint32)
+    call(int(log_size), outs, n_out, rows_out)
+    del keep
+    return FilledRows(rows_out, n_filled.value)

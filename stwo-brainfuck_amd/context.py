@@ -346,9 +346,24 @@ class Context(Owned):
         handle that also carries .n_selected and, with want_order, .order — the source row of every selected row (else None)."""
         return _columns.rows_select(self, table, log_size, where, order_by, columns, rows, pad, repeat_last, out, want_order)
 
-    def rows_select_count(self, table, where=(), order_by=(), rows=None, want_order=False):
-        """The count-only form of bfhip_rows_select: (the number of selected rows, their source rows in order if want_order else None)."""
-        return _columns.rows_select_count(self, table, where, order_by, rows, want_order)
+    def rows_fill(self, table, log_size=None, group=(), step=None, gaps=False, columns=None, order=None, n_order=None, rows=None, out=None):
+        """bfhip_rows_fill: the entries of the table — rows `rows` = (begin, end) in source order, or the source rows `order` (a device
+        pointer to n_order words as rows_select's order_d, or a uint32 array) — with the missing rows inserted: with gaps=True a row for
+        every value of column `step` skipped between two consecutive entries that agree in the `group` columns, and behind the last entry
+        rows without end. columns: ("keep", col[, offset]) | ("set", col, value[, offset]) | ("mark", value[, offset]); offset 0..16 reads
+        the successor rows. Returns Columns with .n_filled = the rows before the tail; log_size None takes the smallest domain that holds
+        them."""
+        return _columns.rows_fill(self, table, log_size, group, step, gaps, columns, order, n_order, rows, out)
+
+    def rows_fill_count(self, table, group=(), step=None, gaps=False, order=None, n_order=None, rows=None):
+        """The count-only form of bfhip_rows_fill: the number of rows before the tail, the inserted ones included."""
+        return _columns.rows_fill_count(self, table, group, step, gaps, order, n_order, rows)
+
+    def rows_select_count(self, table, where=(), order_by=(), rows=None, want_order=False, order_out=None):
+        """The count-only form of bfhip_rows_select: (the number of selected rows, their source rows in order if want_order else None).
+        order_out: a device pointer to one word per candidate row that receives the order instead (nothing is downloaded; the second
+        value is None) — what rows_fill takes as `order`."""
+        return _columns.rows_select_count(self, table, where, order_by, rows, want_order, order_out)
 
     def rows_from_columns(self, col_ptrs, log_size, n_rows=None):
         """bfhip_rows_from_columns: storage-order device columns (pointers, or a Columns handle) back in row order, as a (n_rows,

@@ -8,6 +8,7 @@
 #include "rows.h"
 #include "rows_index.h"
 #include "rows_select.h"
+#include "rows_fill.h"
 #include <string>
 #include <algorithm>
 #include <vector>
@@ -533,6 +534,104 @@ int32_t bfhip_rows_select(bfhip_ctx* ctx, const bfhip_rows_table* table, const b
     }
     unsigned long long bad = ~0ull;
     c.read_back(&bad, src.first_bad, sizeof bad);
+    if (bad != ~0ull) {
+        const u64 row = bad >> SELECT_BAD_COL_BITS; const u32 j = (u32)(bad & ((1u << SELECT_BAD_COL_BITS) - 1));
+        u32 v = 0;
+        c.read_back(&v, (const u32*)(uintptr_t)table_word(j) + row * stride, sizeof v);
+        throw HipError(select_bad_word_message(who, bad, v));
+    }
+    return 0;
+    API_CATCH
+}
+
+// ---- insert the missing rows of a row-order table (include/bfhip.h "Row filling"; rows_fill.hip, the rules in rows_fill.h) ----
+int32_t bfhip_rows_fill(bfhip_ctx* ctx, const bfhip_rows_table* table, const bfhip_rows_fill_desc* fill, uint32_t log_size, const bfhip_fill_out* outs_h,
+                        uint32_t* const* out_cols_h, uint32_t n_out, uint64_t* n_filled) {
+    API_CTX(ctx)
+    Ctx& c = ctx->c;
+    hipStream_t s = c.stream;
+    const std::string who = "bfhip_rows_fill: ";
+    if (!table || !fill || !n_filled) throw HipError(who + "null argument");
+    if (table->reserved != 0) throw HipError(who + "reserved must be 0");
+    if (table->layout != BFHIP_ROWS_ROW_MAJOR && table->layout != BFHIP_ROWS_COLUMN_MAJOR) throw HipError(who + "unknown layout " + std::to_string(table->layout));
+    if (table->flags & ~uint32_t(BFHIP_ROWS_REPEAT_LAST)) throw HipError(who + "unknown flag bits " + std::to_string(table->flags));
+    const bool col_major = table->layout == BFHIP_ROWS_COLUMN_MAJOR;
+    const u64 n_rows = table->n_rows, stride = col_major ? 1 : table->row_stride;
+    if (!col_major && table->row_stride < table->n_cols) throw HipError(who + "row_stride " + std::to_string(table->row_stride) + " is below n_cols " + std::to_string(table->n_cols));
+    const FillPlan plan = fill_validate(who, SelectShape{n_rows, table->n_cols, (table->flags & BFHIP_ROWS_REPEAT_LAST) != 0}, fill, log_size, outs_h, n_out, out_cols_h != nullptr);
+    if (col_major ? !table->cols_h : !table->rows_d) throw HipError(who + "null table pointer");
+    rows_not_sharded(c, who);
+    const u32 n = (u32)fill->n_entries;
+    std::vector<ByteRange> used;      // the source first, then the order and the outputs accepted so far
+    if (col_major) {
+        for (u32 j = 0; j < table->n_cols; j++) {
+            if (!table->cols_h[j]) throw HipError(who + "source column " + std::to_string(j) + " is a null pointer");
+            used.push_back({(u64)(uintptr_t)table->cols_h[j], n_rows * sizeof(u32), "source column " + std::to_string(j)});
+        }
+    } else {
+        used.push_back({(u64)(uintptr_t)table->rows_d, (rows_src_offset(n_rows - 1, stride, table->n_cols - 1) + 1) * sizeof(u32), "the source table"});
+    }
+    auto table_word = [&](u32 j) { return col_major ? (u64)(uintptr_t)table->cols_h[j] : (u64)(uintptr_t)(table->rows_d + j); };
+    if (fill->order_d) used.push_back({(u64)(uintptr_t)fill->order_d, u64(n) * sizeof(u32), "the order"});
+    std::vector<FillOutDev> outs(n_out);
+    for (u32 k = 0; k < n_out; k++) {
+        if (!out_cols_h[k]) throw HipError(who + "output column " + std::to_string(k) + " is a null pointer");
+        const ByteRange out{(u64)(uintptr_t)out_cols_h[k], sizeof(u32) << log_size, "output column " + std::to_string(k)};
+        for (const ByteRange& u : used) if (out.overlaps(u)) throw HipError(who + out.name + " overlaps " + u.name);
+        used.push_back(out);
+        const bfhip_fill_out& o = outs_h[k];
+        const bool mark = o.kind == BFHIP_FILL_MARK;
+        outs[k] = FillOutDev{mark ? 0 : table_word(o.col), out.base, o.kind, o.kind == BFHIP_FILL_KEEP ? 0u : o.value, o.offset, mark ? 0u : o.col,
+                             !mark && o.col == fill->step_col ? 1u : 0u, {0, 0, 0}};
+    }
+    // ---- enqueued from here on ----
+    c.stage_checkpoint(Ctx::stage_round(sizeof(FillOutDev) * n_out) + 256);
+    const unsigned long long records[3] = {~0ull, ~0ull, 0};      // the bad word, the bad order word, the total
+    unsigned long long* d_records;
+    const FillOutDev* d_outs = nullptr;
+    {
+        StageBatch sb(c);
+        if (n_out) d_outs = c.stage(outs.data(), n_out);
+        d_records = c.stage(records, 3);
+        sb.end();
+    }
+    const FillSource src{fill->order_d, fill->row_begin, stride, d_records, d_records + 1};
+    DeviceScratch scratch(c);
+    // (0), (1): the order, the counts, the total
+    u32 *counts = nullptr, *pos = nullptr, *tot = nullptr;
+    u64 T = n;
+    if (fill->order_d) fill_order_check_launch(s, fill->order_d, n, n_rows, src.order_bad);
+    if (plan.gaps) {
+        scratch.alloc(&counts, sizeof(u32) * n);
+        FillCountsArgs ca{};
+        for (u32 j = 0; j < fill->n_group; j++) { ca.group[j] = table_word(fill->group_cols[j]); ca.group_col[j] = fill->group_cols[j]; }
+        ca.step = table_word(fill->step_col); ca.step_col = fill->step_col; ca.n_group = fill->n_group; ca.n = n; ca.src = src; ca.counts = counts; ca.total = d_records + 2;
+        ProfScope ps(s, "k_fill_counts", 4.0 * double(n) * double(2 * (fill->n_group + 1) + 1));
+        fill_counts_launch(s, ca);
+    }
+    if (fill->order_d || plan.gaps) {
+        BF_HIP(hipGetLastError());
+        unsigned long long got[2] = {~0ull, 0};
+        c.read_back(got, d_records + 1, sizeof got);
+        if (got[0] != ~0ull) throw HipError(fill_bad_order_message(who, got[0] >> 32, (u32)got[0], n_rows));
+        if (plan.gaps) T = got[1];
+    }
+    *n_filled = T;
+    fill_check_count(who, plan, T, log_size);
+    // (2) the positions and the columns
+    if (!plan.count_only) {
+        if (plan.gaps) {
+            scratch.alloc(&pos, sizeof(u32) * n); scratch.alloc(&tot, sizeof(u32) * (n / 2048 + 3));
+            ProfScope ps(s, "rows_fill_scan", 12.0 * double(n));
+            exclusive_scan_u32(s, counts, pos, tot, n);
+        }
+        FillGatherArgs ga{};
+        ga.outs = d_outs; ga.pos = pos; ga.src = src; ga.n_entries = n; ga.n_filled = (u32)T; ga.log_size = log_size; ga.n_out = n_out;
+        fill_gather_launch(s, ga, col_major);
+        BF_HIP(hipGetLastError());
+    }
+    unsigned long long bad = ~0ull;
+    if (!plan.count_only || plan.gaps) c.read_back(&bad, src.first_bad, sizeof bad);
     if (bad != ~0ull) {
         const u64 row = bad >> SELECT_BAD_COL_BITS; const u32 j = (u32)(bad & ((1u << SELECT_BAD_COL_BITS) - 1));
         u32 v = 0;

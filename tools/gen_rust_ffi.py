@@ -36,6 +36,8 @@ DOCS = {
     "bfhip_select_key": "`bfhip_select_key`: one sort key of bfhip_rows_select, 8 bytes. flags: BFHIP_SELECT_DESCENDING.",
     "bfhip_select_out": "`bfhip_select_out`: one output column of bfhip_rows_select: source column, row offset, pad value; 12 bytes.",
     "bfhip_rows_select_desc": "`bfhip_rows_select_desc`: the filter, the keys and the candidate rows of bfhip_rows_select, 48 bytes. terms and keys are host arrays.",
+    "bfhip_fill_out": "`bfhip_fill_out`: one output column of bfhip_rows_fill: source column, kind (BFHIP_FILL_KEEP / SET / MARK), the inserted rows' value, element offset; 16 bytes.",
+    "bfhip_rows_fill_desc": "`bfhip_rows_fill_desc`: the entries, the group and step columns of bfhip_rows_fill (include/bfhip.h \"Row filling\"), 48 bytes. group_cols is a host array, order_d a device one.",
     "bfhip_relation_program_table": "`bfhip_relation_program_table`: one table of bfhip_relation_program_summary, 32 bytes. cols_h = host array of device pointers; col_shifts_h may be null.",
     "bfhip_multiplicity_report": "`bfhip_multiplicity_report`: the counts of bfhip_relation_program_multiplicities (include/bfhip.h \"Lookup multiplicities\"), 80 bytes.",
 }
